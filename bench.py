@@ -7,6 +7,10 @@ Workload at N=1 (and per GPU at N>1, weak scaling): BASELINE.json configs[2] -- 
 24 heads/decoder 4), ERA5 1.40625deg -> 0.25deg synthetic grids: x [B,23,128,256] -> pred [B,3,512,1024],
 target [B,3,721,1440] consumed through its top-left 512x1024 crop, bf16 compute / fp32 master, train mode with
 the YAML's dropout 0.1 / drop-path 0.1, loss bayesian_tv, dynamic loss scaling, fused AdamW.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what takes runs of its own: the
+CPU baseline, the other BASELINE configs as child runs and, for a graph-replayed step, the instrumented eager pass behind
+the per-kernel roofline figures.  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -104,6 +108,13 @@ def parse():
                          "all-gather one unit ahead, reduce-scattered gradients, AdamW on 1/N chunks")
     ap.add_argument("--shard-optimizer", action="store_true",
                     help="reduce-scatter gradients, AdamW on 1/N of every unit, all-gather the bf16 copies")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: `cpu_baseline`, `other_configs` (default "
+                         "configuration) and, with the graph on, the instrumented eager pass behind roofline_gemm / "
+                         "roofline_attention; --no-cpu-baseline / --no-other-configs still drop their part")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy: loss.npy, "
+                         "loss_scale.npy and param.<key>.npy = a fixed seeded sample of every fp32 master tensor")
     return ap.parse_args()
 
 
@@ -367,7 +378,7 @@ def other_configs(t_start, budget_s=420.0, configs=None):
         if spent + allow > budget_s:
             out[key] = {"skipped": "time budget: %.0f s spent, %d s allowance, %.0f s budget" % (spent, allow, budget_s), "stands_for": what}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__)] + args + ["--no-cpu-baseline", "--no-other-configs"]
+        cmd = [sys.executable, os.path.abspath(__file__)] + args + ["--full", "--no-cpu-baseline", "--no-other-configs"]
         env = dict(os.environ)
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         t0 = time.perf_counter()
@@ -429,6 +440,28 @@ def launch_check(a, rank, world, local):
     if rank == 0:
         print(json.dumps({"metric": METRIC, "value": None, "unit": "samples/s", "n_gpus": world, "steps": 0, "warmup": 0,
                           "launch_check": True, "ranks_met": ranks, "backend": "gloo", "devices": devs}), flush=True)
+
+
+DUMP_SAMPLE = 16384       # --dump-outputs: elements kept per parameter tensor
+DUMP_LIMIT = 64 << 20     # --dump-outputs: bytes of all arrays together
+
+
+def dump_outputs(path, state, loss, loss_scale):
+    """--dump-outputs: what a caller of the timed step holds after the last one -- the loss it returned, the loss scale and
+    the updated fp32 parameters -- as .npy files.  A tensor of more than DUMP_SAMPLE elements is sampled at positions drawn
+    from a generator with a fixed seed, so that two builds can be compared element for element."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(0)
+    arrays = {"loss": np.array([loss], np.float64), "loss_scale": np.array([loss_scale], np.float64)}
+    per = max(1, min(DUMP_SAMPLE, (DUMP_LIMIT - 1024) // (8 * max(1, len(state)))))
+    for k, t in state.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > per:
+            idx = np.sort(rng.integers(0, flat.numel(), per))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays["param." + k] = flat.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def _attn_roofline(prof, traffic_attn, note):
@@ -573,17 +606,19 @@ def main():
     if (world > 1 or force) and not a.graph and not a.no_comm_stats:
         eng.comm_stats = cl.CommStats()                 # HIP-event accounting of the collectives over the timed region
     if a.graph:
-        # instrumented eager pass for the per-kernel (roofline) numbers, then the captured step for the throughput
-        _hip.timer = _hip.KernelTimer()
-        for i in range(min(3, a.steps)):
-            step(a.warmup + i)
-        fence()
-        prof = _hip.timer.summary()
-        for rec in prof.values():                      # scale the instrumented pass to a.steps steps
-            rec["work"] *= a.steps / min(3, a.steps)
-            rec["ms"] *= a.steps / min(3, a.steps)
-            rec["launches"] = int(rec["launches"] * a.steps / min(3, a.steps))
-        _hip.timer = None
+        # --full: an instrumented eager pass for the per-kernel (roofline) numbers; then the captured step for the throughput
+        prof = {}
+        if a.full:
+            _hip.timer = _hip.KernelTimer()
+            for i in range(min(3, a.steps)):
+                step(a.warmup + i)
+            fence()
+            prof = _hip.timer.summary()
+            for rec in prof.values():                  # scale the instrumented pass to a.steps steps
+                rec["work"] *= a.steps / min(3, a.steps)
+                rec["ms"] *= a.steps / min(3, a.steps)
+                rec["launches"] = int(rec["launches"] * a.steps / min(3, a.steps))
+            _hip.timer = None
         gstep = cl.GraphedTrainStep(eng, loss_fn, batch, VAR_WEIGHTS, scaler=scaler)
 
         def step(i):                                   # noqa: F811  (graphed fwd+bwd, eager scaler + AdamW)
@@ -619,6 +654,11 @@ def main():
         backend_name, ranks_met = dist.get_backend(), dist.get_world_size()
     dt = float(tmax.item())
     loss_val = float(last.detach())
+    if a.dump_outputs:
+        state = eng.state_dict()                       # collective with the sharded engines: every rank takes part
+        if rank == 0:
+            dump_outputs(a.dump_outputs, state, loss_val, scaler.get_scale())
+        del state
 
     if rank == 0:
         sps = dp_world * B * a.steps / dt
@@ -704,7 +744,7 @@ def main():
                                         "of the timed region; no vendor-library GEMM is called",
                               "traffic_note": traffic_note,
                               "launches": gm["launches"],
-                              "avg_launch_ms": gm["ms"] / max(1, gm["launches"])},
+                              "avg_launch_ms": gm["ms"] / max(1, gm["launches"])} if prof else None,   # (graph on: --full)
             # the family FURTHEST below its roofline, with the same fields: forward and backward launches of the
             # flash-attention kernels (csrc/attn.hip); algorithmic FLOPs 4 B H L^2 d forward, 8 B H L^2 d backward (the backward's
             # recomputation of S and its two-kernel split are NOT credited)
@@ -715,10 +755,11 @@ def main():
                 "mfma_frac_of_peak_executed": 3 * f_exec * sps / world / PEAK_BF16,
                 "attn_fwd_tflops": (prof["attn_fwd"]["work"] / prof["attn_fwd"]["ms"] / 1e9) if "attn_fwd" in prof else None,
                 "attn_bwd_tflops": (prof["attn_bwd"]["work"] / prof["attn_bwd"]["ms"] / 1e9) if "attn_bwd" in prof else None,
-                "gemm_ms_per_step": gm["ms"] / a.steps,
+                "gemm_ms_per_step": gm["ms"] / a.steps if prof else None,
                 "library_gemm": {"provider": "none (the torch.matmul / hipBLASLt dispatch of round 1 is deleted)",
                                  "launches": 0, "ms_per_step": 0.0, "share_of_gemm_flops": 0.0},
-                "attn_ms_per_step": (prof.get("attn_fwd", {"ms": 0})["ms"] + prof.get("attn_bwd", {"ms": 0})["ms"]) / a.steps,
+                "attn_ms_per_step": ((prof.get("attn_fwd", {"ms": 0})["ms"] + prof.get("attn_bwd", {"ms": 0})["ms"]) / a.steps
+                                     if prof else None),
                 "final_loss": loss_val, "loss_scale": scaler.get_scale()},
         }
         if eng.comm_stats is not None:                   # did the collectives hide behind backward?
@@ -740,7 +781,9 @@ def main():
             out["data_npz"] = npz_leg(a, step_on, fence, in_vars, OUT_VARS, (h, w), (hy, wy), B, sps, dev)
             out["data"] = "synthetic, resident in HBM (`value`); `data_npz` = the same step fed from a reference-format npz tree"
         default_run = (a.model == "interm_1b" and a.grid == "128x256" and not a.daymet and tp == 1 and not a.fsdp and not a.recompute)
-        if world == 1 and (a.eager_baseline or not a.no_cpu_baseline or (default_run and not a.no_other_configs) or a.other_configs_smoke):
+        cpu_base = a.full and not a.no_cpu_baseline
+        more_configs = a.full and default_run and not a.no_other_configs
+        if world == 1 and (a.eager_baseline or cpu_base or more_configs or a.other_configs_smoke):
             # release the headline run's device memory: the closures hold the engine, the optimizer and the batch too
             import gc as _gc
             step = fence = last = gstep = loss_fn = scaler = x = y = None          # noqa: F841
@@ -752,12 +795,12 @@ def main():
             out["other_configs"] = other_configs(T_PROCESS_START, configs=(
                 ("interm_8m_32x64_b2", "configs[0]-shaped smoke entry (tests)", ["--model", "interm_8m", "--grid", "32x64", "--batch", "2",
                                                                                   "--steps", "3", "--warmup", "1"], 240),))
-        elif world == 1 and default_run and not a.no_other_configs:
+        elif world == 1 and more_configs:
             out["other_configs"] = other_configs(T_PROCESS_START)
         if world == 1 and a.eager_baseline and not a.daymet:
             out["gpu_eager_baseline"] = gpu_eager_baseline(a.model, V, C, a.eager_baseline, dev)
             torch.cuda.empty_cache()
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and cpu_base:
             out["cpu_baseline"] = cpu_baseline(a.model, V, C)
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())

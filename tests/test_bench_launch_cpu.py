@@ -41,3 +41,34 @@ def test_bench_single_rank_launch_check_unchanged_contract():
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 1
+
+
+def test_dump_outputs_writes_a_fixed_sample(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files; a large tensor is sampled at the same positions from run to run"""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("o2_bench_dump", os.path.join(ROOT, "bench.py"))
+    bm = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bm)
+    g = torch.Generator().manual_seed(3)
+    state = {"big.weight": torch.randn(bm.DUMP_SAMPLE * 3 + 5, generator=g), "small.bias": torch.randn(7, generator=g),
+             "table": torch.randn(4, 5, dtype=torch.float64, generator=g)}
+    for sub in ("a", "b"):
+        bm.dump_outputs(os.path.join(tmp_path, sub), state, 1.25, 8192.0)
+    files = sorted(os.listdir(os.path.join(tmp_path, "a")))
+    assert files == ["loss.npy", "loss_scale.npy", "param.big.weight.npy", "param.small.bias.npy", "param.table.npy"]
+    for f in files:
+        a, b = (np.load(os.path.join(tmp_path, sub, f)) for sub in ("a", "b"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    big = np.load(os.path.join(tmp_path, "a", "param.big.weight.npy"))
+    assert big.dtype == np.float32 and big.size == bm.DUMP_SAMPLE and np.isin(big, state["big.weight"].numpy()).all()
+    assert np.array_equal(np.load(os.path.join(tmp_path, "a", "param.small.bias.npy")), state["small.bias"].numpy())
+    assert np.load(os.path.join(tmp_path, "a", "param.table.npy")).dtype == np.float64
+    assert np.load(os.path.join(tmp_path, "a", "loss.npy")).tolist() == [1.25]
+
+
+def test_full_and_dump_outputs_are_options():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], env=_plain_env(),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout

@@ -330,11 +330,11 @@ def test_bench_contract_two_ranks_one_card(tmp_path):
 
 
 def test_bench_single_rank_line_with_baselines(tmp_path):
-    """one rank, small model: ONE stdout line carrying `roofline`, `cpu_baseline` (oracle on the host) and, with
+    """one rank, small model, --full: ONE stdout line carrying `roofline`, `cpu_baseline` (oracle on the host) and, with
     --eager-baseline, `gpu_eager_baseline` (the oracle as eager PyTorch on the GPU)"""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--model", "interm_8m",
-                        "--batch", "2", "--eager-baseline", "2"], cwd=tmp_path, capture_output=True, text=True, timeout=900)
+                        "--batch", "2", "--eager-baseline", "2", "--full"], cwd=tmp_path, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.splitlines()
     assert len(lines) == 1
@@ -389,3 +389,31 @@ def test_bench_sharded_engine_with_graph_replay(tmp_path):
     assert d["config"]["hipgraph"] is True and d["value"] > 0
     loss = d["step_model"]["final_loss"]
     assert loss == loss and 0 < loss < 1e4
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """without --full the line carries the headline fields and none of the extra runs (`cpu_baseline`, `other_configs`);
+    --dump-outputs writes the last timed step's loss and a seeded sample of the updated fp32 parameters as .npy files"""
+    import json
+    import numpy as np
+    out_dir = os.path.join(tmp_path, "outputs")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--model", "interm_8m",
+                        "--grid", "32x64", "--batch", "2", "--dump-outputs", out_dir],
+                       cwd=tmp_path, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert "cpu_baseline" not in d and "other_configs" not in d
+    files = sorted(os.listdir(out_dir))
+    assert "loss.npy" in files and "loss_scale.npy" in files and any(f.startswith("param.") for f in files)
+    total = 0
+    for f in files:
+        a = np.load(os.path.join(out_dir, f))
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(os.path.join(out_dir, "loss.npy"))[0] == d["step_model"]["final_loss"]
