@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define ORBIT2_ABI_VERSION 6
+#define ORBIT2_ABI_VERSION 7
 int orbit2_abi_version(void);
 
 /* ---- bf16 MFMA GEMM with fused epilogue ------------------------------------------------
@@ -82,29 +82,26 @@ int orbit2_gemm_bf16_colsum_rows(const orbit2_gemm_args* args);   /* 0: this cal
  * 8-phase kernel when every problem has K % 64 == 0, M, N >= 256 and the group fills the chip; the 128x128 kernel
  * otherwise): the partially filled last round of each problem is filled with the next one's tiles.  Used for
  * the four weight-gradient GEMMs of a Block (reference: autograd of attention.py:36,40 + mlp.py:50,54).
- * Round 6 (same ABI version: no signature or layout changed, the limit only grew from 8): up to 12 problems, so that a caller can
- * hand over the tiles beyond the group's last whole round of 256 as part-length problems over slices of the contraction (the
- * Python layer's balanced weight-gradient launch: 3 full problems + 2 x 4 quarter-length ones, partial products summed by
- * orbit2_batch_sum).  When every problem sweeps >= 512 K-tiles of 64 the workgroups of an XCD start their tiles together
+ * Up to 12 problems (the limit of ABI 7), so that a caller can hand over the tiles beyond the group's last whole round of 256 as
+ * part-length problems over slices of the contraction (the Python layer's balanced weight-gradient launch: 3 full problems +
+ * 2 x 4 quarter-length ones, partial products summed by orbit2_batch_sum).  When every problem sweeps >= 512 K-tiles of 64 the
+ * workgroups of an XCD start their tiles together
  * (a bounded wait on a self-cleaning counter in a static device array: a pacing hint, never needed for correctness;
  * ORBIT2_W4_PACE = 0 / 1 / 2: off / on (default) / plus check points inside the sweep). */
 #define ORBIT2_GEMM_MAX_GROUP 12
 int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, void* stream);
 
 /* small fp32 GEMM (parameter-table algebra of the folded variable aggregation):
- * C[M,N] = alpha * op(A) * op(B) + beta*C, row-major fp32; ta/tb: 0 = as stored, 1 = transposed. */
-int orbit2_sgemm_f32(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
-                     int ta, int tb, float alpha, float beta, void* stream);
-/* same product with a caller-owned fp32 workspace: skinny problems (a few rows against a D x D weight) are split over K
- * into orbit2_sgemm_f32_ws_floats(M,N,K) / (M*N) slabs and combined deterministically; 0 floats = no split is planned */
+ * C[M,N] = alpha * op(A) * op(B) + beta*C, row-major fp32; ta/tb: 0 = as stored, 1 = transposed.
+ * ws: caller-owned fp32 workspace of orbit2_sgemm_f32_ws_floats(M,N,K) floats: skinny problems (a few rows against a D x D
+ * weight) are split over K into ws_floats / (M*N) slabs and combined deterministically; 0 floats = no split is planned (ws may
+ * then be NULL) */
 int64_t orbit2_sgemm_f32_ws_floats(int M, int N, int K);
 int orbit2_sgemm_f32_ws(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
                         int ta, int tb, float alpha, float beta, float* ws, int64_t ws_floats, void* stream);
 
 /* ---- LayerNorm (vit_blocks.py:46,63; res_slimvit.py:104,294): eps 1e-5, affine ------------ */
-int orbit2_layernorm_fwd(const void* x, const void* gamma, const void* beta, void* y, float* mean, float* rstd,
-                         int rows, int D, float eps, void* stream);
-/* the same with a row pitch on y (ldy >= D elements, a multiple of 8; ABI 5): the output is the A operand of the next GEMM, and
+/* y has a row pitch (ldy >= D elements, a multiple of 8; ldy = D: contiguous): the output is the A operand of the next GEMM, and
  * rows a multiple of 8 KiB apart (D % 4096 == 0: interm_10b) put every row's k-offset on one memory channel */
 int orbit2_layernorm_fwd_ld(const void* x, const void* gamma, const void* beta, void* y, float* mean, float* rstd,
                             int rows, int D, int ldy, float eps, void* stream);
@@ -117,18 +114,13 @@ int orbit2_layernorm_bwd_ws_floats(int rows, int D);
 /* ---- multi-head self-attention core (attention.py:54-78): softmax(q k^T / sqrt(d)) v --------
  * qkv: bf16 [B, L, 3, H, d] (the qkv Linear output as stored, no permute copies);
  * out: bf16 [B, L, H, d]; lse: fp32 [B, H, L].  d in {64, 128, 256}; any L >= 1 (ragged tails are masked).
- * drop_p: dropout on P (attention.py:57,69,76). */
-int orbit2_attn_fwd(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
-                    uint64_t seed, void* stream);
-/* dqkv: bf16 [B, L, 3, H, d];  delta: fp32 workspace of orbit2_attn_bwd_ws_floats(B, L, H) floats (two per-row statistics
+ * drop_p: dropout on P (attention.py:57,69,76).
+ * dqkv: bf16 [B, L, 3, H, d];  delta: fp32 workspace of orbit2_attn_bwd_ws_floats(B, L, H) floats (two per-row statistics
  * tables, -lse log2(e) and -rowsum(dO o O) / dropout scale, padded per (b, h): the dK / dV kernels copy their tiles of it into
  * LDS by LDS-DMA) */
 int64_t orbit2_attn_bwd_ws_floats(int B, int L, int H);
-int orbit2_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
-                    void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, void* stream);
-/* The same two entries with the kernel variant as an ARGUMENT (A/B timing and the bit-equality tests of the fused
- * d = 128 dK+dV pass): flags = 0 is what orbit2_attn_fwd / _bwd run.  Nothing on the launch path reads the environment
- * or any other process-global switch. */
+/* flags: the kernel variant as an ARGUMENT (0 = the default kernels; A/B timing and the bit-equality tests of the fused
+ * d = 128 dK+dV pass).  Nothing on the launch path reads the environment or any other process-global switch. */
 #define ORBIT2_ATTN_4WAVES 1     /* 4-wave / 128-row workgroups (round-1 geometry) instead of 8-wave / 256-row ones */
 #define ORBIT2_ATTN_SPLIT_DKV 2  /* d = 128: dK and dV as two passes instead of the fused one */
 /* The q third of qkv already holds q * log2(e)/sqrt(d) (written so by the qkv GEMM's colscale epilogue: ONE rounding to
@@ -141,13 +133,10 @@ int orbit2_attn_bwd(const void* qkv, const void* out, const void* dout, const fl
  * generated one-wave-per-SIMD kernels (csrc/attn_fwd_asm.h, attn_dq_asm.h; tools/gen_attn_fwd.py, gen_attn_dq.py); this flag
  * keeps the compiler-scheduled kernels instead (A/B timing, tests). */
 #define ORBIT2_ATTN_NO_W4 8
-int orbit2_attn_fwd_ex(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
-                       uint64_t seed, int flags, void* stream);
-int orbit2_attn_bwd_ex(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
-                       void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, void* stream);
-/* The same two with token-row pitches (elements, multiples of 8; ABI 5): qkv[b, l] and dqkv[b, l] start at (b * L + l) * ldq
- * (ldq >= 3 * H * d), out[b, l] at (b * L + l) * ldo (ldo >= H * d) -- these tensors are GEMM operands on the other side, and rows
- * a multiple of 8 KiB apart put every row's k-offset on one memory channel (see orbit2_layernorm_fwd_ld).  dout stays [B, L, H, d]. */
+/* Token-row pitches (elements, multiples of 8): qkv[b, l] and dqkv[b, l] start at (b * L + l) * ldq (ldq >= 3 * H * d),
+ * out[b, l] at (b * L + l) * ldo (ldo >= H * d); the natural pitches ldq = 3 * H * d, ldo = H * d are the contiguous layouts
+ * above.  These tensors are GEMM operands on the other side, and rows a multiple of 8 KiB apart put every row's k-offset on one
+ * memory channel (see orbit2_layernorm_fwd_ld).  dout stays [B, L, H, d]. */
 int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
                        uint64_t seed, int flags, int ldq, int ldo, void* stream);
 int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,

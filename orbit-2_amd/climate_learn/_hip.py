@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # $ORBIT2_HIP_LIB: another build of the same ABI (A/B timing of kernel variants on one box; tools/ab_build.sh)
 LIB_PATH = os.environ.get("ORBIT2_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "liborbit2_hip.so")
 _lib = None
+ABI_VERSION = 7                 # ORBIT2_ABI_VERSION: load() refuses a build of any other version
 
 
 class HipBackendError(RuntimeError):
@@ -49,26 +50,105 @@ class GemmArgs(C.Structure):
     ]
 
 
+# Every prototype of include/orbit2_hip.h: name -> (restype, argtypes).  The header has five parameter kinds: int, int64_t,
+# uint64_t, float and pointers, which are all void* to ctypes except the GEMM's argument block.  With these declared, ctypes
+# refuses a call with too few arguments or an argument of the wrong kind before it reaches the library.
+_I, _I64, _U64, _F, _P, _G = C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_void_p, C.POINTER(GemmArgs)
+PROTOTYPES = {
+    "orbit2_abi_version": (_I, ()),
+    "orbit2_gemm_bf16": (_I, (_G, _P)),
+    "orbit2_gemm_bf16_colsum_rows": (_I, (_G,)),
+    "orbit2_gemm_bf16_grouped": (_I, (_G, _I, _P)),
+    "orbit2_sgemm_f32_ws_floats": (_I64, (_I, _I, _I)),
+    "orbit2_sgemm_f32_ws": (_I, (_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _I64, _P)),
+    "orbit2_layernorm_fwd_ld": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P)),
+    "orbit2_layernorm_bwd": (_I, (_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P, _I, _I, _I, _P)),
+    "orbit2_layernorm_bwd_ws_floats": (_I, (_I, _I)),
+    "orbit2_attn_bwd_ws_floats": (_I64, (_I, _I, _I)),
+    "orbit2_attn_fwd_ld": (_I, (_P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P)),
+    "orbit2_attn_bwd_ld": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P)),
+    "orbit2_varagg_fwd": (_I, (_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P)),
+    "orbit2_varagg_bwd_ws_floats": (_I64, (_I, _I, _I, _I, _I, _I)),
+    "orbit2_varagg_bwd": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P)),
+    "orbit2_tables_gather": (_I, (_P, _I64, _P, _I64, _P, _P, _P, _I, _I, _P)),
+    "orbit2_tables_scatter": (_I, (_P, _P, _I64, _P, _I64, _P, _P, _I, _I, _P)),
+    "orbit2_varagg_bwd_is_fixed_order": (_I, (_I, _I, _I, _I, _I, _I)),
+    "orbit2_dropout_bwd": (_I, (_P, _P, _I, _I, _F, _U64, _P, _I, _P)),
+    "orbit2_dropout_bwd_colsum": (_I, (_P, _P, _I, _I, _F, _U64, _P, _I, _P, _I, _F, _P, _I, _P)),
+    "orbit2_post_reduce": (_I, (_P, _P, _I, _P, _P, _I, _I, _F, _U64, _P, _I, _P)),
+    "orbit2_colsum": (_I, (_P, _I, _I, _I, _I, _P, _I, _F, _P, _I, _P)),
+    "orbit2_colsum_ws_floats": (_I, (_I, _I)),
+    "orbit2_batch_sum": (_I, (_P, _P, _I, _I, _I, _I, _F, _P)),
+    "orbit2_droppath_scales": (_I, (_P, _I, _F, _U64, _P)),
+    "orbit2_transpose_bf16": (_I, (_P, _P, _I, _I, _P)),
+    "orbit2_cast_f32_to_bf16": (_I, (_P, _P, _I64, _P)),
+    "orbit2_cast_bf16_to_f32": (_I, (_P, _P, _I64, _P)),
+    "orbit2_add_rowvec": (_I, (_P, _P, _P, _I, _I, _P)),
+    "orbit2_posembed_fwd": (_I, (_P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P)),
+    "orbit2_posembed_bwd": (_I, (_P, _P, _I, _I, _I, _I, _I, _P)),
+    "orbit2_unpatchify_fwd": (_I, (_P, _P, _I, _I, _I, _I, _I, _I, _P)),
+    "orbit2_unpatchify_bwd": (_I, (_P, _P, _I, _I, _I, _I, _I, _I, _P)),
+    "orbit2_conv3x3_fwd": (_I, (_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P)),
+    "orbit2_conv3x3_bwd_ws_floats": (_I64, (_I, _I, _I, _I, _I)),
+    "orbit2_conv3x3_bwd": (_I, (_P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P)),
+    "orbit2_clamp_channel": (_I, (_P, _I, _I, _I, _I, _P)),
+    "orbit2_clamp_channel_bwd": (_I, (_P, _P, _I, _I, _I, _I, _P)),
+    "orbit2_loss_fwd": (_I, (_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P)),
+    "orbit2_loss_bwd": (_I, (_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P)),
+    "orbit2_eval_moments": (_I, (_P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P)),
+    "orbit2_im2col3x3": (_I, (_P, _P, _I, _I, _I, _I, _P)),
+    "orbit2_col2im3x3": (_I, (_P, _P, _P, _P, _I, _I, _I, _I, _P)),
+    "orbit2_maxpool2_fwd": (_I, (_P, _P, _I, _I, _I, _I, _P)),
+    "orbit2_maxpool2_bwd": (_I, (_P, _P, _P, _P, _I, _I, _I, _I, _P)),
+    "orbit2_lpips_conv1_fwd": (_I, (_P, _P, _P, _P, _I, _I, _I, _P)),
+    "orbit2_lpips_conv1_bwd": (_I, (_P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _P)),
+    "orbit2_lpips_tap_ws_floats": (_I64, (_I, _I, _I)),
+    "orbit2_lpips_tap_fwd": (_I, (_P, _P, _P, _I, _I, _I, _P, _P)),
+    "orbit2_lpips_tap_bwd": (_I, (_P, _P, _P, _F, _P, _I, _I, _I, _P)),
+    "orbit2_l1_mean_ws_floats": (_I64, (_I64,)),
+    "orbit2_l1_mean": (_I, (_P, _P, _P, _I64, _P, _P)),
+    "orbit2_adamw": (_I, (_P, _P, _P, _P, _I, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P)),
+    "orbit2_check_finite": (_I, (_P, _I, _I64, _P, _P)),
+    "orbit2_seed_salt": (_I, (_U64, _I, _P)),
+    "orbit2_selftest": (_I, (_P, _P)),
+    "orbit2_probe_read": (_I, (_P, _I64, _I, _I, _P, _P)),
+}
+
+
+def load(path: str) -> C.CDLL:
+    """Open a build of the library with every entry of PROTOTYPES declared (lib() for this package's build; the A/B tools
+    open other builds with it).  A build of another ABI version, or one that lacks a declared entry, is refused."""
+    if not os.path.exists(path):
+        raise HipBackendError(
+            "liborbit2_hip.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950). This package has no CPU fallback." % path)
+    so = C.CDLL(path)
+    version = so.orbit2_abi_version() if hasattr(so, "orbit2_abi_version") else None
+    if version != ABI_VERSION:
+        raise HipBackendError("%s has ABI version %s, this binding needs %d" % (path, version, ABI_VERSION))
+    missing = [name for name in PROTOTYPES if not hasattr(so, name)]
+    if missing:
+        raise HipBackendError("%s lacks %s" % (path, ", ".join(missing)))
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(so, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return so
+
+
 def lib():
-    """Load the shared library once; fail loudly if it is absent (no fallback path exists)."""
+    """load(LIB_PATH), once; fails loudly if the library is absent (no fallback path exists)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise HipBackendError(
-                "liborbit2_hip.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(hipcc --offload-arch=gfx950). This package has no CPU fallback." % LIB_PATH)
-        _lib = C.CDLL(LIB_PATH)
-        if _lib.orbit2_abi_version() != 6:
-            raise HipBackendError("liborbit2_hip.so ABI version mismatch")
+        _lib = load(LIB_PATH)
     return _lib
 
 
-def _stream() -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def _stream() -> int:
+    return torch.cuda.current_stream().cuda_stream
 
 
-def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
-    return C.c_void_p(0 if t is None else t.data_ptr())
+def _p(t: Optional[torch.Tensor]) -> Optional[int]:
+    return None if t is None else t.data_ptr()
 
 
 def _chk(rc: int, name: str):
@@ -200,12 +280,10 @@ def gemm_grouped(problems):
 def sgemm(A, B, out, M, N, K, lda, ldb, ldc, ta=False, tb=False, alpha=1.0, beta=0.0):
     for t, nm in ((A, "A"), (B, "B"), (out, "C")):
         _dev(t, F32, nm)
-    L = lib()
-    L.orbit2_sgemm_f32_ws_floats.restype = C.c_int64
-    n = int(L.orbit2_sgemm_f32_ws_floats(M, N, K))
+    n = lib().orbit2_sgemm_f32_ws_floats(M, N, K)
     ws = torch.empty(n, dtype=F32, device=out.device) if n else None
-    _chk(L.orbit2_sgemm_f32_ws(_p(A), _p(B), _p(out), M, N, K, lda, ldb, ldc, int(ta), int(tb), C.c_float(alpha),
-                               C.c_float(beta), _p(ws), C.c_int64(n), _stream()), "orbit2_sgemm_f32_ws")
+    _chk(lib().orbit2_sgemm_f32_ws(_p(A), _p(B), _p(out), M, N, K, lda, ldb, ldc, int(ta), int(tb), alpha, beta, _p(ws), n,
+                                   _stream()), "orbit2_sgemm_f32_ws")
     return out
 
 
@@ -218,7 +296,7 @@ def layernorm_fwd(x, gamma, beta, eps=1e-5, out=None):
     ldy = D if out is None else y.stride(0)
     mean = torch.empty(rows, dtype=F32, device=x.device)
     rstd = torch.empty(rows, dtype=F32, device=x.device)
-    _chk(lib().orbit2_layernorm_fwd_ld(_p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, D, ldy, C.c_float(eps),
+    _chk(lib().orbit2_layernorm_fwd_ld(_p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, D, ldy, eps,
                                        _stream()), "orbit2_layernorm_fwd_ld")
     return y, mean, rstd
 
@@ -232,17 +310,17 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, beta_acc=0.0):
     ws = torch.empty(n, dtype=F32, device=x.device)
     fp32 = int(dgamma.dtype == F32)
     _chk(lib().orbit2_layernorm_bwd(_p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dres), _p(dx), _p(dgamma),
-                                    _p(dbeta), fp32, C.c_float(beta_acc), _p(ws), n, rows, D, _stream()),
+                                    _p(dbeta), fp32, beta_acc, _p(ws), n, rows, D, _stream()),
          "orbit2_layernorm_bwd")
     return dx
 
 
-ATTN_4WAVES, ATTN_SPLIT_DKV, ATTN_Q_PRESCALED, ATTN_NO_W4 = 1, 2, 4, 8      # include/orbit2_hip.h: kernel-variant flags of the *_ex attention entries (A/B, tests)
+ATTN_4WAVES, ATTN_SPLIT_DKV, ATTN_Q_PRESCALED, ATTN_NO_W4 = 1, 2, 4, 8      # include/orbit2_hip.h: the kernel-variant flags of the attention entries (A/B, tests)
 
 
 def probe_read(buf, blocks, inflight, sink):
     """diagnostic calibration stream (include/orbit2_hip.h: orbit2_probe_read)"""
-    _chk(lib().orbit2_probe_read(_p(buf), C.c_int64(buf.numel() * buf.element_size()), int(blocks), int(inflight), _p(sink),
+    _chk(lib().orbit2_probe_read(_p(buf), buf.numel() * buf.element_size(), int(blocks), int(inflight), _p(sink),
                                  _stream()), "orbit2_probe_read")
 
 
@@ -281,8 +359,8 @@ def attn_fwd(qkv, B, L, H, d, drop_p=0.0, seed=0, flags=0, out=None):
         # algorithmic bytes: qkv read once, out + lse written once
         e0, e1 = timer.span("attn_fwd", 4.0 * B * H * L * L * d, 2.0 * 4 * B * L * H * d + 4.0 * B * H * L)
         e0.record()
-    _chk(lib().orbit2_attn_fwd_ld(_p(qkv), _p(out), _p(lse), B, L, H, d, C.c_float(drop_p), C.c_uint64(seed), int(flags),
-                                  int(ldq), int(ldo), _stream()), "orbit2_attn_fwd_ld")
+    _chk(lib().orbit2_attn_fwd_ld(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo),
+                                  _stream()), "orbit2_attn_fwd_ld")
     if timer is not None:
         e1.record()
     return out, lse
@@ -296,14 +374,13 @@ def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0):
         dqkv = torch.empty(B * L, ldq, dtype=BF, device=qkv.device)[:, :3 * H * d]
     else:
         dqkv = torch.empty_like(qkv)
-    lib().orbit2_attn_bwd_ws_floats.restype = C.c_int64
-    delta = torch.empty(int(lib().orbit2_attn_bwd_ws_floats(B, L, H)), dtype=F32, device=qkv.device)
+    delta = torch.empty(lib().orbit2_attn_bwd_ws_floats(B, L, H), dtype=F32, device=qkv.device)
     if timer is not None:
         # algorithmic: 2x the forward's FLOPs (recompute not credited); qkv, out, dout read once, dqkv written once
         e0, e1 = timer.span("attn_bwd", 8.0 * B * H * L * L * d, 2.0 * 8 * B * L * H * d + 8.0 * B * H * L)
         e0.record()
     _chk(lib().orbit2_attn_bwd_ld(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, L, H, d,
-                                  C.c_float(drop_p), C.c_uint64(seed), int(flags), int(ldq), int(ldo), _stream()), "orbit2_attn_bwd_ld")
+                                  drop_p, seed, int(flags), int(ldq), int(ldo), _stream()), "orbit2_attn_bwd_ld")
     if timer is not None:
         e1.record()
     return dqkv
@@ -322,8 +399,7 @@ def varagg_fwd(x, stab, gtab, H, D):
 
 def _ws(query, args, device):
     """fp32 workspace of a two-stage (slab + fixed-order combine) reduction: `query` is the entry's *_ws_floats function"""
-    query.restype = C.c_int64
-    n = int(query(*args))
+    n = query(*args)
     if n <= 0:
         raise HipBackendError("workspace query failed for %r" % (args,))
     return torch.empty(n, dtype=F32, device=device)
@@ -353,23 +429,23 @@ def tables_gather(w0, w_stride, b0, b_stride, var_embed, ids, V, D):
     _dev(w0, F32, "token_embeds.0.proj.weight"); _dev(b0, F32, "token_embeds.0.proj.bias"); _dev(var_embed, F32, "var_embed")
     _dev(ids, torch.int32, "ids")
     cmat = torch.empty(5 * V, D, dtype=F32, device=w0.device)
-    _chk(lib().orbit2_tables_gather(_p(w0), C.c_int64(w_stride), _p(b0), C.c_int64(b_stride), _p(var_embed), _p(ids), _p(cmat),
-                                    V, D, _stream()), "orbit2_tables_gather")
+    _chk(lib().orbit2_tables_gather(_p(w0), w_stride, _p(b0), b_stride, _p(var_embed), _p(ids), _p(cmat), V, D, _stream()),
+         "orbit2_tables_gather")
     return cmat
 
 
 def tables_scatter(dcmat, gw0, w_stride, gb0, b_stride, gvar_embed, ids, V, D):
     """accumulates the rows' gradient into the parameters' gradient buffers (same pitches)"""
     _dev(dcmat, F32, "dcmat"); _dev(gw0, F32, "dW"); _dev(gb0, F32, "db"); _dev(gvar_embed, F32, "dvar_embed")
-    _chk(lib().orbit2_tables_scatter(_p(dcmat), _p(gw0), C.c_int64(w_stride), _p(gb0), C.c_int64(b_stride), _p(gvar_embed),
-                                     _p(ids), V, D, _stream()), "orbit2_tables_scatter")
+    _chk(lib().orbit2_tables_scatter(_p(dcmat), _p(gw0), w_stride, _p(gb0), b_stride, _p(gvar_embed), _p(ids), V, D,
+                                     _stream()), "orbit2_tables_scatter")
 
 
 def dropout_bwd(dy, M, N, drop_p, seed, rowscale=None, rows_per_scale=0, out=None):
     _dev(dy, BF, "dy")
     out = torch.empty_like(dy) if out is None else out
-    _chk(lib().orbit2_dropout_bwd(_p(dy), _p(out), M, N, C.c_float(drop_p), C.c_uint64(seed), _p(rowscale),
-                                  rows_per_scale, _stream()), "orbit2_dropout_bwd")
+    _chk(lib().orbit2_dropout_bwd(_p(dy), _p(out), M, N, drop_p, seed, _p(rowscale), rows_per_scale, _stream()),
+         "orbit2_dropout_bwd")
     return out
 
 
@@ -379,9 +455,8 @@ def dropout_bwd_colsum(dy, M, N, drop_p, seed, rowscale, rows_per_scale, colsum_
     out = torch.empty_like(dy)
     n = lib().orbit2_colsum_ws_floats(M, N)
     ws = torch.empty(n, dtype=F32, device=dy.device)
-    _chk(lib().orbit2_dropout_bwd_colsum(_p(dy), _p(out), M, N, C.c_float(drop_p), C.c_uint64(seed), _p(rowscale),
-                                         rows_per_scale, _p(colsum_out), int(colsum_out.dtype == F32), C.c_float(beta), _p(ws),
-                                         n, _stream()), "orbit2_dropout_bwd_colsum")
+    _chk(lib().orbit2_dropout_bwd_colsum(_p(dy), _p(out), M, N, drop_p, seed, _p(rowscale), rows_per_scale, _p(colsum_out),
+                                         int(colsum_out.dtype == F32), beta, _p(ws), n, _stream()), "orbit2_dropout_bwd_colsum")
     return out
 
 
@@ -393,8 +468,8 @@ def post_reduce(x, M, N, addend=None, res_mod=0, residual=None, drop_p=0.0, seed
         if t is not None:
             _dev(t, BF, nm)
     out = x if out is None else out
-    _chk(lib().orbit2_post_reduce(_p(x), _p(addend), res_mod, _p(residual), _p(out), M, N, C.c_float(drop_p),
-                                  C.c_uint64(seed), _p(rowscale), rows_per_scale, _stream()), "orbit2_post_reduce")
+    _chk(lib().orbit2_post_reduce(_p(x), _p(addend), res_mod, _p(residual), _p(out), M, N, drop_p, seed, _p(rowscale),
+                                  rows_per_scale, _stream()), "orbit2_post_reduce")
     return out
 
 
@@ -403,14 +478,14 @@ def colsum(x, M, N, ldx, out, beta=0.0):
         raise HipBackendError("colsum input must be bf16/fp32")
     n = lib().orbit2_colsum_ws_floats(M, N)
     ws = torch.empty(n, dtype=F32, device=x.device)
-    _chk(lib().orbit2_colsum(_p(x), int(x.dtype == F32), M, N, ldx, _p(out), int(out.dtype == F32), C.c_float(beta),
+    _chk(lib().orbit2_colsum(_p(x), int(x.dtype == F32), M, N, ldx, _p(out), int(out.dtype == F32), beta,
                              _p(ws), n, _stream()), "orbit2_colsum")
     return out
 
 
 def batch_sum(x, B, rows, N, out, beta=0.0):
     _dev(x, BF, "x")
-    _chk(lib().orbit2_batch_sum(_p(x), _p(out), B, rows, N, int(out.dtype == F32), C.c_float(beta), _stream()),
+    _chk(lib().orbit2_batch_sum(_p(x), _p(out), B, rows, N, int(out.dtype == F32), beta, _stream()),
          "orbit2_batch_sum")
     return out
 
@@ -418,14 +493,14 @@ def batch_sum(x, B, rows, N, out, beta=0.0):
 def cast_to_bf16(src, dst=None):
     _dev(src, F32, "src")
     dst = torch.empty(src.shape, dtype=BF, device=src.device) if dst is None else dst
-    _chk(lib().orbit2_cast_f32_to_bf16(_p(src), _p(dst), C.c_int64(src.numel()), _stream()), "orbit2_cast_f32_to_bf16")
+    _chk(lib().orbit2_cast_f32_to_bf16(_p(src), _p(dst), src.numel(), _stream()), "orbit2_cast_f32_to_bf16")
     return dst
 
 
 def cast_to_f32(src, dst=None):
     _dev(src, BF, "src")
     dst = torch.empty(src.shape, dtype=F32, device=src.device) if dst is None else dst
-    _chk(lib().orbit2_cast_bf16_to_f32(_p(src), _p(dst), C.c_int64(src.numel()), _stream()), "orbit2_cast_bf16_to_f32")
+    _chk(lib().orbit2_cast_bf16_to_f32(_p(src), _p(dst), src.numel(), _stream()), "orbit2_cast_bf16_to_f32")
     return dst
 
 
@@ -443,7 +518,7 @@ def posembed_fwd(pe, sw, sb, res, oh, ow, nh, nw):
     if sw is not None:
         _dev(sw, F32, "spatial_embed.weight"); _dev(sb, F32, "spatial_embed.bias")
     out = torch.empty(nh * nw, D, dtype=F32, device=pe.device)
-    _chk(lib().orbit2_posembed_fwd(_p(pe), _p(sw), _p(sb), C.c_float(res), _p(out), oh, ow, nh, nw, D, _stream()),
+    _chk(lib().orbit2_posembed_fwd(_p(pe), _p(sw), _p(sb), res, _p(out), oh, ow, nh, nw, D, _stream()),
          "orbit2_posembed_fwd")
     return out
 
@@ -542,13 +617,12 @@ def adamw(p, m, v, g, p16, n, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, f
     _dev(p, F32, "p"); _dev(m, F32, "m"); _dev(v, F32, "v")
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
-    _chk(lib().orbit2_adamw(_p(p), _p(m), _p(v), _p(g), int(g.dtype == F32), _p(p16), C.c_int64(n), C.c_float(lr),
-                            C.c_float(beta1), C.c_float(beta2), C.c_float(eps), C.c_float(wd), C.c_float(bc1),
-                            C.c_float(bc2), C.c_float(grad_scale), _p(found_inf), _stream()), "orbit2_adamw")
+    _chk(lib().orbit2_adamw(_p(p), _p(m), _p(v), _p(g), int(g.dtype == F32), _p(p16), n, lr, beta1, beta2, eps, wd, bc1, bc2,
+                            grad_scale, _p(found_inf), _stream()), "orbit2_adamw")
 
 
 def check_finite(g, n, found_inf):
-    _chk(lib().orbit2_check_finite(_p(g), int(g.dtype == F32), C.c_int64(n), _p(found_inf), _stream()),
+    _chk(lib().orbit2_check_finite(_p(g), int(g.dtype == F32), n, _p(found_inf), _stream()),
          "orbit2_check_finite")
 
 
@@ -561,7 +635,7 @@ def selftest(device="cuda") -> int:
 
 def droppath_scales(B, p, seed, device):
     out = torch.empty(B, dtype=F32, device=device)
-    _chk(lib().orbit2_droppath_scales(_p(out), B, C.c_float(p), C.c_uint64(seed), _stream()), "orbit2_droppath_scales")
+    _chk(lib().orbit2_droppath_scales(_p(out), B, p, seed, _stream()), "orbit2_droppath_scales")
     return out
 
 
@@ -614,7 +688,7 @@ def lpips_conv1_bwd(dz, w1, pred, target, l1_coef, gscale=None):
     N, _, H, W = pred.shape
     dimg = torch.empty_like(pred)
     gs = None if gscale is None else _p(_dev(gscale, F32, "gscale"))
-    _chk(lib().orbit2_lpips_conv1_bwd(_p(dz), _p(w1), _p(pred), _p(target), C.c_float(l1_coef), gs, _p(dimg), N, H, W,
+    _chk(lib().orbit2_lpips_conv1_bwd(_p(dz), _p(w1), _p(pred), _p(target), l1_coef, gs, _p(dimg), N, H, W,
                                       _stream()), "orbit2_lpips_conv1_bwd")
     return dimg
 
@@ -629,15 +703,15 @@ def lpips_tap_bwd(feats, lin, coef, B, HW, Cc, gscale=None):
     _dev(feats, BF, "feats"); _dev(lin, F32, "lin")
     g = torch.empty(B * HW, Cc, dtype=BF, device=feats.device)
     gs = None if gscale is None else _p(_dev(gscale, F32, "gscale"))
-    _chk(lib().orbit2_lpips_tap_bwd(_p(feats), _p(lin), _p(g), C.c_float(coef), gs, B, HW, Cc, _stream()),
+    _chk(lib().orbit2_lpips_tap_bwd(_p(feats), _p(lin), _p(g), coef, gs, B, HW, Cc, _stream()),
          "orbit2_lpips_tap_bwd")
     return g
 
 
 def l1_mean(a, b, out):
     _dev(a, F32, "a"); _dev(b, F32, "b"); _dev(out, F32, "out")
-    ws = _ws(lib().orbit2_l1_mean_ws_floats, (C.c_int64(a.numel()),), a.device)
-    _chk(lib().orbit2_l1_mean(_p(a), _p(b), _p(out), C.c_int64(a.numel()), _p(ws), _stream()), "orbit2_l1_mean")
+    ws = _ws(lib().orbit2_l1_mean_ws_floats, (a.numel(),), a.device)
+    _chk(lib().orbit2_l1_mean(_p(a), _p(b), _p(out), a.numel(), _p(ws), _stream()), "orbit2_l1_mean")
 
 
 def eval_moments(pred, target, lat_w=None, clim=None):
@@ -656,4 +730,4 @@ def eval_moments(pred, target, lat_w=None, clim=None):
 
 def seed_salt(value: int, add: bool = False):
     """device-side salt xored into every kernel seed (see include/orbit2_hip.h:orbit2_seed_salt); stream-ordered"""
-    _chk(lib().orbit2_seed_salt(C.c_uint64(value & 0xFFFFFFFFFFFFFFFF), int(add), _stream()), "orbit2_seed_salt")
+    _chk(lib().orbit2_seed_salt(value, int(add), _stream()), "orbit2_seed_salt")

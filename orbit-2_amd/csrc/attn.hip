@@ -1684,7 +1684,7 @@ static int attn_check(const void* a, const void* b, int B, int L, int H, int d, 
 
 // waves per workgroup: 8 (256-row tiles, K/V or Q/dO tiles shared by twice the waves) whenever the sequence has at least
 // one such tile and the kernel fits two waves per SIMD (d = 64, 128); ORBIT2_ATTN_4WAVES keeps the round-1 geometry (A/B).
-// The variant is an ARGUMENT of the *_ex entry points (no process-global switch: a forward / backward pair cannot disagree
+// The variant is an ARGUMENT of the entry points (no process-global switch: a forward / backward pair cannot disagree
 // behind the caller's back, nothing is read from the environment on the launch path).
 static int attn_waves(int L, int d, int flags) {
   if (d == 256 || L < 256) return 4;
@@ -1713,16 +1713,6 @@ static void launch_fwd_r(bool ragged, const void* qkv, void* out, float* lse, in
                          float dscale, uint64_t seed, hipStream_t s, int ldo, int ldq) {
   if (ragged) launch_fwd<DV, DR, true, NW>(qkv, out, lse, B, L, H, sc_log2, thr, dscale, seed, s, ldo, ldq);
   else launch_fwd<DV, DR, false, NW>(qkv, out, lse, B, L, H, sc_log2, thr, dscale, seed, s, ldo, ldq);
-}
-
-extern "C" int orbit2_attn_fwd(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
-                               uint64_t seed, void* stream) {
-  return orbit2_attn_fwd_ex(qkv, out, lse, B, L, H, d, drop_p, seed, 0, stream);
-}
-
-extern "C" int orbit2_attn_fwd_ex(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
-                                  uint64_t seed, int flags, void* stream) {
-  return orbit2_attn_fwd_ld(qkv, out, lse, B, L, H, d, drop_p, seed, flags, 3 * H * d, H * d, stream);
 }
 
 extern "C" int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
@@ -1814,17 +1804,6 @@ static int attn_lpad(int L) { return ((L + 63) / 64) * 64 + 64; }     // padded 
 extern "C" int64_t orbit2_attn_bwd_ws_floats(int B, int L, int H) {
   if (B <= 0 || L <= 0 || H <= 0) return 0;
   return (int64_t)2 * B * H * attn_lpad(L);
-}
-
-extern "C" int orbit2_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
-                               void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, void* stream) {
-  return orbit2_attn_bwd_ex(qkv, out, dout, lse, delta, dqkv, B, L, H, d, drop_p, seed, 0, stream);
-}
-
-extern "C" int orbit2_attn_bwd_ex(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
-                                  void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags,
-                                  void* stream) {
-  return orbit2_attn_bwd_ld(qkv, out, dout, lse, delta, dqkv, B, L, H, d, drop_p, seed, flags, 3 * H * d, H * d, stream);
 }
 
 extern "C" int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,

@@ -1590,8 +1590,3 @@ extern "C" int orbit2_sgemm_f32_ws(const float* A, const float* B, float* C, int
   }
   return O2_OK;
 }
-
-extern "C" int orbit2_sgemm_f32(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
-                                int ta, int tb, float alpha, float beta, void* stream) {
-  return orbit2_sgemm_f32_ws(A, B, C, M, N, K, lda, ldb, ldc, ta, tb, alpha, beta, nullptr, 0, stream);
-}

@@ -691,11 +691,6 @@ inline int grid_for(int64_t work_items, int per_block) {
     else { CALL(16); }                    \
   } while (0)
 
-extern "C" int orbit2_layernorm_fwd(const void* x, const void* gamma, const void* beta, void* y, float* mean,
-                                    float* rstd, int rows, int D, float eps, void* stream) {
-  return orbit2_layernorm_fwd_ld(x, gamma, beta, y, mean, rstd, rows, D, D, eps, stream);
-}
-
 extern "C" int orbit2_layernorm_fwd_ld(const void* x, const void* gamma, const void* beta, void* y, float* mean,
                                        float* rstd, int rows, int D, int ldy, float eps, void* stream) {
   if (!x || !gamma || !beta || !y || !mean || !rstd || rows <= 0 || D <= 0 || (D & 7) || D > LN_MAXD || ldy < D || (ldy & 7))

@@ -1,23 +1,132 @@
-"""CPU checks of the C-ABI library: it builds, loads, and exports every symbol include/orbit2_hip.h declares."""
+"""CPU checks of the C-ABI library: it builds, loads, exports exactly what include/orbit2_hip.h declares, and climate_learn._hip
+declares every prototype the way the header does."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
+
+import pytest
 
 from tests.conftest import ROOT
 
+HEADER = os.path.join(ROOT, "include", "orbit2_hip.h")
+# the forwarding entries ABI 7 removed: each was a one-line call of the entry that replaced it
+REMOVED = ("orbit2_attn_fwd", "orbit2_attn_fwd_ex", "orbit2_attn_bwd", "orbit2_attn_bwd_ex", "orbit2_layernorm_fwd",
+           "orbit2_sgemm_f32")
 
-def test_library_exports_every_declared_symbol():
+
+def _header():
+    """the header without its comments"""
+    return re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(HEADER).read(), flags=re.S)
+
+
+def _kind(param):
+    """the parameter kind of one C parameter declaration: int, int64_t, uint64_t, float, void* or orbit2_gemm_args*"""
+    decl = " ".join(param.split())
+    if "*" in decl:
+        return "orbit2_gemm_args*" if "orbit2_gemm_args" in decl else "void*"
+    kind = decl.rsplit(" ", 1)[0]
+    assert kind in ("int", "int64_t", "uint64_t", "float"), "unexpected parameter kind: " + param
+    return kind
+
+
+def _prototypes():
+    """name -> (return kind, argument kinds) of every orbit2_* prototype of the header"""
+    protos = {}
+    for ret, name, params in re.findall(r"\b(int|int64_t)\s+(orbit2_\w+)\s*\(([^)]*)\)\s*;", _header()):
+        assert name not in protos, "declared twice: " + name
+        params = params.strip()
+        protos[name] = (ret, tuple(_kind(p) for p in params.split(",")) if params not in ("", "void") else ())
+    return protos
+
+
+def _exports(path):
+    """the orbit2_* functions the library defines in its dynamic symbol table"""
+    readelf = shutil.which("llvm-readelf") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-readelf")
+    out = subprocess.run([readelf, "--dyn-syms", "-W", path], capture_output=True, text=True, check=True).stdout
+    rows = [line.split() for line in out.splitlines()]        # Num: Value Size Type Bind Vis Ndx Name
+    return {r[7] for r in rows if len(r) >= 8 and r[3] == "FUNC" and r[6] != "UND" and r[7].startswith("orbit2_")}
+
+
+def test_library_exports_exactly_the_declared_symbols():
     import __graft_entry__ as ge
     ge.build()
     from climate_learn import _hip
     assert os.path.exists(_hip.LIB_PATH)
     lib = ctypes.CDLL(_hip.LIB_PATH)
-    hdr = open(os.path.join(ROOT, "include", "orbit2_hip.h")).read()
+    hdr = open(HEADER).read()
     names = sorted(set(re.findall(r"\b(?:int|int64_t)\s+(orbit2_\w+)\s*\(", hdr)))
     assert len(names) >= 25
     for n in names:
         assert hasattr(lib, n), "missing export " + n
-    assert lib.orbit2_abi_version() == 6
+    assert lib.orbit2_abi_version() == 7
+    # ... and the other way: the library exports nothing the header does not declare, none of the removed entries among it
+    exported = _exports(_hip.LIB_PATH)
+    assert exported == set(_prototypes()), "exported, not declared: %s; declared, not exported: %s" % (
+        sorted(exported - set(_prototypes())), sorted(set(_prototypes()) - exported))
+    for n in REMOVED:
+        assert n not in exported and n not in names and not hasattr(lib, n)
+
+
+def test_binding_declares_every_prototype_as_the_header_does():
+    from climate_learn import _hip
+    kinds = {ctypes.c_int: "int", ctypes.c_int64: "int64_t", ctypes.c_uint64: "uint64_t", ctypes.c_float: "float",
+             ctypes.c_void_p: "void*", ctypes.POINTER(_hip.GemmArgs): "orbit2_gemm_args*"}
+    header = _prototypes()
+    assert len(header) >= 50
+    assert set(_hip.PROTOTYPES) == set(header)
+    for name, (restype, argtypes) in _hip.PROTOTYPES.items():
+        assert (kinds[restype], tuple(kinds[a] for a in argtypes)) == header[name], name
+    # and load() applied exactly that table to the library the package uses
+    lib = _hip.lib()
+    for name, (restype, argtypes) in _hip.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and tuple(fn.argtypes) == tuple(argtypes), name
+
+
+def test_binding_constants_match_the_header():
+    from climate_learn import _hip
+    defines = dict(re.findall(r"^#define\s+ORBIT2_(\w+)\s+(\d+)", _header(), flags=re.M))
+    assert int(defines["ABI_VERSION"]) == _hip.ABI_VERSION == 7
+    assert int(defines["GEMM_MAX_GROUP"]) == _hip.GEMM_MAX_GROUP
+    flags = {k: int(v) for k, v in defines.items() if k.startswith("ATTN_")}
+    assert flags and flags == {k: getattr(_hip, k) for k in dir(_hip) if k.startswith("ATTN_")}
+    assert _hip.lib().orbit2_abi_version() == 7
+
+
+def test_load_refuses_another_abi_version(tmp_path):
+    from climate_learn import _hip
+    with pytest.raises(_hip.HipBackendError, match="not found"):
+        _hip.load(str(tmp_path / "liborbit2_hip.so"))
+    # a shared object of no version at all (ctypes' own extension module has no orbit2_abi_version) is refused before use
+    import _ctypes
+    with pytest.raises(_hip.HipBackendError, match="ABI version None"):
+        _hip.load(_ctypes.__file__)
+
+
+def test_mistyped_calls_never_reach_the_library():
+    """host-only entries that launch nothing: a call with too few arguments or an argument of the wrong kind is refused by
+    ctypes; the int64_t queries return int64_t whatever ran before them"""
+    import torch
+    from climate_learn import _hip
+    lib = _hip.lib()
+    assert lib.orbit2_colsum_ws_floats(1024, 64) > 0
+    assert lib.orbit2_attn_bwd_ws_floats(64, 1 << 20, 64) == 2 * 64 * 64 * ((1 << 20) + 64)      # > 2^31: needs the int64_t
+    with pytest.raises(TypeError):
+        lib.orbit2_colsum_ws_floats(1024)
+    with pytest.raises(TypeError):
+        lib.orbit2_attn_bwd_ws_floats(2, 1024)
+    with pytest.raises(TypeError):
+        lib.orbit2_gemm_bf16_colsum_rows()
+    with pytest.raises(ctypes.ArgumentError):
+        lib.orbit2_colsum_ws_floats(1024.0, 64)                      # a float for an int
+    with pytest.raises(ctypes.ArgumentError):
+        lib.orbit2_attn_bwd_ws_floats(2, 1024, 16.5)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.orbit2_gemm_bf16_colsum_rows(torch.zeros(46))             # a tensor for a pointer
+    with pytest.raises(ctypes.ArgumentError):
+        lib.orbit2_gemm_bf16_colsum_rows(0x10000)                     # an address for the argument block
 
 
 def test_gemm_args_struct_matches_header():

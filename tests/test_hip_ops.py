@@ -619,7 +619,7 @@ def test_attention_fwd_bwd(hip, d, H, L, B, p):
 def test_attention_dkv_one_pass_equals_two_passes(hip, d, L, p):
     """dK and dV come from ONE pass at d = 128 (>= 256 tokens: V rows in LDS, csrc/attn.hip attn_bwd_dkv128_kernel) and -- round
     3 -- at d = 256 (attn_bwd_dkv256_kernel: 32-row query tiles, one wave per SIMD); the two-pass kernels stay selectable
-    (flag ORBIT2_ATTN_SPLIT_DKV of orbit2_attn_bwd_ex) and must give the same bits -- odd tile counts (the pair loop's last
+    (flag ORBIT2_ATTN_SPLIT_DKV of orbit2_attn_bwd_ld) and must give the same bits -- odd tile counts (the pair loop's last
     tile is past the end) and ragged tails included"""
     B, H = 2, (3 if d == 128 else 2)
     g = torch.Generator().manual_seed(L)
@@ -1067,7 +1067,7 @@ def test_posembed_table_forward_backward(hip, oh, nh, D):
 
 def test_posembed_argument_checks(hip):
     x = torch.zeros(8 * 16, 6, device="cuda")
-    assert hip.lib().orbit2_posembed_fwd(hip._p(x), None, None, hip.C.c_float(0.0), hip._p(x), 8, 16, 8, 16, 6, None) == -1   # D % 4
+    assert hip.lib().orbit2_posembed_fwd(hip._p(x), None, None, 0.0, hip._p(x), 8, 16, 8, 16, 6, None) == -1   # D % 4
     y = torch.zeros(8 * 16, 8, device="cuda")
-    assert hip.lib().orbit2_posembed_fwd(hip._p(y), hip._p(y), None, hip.C.c_float(0.0), hip._p(y), 8, 16, 8, 16, 8, None) == -1  # sw without sb
+    assert hip.lib().orbit2_posembed_fwd(hip._p(y), hip._p(y), None, 0.0, hip._p(y), 8, 16, 8, 16, 8, None) == -1  # sw without sb
     assert hip.lib().orbit2_posembed_bwd(hip._p(y), hip._p(y), 8, 16, 8, 12, 8, None) == -1       # same height, other width

@@ -1,4 +1,4 @@
-"""A/B of attention-backward variants selected by the flags argument of orbit2_attn_bwd_ex (include/orbit2_hip.h):
+"""A/B of attention-backward variants selected by the flags argument of orbit2_attn_bwd_ld (include/orbit2_hip.h):
     python tools/attn_bwd_ab.py flags=2 [--batch B]        (2 = ORBIT2_ATTN_SPLIT_DKV, 1 = ORBIT2_ATTN_4WAVES)
 runs the default build and the build with the given switches interleaved on the interm_1b shape (and a ragged and a d = 64
 shape for equality), prints the largest deviation of dQ/dK/dV between the two and the median times."""

@@ -1,23 +1,23 @@
 """Same-box, same-process A/B of two builds of the attention kernels:
     tools/ab_build.sh <git-rev> <name>;   on the GPU box:  python tools/attn_lib_ab.py orbit-2_amd/lib/alt/<name>.so [B]
-loads the working-tree library and the other build side by side (ctypes), checks that forward and backward agree and times
+loads the working-tree library and the other build (of the same ABI version: _hip.load) side by side, checks that forward and backward agree and times
 them interleaved (median of 5 rounds of 4 launches) at the interm_1b shape and at d = 64 / d = 256."""
-import ctypes as C, os, sys
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "orbit-2_amd")]
 import torch
 from climate_learn import _hip
 
-alt = C.CDLL(os.path.abspath(sys.argv[1]))
+alt = _hip.load(os.path.abspath(sys.argv[1]))
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 BF, F32 = torch.bfloat16, torch.float32
-P = lambda t: C.c_void_p(t.data_ptr())
-S = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+P = lambda t: t.data_ptr()
+S = lambda: torch.cuda.current_stream().cuda_stream
 
 def fwd(lib, qkv, out, lse, Bx, L, H, d, p):
-    assert lib.orbit2_attn_fwd(P(qkv), P(out), P(lse), Bx, L, H, d, C.c_float(p), C.c_uint64(11), S()) == 0
+    assert lib.orbit2_attn_fwd_ld(P(qkv), P(out), P(lse), Bx, L, H, d, p, 11, 0, 3 * H * d, H * d, S()) == 0
 def bwd(lib, qkv, out, do, lse, delta, dqkv, Bx, L, H, d, p):
-    assert lib.orbit2_attn_bwd(P(qkv), P(out), P(do), P(lse), P(delta), P(dqkv), Bx, L, H, d, C.c_float(p), C.c_uint64(11), S()) == 0
+    assert lib.orbit2_attn_bwd_ld(P(qkv), P(out), P(do), P(lse), P(delta), P(dqkv), Bx, L, H, d, p, 11, 0, 3 * H * d, H * d, S()) == 0
 def t(f, n=4):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()

@@ -1,4 +1,4 @@
-"""8-wave (256-row workgroups, default) vs 4-wave (flag ORBIT2_ATTN_4WAVES of the *_ex entries, the round-1 geometry) attention kernels: equality of
+"""8-wave (256-row workgroups, default) vs 4-wave (flag ORBIT2_ATTN_4WAVES of the attention entries, the round-1 geometry) attention kernels: equality of
 the results (the per-wave arithmetic is the same: bit-identical) and interleaved timing at the interm_1b / interm_117m shapes."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -4,7 +4,7 @@ n K-tiles (`kwrap=n`: same MFMAs, LDS reads and LDS-DMA pieces; the panels come 
   python tools/dw_traffic_ab.py base.so kwrap8.so kwrap2.so          interleaved timing: the Block's four dW products at batch 16
   python tools/dw_traffic_ab.py --pmc                                 workload of one rocprofv3 --pmc pass (library = $ORBIT2_HIP_LIB)
 Record: profiles/r06_dw_traffic_clock.txt (tools/dw_traffic.sh)."""
-import ctypes as C, os, sys
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "orbit-2_amd")]
 import torch
@@ -40,7 +40,7 @@ if "--pmc" in sys.argv:
 
 paths = [a for a in sys.argv[1:] if a.endswith(".so")]
 SINGLE = "--no-single" not in sys.argv
-libs = [(os.path.basename(p).replace(".so", ""), C.CDLL(os.path.abspath(p))) for p in paths]
+libs = [(os.path.basename(p).replace(".so", ""), _hip.load(os.path.abspath(p))) for p in paths]
 probs, fl = problems()
 res = {n: [] for n, _ in libs}
 for rnd in range(5):

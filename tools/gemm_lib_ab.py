@@ -8,11 +8,11 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "orbit-2_amd")]
 import torch
 from climate_learn import _hip
 
-alt = C.CDLL(os.path.abspath(sys.argv[1]))
+alt = _hip.load(os.path.abspath(sys.argv[1]))
 check = "--nocheck" not in sys.argv
 libs = {"tree": _hip.lib(), "alt": alt}
 BF = torch.bfloat16
-S = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+S = lambda: torch.cuda.current_stream().cuda_stream
 def t(f, n=3):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()

@@ -1,13 +1,13 @@
 """Times the 4-wave GEMM kernel (tile hint 260) of SEVERAL builds of the library in one process, interleaved rounds
 (schedule variants built by tools/mkvar_w4.sh into orbit-2_amd/lib/alt/):  python tools/gemm_multi_ab.py lib1.so lib2.so ...
 The first library is the reference for the bitwise comparison."""
-import ctypes as C, os, sys
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "orbit-2_amd")]
 import torch
 from climate_learn import _hip
 paths = [a for a in sys.argv[1:] if a.endswith(".so")]
-libs = [(os.path.basename(p).replace(".so", ""), C.CDLL(os.path.abspath(p))) for p in paths]
+libs = [(os.path.basename(p).replace(".so", ""), _hip.load(os.path.abspath(p))) for p in paths]
 r = lambda *s: (torch.randn(*s, device="cuda") * 0.5).to(torch.bfloat16)
 def t(f, n=5):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -1,11 +1,11 @@
 """LayerNorm backward of the Block (131072 x 3072, with the residual stream's gradient fused) on two builds of the library,
 interleaved: lib/alt/ln0.so (-DO2_LN_FMA=0: the expressions of rounds 2-5) against the product; bytes moved = 4 tensors."""
-import ctypes as C, os, sys
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "orbit-2_amd")]
 import torch
 from climate_learn import _hip
-libs = [("ln0", C.CDLL(os.path.join(ROOT, "orbit-2_amd", "lib", "alt", "ln0.so"))), ("product", C.CDLL(_hip.LIB_PATH))]
+libs = [("ln0", _hip.load(os.path.join(ROOT, "orbit-2_amd", "lib", "alt", "ln0.so"))), ("product", _hip.lib())]
 M, D = 131072, 3072
 x = torch.randn(M, D, device="cuda").bfloat16(); dy = torch.randn(M, D, device="cuda").bfloat16(); dres = torch.randn(M, D, device="cuda").bfloat16()
 g = torch.randn(D, device="cuda").bfloat16(); b = torch.randn(D, device="cuda").bfloat16()

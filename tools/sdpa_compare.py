@@ -1,5 +1,5 @@
 """Reference measurement only: the framework's fused attention (torch SDPA -> AOTriton / CK flash on ROCm) on the
-interm_1b attention shape, beside orbit2_attn_{fwd,bwd}.  The product path never calls SDPA."""
+interm_1b attention shape, beside orbit2_attn_{fwd,bwd}_ld.  The product path never calls SDPA."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "orbit-2_amd")]
