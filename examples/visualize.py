@@ -52,6 +52,14 @@ def main():
         print("load pretrained model", tr["pretrain"], flush=True)
         cl.utils.load_pretrained_weights(model, str(tr["pretrain"]), verbose=True)
     model = model.to(device).eval()
+    # trainer.data_type (the reference's examples/intermediate_downscaling.py:593-607): float32 = the fp32 forward kernels,
+    # bfloat16 (or absent) = the bf16 ones
+    data_type = tr.get("data_type", "bfloat16")
+    if data_type == "float32":
+        model.set_compute_dtype(torch.float32)
+    elif data_type != "bfloat16":
+        raise RuntimeError("Data type not supported")
+    print("compute_dtype", model.compute_dtype, flush=True)
     model.data_config(dc["spatial_resolution"][data_key], model.img_size, len(in_vars), len(out_vars))
     denorm = test_transforms[0]
     variable = "total_precipitation_24hr" if "total_precipitation_24hr" in out_vars else out_vars[0]

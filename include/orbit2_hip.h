@@ -26,6 +26,9 @@ extern "C" {
 #endif
 
 #define ORBIT2_ABI_VERSION 7
+/* The fp32 forward entries (orbit2_gemm_f32, orbit2_attn_fwd_f32, orbit2_layernorm_fwd_f32, orbit2_varagg_fwd_f32,
+ * orbit2_unpatchify_fwd_f32) were ADDED at version 7: no existing entry, structure or constant changed, so the number stays.  A
+ * binding that declares them refuses an older build of version 7 by name ("lacks orbit2_gemm_f32, ..."). */
 int orbit2_abi_version(void);
 
 /* ---- bf16 MFMA GEMM with fused epilogue ------------------------------------------------
@@ -78,6 +81,18 @@ typedef struct {
 int orbit2_gemm_bf16(const orbit2_gemm_args* args, void* stream);
 int orbit2_gemm_bf16_colsum_rows(const orbit2_gemm_args* args);   /* 0: this call cannot fuse the column sums (colsum_ws must be NULL) */
 
+/* ---- fp32 GEMM with fused epilogue (the fp32 forward path) ---------------------------------
+ * The same argument block with EVERY tensor pointer (A, B, C, bias, residual) read as fp32; out_fp32 must be 1.  fp32 operands,
+ * fp32 accumulate on v_mfma_f32_32x32x2_f32 (every product rounded once; the contraction is summed within groups of 8 in the order
+ * 0, 4, 1, 5, 2, 6, 3, 7), fp32 out.  Replaces the same nn.Linear forwards as orbit2_gemm_bf16 when the reference runs with
+ * trainer.data_type: float32 (examples/intermediate_downscaling.py:593-607; examples/visualize.py:251 hard-codes it): attention.py:36,40,
+ * 50,81; mlp.py:50,54,63,67; res_slimvit.py:115-120,326; attention.py:129,177.  B is the fp32 master weight [N][ldb] as stored.
+ * Implemented: a_kc = b_kc = 1; any M; N, K, lda, ldb, ldc % 4 == 0; 16-byte aligned bases; bias, colscale / colscale_n (% 4), act 0 / 1,
+ * residual with ldr / res_mod / res_first, beta; tile_hint 0 (auto), 64 (64 x 64 tiles), 128 (128 x 128 tiles).
+ * Everything else (other operand forms, drop_p != 0, save_pre, save_dact, mul, dgelu_pre, rowscale, colsum_ws, act 2, out_fp32 = 0,
+ * other tile_hint values) returns O2_ERR_UNSUPPORTED (-3) before any launch. */
+int orbit2_gemm_f32(const orbit2_gemm_args* args, void* stream);
+
 /* n (<= ORBIT2_GEMM_MAX_GROUP) independent problems of ONE operand form (same a_kc, b_kc) in one launch (the 256x256
  * 8-phase kernel when every problem has K % 64 == 0, M, N >= 256 and the group fills the chip; the 128x128 kernel
  * otherwise): the partially filled last round of each problem is filled with the next one's tiles.  Used for
@@ -105,6 +120,10 @@ int orbit2_sgemm_f32_ws(const float* A, const float* B, float* C, int M, int N, 
  * rows a multiple of 8 KiB apart (D % 4096 == 0: interm_10b) put every row's k-offset on one memory channel */
 int orbit2_layernorm_fwd_ld(const void* x, const void* gamma, const void* beta, void* y, float* mean, float* rstd,
                             int rows, int D, int ldy, float eps, void* stream);
+/* the same with fp32 x, gamma, beta, y (vit_blocks.py:46,63; res_slimvit.py:104,294 under data_type float32): D, ldy % 4 == 0,
+ * two-pass variance; mean / rstd may be NULL (nothing reads them without a backward) */
+int orbit2_layernorm_fwd_f32(const void* x, const void* gamma, const void* beta, void* y, float* mean, float* rstd,
+                             int rows, int D, int ldy, float eps, void* stream);
 /* dx = LN'(dy) [+ dres];  dgamma/dbeta: bf16 or fp32 [D] (beta_acc accumulates).  ws: fp32 >= 2*D*nblk */
 int orbit2_layernorm_bwd(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
                          const void* dres, void* dx, void* dgamma, void* dbeta, int grads_fp32, float beta_acc,
@@ -141,6 +160,12 @@ int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B, int L, int
                        uint64_t seed, int flags, int ldq, int ldo, void* stream);
 int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                        void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq, int ldo, void* stream);
+/* orbit2_attn_fwd_ld with fp32 qkv / out (attention.py:54-78 under data_type float32, components/attention.py:66-70): streaming
+ * softmax in fp32, both products on v_mfma_f32_32x32x2_f32.  ldq, ldo % 4 == 0.  No dropout: drop_p != 0 returns
+ * O2_ERR_UNSUPPORTED, as does any flag other than ORBIT2_ATTN_Q_PRESCALED (honoured as above: without it the kernel multiplies
+ * q by log2(e)/sqrt(d) in fp32 when it loads it). */
+int orbit2_attn_fwd_f32(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
+                        uint64_t seed, int flags, int ldq, int ldo, void* stream);
 
 /* ---- folded patch-embed + variable aggregation (res_slimvit.py:250-265, 205-230;
  *      patch_embed.py:44-52; attention.py:132-176) ---------------------------------------------
@@ -149,6 +174,9 @@ int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* dout, const
  * attw: fp32 [B*L, H, V] softmax weights saved for backward.  patch must be 2. */
 int orbit2_varagg_fwd(const float* x, const float* stab, const float* gtab, void* z, float* attw, int B, int V,
                       int h, int w, int H, int D, void* stream);
+/* the same forward with z written as fp32 [B*L, D] (the fp32 forward path; same reference lines); attw may be NULL */
+int orbit2_varagg_fwd_f32(const float* x, const float* stab, const float* gtab, float* z, float* attw, int B, int V,
+                          int h, int w, int H, int D, void* stream);
 /* dstab/dgtab are ACCUMULATED into (caller zeroes them).  ws: fp32 workspace of orbit2_varagg_bwd_ws_floats(...) floats (ABI 4):
  * every (head, token range) workgroup stores its partial tables in its own slab and the ranges are added in a fixed order --
  * no float atomics, bitwise reproducible. */
@@ -213,6 +241,8 @@ int orbit2_posembed_bwd(const float* dout, float* dpe, int oh, int ow, int nh, i
 /* ---- hi-res tail -------------------------------------------------------------------------- */
 /* unpatchify (res_slimvit.py:167-179): t bf16 [B, L, C*(s*p)^2] -> img [B, C, h*s, w*s] (fp32) */
 int orbit2_unpatchify_fwd(const void* t, float* img, int B, int C, int h, int w, int p, int s, void* stream);
+/* the same with t fp32 (res_slimvit.py:167-179 under data_type float32) */
+int orbit2_unpatchify_fwd_f32(const float* t, float* img, int B, int C, int h, int w, int p, int s, void* stream);
 int orbit2_unpatchify_bwd(const float* dimg, void* dt, int B, int C, int h, int w, int p, int s, void* stream);
 /* 3x3 conv, stride 1, zero pad 1 (res_slimvit.py:108,111,122).  in: fp32 [B,Cin,H,W] gathered through
  * chan_idx (NULL = identity; res_slimvit.py:237 channel gather); weight fp32 [Cout,Cin,3,3]; bias [Cout].

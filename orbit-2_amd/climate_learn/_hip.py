@@ -58,16 +58,20 @@ PROTOTYPES = {
     "orbit2_abi_version": (_I, ()),
     "orbit2_gemm_bf16": (_I, (_G, _P)),
     "orbit2_gemm_bf16_colsum_rows": (_I, (_G,)),
+    "orbit2_gemm_f32": (_I, (_G, _P)),
     "orbit2_gemm_bf16_grouped": (_I, (_G, _I, _P)),
     "orbit2_sgemm_f32_ws_floats": (_I64, (_I, _I, _I)),
     "orbit2_sgemm_f32_ws": (_I, (_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _I64, _P)),
     "orbit2_layernorm_fwd_ld": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P)),
+    "orbit2_layernorm_fwd_f32": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P)),
     "orbit2_layernorm_bwd": (_I, (_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P, _I, _I, _I, _P)),
     "orbit2_layernorm_bwd_ws_floats": (_I, (_I, _I)),
     "orbit2_attn_bwd_ws_floats": (_I64, (_I, _I, _I)),
     "orbit2_attn_fwd_ld": (_I, (_P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P)),
+    "orbit2_attn_fwd_f32": (_I, (_P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P)),
     "orbit2_attn_bwd_ld": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P)),
     "orbit2_varagg_fwd": (_I, (_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P)),
+    "orbit2_varagg_fwd_f32": (_I, (_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P)),
     "orbit2_varagg_bwd_ws_floats": (_I64, (_I, _I, _I, _I, _I, _I)),
     "orbit2_varagg_bwd": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P)),
     "orbit2_tables_gather": (_I, (_P, _I64, _P, _I64, _P, _P, _P, _I, _I, _P)),
@@ -87,6 +91,7 @@ PROTOTYPES = {
     "orbit2_posembed_fwd": (_I, (_P, _P, _P, _F, _P, _I, _I, _I, _I, _I, _P)),
     "orbit2_posembed_bwd": (_I, (_P, _P, _I, _I, _I, _I, _I, _P)),
     "orbit2_unpatchify_fwd": (_I, (_P, _P, _I, _I, _I, _I, _I, _I, _P)),
+    "orbit2_unpatchify_fwd_f32": (_I, (_P, _P, _I, _I, _I, _I, _I, _I, _P)),
     "orbit2_unpatchify_bwd": (_I, (_P, _P, _I, _I, _I, _I, _I, _I, _P)),
     "orbit2_conv3x3_fwd": (_I, (_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P)),
     "orbit2_conv3x3_bwd_ws_floats": (_I64, (_I, _I, _I, _I, _I)),
@@ -253,6 +258,34 @@ def gemm(A, B, out, M, N, K, lda, ldb, ldc, want_colsum=False, **kw):
     return (out, parts) if want_colsum else out
 
 
+def gemm_f32(A, B, out, M, N, K, lda, ldb, ldc, bias=None, act=0, residual=None, ldr=0, res_mod=0, res_first=False, beta=0.0,
+             tile=0, colscale=None):
+    """out[M,N] = epilogue(A x B^T) in fp32 (include/orbit2_hip.h:orbit2_gemm_f32): A [M][lda], B [N][ldb] the fp32 weight as
+    stored, every tensor fp32; forward form and forward epilogue only"""
+    for t, nm in ((A, "A"), (B, "B"), (out, "out")):
+        _dev_rows(t, F32, nm)
+    a = GemmArgs()
+    a.A, a.B, a.C = A.data_ptr(), B.data_ptr(), out.data_ptr()
+    a.M, a.N, a.K, a.lda, a.ldb, a.ldc = M, N, K, lda, ldb, ldc
+    a.a_kc = a.b_kc = 1
+    a.bias = None if bias is None else _dev(bias, F32, "bias").data_ptr()
+    a.act = act
+    a.residual = None if residual is None else _dev_rows(residual, F32, "residual").data_ptr()
+    a.ldr, a.res_mod, a.res_first = ldr, res_mod, int(res_first)
+    a.out_fp32 = 1
+    a.beta = float(beta)
+    a.tile_hint = int(tile)
+    a.colscale_n, a.colscale = (0, 1.0) if colscale is None else (int(colscale[0]), float(colscale[1]))
+    if timer is not None:
+        e0, e1 = timer.span("gemm_f32", 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N))
+        e0.record()
+        _chk(lib().orbit2_gemm_f32(C.byref(a), _stream()), "orbit2_gemm_f32")
+        e1.record()
+    else:
+        _chk(lib().orbit2_gemm_f32(C.byref(a), _stream()), "orbit2_gemm_f32")
+    return out
+
+
 GEMM_MAX_GROUP = 12
 
 
@@ -299,6 +332,20 @@ def layernorm_fwd(x, gamma, beta, eps=1e-5, out=None):
     _chk(lib().orbit2_layernorm_fwd_ld(_p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, D, ldy, eps,
                                        _stream()), "orbit2_layernorm_fwd_ld")
     return y, mean, rstd
+
+
+def layernorm_fwd_f32(x, gamma, beta, eps=1e-5, out=None, stats=False):
+    """fp32 LayerNorm (orbit2_layernorm_fwd_f32); returns y, or (y, mean, rstd) with stats=True"""
+    _dev(x, F32, "x"); _dev(gamma, F32, "gamma"); _dev(beta, F32, "beta")
+    D = x.shape[-1]
+    rows = x.numel() // D
+    y = torch.empty_like(x) if out is None else _dev_rows(out, F32, "out")
+    ldy = D if out is None else y.stride(0)
+    mean = torch.empty(rows, dtype=F32, device=x.device) if stats else None
+    rstd = torch.empty(rows, dtype=F32, device=x.device) if stats else None
+    _chk(lib().orbit2_layernorm_fwd_f32(_p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, D, ldy, eps,
+                                        _stream()), "orbit2_layernorm_fwd_f32")
+    return (y, mean, rstd) if stats else y
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, beta_acc=0.0):
@@ -366,6 +413,27 @@ def attn_fwd(qkv, B, L, H, d, drop_p=0.0, seed=0, flags=0, out=None):
     return out, lse
 
 
+def attn_fwd_f32(qkv, B, L, H, d, drop_p=0.0, flags=0, out=None):
+    """fp32 attention core (orbit2_attn_fwd_f32): qkv fp32 [B * L, 3 * H * d] (any token-row pitch) or contiguous
+    [B, L, 3, H, d]; returns (out [B, L, H * d] fp32 or the given `out`, lse [B, H, L])"""
+    _dev_rows(qkv, F32, "qkv")
+    ldq = qkv.stride(0) if qkv.dim() == 2 else 3 * H * d
+    if out is None:
+        out, ldo = torch.empty(B, L, H * d, dtype=F32, device=qkv.device), H * d
+    else:
+        out = _dev_rows(out, F32, "out")
+        ldo = out.stride(0)
+    lse = torch.empty(B, H, L, dtype=F32, device=qkv.device)
+    if timer is not None:
+        e0, e1 = timer.span("attn_fwd_f32", 4.0 * B * H * L * L * d, 4.0 * 4 * B * L * H * d + 4.0 * B * H * L)
+        e0.record()
+    _chk(lib().orbit2_attn_fwd_f32(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, 0, int(flags), int(ldq), int(ldo),
+                                   _stream()), "orbit2_attn_fwd_f32")
+    if timer is not None:
+        e1.record()
+    return out, lse
+
+
 def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0):
     _dev_rows(qkv, BF, "qkv"); _dev_rows(out, BF, "out"); _dev(dout, BF, "dout"); _dev(lse, F32, "lse")
     ldo = out.stride(0) if out.dim() == 2 else H * d           # [B * L, H * d] with a token-row pitch, or contiguous [B, L, H * d]
@@ -395,6 +463,18 @@ def varagg_fwd(x, stab, gtab, H, D):
     _chk(lib().orbit2_varagg_fwd(_p(x), _p(stab), _p(gtab), _p(z), _p(attw), B, V, h, w, H, D, _stream()),
          "orbit2_varagg_fwd")
     return z, attw
+
+
+def varagg_fwd_f32(x, stab, gtab, H, D, want_attw=False):
+    """the folded variable aggregation with fp32 tokens (orbit2_varagg_fwd_f32); returns z, or (z, attw) with want_attw"""
+    _dev(x, F32, "x"); _dev(stab, F32, "stab"); _dev(gtab, F32, "gtab")
+    B, V, h, w = x.shape
+    ntok = B * (h // 2) * (w // 2)
+    z = torch.empty(ntok, D, dtype=F32, device=x.device)
+    attw = torch.empty(ntok, H, V, dtype=F32, device=x.device) if want_attw else None
+    _chk(lib().orbit2_varagg_fwd_f32(_p(x), _p(stab), _p(gtab), _p(z), _p(attw), B, V, h, w, H, D, _stream()),
+         "orbit2_varagg_fwd_f32")
+    return (z, attw) if want_attw else z
 
 
 def _ws(query, args, device):
@@ -535,6 +615,13 @@ def unpatchify_fwd(t, B, Cc, h, w, p, s):
     _dev(t, BF, "t")
     img = torch.empty(B, Cc, h * s, w * s, dtype=F32, device=t.device)
     _chk(lib().orbit2_unpatchify_fwd(_p(t), _p(img), B, Cc, h, w, p, s, _stream()), "orbit2_unpatchify_fwd")
+    return img
+
+
+def unpatchify_fwd_f32(t, B, Cc, h, w, p, s):
+    _dev(t, F32, "t")
+    img = torch.empty(B, Cc, h * s, w * s, dtype=F32, device=t.device)
+    _chk(lib().orbit2_unpatchify_fwd_f32(_p(t), _p(img), B, Cc, h, w, p, s, _stream()), "orbit2_unpatchify_fwd_f32")
     return img
 
 

@@ -10,6 +10,9 @@ compute is the hand-written HIP path:
     head            : final LN + decoder_depth x (Linear+GELU) + Linear                    (one autograd node)
     tail            : unpatchify -> 3x3 conv with the residual branch added in its epilogue
 
+`set_compute_dtype(torch.float32)` switches the built model to the forward-only fp32 pipeline (climate_learn/_fp32.py:
+fp32 tokens, fp32 GEMM / attention / LayerNorm kernels reading the fp32 master parameters); the default is bf16.
+
 There is no CPU / eager fallback: inputs must live on a gfx950 device.
 """
 from __future__ import annotations
@@ -20,7 +23,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ... import _ops
+from ... import _fp32, _ops
 from ...dist import tp as _tp
 from ...utils.fused_attn import FusedAttn
 from .components.attention import VariableMapping_Attention
@@ -102,8 +105,22 @@ class Res_Slim_ViT(nn.Module):
             p._o2_lowp = False
         self.initialize_weights()
         self._idx_cache = {}
+        self._compute_dtype = torch.bfloat16
         if tensor_par_size > 1:
             _tp.tag_sharded(self)
+
+    # ------------------------------------------------------------------ compute precision
+    @property
+    def compute_dtype(self):
+        """precision of the token path: torch.bfloat16 (default; training and inference) or torch.float32 (forward-only
+        inference, the reference's `data_type: float32`).  A plain attribute of the object: not part of `state_dict`."""
+        return self._compute_dtype
+
+    def set_compute_dtype(self, dtype):
+        if dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError("compute_dtype must be torch.bfloat16 or torch.float32, got %r" % (dtype,))
+        self._compute_dtype = dtype
+        return self
 
     # ------------------------------------------------------------------ init (res_slimvit.py:125-145)
     def initialize_weights(self):
@@ -243,6 +260,9 @@ class Res_Slim_ViT(nn.Module):
         B, V, h, w = x.shape
         if (h, w) != tuple(self.img_size):
             raise ValueError("input grid %s differs from data_config'd img_size %s" % ((h, w), self.img_size))
+        if self._compute_dtype == torch.float32:
+            _fp32.refuse(self)
+            return _fp32.forward(self, x, in_variables, out_variables)
         cidx = self._chan_idx(in_variables, out_variables, x.device)
         c0, c3 = self.path2[0], self.path2[3]
         r = _ops.Conv3x3Fn.apply(x, c0.weight, c0.bias, cidx, 1, self.superres_mag, None)

@@ -14,7 +14,8 @@ inline int grid_for(int64_t n, int per_block) {
 
 // ---- unpatchify (res_slimvit.py:167-179): pure index permutation -------------------------------
 // img[b][c][hh*p+pp][ww*p+qq] = t[b][ (((hh*wf + ww)*p + pp)*p + qq)*C + c ],  hf = h*s/p, wf = w*s/p
-template <bool BWD>
+// T_FP32 (forward only): t holds fp32 tokens (the fp32 forward path)
+template <bool BWD, bool T_FP32 = false>
 __global__ __launch_bounds__(256) void unpatchify_kernel(bf16_t* __restrict__ t, float* __restrict__ img, int B, int C,
                                                          int Hh, int Wh, int p) {
   const int64_t per = (int64_t)C * Hh * Wh;
@@ -30,7 +31,7 @@ __global__ __launch_bounds__(256) void unpatchify_kernel(bf16_t* __restrict__ t,
       const int y = (int)(r / Wh), x = (int)(r - (int64_t)y * Wh);
       const int hh = y / p, pp = y - hh * p, ww = x / p, qq = x - ww * p;
       const int64_t ti = ((((int64_t)hh * wf + ww) * p + pp) * p + qq) * C + c;
-      img[e] = bf2f(t[(int64_t)b * per + ti]);
+      img[e] = T_FP32 ? reinterpret_cast<const float*>(t)[(int64_t)b * per + ti] : bf2f(t[(int64_t)b * per + ti]);
     } else {
       // e enumerates t elements
       const int c = (int)(r % C);
@@ -345,6 +346,15 @@ extern "C" int orbit2_unpatchify_fwd(const void* t, float* img, int B, int C, in
   const int64_t n = (int64_t)B * C * h * s * w * s;
   hipLaunchKernelGGL(unpatchify_kernel<false>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)t,
                      img, B, C, h * s, w * s, p);
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+extern "C" int orbit2_unpatchify_fwd_f32(const float* t, float* img, int B, int C, int h, int w, int p, int s,
+                                         void* stream) {
+  if (!t || !img || B <= 0 || C <= 0 || p <= 0 || s <= 0 || (h * s) % p || (w * s) % p) return O2_ERR_ARG;
+  const int64_t n = (int64_t)B * C * h * s * w * s;
+  hipLaunchKernelGGL((unpatchify_kernel<false, true>), dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
+                     (bf16_t*)t, img, B, C, h * s, w * s, p);
   O2_CHECK_LAUNCH();
   return O2_OK;
 }

@@ -63,6 +63,58 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* __restrict__ 
   }
 }
 
+// fp32 twin of ln_fwd_kernel (the fp32 forward path): one wave per row, NC float4 chunks per lane, two-pass variance from the
+// register-resident row; mean / rstd optional
+template <int NC>
+__global__ __launch_bounds__(256) void ln_fwd_f32_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, float* __restrict__ y,
+                                                         float* __restrict__ mean, float* __restrict__ rstd, int rows,
+                                                         int D, float eps, int ldy) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int nch = D >> 2;
+  const float* xr = x + (size_t)row * D;
+  f32x4 v[NC];
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int ch = lane + c * 64;
+    if (ch < nch) {
+      v[c] = *reinterpret_cast<const f32x4*>(xr + ch * 4);
+      s += (v[c][0] + v[c][1]) + (v[c][2] + v[c][3]);
+    }
+  }
+  const float mu = wave_sum(s) / (float)D;
+  float q = 0.f;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int ch = lane + c * 64;
+    if (ch < nch) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { const float d = v[c][j] - mu; q = fmaf(d, d, q); }
+    }
+  }
+  const float rs = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+  if (lane == 0) {
+    if (mean) mean[row] = mu;
+    if (rstd) rstd[row] = rs;
+  }
+  float* yr = y + (size_t)row * ldy;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int ch = lane + c * 64;
+    if (ch < nch) {
+      const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + ch * 4);
+      const f32x4 b = *reinterpret_cast<const f32x4*>(beta + ch * 4);
+      f32x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = fmaf((v[c][j] - mu) * rs, g[j], b[j]);
+      *reinterpret_cast<f32x4*>(yr + ch * 4) = o;
+    }
+  }
+}
+
 // Each wave walks LN_RPW consecutive rows (two passes per row: statistics, then dx from the L1/L2-hot
 // lines) and keeps its dgamma/dbeta partial sums in registers; one partial row per block (D % 4 == 0).
 constexpr int LN_RPW = 16;
@@ -701,6 +753,20 @@ extern "C" int orbit2_layernorm_fwd_ld(const void* x, const void* gamma, const v
                      (const bf16_t*)x, (const bf16_t*)gamma, (const bf16_t*)beta, (bf16_t*)y, mean, rstd,  \
                      rows, D, eps, ldy)
   LN_DISPATCH(nc, CALL);
+#undef CALL
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+extern "C" int orbit2_layernorm_fwd_f32(const void* x, const void* gamma, const void* beta, void* y, float* mean,
+                                        float* rstd, int rows, int D, int ldy, float eps, void* stream) {
+  if (!x || !gamma || !beta || !y || rows <= 0 || D <= 0 || (D & 3) || D > LN_MAXD || ldy < D || (ldy & 3)) return O2_ERR_ARG;
+  const int nc = (D / 4 + 63) / 64;                                  // float4 chunks per lane: up to 32 at D = 8192
+#define CALL(N)                                                                                              \
+  hipLaunchKernelGGL(ln_fwd_f32_kernel<N>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream,          \
+                     (const float*)x, (const float*)gamma, (const float*)beta, (float*)y, mean, rstd, rows,  \
+                     D, eps, ldy)
+  if (nc <= 2) { CALL(2); } else if (nc <= 4) { CALL(4); } else if (nc <= 8) { CALL(8); } else if (nc <= 16) { CALL(16); } else { CALL(32); }
 #undef CALL
   O2_CHECK_LAUNCH();
   return O2_OK;

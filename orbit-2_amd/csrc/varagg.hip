@@ -21,7 +21,8 @@ constexpr int VA_MAXV = 32;   // max variables
 constexpr int VA_MAXH = 32;   // max heads
 
 // LDS: pt[T][V][5], aw[T][H][V]
-template <bool BWD>
+// ZF32 (forward only): z is written as fp32 and attw may be NULL (the fp32 forward path saves nothing for a backward)
+template <bool BWD, bool ZF32 = false>
 __global__ __launch_bounds__(256) void varagg_kernel(const float* __restrict__ x, const float* __restrict__ stab,
                                                      const float* __restrict__ gtab, bf16_t* __restrict__ z,
                                                      float* __restrict__ attw, const bf16_t* __restrict__ dz,
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(256) void varagg_kernel(const float* __restrict__ x
         for (int c = 0; c < 5; ++c) s += st[v * 5 + c] * pp[v * 5 + c];
         const float a = __expf(s - mx) * inv;
         aw[(t * H + hh) * V + v] = a;
-        if (tok < ntok) attw[((size_t)tok * H + hh) * V + v] = a;
+        if (tok < ntok && (!ZF32 || attw)) attw[((size_t)tok * H + hh) * V + v] = a;
       }
     }
   } else {
@@ -120,8 +121,13 @@ __global__ __launch_bounds__(256) void varagg_kernel(const float* __restrict__ x
       for (int t = 0; t < VA_T; ++t) {
         const int64_t tok = tok0 + t;
         if (tok < ntok) {
-          u32x2 o; o[0] = pack_bf2(acc[t][0], acc[t][1]); o[1] = pack_bf2(acc[t][2], acc[t][3]);
-          *reinterpret_cast<u32x2*>(z + (size_t)tok * D + i0) = o;
+          if (ZF32) {
+            const f32x4 o = {acc[t][0], acc[t][1], acc[t][2], acc[t][3]};
+            *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(z) + (size_t)tok * D + i0) = o;
+          } else {
+            u32x2 o; o[0] = pack_bf2(acc[t][0], acc[t][1]); o[1] = pack_bf2(acc[t][2], acc[t][3]);
+            *reinterpret_cast<u32x2*>(z + (size_t)tok * D + i0) = o;
+          }
         }
       }
     } else {
@@ -461,6 +467,20 @@ extern "C" int orbit2_varagg_fwd(const float* x, const float* stab, const float*
   const int64_t ntok = (int64_t)B * (h / 2) * (w / 2);
   const size_t shm = sizeof(float) * (size_t)(VA_T * V * 5 + 2 * VA_T * H * V);
   hipLaunchKernelGGL(varagg_kernel<false>, dim3((unsigned)((ntok + VA_T - 1) / VA_T)), dim3(256), shm,
+                     (hipStream_t)stream, x, stab, gtab, (bf16_t*)z, attw, (const bf16_t*)nullptr, (float*)nullptr,
+                     (float*)nullptr, B, V, h, w, H, D);
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+extern "C" int orbit2_varagg_fwd_f32(const float* x, const float* stab, const float* gtab, float* z, float* attw, int B,
+                                     int V, int h, int w, int H, int D, void* stream) {
+  if (!x || !stab || !gtab || !z) return O2_ERR_ARG;              // attw may be NULL
+  int rc = va_check(B, V, h, w, H, D);
+  if (rc) return rc;
+  const int64_t ntok = (int64_t)B * (h / 2) * (w / 2);
+  const size_t shm = sizeof(float) * (size_t)(VA_T * V * 5 + 2 * VA_T * H * V);
+  hipLaunchKernelGGL((varagg_kernel<false, true>), dim3((unsigned)((ntok + VA_T - 1) / VA_T)), dim3(256), shm,
                      (hipStream_t)stream, x, stab, gtab, (bf16_t*)z, attw, (const bf16_t*)nullptr, (float*)nullptr,
                      (float*)nullptr, B, V, h, w, H, D);
   O2_CHECK_LAUNCH();
