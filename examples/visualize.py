@@ -6,7 +6,12 @@
 Builds the model from the YAML (same schema as the training configs), optionally loads `trainer.pretrain`
 (shape-tolerant, like the reference), cuts test sample 0 into `tiling.div`^2 tiles with an `overlap` halo, runs the
 HIP forward on every tile, stitches the interiors, and reports the denormalised rmse / pearson / mean_bias of the
-stitched field (the reference's validation metrics, loaders.py:247-255).  Forward only; one process, one GPU."""
+stitched field (the reference's validation metrics, loaders.py:247-255).  Forward only; one process, one GPU.
+
+An optional `mc_dropout: {members: N, seed: S}` block (configs/inference_mc.yaml) adds, after the deterministic run, an
+MC-dropout ensemble of N stitched predictions (climate_learn.utils.mc_dropout_statistics: streamed mean and spread, same
+tiling), prints gaussian_crps / gaussian_spread / gaussian_spread_skill_ratio and the 1-sigma coverage of the denormalised
+field, and saves the mean and the spread as <rank>_mc_mean.npy / <rank>_mc_spread.npy."""
 import os
 import sys
 
@@ -72,6 +77,33 @@ def main():
     gt = denorm(y[:, :, : pred.shape[2], : pred.shape[3]].float())
     for loss in test_losses:
         print(loss.name, [round(float(v), 6) for v in loss(pred, gt).reshape(-1)], flush=True)
+    mcd = conf.get("mc_dropout")
+    if mcd:
+        return mc_dropout_report(model, (x, y, iv, ov), gt, denorm, int(mcd["members"]), int(mcd.get("seed", 0)), div, overlap,
+                                 local_rank)
+
+
+def mc_dropout_report(model, batch, gt, denorm, members, seed, div, overlap, rank):
+    """MC-dropout ensemble of the stitched field: denormalised mean and spread (the spread takes the denormalisation's
+    scale only, not its shift), the Gaussian scores against the denormalised ground truth, and the 1-sigma coverage"""
+    from climate_learn.metrics import functional as fn
+    cl.manual_seed(seed)
+    stats = cl.utils.mc_dropout_statistics(batch, model, members, div=div, overlap=overlap)
+    model.eval()                                                            # leave MC-dropout mode
+    mean = denorm(stats.mean)
+    spread = denorm(stats.std) - denorm(torch.zeros_like(stats.mean))
+    normal = torch.distributions.Normal(mean, spread, validate_args=False)
+    print("mc_dropout members %d seed %d" % (stats.n, seed), flush=True)
+    for name, val in (("gaussian_crps", fn.gaussian_crps(normal, gt)), ("gaussian_spread", fn.gaussian_spread(normal)),
+                      ("gaussian_spread_skill_ratio", fn.gaussian_spread_skill_ratio(normal, gt)),
+                      ("coverage_1sigma", fn.gaussian_coverage(normal, gt))):
+        print(name, [round(float(v), 6) for v in val.reshape(-1)], flush=True)
+    res = {"mean": mean.detach().cpu().numpy(), "spread": spread.detach().cpu().numpy()}
+    import numpy as np
+    np.save("%d_mc_mean.npy" % rank, res["mean"])
+    np.save("%d_mc_spread.npy" % rank, res["spread"])
+    print("mc_dropout saved", {k: v.shape for k, v in res.items()}, flush=True)
+    return res
 
 
 if __name__ == "__main__":

@@ -279,6 +279,21 @@ int orbit2_loss_bwd(const float* pred, const float* target, int Ht, int Wt, cons
 int orbit2_eval_moments(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* clim,
                         double* out, int B, int C, int H, int W, void* stream);
 
+/* ---- MC-dropout ensembles (utils/mc_dropout.py) and the Gaussian scores (metrics/functional.py:340-386) ------
+ * Both entries were ADDED at version 7 (nothing existing changed; a binding that declares them refuses an older build by name).
+ * orbit2_ensemble_update: the k-th (1-based) Welford step over n fp32 elements, in place:
+ *   d = member - mean; mean += d / k; m2 += d * (member - mean).   k = 1 initialises (mean = member, m2 = 0; neither is read).
+ * After N steps m2 / (N - 1) is the unbiased variance.  The three buffers must be distinct; 16-byte aligned bases take the
+ * float4 path.  NULL, n <= 0, k < 1 or aliased buffers return O2_ERR_ARG before any launch. */
+int orbit2_ensemble_update(const float* member, float* mean, float* m2, int64_t n, int k, void* stream);
+/* mean, std fp32 [B,C,H,W]; target fp32 [B,C,Ht,Wt] (top-left crop; Ht >= H, Wt >= W); lat_w fp32 [H] or NULL (w = 1).
+ * out[b][c][4] (double) = {sum w crps, sum w std^2, sum w (mean - target)^2, sum 1{|target - mean| <= std}} with the closed-form
+ * Gaussian CRPS std (z (2 Phi(z) - 1) + 2 phi(z) - 1 / sqrt(pi)), z = (target - mean) / std; at std == 0 crps = |target - mean|
+ * and the point is covered only if target == mean (no NaN / Inf for finite inputs).  NULL mean / std / target / out, a
+ * non-positive size, a target smaller than the prediction or B * C > 65535 return O2_ERR_ARG before any launch. */
+int orbit2_gaussian_scores(const float* mean, const float* std_, const float* target, int Ht, int Wt, const float* lat_w,
+                           double* out, int B, int C, int H, int W, void* stream);
+
 /* ---- perceptual loss = L1 + 0.5 * mean_b LPIPS-VGG16 (metrics/functional.py:17-33, metrics.py:119-187) ------
  * Feature maps are NHWC bf16, so each 3x3 VGG convolution is im2col + orbit2_gemm_bf16 (bias, act = 2) forward and
  * orbit2_gemm_bf16 + col2im backward (input gradient only: LPIPS weights are frozen, metrics.py:127-128).

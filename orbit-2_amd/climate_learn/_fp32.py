@@ -40,6 +40,9 @@ def refuse(model):
     if model.training:
         raise RuntimeError("Res_Slim_ViT fp32 compute is forward-only inference: dropout / DropPath are not built in fp32 "
                            "(training mode is set; call model.eval())")
+    if any(getattr(m, "mc_dropout", False) for m in model.modules()):
+        raise RuntimeError("Res_Slim_ViT fp32 compute has no dropout kernels: MC dropout is built for the bf16 path "
+                           "(enable_dropout() was called; model.eval() leaves the mode, or set_compute_dtype(torch.bfloat16))")
     if model.tensor_par_size > 1:
         raise RuntimeError("Res_Slim_ViT fp32 compute is not built for tensor parallelism (tensor_par_size > 1)")
     prm = list(model.parameters())

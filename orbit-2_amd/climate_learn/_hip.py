@@ -101,6 +101,8 @@ PROTOTYPES = {
     "orbit2_loss_fwd": (_I, (_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P)),
     "orbit2_loss_bwd": (_I, (_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P)),
     "orbit2_eval_moments": (_I, (_P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P)),
+    "orbit2_ensemble_update": (_I, (_P, _P, _P, _I64, _I, _P)),
+    "orbit2_gaussian_scores": (_I, (_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P)),
     "orbit2_im2col3x3": (_I, (_P, _P, _I, _I, _I, _I, _P)),
     "orbit2_col2im3x3": (_I, (_P, _P, _P, _P, _I, _I, _I, _I, _P)),
     "orbit2_maxpool2_fwd": (_I, (_P, _P, _I, _I, _I, _I, _P)),
@@ -812,6 +814,39 @@ def eval_moments(pred, target, lat_w=None, clim=None):
     out = torch.empty(B, Cc, 12, dtype=torch.float64, device=pred.device)
     _chk(lib().orbit2_eval_moments(_p(pred), _p(target), target.shape[2], target.shape[3], _p(lat_w), _p(clim), _p(out),
                                    B, Cc, H, W, _stream()), "orbit2_eval_moments")
+    return out
+
+
+def ensemble_update(member, mean, m2, k: int):
+    """the k-th (1-based) Welford step of the running ensemble moments, in place on `mean` and `m2`
+    (include/orbit2_hip.h:orbit2_ensemble_update); k = 1 initialises them, so they may be torch.empty"""
+    _dev(member, F32, "member"); _dev(mean, F32, "mean"); _dev(m2, F32, "m2")
+    if mean.shape != member.shape or m2.shape != member.shape:
+        raise HipBackendError("ensemble_update: member %s, mean %s and m2 %s must have one shape"
+                              % (tuple(member.shape), tuple(mean.shape), tuple(m2.shape)))
+    _chk(lib().orbit2_ensemble_update(_p(member), _p(mean), _p(m2), member.numel(), int(k), _stream()),
+         "orbit2_ensemble_update")
+
+
+def gaussian_scores(mean, std, target, lat_w=None):
+    """[B,C,4] float64 sums {w crps, w std^2, w (mean - target)^2, 1{|target - mean| <= std}} of a Gaussian prediction
+    (include/orbit2_hip.h:orbit2_gaussian_scores); the target may be larger than the prediction (top-left crop)"""
+    _dev(mean, F32, "mean"); _dev(std, F32, "std"); _dev(target, F32, "target")
+    if mean.dim() != 4 or target.dim() != 4:
+        raise HipBackendError("gaussian_scores takes [B,C,H,W] fields")
+    if std.shape != mean.shape:
+        raise HipBackendError("gaussian_scores: mean %s and std %s differ in shape" % (tuple(mean.shape), tuple(std.shape)))
+    if tuple(target.shape[:2]) != tuple(mean.shape[:2]):
+        raise HipBackendError("gaussian_scores: target %s does not match the prediction's [B,C] %s"
+                              % (tuple(target.shape), tuple(mean.shape[:2])))
+    B, Cc, H, W = mean.shape
+    if lat_w is not None:
+        _dev(lat_w, F32, "lat_w")
+        if lat_w.numel() < H:
+            raise HipBackendError("lat_w has %d entries, the prediction %d rows" % (lat_w.numel(), H))
+    out = torch.empty(B, Cc, 4, dtype=torch.float64, device=mean.device)
+    _chk(lib().orbit2_gaussian_scores(_p(mean), _p(std), _p(target), target.shape[2], target.shape[3], _p(lat_w), _p(out),
+                                      B, Cc, H, W, _stream()), "orbit2_gaussian_scores")
     return out
 
 

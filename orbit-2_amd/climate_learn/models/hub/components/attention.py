@@ -6,10 +6,10 @@ import torch.nn as nn
 from .... import _ops
 from ....utils.fused_attn import FusedAttn
 from ....dist import tp as _tp
-from .mlp import HipLinear
+from .mlp import HipLinear, McDropoutMode
 
 
-class Attention(nn.Module):
+class Attention(McDropoutMode, nn.Module):
     def __init__(self, dim, fused_attn=FusedAttn.HIP, num_heads=8, qkv_bias=False, qk_norm=False, proj_bias=True,
                  attn_drop=0.0, proj_drop=0.0, norm_layer=nn.LayerNorm, tensor_par_size=1, tensor_par_group=None):
         super().__init__()
@@ -26,10 +26,16 @@ class Attention(nn.Module):
         self.attn_drop_p, self.proj_drop_p = float(attn_drop), float(proj_drop)
 
     def attn_p(self):
-        """P-dropout probability actually applied (CK semantics: also in eval mode)."""
-        if self.training or FusedAttn(self.fused_attn).dropout_in_eval:
+        """P-dropout probability actually applied (CK semantics: also in eval mode; MC-dropout mode: per backend,
+        FusedAttn.dropout_in_mc)."""
+        backend = FusedAttn(self.fused_attn)
+        if self.training or backend.dropout_in_eval or (self.mc_dropout and backend.dropout_in_mc):
             return self.attn_drop_p
         return 0.0
+
+    def proj_p(self):
+        """proj_drop probability actually applied: train mode or MC-dropout mode"""
+        return self.proj_drop_p if (self.training or self.mc_dropout) else 0.0
 
     def forward(self, x):
         tp, grp = self.tensor_par_size, self.tensor_par_group
@@ -37,7 +43,7 @@ class Attention(nn.Module):
             x = _tp.IdentityFwdAllReduceBwd.apply(x, grp)
         qkv = self.qkv(x)
         o = _ops.AttnCoreFn.apply(qkv, self.num_heads // tp, self.attn_p(), _tp.group_rank(grp) if tp > 1 else 0)
-        y = self.proj(o, self.proj_drop_p if self.training else 0.0)
+        y = self.proj(o, self.proj_p())
         return _tp.AllReduceFwdIdentityBwd.apply(y, grp) if tp > 1 else y
 
 

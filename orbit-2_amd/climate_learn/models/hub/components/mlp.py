@@ -6,6 +6,20 @@ import torch.nn as nn
 from .... import _ops
 
 
+class McDropoutMode:
+    """Mixin of the modules that decide a dropout probability (Res_Slim_ViT, Block, Attention, Mlp).  Dropout is not a
+    module here but a probability handed to the fused kernels, so the reference's MC-dropout helper (utils/mc_dropout.py:
+    eval(), then its nn.Dropout modules back to train mode) becomes a flag: `utils.mc_dropout.enable_dropout` sets
+    `mc_dropout` on every such module, and any later train() / eval() clears it, as the reference's .eval() does to its
+    Dropout modules.  In the mode the element dropouts (pos_drop, proj_drop, mlp drop1 / drop2) are on, DropPath stays off,
+    and attention-probability dropout follows FusedAttn.dropout_in_mc."""
+    mc_dropout = False
+
+    def train(self, mode: bool = True):
+        self.mc_dropout = False
+        return super().train(mode)
+
+
 class HipLinear(nn.Module):
     """Parameter holder with nn.Linear's names/shapes; compute goes through the HIP GEMM."""
 
@@ -23,7 +37,7 @@ class HipLinear(nn.Module):
         return _ops.LinearFn.apply(x, self.weight, self.bias, p_drop, residual)
 
 
-class Mlp(nn.Module):
+class Mlp(McDropoutMode, nn.Module):
     def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, norm_layer=None,
                  bias=True, drop=0.0, use_conv=False, tensor_par_size: int = 1, tensor_par_group=None):
         super().__init__()
@@ -37,9 +51,13 @@ class Mlp(nn.Module):
         self.fc2 = HipLinear(hidden_features // tensor_par_size, out_features, bias=bias)
         self.drop = float(drop)
 
+    def drop_p(self):
+        """probability of drop1 / drop2 actually applied: train mode or MC-dropout mode"""
+        return self.drop if (self.training or self.mc_dropout) else 0.0
+
     def forward(self, x):
         from ....dist import tp as _tp
-        p = self.drop if self.training else 0.0
+        p = self.drop_p()
         cfg = {"ln": False, "p_mid": p, "p_out": p}
         if self.tensor_par_size > 1:
             x = _tp.IdentityFwdAllReduceBwd.apply(x, self.tensor_par_group)

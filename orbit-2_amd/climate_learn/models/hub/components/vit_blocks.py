@@ -11,7 +11,7 @@ import torch.nn as nn
 from .... import _ops
 from ....utils.fused_attn import FusedAttn
 from .attention import Attention
-from .mlp import Mlp
+from .mlp import McDropoutMode, Mlp
 
 
 class HipLayerNorm(nn.Module):
@@ -33,7 +33,7 @@ class LayerScale(nn.Module):
         raise NotImplementedError("LayerScale is unused by Res_Slim_ViT (init_values=None)")
 
 
-class Block(nn.Module):
+class Block(McDropoutMode, nn.Module):
     def __init__(self, dim, num_heads, fused_attn=FusedAttn.HIP, mlp_ratio=4.0, qkv_bias=False, qk_norm=False,
                  proj_bias=True, proj_drop=0.0, attn_drop=0.0, init_values=None, drop_path=0.0, act_layer=nn.GELU,
                  norm_layer=nn.LayerNorm, mlp_layer=Mlp, tensor_par_size=1, tensor_par_group=None):
@@ -51,17 +51,21 @@ class Block(nn.Module):
         self.recompute = False
         self.tensor_par_group = tensor_par_group if tensor_par_size > 1 else None
 
-    def forward(self, x):
+    def dropout_probs(self):
+        """the probabilities forward() hands to BlockFn, decided on the host: train mode = all four; eval = none (CK keeps
+        attention-probability dropout); MC-dropout mode (utils/mc_dropout.py) = the element dropouts of the sub-modules that
+        carry the flag, attention-probability dropout per backend (FusedAttn.dropout_in_mc), and NO DropPath -- the
+        reference's helper wakes nn.Dropout modules only, drop_path1 / drop_path2 stay in eval mode"""
         tr = self.training
-        cfg = {
-            "heads": self.attn.num_heads,
+        return {
             "attn_drop": self.attn.attn_p(),
-            "proj_drop": self.attn.proj_drop_p if tr else 0.0,
-            "mlp_drop": self.mlp.drop if tr else 0.0,
+            "proj_drop": self.attn.proj_drop_p if (tr or self.attn.mc_dropout) else 0.0,
+            "mlp_drop": self.mlp.drop if (tr or self.mlp.mc_dropout) else 0.0,
             "drop_path": self.drop_path if tr else 0.0,
-            "recompute": self.recompute,
-            "tp_group": self.tensor_par_group,
         }
+
+    def forward(self, x):
+        cfg = dict(self.dropout_probs(), heads=self.attn.num_heads, recompute=self.recompute, tp_group=self.tensor_par_group)
         a, m = self.attn, self.mlp
         x = _ops.unit_enter(self, x)   # parameter-sharding engine: gather this Block's weights (no-op otherwise)
         y = _ops.BlockFn.apply(x, cfg, self.norm1.weight, self.norm1.bias, a.qkv.weight, a.qkv.bias,

@@ -27,7 +27,7 @@ from ... import _fp32, _ops
 from ...dist import tp as _tp
 from ...utils.fused_attn import FusedAttn
 from .components.attention import VariableMapping_Attention
-from .components.mlp import HipLinear
+from .components.mlp import HipLinear, McDropoutMode
 from .components.patch_embed import PatchEmbed, _ConvParams
 from .components.pos_embed import _orig_grid, get_2d_sincos_pos_embed
 from .components.vit_blocks import Block, HipLayerNorm
@@ -49,7 +49,7 @@ class _PixelShuffle(_Gelu):
 
 
 @register("res_slimvit")
-class Res_Slim_ViT(nn.Module):
+class Res_Slim_ViT(McDropoutMode, nn.Module):
     def __init__(self, default_vars, img_size, in_channels, out_channels, history, superres_mag=4, cnn_ratio=4,
                  patch_size=16, drop_path=0.1, drop_rate=0.1, learn_pos_emb=False, embed_dim=1024, depth=24,
                  decoder_depth=8, num_heads=16, mlp_ratio=4.0, tensor_par_size=1, tensor_par_group=None,
@@ -240,11 +240,15 @@ class Res_Slim_ViT(nn.Module):
         return _ops.PosResFn.apply(self.pos_embed, self.spatial_embed.weight, self.spatial_embed.bias,
                                    float(self.spatial_resolution), oh, ow, nh, nw)
 
+    def pos_p(self):
+        """pos_drop probability actually applied: train mode or MC-dropout mode (utils/mc_dropout.py)"""
+        return self.pos_drop_p if (self.training or self.mc_dropout) else 0.0
+
     # ------------------------------------------------------------------ forward (res_slimvit.py:245-338)
     def forward_encoder(self, x, variables):
         ids = self.get_var_ids(tuple(variables))
         stab, gtab = self._tables(ids)
-        p = self.pos_drop_p if self.training else 0.0
+        p = self.pos_p()
         t = _ops.EmbedFn.apply(x, stab, gtab, self._posres(), self.var_agg.proj.weight, self.var_agg.proj.bias,
                                self.num_heads // self.tensor_par_size, p, self.tensor_par_group)
         for blk in self.blocks:

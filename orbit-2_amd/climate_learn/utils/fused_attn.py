@@ -15,3 +15,11 @@ class FusedAttn(enum.Enum):
     @property
     def dropout_in_eval(self) -> bool:
         return self is FusedAttn.CK
+
+    @property
+    def dropout_in_mc(self) -> bool:
+        """P-dropout in MC-dropout mode (utils/mc_dropout.py: eval() + enable_dropout()).  The reference's helper switches the
+        nn.Dropout *modules* to train mode and leaves every Attention module in eval mode: CK applies it anyway, NONE goes
+        through its `attn_drop` module (attention.py:76 there: on), DEFAULT hands SDPA `self.training` of the Attention
+        module (attention.py:69 there: off).  HIP has no SDPA quirk to mirror and follows the written-out form (on)."""
+        return self is not FusedAttn.DEFAULT

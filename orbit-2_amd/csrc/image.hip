@@ -512,6 +512,137 @@ extern "C" int orbit2_eval_moments(const float* pred, const float* target, int H
   return O2_OK;
 }
 
+// ---- MC-dropout ensembles (utils/mc_dropout.py; metrics/functional.py:340-386 gaussian_crps / _spread / _spread_skill_ratio) ----
+// The k-th (1-based) Welford step of the running per-element mean and sum of squared deviations, in place:
+//   d = x - mean;  mean += d / k;  m2 += d * (x - mean)          (k = 1: mean = x, m2 = 0 -- neither is read)
+// so N members of a [B, C, H, W] field leave mean and m2 = (N - 1) * unbiased variance without N fields being held.  A pure
+// stream (12 bytes read, 8 written per element): float4 per lane when the three bases are 16-byte aligned, grid-stride over at
+// most 2048 workgroups, the n % 4 tail (or everything, for unaligned bases) by scalar lanes.
+namespace {
+__device__ __forceinline__ void welford_step(float x, float& mean, float& m2, float kf) {
+  const float d = x - mean;
+  mean += d / kf;
+  m2 = fmaf(d, x - mean, m2);
+}
+
+__global__ __launch_bounds__(256) void ensemble_update_kernel(const float* __restrict__ member, float* __restrict__ mean,
+                                                              float* __restrict__ m2, int64_t n, int64_t n4, int k) {
+  const float kf = (float)k;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthr = (int64_t)gridDim.x * 256;
+  const f32x4* x4 = reinterpret_cast<const f32x4*>(member);
+  f32x4* mean4 = reinterpret_cast<f32x4*>(mean);
+  f32x4* m24 = reinterpret_cast<f32x4*>(m2);
+  if (k == 1) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = tid; i < n4; i += nthr) {
+      mean4[i] = x4[i];
+      m24[i] = zero;
+    }
+    for (int64_t i = 4 * n4 + tid; i < n; i += nthr) {
+      mean[i] = member[i];
+      m2[i] = 0.f;
+    }
+    return;
+  }
+  for (int64_t i = tid; i < n4; i += nthr) {
+    const f32x4 x = x4[i];
+    f32x4 mu = mean4[i], s = m24[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float mj = mu[j], sj = s[j];
+      welford_step(x[j], mj, sj, kf);
+      mu[j] = mj;
+      s[j] = sj;
+    }
+    mean4[i] = mu;
+    m24[i] = s;
+  }
+  for (int64_t i = 4 * n4 + tid; i < n; i += nthr) {
+    float mu = mean[i], s = m2[i];
+    welford_step(member[i], mu, s, kf);
+    mean[i] = mu;
+    m2[i] = s;
+  }
+}
+}  // namespace
+
+extern "C" int orbit2_ensemble_update(const float* member, float* mean, float* m2, int64_t n, int k, void* stream) {
+  if (!member || !mean || !m2 || n <= 0 || k < 1 || member == mean || member == m2 || mean == m2) return O2_ERR_ARG;
+  const bool aligned = (((uintptr_t)member | (uintptr_t)mean | (uintptr_t)m2) & 15) == 0;
+  const int64_t n4 = aligned ? n / 4 : 0;
+  const int64_t lanes = n4 > 0 ? n4 : n;
+  int64_t nblk = (lanes + 255) / 256;
+  if (nblk > 2048) nblk = 2048;
+  hipLaunchKernelGGL(ensemble_update_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, member, mean, m2, n, n4,
+                     k);
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+// Scores of a Gaussian prediction N(mean, std^2) against a target, four sums per (b, c) image (target: top-left crop,
+// w = lat_w[y] or 1), double accumulation across the grid as in orbit2_eval_moments:
+//   0 sum w crps, 1 sum w std^2, 2 sum w (mean - target)^2, 3 sum 1{|target - mean| <= std}
+// crps is the closed form of the Gaussian CRPS, std (z (2 Phi(z) - 1) + 2 phi(z) - 1 / sqrt(pi)) with z = (target - mean) / std
+// (functional.py:353 there has 1 / pi, and cannot be called: see metrics/functional.py:gaussian_crps here).  It is evaluated as
+//   |d| erf(|z| / sqrt 2) + std (2 phi(z) - 1 / sqrt(pi)),  d = target - mean,
+// the same expression with std z = d multiplied out: no product of a huge z with a tiny std, and at std == 0 (constant output
+// channels are copied from the target into every member) it IS the limit |d| -- no NaN, no Inf, and such a point counts as
+// covered only where target == mean.
+namespace {
+constexpr int GS_NM = 4;
+__global__ __launch_bounds__(256) void gaussian_scores_kernel(const float* __restrict__ mean, const float* __restrict__ std_,
+                                                              const float* __restrict__ target, int Ht, int Wt,
+                                                              const float* __restrict__ lat_w, double* __restrict__ out, int H,
+                                                              int W) {
+  __shared__ float red[4][GS_NM];
+  const int bc = blockIdx.y;
+  const float* m = mean + (size_t)bc * H * W;
+  const float* sd = std_ + (size_t)bc * H * W;
+  const float* t = target + (size_t)bc * Ht * Wt;
+  float s[GS_NM] = {0.f, 0.f, 0.f, 0.f};
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < H * W; i += gridDim.x * 256) {
+    const int y = i / W, x = i - y * W;
+    const float sg = sd[i];
+    const float d = t[(size_t)y * Wt + x] - m[i];
+    const float w = lat_w ? lat_w[y] : 1.f;
+    const float ad = fabsf(d);
+    float crps = ad;
+    if (sg > 0.f) {
+      const float z = ad / sg;                         // may be +inf (a denormal std): erf -> 1, phi -> 0, crps -> |d| - std / sqrt(pi)
+      const float phi = 0.3989422804014327f * expf(-0.5f * z * z);
+      crps = ad * erff(z * 0.70710678118654752f) + sg * (2.f * phi - 0.5641895835477563f);
+    }
+    s[0] += w * crps;
+    s[1] += w * sg * sg;
+    s[2] += w * d * d;
+    s[3] += ad <= sg ? 1.f : 0.f;
+  }
+#pragma unroll
+  for (int k = 0; k < GS_NM; ++k) {
+    const float v = wave_sum(s[k]);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < GS_NM) {
+    const int k = threadIdx.x;
+    atomicAdd(out + (size_t)bc * GS_NM + k, (double)red[0][k] + (double)red[1][k] + (double)red[2][k] + (double)red[3][k]);
+  }
+}
+}  // namespace
+
+extern "C" int orbit2_gaussian_scores(const float* mean, const float* std_, const float* target, int Ht, int Wt,
+                                      const float* lat_w, double* out, int B, int C, int H, int W, void* stream) {
+  if (!mean || !std_ || !target || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Ht < H || Wt < W) return O2_ERR_ARG;
+  if ((int64_t)B * C > 65535 || (int64_t)H * W > (int64_t)INT32_MAX - 64 * 256) return O2_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(out, 0, sizeof(double) * (size_t)B * C * GS_NM, s) != hipSuccess) return O2_ERR_LAUNCH;
+  int nblk = (H * W + 256 * 8 - 1) / (256 * 8);
+  if (nblk > 64) nblk = 64;
+  hipLaunchKernelGGL(gaussian_scores_kernel, dim3(nblk, B * C), dim3(256), 0, s, mean, std_, target, Ht, Wt, lat_w, out, H, W);
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
 // ---- position-embedding table of a step: bicubic re-grid + resolution embedding --------------------------------------------
 // out[(oy nw + ox)][:] = bicubic(pe)[oy][ox][:] + sw[:] * res + sb[:]
 // (components/pos_embed.py:103-138 interpolate_pos_embed_on_the_fly: the [1, L0, D] table seen as a channel-last [oh][ow][D] grid,
