@@ -62,7 +62,8 @@ typedef struct {
   int tile_hint;           /* 0 = auto; tests / tuning: 128 = 128-tile kernel on 128 x 128 tiles, 64 = the same kernel on 64-row tiles
                               (A K-contiguous; auto takes them when the 128 x 128 grid is under two tiles per CU), 256 = 8-wave 8-phase kernel (K % 64 == 0),
                               260 = 4-wave kernel (M, N % 256 == 0, K % 64 == 0), 262 = 4-wave kernel with the runtime epilogue in
-                              place of the compile-time kinds */
+                              place of the compile-time kinds; also accepted: 257, 258 = 256 (hints of older A/B tools), 261 = the stamped
+                              form of 260 (O2_ERR_UNSUPPORTED unless built with O2_W4_STAMP); any other value = 0 */
   int colscale_n;          /* columns n < colscale_n (a multiple of 8; 0 = none) are multiplied by colscale in fp32 right after */
   float colscale;          /*   the bias: the qkv Linear stores q * log2(e)/sqrt(d) (attention.py:50,54: q * scale), rounded ONCE */
   void* save_dact;         /* int16 [M][ldc] or NULL (needs act == 1): GELU'(pre) x (kept ? 1 / (1 - p) : 0) of THIS element as signed

@@ -227,7 +227,8 @@ _DW_SPLIT = 8     # K-split of a weight gradient whose output is too few tiles t
 def _dw_split_ok(M, N, K):
     """a lone weight gradient with < 192 tiles of 256 x 256 (the head's 192 x D output layer: 12; a D x D layer at D = 3072: 144)
     and a long contraction (tokens): alone it runs on 48-144 workgroups for 2048 K-tiles; split over the tokens into _DW_SPLIT
-    partial products (ONE grouped launch, bf16 partials summed in fp32 in a fixed order: deterministic) it fills the chip"""
+    partial products (ONE grouped launch, bf16 partials summed in fp32 in a fixed order: deterministic) it fills the chip.
+    (192 mirrors csrc/gemm.hip: gemm_fills_chip / gemm_group_fills_chip, the one place the library states the rule.)"""
     tiles = ((N + 255) // 256) * ((K + 255) // 256)
     return _DW_SPLIT > 1 and tiles < 192 and M >= 32768 and M % (_DW_SPLIT * 64) == 0 and N % 8 == 0 and K % 8 == 0
 
@@ -262,7 +263,8 @@ def _dw_balance_plan(shapes, S, slots=256):
     Block's four weight gradients at interm_1b: 1728 tiles = 6.75 rounds, 7 sweeps paid).  Plan: R = T % slots tiles leave the
     full-length set -- whole problems, smallest first, then whole tile rows of the next one -- and are split S ways over the
     tokens: F = T - R full tiles fill whole rounds, the R x S part-length units (R x S a multiple of `slots`) fill whole rounds of
-    1 / S the length.  Returns [(problem index, first tile row, tile rows)] to split, or None when no exact plan exists."""
+    1 / S the length.  Returns [(problem index, first tile row, tile rows)] to split, or None when no exact plan exists.
+    (`slots` = the 256 workgroups of a round, as in csrc/gemm.hip: gemm_fills_chip.)"""
     T = sum(tm * tn for tm, tn in shapes)
     R = T % slots
     if S < 2 or R == 0 or T < slots or (R * S) % slots:

@@ -1682,37 +1682,79 @@ static int attn_check(const void* a, const void* b, int B, int L, int H, int d, 
   return O2_OK;
 }
 
-// waves per workgroup: 8 (256-row tiles, K/V or Q/dO tiles shared by twice the waves) whenever the sequence has at least
-// one such tile and the kernel fits two waves per SIMD (d = 64, 128); ORBIT2_ATTN_4WAVES keeps the round-1 geometry (A/B).
-// The variant is an ARGUMENT of the entry points (no process-global switch: a forward / backward pair cannot disagree
-// behind the caller's back, nothing is read from the environment on the launch path).
-static int attn_waves(int L, int d, int flags) {
-  if (d == 256 || L < 256) return 4;
-  return (flags & ORBIT2_ATTN_4WAVES) ? 4 : 8;
-}
-// the FORWARD at d = 64 is faster with 4-wave workgroups, two per CU (round 3, same-box: -5 % without, -12 % with dropout at
-// L = 4096; the backward is neutral, d = 128 gains 2.5-6 % / 21-23 % from 8 waves): forward and backward pick independently
-static int attn_waves_fwd(int L, int d, int flags) {
-  return d == 64 ? 4 : attn_waves(L, d, flags);
+// ---- kernel selection.  attn_plan decides which kernel runs each pass of a call, on which grid and with which scalars; it
+// launches nothing, and the entry points below map it to instantiations.  The variant is an ARGUMENT of the entry points (flags):
+// a forward / backward pair cannot disagree behind the caller's back, nothing is read from the environment on the launch path.
+enum AttnDkv {
+  DKV_W4,         // the generated one-wave-per-SIMD dK + dV kernel: 128 keys per workgroup
+  DKV_FUSED64,    // d = 64: dK and dV in one pass (fits two waves per SIMD)
+  DKV_FUSED128,   // d = 128, 8 waves: one pass, V rows in LDS
+  DKV_FUSED256,   // d = 256: one pass at one wave per SIMD (interm_10b)
+  DKV_SPLIT       // dK and dV as two passes
+};
+struct AttnLaunch { dim3 grid, block; };
+struct AttnPlan {
+  bool fwd_w4, dq_w4;            // the generated one-wave-per-SIMD kernels (256-row workgroups) take the forward / the dQ pass
+  bool fwd_lazy;                 // compiler-scheduled forward: the lazy-rescaling kernel (every call without dropout)
+  AttnDkv dkv;
+  int nw_fwd, nw;                // compiler-scheduled kernels: waves per workgroup (32 rows each), forward and backward
+  bool ragged_fwd, ragged;       //   and whether L leaves a partial workgroup
+  AttnLaunch fwd, dq, dkv_l;     // grid and block of each pass
+  bool drop;
+  unsigned thr;                  // scalar arguments, computed once
+  float dscale, scale, opmul, kgrad;          // opmul: the kernels' multiplier of q (or k); kgrad: of the key-side gradient
+  float dq_w4_scale, dkv_w4_kgrad, dkv_w4_dscale;
+};
+
+// can the generated kernels take this call?  d = 128 with q stored pre-scaled, whole 256-row tiles, the hash table of the
+// sequence in LDS (O2_AF_MAX_L), 32-bit byte offsets (attn_w4_range_ok), and no request for the compiler-scheduled ones
+static bool attn_w4_ok(int d, int L, int flags, int ldq, int ldo) {
+  return d == 128 && (flags & ORBIT2_ATTN_Q_PRESCALED) && !(flags & ORBIT2_ATTN_NO_W4) && L % 256 == 0 && L <= O2_AF_MAX_L &&
+         attn_w4_range_ok(L, ldq, ldo);
 }
 
-template <int DV, bool DR, bool RG, int NW>
-static void launch_fwd(const void* qkv, void* out, float* lse, int B, int L, int H, float sc_log2, unsigned thr, float dscale,
-                       uint64_t seed, hipStream_t s, int ldo, int ldq) {
-  dim3 grid(((L + NW * 32 - 1) / (NW * 32)) * H * B), block(NW * 64);
-  if constexpr (!DR) {
-    hipLaunchKernelGGL((attn_fwd_lazy_kernel<DV, RG, NW>), grid, block, 0, s, (const bf16_t*)qkv, (bf16_t*)out, lse, L, H, sc_log2,
-                       thr, dscale, seed, ldo, ldq);
-    return;
-  }
-  hipLaunchKernelGGL((attn_fwd_kernel<DV, DR, RG, NW>), grid, block, 0, s, (const bf16_t*)qkv, (bf16_t*)out, lse, L, H, sc_log2,
-                     thr, dscale, seed, ldo, ldq);
+static AttnPlan attn_plan(int d, int L, int B, int H, int flags, int ldq, int ldo, float drop_p) {
+  AttnPlan p;
+  const bool pre = (flags & ORBIT2_ATTN_Q_PRESCALED) != 0, split = (flags & ORBIT2_ATTN_SPLIT_DKV) != 0;
+  p.thr = (unsigned)(drop_p * 256.0f + 0.5f);
+  p.drop = p.thr != 0;
+  p.fwd_lazy = !p.drop;
+  p.dscale = 256.0f / (256.0f - (float)p.thr);
+  p.scale = 1.0f / sqrtf((float)d);
+  p.opmul = pre ? 1.0f : p.scale * 1.4426950408889634f;      // (q stored pre-scaled: the kernels' multiplier is 1)
+  p.kgrad = pre ? 0.6931471805599453f : p.scale;
+  p.dq_w4_scale = p.drop ? p.scale * p.dscale : p.scale;
+  p.dkv_w4_kgrad = p.drop ? p.kgrad * p.dscale : p.kgrad;
+  p.dkv_w4_dscale = p.drop ? p.dscale : 1.0f;
+  // waves per workgroup: 8 (256-row tiles, K/V or Q/dO tiles shared by twice the waves) whenever the sequence has at least one
+  // such tile and the kernel fits two waves per SIMD (d = 64, 128); ORBIT2_ATTN_4WAVES keeps the round-1 geometry (A/B).
+  // The FORWARD at d = 64 is faster with 4-wave workgroups, two per CU (round 3, same-box: -5 % without, -12 % with dropout at
+  // L = 4096; the backward is neutral, d = 128 gains 2.5-6 % / 21-23 % from 8 waves): forward and backward pick independently
+  p.nw = (d == 256 || L < 256 || (flags & ORBIT2_ATTN_4WAVES)) ? 4 : 8;
+  p.nw_fwd = d == 64 ? 4 : p.nw;
+  p.ragged = (L % (p.nw * 32)) != 0;
+  p.ragged_fwd = (L % (p.nw_fwd * 32)) != 0;
+  p.fwd_w4 = attn_w4_ok(d, L, flags, ldq, ldo);
+  p.dq_w4 = attn_w4_ok(d, L, flags, ldq, ldq);               // (dO / dqkv rows are no wider than the qkv pitch)
+  // (the generated dK + dV kernel numbers query rows across the batch in 32 bits)
+  p.dkv = (p.dq_w4 && !split && (uint64_t)B * (uint64_t)H * (uint64_t)L < (1ull << 32)) ? DKV_W4 : d == 64 ? DKV_FUSED64
+          : split ? DKV_SPLIT : d == 256 ? DKV_FUSED256 : p.nw == 8 ? DKV_FUSED128 : DKV_SPLIT;
+  const auto rows = [&](int r, int threads) { return AttnLaunch{dim3((unsigned)(((L + r - 1) / r) * H * B)), dim3(threads)}; };
+  p.fwd = p.fwd_w4 ? rows(256, 256) : rows(p.nw_fwd * 32, p.nw_fwd * 64);
+  p.dq = p.dq_w4 ? rows(256, 256) : rows(p.nw * 32, p.nw * 64);
+  p.dkv_l = p.dkv == DKV_W4 ? rows(128, 256) : rows(p.nw * 32, p.nw * 64);
+  return p;
 }
-template <int DV, bool DR, int NW>
-static void launch_fwd_r(bool ragged, const void* qkv, void* out, float* lse, int B, int L, int H, float sc_log2, unsigned thr,
-                         float dscale, uint64_t seed, hipStream_t s, int ldo, int ldq) {
-  if (ragged) launch_fwd<DV, DR, true, NW>(qkv, out, lse, B, L, H, sc_log2, thr, dscale, seed, s, ldo, ldq);
-  else launch_fwd<DV, DR, false, NW>(qkv, out, lse, B, L, H, sc_log2, thr, dscale, seed, s, ldo, ldq);
+
+// the (d, waves) pairs the compiler-scheduled kernels are instantiated for, times dropout and ragged: f(D, NW, DROP, RAGGED)
+template <class F> static void attn_with_variant(int d, int nw, bool drop, bool ragged, F&& f) {
+  o2_with_flags([&](auto DR, auto RG) {
+    if (d == 256) f(o2_int<256>{}, o2_int<4>{}, DR, RG);
+    else if (d == 128 && nw == 8) f(o2_int<128>{}, o2_int<8>{}, DR, RG);
+    else if (d == 128) f(o2_int<128>{}, o2_int<4>{}, DR, RG);
+    else if (nw == 8) f(o2_int<64>{}, o2_int<8>{}, DR, RG);
+    else f(o2_int<64>{}, o2_int<4>{}, DR, RG);
+  }, drop, ragged);
 }
 
 extern "C" int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
@@ -1720,83 +1762,23 @@ extern "C" int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B,
   int rc = attn_check(qkv, out, B, L, H, d, drop_p);
   if (rc) return rc;
   if (!lse || ldo < H * d || (ldo & 7) || ldq < 3 * H * d || (ldq & 7)) return O2_ERR_ARG;
-  // (q stored pre-scaled: the kernels' multiplier is 1)
-  const float sc_log2 = (flags & ORBIT2_ATTN_Q_PRESCALED) ? 1.0f : (1.0f / sqrtf((float)d)) * 1.4426950408889634f;
-  const unsigned thr = (unsigned)(drop_p * 256.0f + 0.5f);
-  const float dscale = 256.0f / (256.0f - (float)thr);
+  const AttnPlan p = attn_plan(d, L, B, H, flags, ldq, ldo, drop_p);
   hipStream_t s = (hipStream_t)stream;
-  if (d == 128 && (flags & ORBIT2_ATTN_Q_PRESCALED) && !(flags & ORBIT2_ATTN_NO_W4) && L % 256 == 0 && L <= O2_AF_MAX_L &&
-      attn_w4_range_ok(L, ldq, ldo)) {
-    dim3 grid((unsigned)((L / 256) * H * B)), block(256);
-    if (thr) hipLaunchKernelGGL((attn_fwd_w4_kernel<true>), grid, block, 0, s, (const bf16_t*)qkv, (bf16_t*)out, lse, L, H, thr, dscale, seed, ldo, ldq);
-    else hipLaunchKernelGGL((attn_fwd_w4_kernel<false>), grid, block, 0, s, (const bf16_t*)qkv, (bf16_t*)out, lse, L, H, thr, dscale, seed, ldo, ldq);
-    O2_CHECK_LAUNCH();
-    return O2_OK;
-  }
-  const int nw = attn_waves_fwd(L, d, flags);
-  const bool ragged = (L % (nw * 32)) != 0;
-#define O2_FWD(DV, NWV)                                                                              \
-  do {                                                                                               \
-    if (thr) launch_fwd_r<DV, true, NWV>(ragged, qkv, out, lse, B, L, H, sc_log2, thr, dscale, seed, s, ldo, ldq);  \
-    else launch_fwd_r<DV, false, NWV>(ragged, qkv, out, lse, B, L, H, sc_log2, thr, dscale, seed, s, ldo, ldq);     \
-  } while (0)
-  if (d == 256) O2_FWD(256, 4);
-  else if (d == 128) { if (nw == 8) O2_FWD(128, 8); else O2_FWD(128, 4); }
-  else { if (nw == 8) O2_FWD(64, 8); else O2_FWD(64, 4); }
+  const bf16_t* q_ = (const bf16_t*)qkv;
+  bf16_t* o_ = (bf16_t*)out;
+#define O2_FWD(KERN, ...) hipLaunchKernelGGL(KERN, p.fwd.grid, p.fwd.block, 0, s, q_, o_, lse, L, H, __VA_ARGS__, seed, ldo, ldq)
+  if (p.fwd_w4)
+    o2_with_flags([&](auto DR) { O2_FWD((attn_fwd_w4_kernel<DR>), p.thr, p.dscale); }, p.drop);
+  else
+    attn_with_variant(d, p.nw_fwd, p.drop, p.ragged_fwd, [&](auto DV, auto NW, auto DR, auto RG) {
+      if constexpr (!DR) {                  // (the lazy-rescaling kernel has no dropout form)
+        if (p.fwd_lazy) { O2_FWD((attn_fwd_lazy_kernel<DV, RG, NW>), p.opmul, p.thr, p.dscale); return; }
+      }
+      O2_FWD((attn_fwd_kernel<DV, DR, RG, NW>), p.opmul, p.thr, p.dscale);
+    });
 #undef O2_FWD
   O2_CHECK_LAUNCH();
   return O2_OK;
-}
-
-template <int DV, bool DR, bool RG, int NW>
-static void launch_bwd(const bf16_t* q_, const bf16_t* do_, const float* lse, const float* delta, bf16_t* dq_, int B, int L,
-                       int H, float scale, unsigned thr, float dscale, uint64_t seed, hipStream_t s, int flags, int Lp, int ldq) {
-  dim3 grid(((L + NW * 32 - 1) / (NW * 32)) * H * B), block(NW * 64);
-  const bool pre = (flags & ORBIT2_ATTN_Q_PRESCALED) != 0;
-  const float opmul = pre ? 1.0f : scale * 1.4426950408889634f, kgrad = pre ? 0.6931471805599453f : scale;
-  const bool w4_range = attn_w4_range_ok(L, ldq, ldq);     // (dO / dqkv rows are no wider than the qkv pitch)
-  if (DV == 128 && pre && !(flags & ORBIT2_ATTN_NO_W4) && L % 256 == 0 && L <= O2_AF_MAX_L && w4_range) {
-    // the generated one-wave-per-SIMD dQ kernel (256-row workgroups whatever NW is)
-    hipLaunchKernelGGL((attn_bwd_dq_w4_kernel<DR>), dim3((unsigned)((L / 256) * H * B)), dim3(256), 0, s, q_, do_, lse, delta, dq_,
-                       L, H, thr, DR ? scale * dscale : scale, seed, Lp, ldq);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DV, DR, RG, NW>), grid, block, 0, s, q_, do_, lse, delta, dq_, L, H, scale, thr, dscale,
-                       seed, opmul, Lp, ldq);
-  }
-  if (DV == 128 && pre && !(flags & (ORBIT2_ATTN_NO_W4 | ORBIT2_ATTN_SPLIT_DKV)) && L % 256 == 0 && L <= O2_AF_MAX_L &&
-      (uint64_t)B * (uint64_t)H * (uint64_t)L < (1ull << 32) && w4_range) {
-    // the generated one-wave-per-SIMD dK + dV kernel: 128 keys per workgroup
-    hipLaunchKernelGGL((attn_bwd_dkv_w4_kernel<DR>), dim3((unsigned)((L / 128) * H * B)), dim3(256), 0, s, q_, do_, lse, delta, dq_,
-                       L, H, thr, DR ? kgrad * dscale : kgrad, DR ? dscale : 1.0f, seed, Lp, ldq);
-    return;
-  }
-  if constexpr (DV == 64) {       // dK and dV in one pass (fits two waves per SIMD)
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<DV, DR, 0, RG, NW>), grid, block, 0, s, q_, do_, lse, delta, dq_, L, H, scale, thr,
-                       dscale, seed, opmul, kgrad, Lp, ldq);
-  } else if (DV == 256 && !(flags & ORBIT2_ATTN_SPLIT_DKV)) {             // one pass at one wave per SIMD (interm_10b)
-    hipLaunchKernelGGL((attn_bwd_dkv256_kernel<DR, RG>), grid, block, 0, s, q_, do_, lse, delta, dq_, L, H, scale, thr, dscale,
-                       seed, opmul, kgrad, Lp, ldq);
-  } else if (DV == 128 && NW == 8 && !(flags & ORBIT2_ATTN_SPLIT_DKV)) {   // one pass, V rows in LDS
-    hipLaunchKernelGGL((attn_bwd_dkv128_kernel<DR, RG>), grid, block, 0, s, q_, do_, lse, delta, dq_, L, H, scale, thr, dscale,
-                       seed, opmul, kgrad, Lp, ldq);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<DV, DR, 1, RG, NW>), grid, block, 0, s, q_, do_, lse, delta, dq_, L, H, scale, thr,
-                       dscale, seed, opmul, kgrad, Lp, ldq);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<DV, DR, 2, RG, NW>), grid, block, 0, s, q_, do_, lse, delta, dq_, L, H, scale, thr,
-                       dscale, seed, opmul, kgrad, Lp, ldq);
-  }
-}
-template <int DV, int NW>
-static void launch_bwd_r(bool drop, bool ragged, const bf16_t* q_, const bf16_t* do_, const float* lse, const float* delta,
-                         bf16_t* dq_, int B, int L, int H, float scale, unsigned thr, float dscale, uint64_t seed, hipStream_t s,
-                         int flags, int Lp, int ldq) {
-  if (drop) {
-    if (ragged) launch_bwd<DV, true, true, NW>(q_, do_, lse, delta, dq_, B, L, H, scale, thr, dscale, seed, s, flags, Lp, ldq);
-    else launch_bwd<DV, true, false, NW>(q_, do_, lse, delta, dq_, B, L, H, scale, thr, dscale, seed, s, flags, Lp, ldq);
-  } else {
-    if (ragged) launch_bwd<DV, false, true, NW>(q_, do_, lse, delta, dq_, B, L, H, scale, thr, dscale, seed, s, flags, Lp, ldq);
-    else launch_bwd<DV, false, false, NW>(q_, do_, lse, delta, dq_, B, L, H, scale, thr, dscale, seed, s, flags, Lp, ldq);
-  }
 }
 
 static int attn_lpad(int L) { return ((L + 63) / 64) * 64 + 64; }     // padded row stride of the statistics tables
@@ -1812,31 +1794,47 @@ extern "C" int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* 
   int rc = attn_check(qkv, out, B, L, H, d, drop_p);
   if (rc) return rc;
   if (!dout || !lse || !delta || !dqkv || ldo < H * d || (ldo & 7) || ldq < 3 * H * d || (ldq & 7)) return O2_ERR_ARG;
-  const float scale = 1.0f / sqrtf((float)d);
-  const unsigned thr = (unsigned)(drop_p * 256.0f + 0.5f);
-  const float dscale = 256.0f / (256.0f - (float)thr);
+  const AttnPlan p = attn_plan(d, L, B, H, flags, ldq, ldo, drop_p);
   hipStream_t s = (hipStream_t)stream;
   // per-row statistics tables (attn_delta_kernel): delta = workspace of orbit2_attn_bwd_ws_floats(B, L, H) floats
   const int Lp = attn_lpad(L);
-  float* ws0 = delta;
-  float* ws1 = delta + (size_t)B * H * Lp;
+  const float *ws0 = delta, *ws1 = delta + (size_t)B * H * Lp;
   const int64_t nrows = (int64_t)B * Lp * H;
   hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((nrows * 16 + 255) / 256)), dim3(256), 0, s,
-                     (const bf16_t*)out, (const bf16_t*)dout, lse, delta, B, L, H, d, Lp, 1.0f / dscale, ldo);
+                     (const bf16_t*)out, (const bf16_t*)dout, lse, delta, B, L, H, d, Lp, 1.0f / p.dscale, ldo);
   O2_CHECK_LAUNCH();
-  const bf16_t* q_ = (const bf16_t*)qkv;
-  const bf16_t* do_ = (const bf16_t*)dout;
+  const bf16_t *q_ = (const bf16_t*)qkv, *do_ = (const bf16_t*)dout;
   bf16_t* dq_ = (bf16_t*)dqkv;
-  const int nw = attn_waves(L, d, flags);
-  const bool ragged = (L % (nw * 32)) != 0;
-  if (d == 256) launch_bwd_r<256, 4>(thr != 0, ragged, q_, do_, ws0, ws1, dq_, B, L, H, scale, thr, dscale, seed, s, flags, Lp, ldq);
-  else if (d == 128) {
-    if (nw == 8) launch_bwd_r<128, 8>(thr != 0, ragged, q_, do_, ws0, ws1, dq_, B, L, H, scale, thr, dscale, seed, s, flags, Lp, ldq);
-    else launch_bwd_r<128, 4>(thr != 0, ragged, q_, do_, ws0, ws1, dq_, B, L, H, scale, thr, dscale, seed, s, flags, Lp, ldq);
-  } else {
-    if (nw == 8) launch_bwd_r<64, 8>(thr != 0, ragged, q_, do_, ws0, ws1, dq_, B, L, H, scale, thr, dscale, seed, s, flags, Lp, ldq);
-    else launch_bwd_r<64, 4>(thr != 0, ragged, q_, do_, ws0, ws1, dq_, B, L, H, scale, thr, dscale, seed, s, flags, Lp, ldq);
+  // a backward launch: the operands every kernel takes, its own scalars, the table pitch and the row pitch
+#define O2_BWD(KERN, PASS, ...) \
+  hipLaunchKernelGGL(KERN, p.PASS.grid, p.PASS.block, 0, s, q_, do_, ws0, ws1, dq_, L, H, __VA_ARGS__, Lp, ldq)
+#define O2_BWD_CS p.scale, p.thr, p.dscale, seed, p.opmul          /* scalars of the compiler-scheduled kernels */
+  if (p.dq_w4)
+    o2_with_flags([&](auto DR) { O2_BWD((attn_bwd_dq_w4_kernel<DR>), dq, p.thr, p.dq_w4_scale, seed); }, p.drop);
+  else
+    attn_with_variant(d, p.nw, p.drop, p.ragged,
+                      [&](auto DV, auto NW, auto DR, auto RG) { O2_BWD((attn_bwd_dq_kernel<DV, DR, RG, NW>), dq, O2_BWD_CS); });
+  switch (p.dkv) {
+    case DKV_W4:
+      o2_with_flags([&](auto DR) { O2_BWD((attn_bwd_dkv_w4_kernel<DR>), dkv_l, p.thr, p.dkv_w4_kgrad, p.dkv_w4_dscale, seed); }, p.drop);
+      break;
+    case DKV_FUSED128:
+      o2_with_flags([&](auto DR, auto RG) { O2_BWD((attn_bwd_dkv128_kernel<DR, RG>), dkv_l, O2_BWD_CS, p.kgrad); }, p.drop, p.ragged);
+      break;
+    case DKV_FUSED256:
+      o2_with_flags([&](auto DR, auto RG) { O2_BWD((attn_bwd_dkv256_kernel<DR, RG>), dkv_l, O2_BWD_CS, p.kgrad); }, p.drop, p.ragged);
+      break;
+    case DKV_FUSED64:
+    case DKV_SPLIT:     // one kernel template: pass 0 = dK and dV together (instantiated at d = 64), passes 1, 2 = dK, dV (d = 128, 256)
+      attn_with_variant(d, p.nw, p.drop, p.ragged, [&](auto DV, auto NW, auto DR, auto RG) {
+        auto pass = [&](auto WHICH) { O2_BWD((attn_bwd_dkv_kernel<DV, DR, WHICH, RG, NW>), dkv_l, O2_BWD_CS, p.kgrad); };
+        if constexpr (DV == 64) pass(o2_int<0>{});
+        else { pass(o2_int<1>{}); pass(o2_int<2>{}); }
+      });
+      break;
   }
+#undef O2_BWD
+#undef O2_BWD_CS
   O2_CHECK_LAUNCH();
   return O2_OK;
 }

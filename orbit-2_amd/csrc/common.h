@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #define O2_OK 0
 #define O2_ERR_ARG (-1)
@@ -227,6 +228,15 @@ static inline void o2_sum_parts(const float* parts, int nparts, int64_t stride, 
     hipLaunchKernelGGL(o2_sum_parts_kernel<1>, dim3((unsigned)((nelem + 255) / 256)), dim3(256), 0, s, parts, nparts, stride,
                        out, nelem, scale, accumulate);
   }
+}
+
+// ---- host dispatch: run-time flags as compile-time constants.  o2_with_flags(f, a, b, ...) calls f(A, B, ...) with
+// std::true_type / std::false_type objects, so a generic lambda can name a kernel template once: kernel<A, B> for all forms.
+template <int V> using o2_int = std::integral_constant<int, V>;
+template <class F> static inline void o2_with_flags(F&& f) { f(); }
+template <class F, class... Rest> static inline void o2_with_flags(F&& f, bool flag, Rest... rest) {
+  if (flag) o2_with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else o2_with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
 #define O2_CHECK_LAUNCH()                                   \

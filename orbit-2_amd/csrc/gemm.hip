@@ -1332,23 +1332,116 @@ static int gemm_make_epi(const orbit2_gemm_args* a, Epi& e) {
   return O2_OK;
 }
 
-extern "C" int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, void* stream) {
-  if (!args || n <= 0 || n > ORBIT2_GEMM_MAX_GROUP) return O2_ERR_ARG;
-  if (n == 1) return orbit2_gemm_bf16(args, stream);
-  for (int i = 0; i < n; ++i)
-    if (args[i].colsum_ws) return O2_ERR_UNSUPPORTED;      // single launches only (orbit2_gemm_bf16_colsum_rows)
-  GArgs g;
+// ---- kernel selection.  gemm_plan / gemm_group_plan decide which kernel takes a call and on which grid; they launch nothing.
+// The entry points below make the epilogue, plan, and map the plan to an instantiation.
+enum GemmFamily {
+  GEMM_128,        // 128 x 128 tiles, 2 workgroups/CU, ragged K: small or ragged problems
+  GEMM_128_HALF,   // the same kernel on 64-row tiles (A K-contiguous)
+  GEMM_256T,       // 8-wave 8-phase kernel, 256 x 256 tiles, ragged M / N
+  GEMM_256W        // 4-wave kernel (one wave per SIMD), whole 256 x 256 tiles
+};
+struct GemmPlan {
+  GemmFamily family;
+  bool a_kc, b_kc;          // operand form
+  int ek;                   // GEMM_256W: compile-time epilogue kind (0: the runtime epilogue)
+  bool stamped;             // GEMM_256W: the stamped diagnostic form (hint 261)
+  int tiles_m, tiles_n;
+  unsigned grid, block;
+  bool fuses_colsum;        // this launch fills colsum_ws (orbit2_gemm_bf16_colsum_rows)
+};
+static unsigned gemm_block(GemmFamily f) { return f == GEMM_256T ? 512 : 256; }
+// the 4-wave kernels number the operand forms: 0 both K-contiguous, 1 A only, 2 neither, 3 B only
+constexpr int w4_form(bool a_kc, bool b_kc) { return a_kc ? (b_kc ? 0 : 1) : (b_kc ? 3 : 2); }
+// the compile-time epilogue kinds are instantiated in the forms whose hot layers have them: kinds 1 (fc1) and 2 (proj, fc2) in
+// the forward form, kind 3 (fc2's input gradient) in the input-gradient form
+constexpr int w4_compiled_kind(int form, int kind) {
+  return ((form == 0 && (kind == 1 || kind == 2)) || (form == 1 && kind == 3)) ? kind : 0;
+}
+
+// "fills the chip": 256 x 256 tiles run one per CU in rounds of 256, so a 256-tile kernel needs at least 192 tiles and rounds
+// that are at least 70 % full on average (measured: tools/gemm_p8_ab.py, gemm_t8_ab.py, gemm_w4_ab.py; profiles/r02_gemm_*)
+static bool gemm_fills_chip(long t256) {
+  const long rounds = (t256 + 255) / 256;
+  const double util = (double)t256 / (double)(rounds * 256);
+  return t256 >= 192 && util >= 0.70;
+}
+// a group has no utilisation term: it exists to fill each problem's last round with the next one's tiles, and the caller
+// balances the group's own last round (climate_learn/_ops.py: _dw_balance_plan), so only the tile count matters
+static bool gemm_group_fills_chip(long t256) { return t256 >= 192; }
+
+static int gemm_plan(const orbit2_gemm_args* a, const Epi& e, GemmPlan& p) {
+  p = GemmPlan{};
+  p.a_kc = a->a_kc != 0;
+  p.b_kc = a->b_kc != 0;
+  const int form = w4_form(p.a_kc, p.b_kc);
+  // tile choice: the 256^2 kernels (1 workgroup/CU) need enough tiles to fill the chip; the 128^2 kernel (2 workgroups/CU)
+  // takes small or ragged problems.  tile_hint forces one (tests / tuning).
+  int tile = a->tile_hint;
+  if (tile == 257 || tile == 258) tile = 256;       // hints of the round-2 A/B tools: the same kernel
+  if (tile == 64) tile = 128;                         // the 128-wide kernel on 64-row tiles (below)
+  if (tile != 128 && tile != 256 && tile != 260 && tile != 261 && tile != 262) {
+    // measured on MI355X (profiles/r02_gemm_*, r03_gemm_w4_*): a 256-tile kernel wins in every operand form whenever its tiles
+    // fill the chip -- the 4-wave kernel on whole tiles (+7 ... +16 % over the 8-phase kernel), the 8-phase kernel on ragged M / N
+    const long t256 = (long)((a->M + 255) / 256) * ((a->N + 255) / 256);
+    tile = (a->K % BK3 == 0 && a->K >= 2 * BK3 && a->M >= 256 && a->N >= 256 && gemm_fills_chip(t256)) ? 256 : 128;
+    // the 4-wave kernel: whole tiles, and an epilogue that is not vector-ALU heavy -- one wave per SIMD issues vector
+    // instructions at half the rate two waves reach, so GELU / GELU' / dropout epilogues (~35 instructions per value) cost it
+    // more than its main loop gains (profiles/r03_gemm_w4_epilogues.txt); K-contiguous operands whose rows are BOTH a
+    // multiple of 8 KiB apart (fc2-shaped: every row's k-offset on the same memory channel) also stay on the 8-phase kernel
+    // (the hot heavy combinations have compile-time epilogues there -- w4_compiled_kind -- and do go to it)
+    const int ek = w4_epi_kind(e);
+    const bool heavy = (e.act != 0 || e.thr != 0 || e.dgelu_pre != nullptr) && !((ek == 1 || ek == 2) && form == 0);
+    const bool camped = p.a_kc && p.b_kc && a->K >= 8192 && a->lda % 4096 == 0 && a->ldb % 4096 == 0;
+    if (tile == 256 && a->M % 256 == 0 && a->N % 256 == 0 && !heavy && !camped) tile = 260;
+  }
+  if (tile >= 260) {                                  // (260, 261, 262) the 4-wave kernel: whole tiles
+    if (a->M % 256 || a->N % 256 || a->K % BK3) return O2_ERR_ARG;
+    p.family = GEMM_256W;
+    p.stamped = tile == 261;
+#ifndef O2_W4_STAMP
+    if (p.stamped) return O2_ERR_UNSUPPORTED;
+#endif
+    // (hint 262: the runtime epilogue in place of the compile-time kinds -- A/B, bit-identity tests)
+    p.ek = (tile == 260) ? w4_compiled_kind(form, w4_epi_kind(e)) : 0;
+    // kind 3 is the only epilogue that fills colsum_ws; offered under the documented hints (auto, 260) and two K-tiles or more
+    p.fuses_colsum = p.ek == 3 && a->K >= 2 * BK3 && (a->tile_hint == 0 || a->tile_hint == 260);
+  } else {
+    p.family = tile == 256 ? GEMM_256T : GEMM_128;
+    if (a->tile_hint == 64 && !p.a_kc) return O2_ERR_ARG;
+  }
+  const int T = p.family == GEMM_128 ? BM : BM2;      // square tiles
+  p.tiles_m = (a->M + T - 1) / T;
+  p.tiles_n = (a->N + T - 1) / T;
+  // fewer 128 x 128 tiles than two per CU and a K-contiguous A: 64-row tiles, so that every CU still holds two workgroups
+  // (hint 64 forces them, hint 128 forbids them)
+  if (p.family == GEMM_128 && p.a_kc &&
+      (a->tile_hint == 64 || (a->tile_hint != 128 && (long)p.tiles_m * p.tiles_n < 2 * 256 && a->M > 64))) {
+    p.family = GEMM_128_HALF;
+    p.tiles_m = (a->M + 63) / 64;
+  }
+  p.grid = (unsigned)(p.tiles_m * p.tiles_n);
+  p.block = gemm_block(p.family);
+  return O2_OK;
+}
+
+// a group (n >= 2): the kernel family for all of it, and in g every problem with its tile range and the pacing mode
+static int gemm_group_plan(const orbit2_gemm_args* args, int n, GemmFamily& family, GArgs& g) {
   g.n = n;
   g.pace = 0;
-  // 256-tile 8-phase kernel when every problem of the group can take it and the group fills the chip; 128-tile otherwise
-  bool big = args[0].tile_hint != 128;
+  // 256-tile kernels when every problem of the group can take them and the group fills the chip -- the 4-wave kernel when all
+  // tiles are whole (hint 256 on the first problem forces the 8-phase kernel, 128 the 128-tile kernel); 128-tile otherwise
+  bool big = args[0].tile_hint != 128, whole = args[0].tile_hint != 256;
   long t256 = 0;
+  int kmin = args[0].K;
   for (int i = 0; i < n; ++i) {
     const orbit2_gemm_args* a = args + i;
     if (a->K % BK3 || a->K < 2 * BK3 || a->M < 256 || a->N < 256) big = false;
+    whole = whole && a->M % 256 == 0 && a->N % 256 == 0;
     t256 += (long)((a->M + 255) / 256) * ((a->N + 255) / 256);
+    kmin = a->K < kmin ? a->K : kmin;
   }
-  if (args[0].tile_hint < 256 && t256 < 192) big = false;
+  if (args[0].tile_hint < 256 && !gemm_group_fills_chip(t256)) big = false;
+  family = !big ? GEMM_128 : whole ? GEMM_256W : GEMM_256T;
   const int TB = big ? 256 : 128;
   int total = 0;
   for (int i = 0; i < n; ++i) {
@@ -1363,181 +1456,81 @@ extern "C" int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, voi
     total += P.tiles_m * P.tiles_n;
     P.tile_end = total;
   }
-  hipStream_t s = (hipStream_t)stream;
-  if (big) {
-    bool whole = args[0].tile_hint != 256;           // the 4-wave kernel takes whole tiles only (hint 256 forces the 8-phase kernel)
-    for (int i = 0; i < n; ++i) whole = whole && args[i].M % 256 == 0 && args[i].N % 256 == 0;
-    if (whole) {
-      dim3 grid(total), block(256);
-      // cohort start barrier: every problem's tiles sweep >= 512 K-tiles (a round lasts >= 0.6 ms: the bounded wait is noise
-      // against it, and a lost cohort costs a whole sweep of re-fetched strips)
-      // ORBIT2_W4_PACE: 0 off, 1 (default) the cohort start barrier, 2 + the check points inside the sweep.  2 brings the launch's
-      // bytes beyond L2 to the tile-walk bound (48 GB, 3.7 x algorithmic; 1.71 GHz stand-alone) and -2.3 % stand-alone, but the
-      // SAME time in the step (166.6 vs 166.6 ms per step, profiles/r06_pace2b_instep.txt): every column group then sweeps at the
-      // slowest group's rate, which is what a round takes anyway.  Kept selectable, not default.
-      static const int pace_env = [] { const char* e = getenv("ORBIT2_W4_PACE"); return e ? atoi(e) : 1; }();
-      int kmin = args[0].K;
-      for (int i = 1; i < n; ++i) kmin = args[i].K < kmin ? args[i].K : kmin;
-      g.pace = (O2_W4_WALK && pace_env && kmin >= 512 * BK3 && total > 256) ? pace_env : 0;
-      if (args[0].a_kc && args[0].b_kc) hipLaunchKernelGGL((gemm256w_grouped_kernel<0>), grid, block, 0, s, g);
-      else if (args[0].a_kc) hipLaunchKernelGGL((gemm256w_grouped_kernel<1>), grid, block, 0, s, g);
-      else if (args[0].b_kc) hipLaunchKernelGGL((gemm256w_grouped_kernel<3>), grid, block, 0, s, g);
-      else hipLaunchKernelGGL((gemm256w_grouped_kernel<2>), grid, block, 0, s, g);
-      O2_CHECK_LAUNCH();
-      return O2_OK;
-    }
-    dim3 grid(total), block(512);
-    if (args[0].a_kc && args[0].b_kc) hipLaunchKernelGGL((gemm256t_grouped_kernel<true, true>), grid, block, 0, s, g);
-    else if (args[0].a_kc) hipLaunchKernelGGL((gemm256t_grouped_kernel<true, false>), grid, block, 0, s, g);
-    else if (args[0].b_kc) hipLaunchKernelGGL((gemm256t_grouped_kernel<false, true>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((gemm256t_grouped_kernel<false, false>), grid, block, 0, s, g);
-    O2_CHECK_LAUNCH();
-    return O2_OK;
+  if (family == GEMM_256W) {
+    // cohort start barrier: every problem's tiles sweep >= 512 K-tiles (a round lasts >= 0.6 ms: the bounded wait is noise
+    // against it, and a lost cohort costs a whole sweep of re-fetched strips)
+    // ORBIT2_W4_PACE: 0 off, 1 (default) the cohort start barrier, 2 + the check points inside the sweep.  2 brings the launch's
+    // bytes beyond L2 to the tile-walk bound (48 GB, 3.7 x algorithmic; 1.71 GHz stand-alone) and -2.3 % stand-alone, but the
+    // SAME time in the step (166.6 vs 166.6 ms per step, profiles/r06_pace2b_instep.txt): every column group then sweeps at the
+    // slowest group's rate, which is what a round takes anyway.  Kept selectable, not default.
+    static const int pace_env = [] { const char* e = getenv("ORBIT2_W4_PACE"); return e ? atoi(e) : 1; }();
+    g.pace = (O2_W4_WALK && pace_env && kmin >= 512 * BK3 && total > 256) ? pace_env : 0;
   }
-  dim3 grid(total), block(256);
-  if (args[0].a_kc && args[0].b_kc) hipLaunchKernelGGL((gemm128_grouped_kernel<true, true>), grid, block, 0, s, g);
-  else if (args[0].a_kc) hipLaunchKernelGGL((gemm128_grouped_kernel<true, false>), grid, block, 0, s, g);
-  else if (args[0].b_kc) hipLaunchKernelGGL((gemm128_grouped_kernel<false, true>), grid, block, 0, s, g);
-  else hipLaunchKernelGGL((gemm128_grouped_kernel<false, false>), grid, block, 0, s, g);
-  O2_CHECK_LAUNCH();
   return O2_OK;
-}
-
-// does this call run on the 4-wave kernel with epilogue kind 3 (the only path that fills colsum_ws)?  Mirrors the dispatch below.
-static bool gemm_fuses_colsum(const orbit2_gemm_args* a, const Epi& e) {
-  if (!(a->a_kc && !a->b_kc) || a->M % 256 || a->N % 256 || a->K % 64 || a->K < 128 || w4_epi_kind(e) != 3) return false;
-  if (a->tile_hint == 260) return true;
-  if (a->tile_hint != 0) return false;
-  const long t256 = (long)(a->M / 256) * (a->N / 256);
-  const long rounds = (t256 + 255) / 256;
-  return t256 >= 192 && (double)t256 / (double)(rounds * 256) >= 0.70;
-}
-
-extern "C" int orbit2_gemm_bf16_colsum_rows(const orbit2_gemm_args* a) {
-  Epi e;
-  if (!a || gemm_make_epi(a, e)) return 0;
-  return gemm_fuses_colsum(a, e) ? a->M / 256 : 0;
 }
 
 extern "C" int orbit2_gemm_bf16(const orbit2_gemm_args* a, void* stream) {
   Epi e;
-  const int rc_epi = gemm_make_epi(a, e);
-  if (rc_epi) return rc_epi;
-  if (a->colsum_ws && !gemm_fuses_colsum(a, e)) return O2_ERR_UNSUPPORTED;   // ask orbit2_gemm_bf16_colsum_rows first
+  GemmPlan p;
+  int rc = gemm_make_epi(a, e);
+  if (rc) return rc;
+  rc = gemm_plan(a, e, p);
+  if (a->colsum_ws && !p.fuses_colsum) return O2_ERR_UNSUPPORTED;   // ask orbit2_gemm_bf16_colsum_rows first
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const bf16_t* A = (const bf16_t*)a->A;
-  const bf16_t* B = (const bf16_t*)a->B;
-  // tile choice: the 256^2 8-phase kernel (1 workgroup/CU) needs enough tiles to fill the chip; the 128^2 kernel
-  // (2 workgroups/CU) takes small or ragged problems.  tile_hint forces one (tests / tuning).
-  const long t256 = (long)((a->M + 255) / 256) * ((a->N + 255) / 256);
-  int tile = a->tile_hint;
-  if (tile == 257 || tile == 258) tile = 256;       // hints of the round-2 A/B tools: the same kernel
-  if (tile == 64) tile = 128;                         // the 128-wide kernel on 64-row tiles (see the dispatch at the end)
-  if (tile != 128 && tile != 256 && tile != 260 && tile != 261 && tile != 262) {
-    // measured on MI355X (tools/gemm_p8_ab.py, tools/gemm_t8_ab.py, tools/gemm_w4_ab.py; profiles/r02_gemm_*, r03_gemm_w4_*): a
-    // 256-tile kernel wins in every operand form whenever its tiles fill the chip -- the 4-wave kernel on whole tiles
-    // (+7 ... +16 % over the 8-phase kernel), the 8-phase kernel on ragged M / N; the 128^2 kernel (2 workgroups/CU, ragged K)
-    // takes small or ragged problems
-    const long rounds = (t256 + 255) / 256;
-    const double util = (double)t256 / (double)(rounds * 256);
-    tile = (a->K % BK3 == 0 && a->K >= 2 * BK3 && a->M >= 256 && a->N >= 256 && t256 >= 192 && util >= 0.70) ? 256 : 128;
-    // the 4-wave kernel: whole tiles, and an epilogue that is not vector-ALU heavy -- one wave per SIMD issues vector
-    // instructions at half the rate two waves reach, so GELU / GELU' / dropout epilogues (~35 instructions per value) cost it
-    // more than its main loop gains (profiles/r03_gemm_w4_epilogues.txt); K-contiguous operands whose rows are BOTH a
-    // multiple of 8 KiB apart (fc2-shaped: every row's k-offset on the same memory channel) also stay on the 8-phase kernel
-    // (the three hot heavy combinations have compile-time epilogues there -- w4_epi_kind -- and do go to it)
-    const int form_ = a->a_kc ? (a->b_kc ? 0 : 1) : (a->b_kc ? 3 : 2);
-    const int ek_ = w4_epi_kind(e);
-    const bool heavy = (e.act != 0 || e.thr != 0 || e.dgelu_pre != nullptr) && !((ek_ == 1 || ek_ == 2) && form_ == 0);
-    const bool camped = a->a_kc && a->b_kc && a->K >= 8192 && a->lda % 4096 == 0 && a->ldb % 4096 == 0;
-    if (tile == 256 && a->M % 256 == 0 && a->N % 256 == 0 && !heavy && !camped) tile = 260;
-  }
-  const bool w4_runtime_epi = tile == 262;             // hint 262: the 4-wave kernel with the runtime epilogue (A/B, bit-identity tests)
-  if (tile == 262) tile = 260;
-  if (tile == 260 || tile == 261) {                   // 4-wave kernel: whole tiles (261: its stamped diagnostic form)
-    if (a->M % 256 || a->N % 256 || a->K % BK3) return O2_ERR_ARG;
-    const int tiles_m = a->M / BM2, tiles_n = a->N / BN2;
-    const dim3 grid(tiles_m * tiles_n), block(256);
-    const int form = a->a_kc ? (a->b_kc ? 0 : 1) : (a->b_kc ? 3 : 2);
-#define O2_W4_LAUNCH(F, S) hipLaunchKernelGGL((gemm256w_kernel<F, S>), grid, block, 0, s, A, B, a->M, a->N, a->K, a->lda, a->ldb, tiles_m, tiles_n, e)
-    const int ek = w4_runtime_epi ? 0 : w4_epi_kind(e);
-#define O2_W4_LAUNCH_EK(F, EKV) hipLaunchKernelGGL((gemm256w_kernel<F, false, EKV>), grid, block, 0, s, A, B, a->M, a->N, a->K, a->lda, a->ldb, tiles_m, tiles_n, e)
-    if (tile == 260 && form == 0 && ek == 1) { O2_W4_LAUNCH_EK(0, 1); }
-    else if (tile == 260 && form == 0 && ek == 2) { O2_W4_LAUNCH_EK(0, 2); }
-    else if (tile == 260 && form == 1 && ek == 3) { O2_W4_LAUNCH_EK(1, 3); }
-    else if (tile == 260) {
-      switch (form) {
-        case 0: O2_W4_LAUNCH(0, false); break;
-        case 1: O2_W4_LAUNCH(1, false); break;
-        case 2: O2_W4_LAUNCH(2, false); break;
-        default: O2_W4_LAUNCH(3, false); break;
-      }
-    } else {
+#define O2_GEMM_LAUNCH(...)                                                                                              \
+  hipLaunchKernelGGL((__VA_ARGS__), dim3(p.grid), dim3(p.block), 0, s, (const bf16_t*)a->A, (const bf16_t*)a->B, a->M, a->N, \
+                     a->K, a->lda, a->ldb, p.tiles_m, p.tiles_n, e)
+  o2_with_flags([&](auto AK, auto BK) {
+    constexpr int FORM = w4_form(AK, BK);
+    switch (p.family) {
+      case GEMM_128: O2_GEMM_LAUNCH(gemm128_kernel<AK, BK>); break;
+      case GEMM_128_HALF: if constexpr (AK) O2_GEMM_LAUNCH(gemm128_kernel<true, BK, 64>); break;
+      case GEMM_256T: O2_GEMM_LAUNCH(gemm256t_kernel<AK, BK>); break;
+      case GEMM_256W: {
+        auto kind = [&](auto EK) {        // one instantiation per compiled (form, kind) pair; p.ek names exactly one of them
+          if constexpr (w4_compiled_kind(FORM, EK) == EK)
+            if (p.ek == EK) O2_GEMM_LAUNCH(gemm256w_kernel<FORM, false, EK>);
+        };
+        if (!p.stamped) { kind(o2_int<0>{}); kind(o2_int<1>{}); kind(o2_int<2>{}); kind(o2_int<3>{}); }
 #ifdef O2_W4_STAMP
-      switch (form) {
-        case 0: O2_W4_LAUNCH(0, true); break;
-        case 1: O2_W4_LAUNCH(1, true); break;
-        case 2: O2_W4_LAUNCH(2, true); break;
-        default: O2_W4_LAUNCH(3, true); break;
-      }
-#else
-      return O2_ERR_UNSUPPORTED;
+        else O2_GEMM_LAUNCH(gemm256w_kernel<FORM, true>);
 #endif
+        break;
+      }
     }
-#undef O2_W4_LAUNCH
-#undef O2_W4_LAUNCH_EK
-    O2_CHECK_LAUNCH();
-    return O2_OK;
-  }
-  if (tile == 256) {
-    const int tiles_m = (a->M + BM2 - 1) / BM2, tiles_n = (a->N + BN2 - 1) / BN2;
-    dim3 grid(tiles_m * tiles_n), block(512);
-    if (a->a_kc && a->b_kc)
-      hipLaunchKernelGGL((gemm256t_kernel<true, true>), grid, block, 0, s, A, B, a->M, a->N, a->K, a->lda, a->ldb,
-                         tiles_m, tiles_n, e);
-    else if (a->a_kc && !a->b_kc)
-      hipLaunchKernelGGL((gemm256t_kernel<true, false>), grid, block, 0, s, A, B, a->M, a->N, a->K, a->lda, a->ldb,
-                         tiles_m, tiles_n, e);
-    else if (!a->a_kc && a->b_kc)
-      hipLaunchKernelGGL((gemm256t_kernel<false, true>), grid, block, 0, s, A, B, a->M, a->N, a->K, a->lda, a->ldb,
-                         tiles_m, tiles_n, e);
-    else
-      hipLaunchKernelGGL((gemm256t_kernel<false, false>), grid, block, 0, s, A, B, a->M, a->N, a->K, a->lda, a->ldb,
-                         tiles_m, tiles_n, e);
-    O2_CHECK_LAUNCH();
-    return O2_OK;
-  }
-  int tiles_m = (a->M + BM - 1) / BM;
-  const int tiles_n = (a->N + BN - 1) / BN;
-  // fewer 128 x 128 tiles than two per CU and a K-contiguous A: 64-row tiles, so that every CU still holds two workgroups
-  // (hint 64 forces them, hint 128 forbids them)
-  if (a->tile_hint == 64 && !a->a_kc) return O2_ERR_ARG;
-  const bool half_rows = a->a_kc && (a->tile_hint == 64 || (a->tile_hint != 128 && (long)tiles_m * tiles_n < 2 * 256 && a->M > 64));
-  if (half_rows) {
-    tiles_m = (a->M + 63) / 64;
-    dim3 grid(tiles_m * tiles_n), block(256);
-    if (a->b_kc)
-      hipLaunchKernelGGL((gemm128_kernel<true, true, 64>), grid, block, 0, s, A, B, a->M, a->N, a->K, a->lda, a->ldb, tiles_m,
-                         tiles_n, e);
-    else
-      hipLaunchKernelGGL((gemm128_kernel<true, false, 64>), grid, block, 0, s, A, B, a->M, a->N, a->K, a->lda, a->ldb, tiles_m,
-                         tiles_n, e);
-    O2_CHECK_LAUNCH();
-    return O2_OK;
-  }
-  dim3 grid(tiles_m * tiles_n), block(256);
-  if (a->a_kc && a->b_kc)
-    hipLaunchKernelGGL((gemm128_kernel<true, true>), grid, block, 0, s, A, B, a->M, a->N, a->K, a->lda, a->ldb,
-                       tiles_m, tiles_n, e);
-  else if (a->a_kc && !a->b_kc)
-    hipLaunchKernelGGL((gemm128_kernel<true, false>), grid, block, 0, s, A, B, a->M, a->N, a->K, a->lda, a->ldb,
-                       tiles_m, tiles_n, e);
-  else if (!a->a_kc && a->b_kc)
-    hipLaunchKernelGGL((gemm128_kernel<false, true>), grid, block, 0, s, A, B, a->M, a->N, a->K, a->lda, a->ldb,
-                       tiles_m, tiles_n, e);
-  else
-    hipLaunchKernelGGL((gemm128_kernel<false, false>), grid, block, 0, s, A, B, a->M, a->N, a->K, a->lda, a->ldb,
-                       tiles_m, tiles_n, e);
+  }, p.a_kc, p.b_kc);
+#undef O2_GEMM_LAUNCH
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+extern "C" int orbit2_gemm_bf16_colsum_rows(const orbit2_gemm_args* a) {
+  Epi e;
+  GemmPlan p;
+  if (!a || gemm_make_epi(a, e)) return 0;
+  gemm_plan(a, e, p);                       // (a refused call leaves the flag clear)
+  return p.fuses_colsum ? a->M / 256 : 0;
+}
+
+extern "C" int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, void* stream) {
+  if (!args || n <= 0 || n > ORBIT2_GEMM_MAX_GROUP) return O2_ERR_ARG;
+  if (n == 1) return orbit2_gemm_bf16(args, stream);
+  for (int i = 0; i < n; ++i)
+    if (args[i].colsum_ws) return O2_ERR_UNSUPPORTED;      // single launches only (orbit2_gemm_bf16_colsum_rows)
+  GemmFamily family;
+  GArgs g;
+  const int rc = gemm_group_plan(args, n, family, g);
+  if (rc) return rc;
+  const dim3 grid(g.p[n - 1].tile_end), block(gemm_block(family));
+  hipStream_t s = (hipStream_t)stream;
+  o2_with_flags([&](auto AK, auto BK) {
+    switch (family) {
+      case GEMM_256W: hipLaunchKernelGGL((gemm256w_grouped_kernel<w4_form(AK, BK)>), grid, block, 0, s, g); break;
+      case GEMM_256T: hipLaunchKernelGGL((gemm256t_grouped_kernel<AK, BK>), grid, block, 0, s, g); break;
+      default: hipLaunchKernelGGL((gemm128_grouped_kernel<AK, BK>), grid, block, 0, s, g); break;
+    }
+  }, args[0].a_kc != 0, args[0].b_kc != 0);
   O2_CHECK_LAUNCH();
   return O2_OK;
 }
