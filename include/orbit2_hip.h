@@ -81,6 +81,16 @@ typedef struct {
 } orbit2_gemm_args;
 int orbit2_gemm_bf16(const orbit2_gemm_args* args, void* stream);
 int orbit2_gemm_bf16_colsum_rows(const orbit2_gemm_args* args);   /* 0: this call cannot fuse the column sums (colsum_ws must be NULL) */
+/* orbit2_gemm_bf16 with a PATH GATE: gate = fp32 [ceil(M / rows_per_gate)], entry e covering rows e * rows_per_gate onwards (the
+ * per-sample DropPath scales of a Block and its token count: vit_blocks.py:77,80 / timm DropPath).  gate[e] == 0.0f says that
+ * everything computed from these rows is multiplied by 0 further down the branch.  The gate is a HINT: an output tile whose rows
+ * all lie in one such entry MAY skip its contraction and epilogue and store what annihilated inputs give -- zeros in C, save_pre,
+ * save_dact and its colsum_ws row; the residual rows when rowscale == gate and rows_per_scale == rows_per_gate (the row scale
+ * would have multiplied the product by 0) -- so nothing a later kernel reads is left unwritten.  A tile that straddles entries, a
+ * kernel family without the check (today every family but the 4-wave 256 x 256 kernel) and an epilogue outside that list
+ * (fp32 output, beta, another row scale) compute as orbit2_gemm_bf16 does; kept rows are bit-identical, and the kernel, grid and
+ * block are those of the ungated call (orbit2_gemm_bf16_colsum_rows answers for both).  gate == NULL: orbit2_gemm_bf16. */
+int orbit2_gemm_bf16_gated(const orbit2_gemm_args* args, const float* gate, int rows_per_gate, void* stream);
 
 /* ---- fp32 GEMM with fused epilogue (the fp32 forward path) ---------------------------------
  * The same argument block with EVERY tensor pointer (A, B, C, bias, residual) read as fp32; out_fp32 must be 1.  fp32 operands,
@@ -106,6 +116,14 @@ int orbit2_gemm_f32(const orbit2_gemm_args* args, void* stream);
  * ORBIT2_W4_PACE = 0 / 1 / 2: off / on (default) / plus check points inside the sweep). */
 #define ORBIT2_GEMM_MAX_GROUP 12
 int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, void* stream);
+/* The same with a K GATE per problem (weight gradients dW = dY^T . X, a_kc = b_kc = 0): kgates[i] = fp32 [K_i / k_per_gate[i]] or
+ * NULL, entry e covering rows e * k_per_gate[i] onwards of problem i's contraction (the tokens of one sample; for a problem over a
+ * slice of the tokens, the entries of that slice).  kgates[i][e] == 0.0f says that those rows of dY are ZEROS (the path gate of
+ * orbit2_gemm_bf16_gated left them so): the 4-wave kernel sweeps the kept ranges only.  A hint like the path gate: other kernel
+ * families, other operand forms and entries that are not whole 64-deep K-tiles ignore it; the products are the same (a skipped
+ * range adds zeros).  kgates == NULL: orbit2_gemm_bf16_grouped. */
+int orbit2_gemm_bf16_grouped_gated(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate,
+                                   void* stream);
 
 /* small fp32 GEMM (parameter-table algebra of the folded variable aggregation):
  * C[M,N] = alpha * op(A) * op(B) + beta*C, row-major fp32; ta/tb: 0 = as stored, 1 = transposed.
@@ -161,6 +179,15 @@ int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B, int L, int
                        uint64_t seed, int flags, int ldq, int ldo, void* stream);
 int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                        void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq, int ldo, void* stream);
+/* The same with a path gate (see orbit2_gemm_bf16_gated): gate = fp32 [B], one entry per sample.  A workgroup of a sample with
+ * gate[b] == 0.0f MAY skip its work and zero-fill what it owns: its rows of out and lse (forward), of the q third (dQ pass), of
+ * the k and v thirds (dK + dV pass) of dqkv.  The generated d = 128 kernels implement it; every other kernel (and the statistics
+ * pass) ignores the gate.  gate == NULL: the _ld entries. */
+int orbit2_attn_fwd_gated(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
+                          uint64_t seed, int flags, int ldq, int ldo, const float* gate, void* stream);
+int orbit2_attn_bwd_gated(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+                          void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq, int ldo,
+                          const float* gate, void* stream);
 /* orbit2_attn_fwd_ld with fp32 qkv / out (attention.py:54-78 under data_type float32, components/attention.py:66-70): streaming
  * softmax in fp32, both products on v_mfma_f32_32x32x2_f32.  ldq, ldo % 4 == 0.  No dropout: drop_p != 0 returns
  * O2_ERR_UNSUPPORTED, as does any flag other than ORBIT2_ATTN_Q_PRESCALED (honoured as above: without it the kernel multiplies

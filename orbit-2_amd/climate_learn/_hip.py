@@ -58,8 +58,10 @@ PROTOTYPES = {
     "orbit2_abi_version": (_I, ()),
     "orbit2_gemm_bf16": (_I, (_G, _P)),
     "orbit2_gemm_bf16_colsum_rows": (_I, (_G,)),
+    "orbit2_gemm_bf16_gated": (_I, (_G, _P, _I, _P)),
     "orbit2_gemm_f32": (_I, (_G, _P)),
     "orbit2_gemm_bf16_grouped": (_I, (_G, _I, _P)),
+    "orbit2_gemm_bf16_grouped_gated": (_I, (_G, _I, _P, _P, _P)),
     "orbit2_sgemm_f32_ws_floats": (_I64, (_I, _I, _I)),
     "orbit2_sgemm_f32_ws": (_I, (_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _I64, _P)),
     "orbit2_layernorm_fwd_ld": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P)),
@@ -70,6 +72,8 @@ PROTOTYPES = {
     "orbit2_attn_fwd_ld": (_I, (_P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P)),
     "orbit2_attn_fwd_f32": (_I, (_P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P)),
     "orbit2_attn_bwd_ld": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P)),
+    "orbit2_attn_fwd_gated": (_I, (_P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P, _P)),
+    "orbit2_attn_bwd_gated": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P, _P)),
     "orbit2_varagg_fwd": (_I, (_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P)),
     "orbit2_varagg_fwd_f32": (_I, (_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P)),
     "orbit2_varagg_bwd_ws_floats": (_I64, (_I, _I, _I, _I, _I, _I)),
@@ -238,10 +242,23 @@ def _gemm_fill(a, A, B, out, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, bias=
     return 2.0 * M * N * K, 2.0 * (M * K + N * K) + M * N * (4.0 if out.dtype == F32 else 2.0)
 
 
-def gemm(A, B, out, M, N, K, lda, ldb, ldc, want_colsum=False, **kw):
+def gemm(A, B, out, M, N, K, lda, ldb, ldc, want_colsum=False, gate=None, rows_per_gate=0, **kw):
     """out[M,N] = epilogue(A x B); see include/orbit2_hip.h:orbit2_gemm_bf16.
     want_colsum: returns (out, parts) -- parts = fp32 [M / 256, N] per-tile-row column sums of the stored output when this call
-    can fuse them (orbit2_gemm_bf16_colsum_rows), else None: the caller then runs `colsum` on `out` itself."""
+    can fuse them (orbit2_gemm_bf16_colsum_rows), else None: the caller then runs `colsum` on `out` itself.
+    gate: fp32 [ceil(M / rows_per_gate)] path gate (orbit2_gemm_bf16_gated): rows of an entry that is 0.0 may be stored as zeros
+    (as the residual rows when `rowscale` is the gate) without being computed."""
+    if gate is not None:
+        _dev(gate, F32, "gate")
+        if rows_per_gate <= 0 or gate.numel() * rows_per_gate < M:
+            raise HipBackendError("gemm gate needs rows_per_gate > 0 and one entry per rows_per_gate rows")
+
+    def launch(a):
+        if gate is None:
+            _chk(lib().orbit2_gemm_bf16(C.byref(a), _stream()), "orbit2_gemm_bf16")
+        else:
+            _chk(lib().orbit2_gemm_bf16_gated(C.byref(a), gate.data_ptr(), rows_per_gate, _stream()), "orbit2_gemm_bf16_gated")
+
     a = GemmArgs()
     flops, nbytes = _gemm_fill(a, A, B, out, M, N, K, lda, ldb, ldc, **kw)
     parts = None
@@ -253,10 +270,10 @@ def gemm(A, B, out, M, N, K, lda, ldb, ldc, want_colsum=False, **kw):
     if timer is not None:
         e0, e1 = timer.span("gemm_bf16", flops, nbytes)
         e0.record()
-        _chk(lib().orbit2_gemm_bf16(C.byref(a), _stream()), "orbit2_gemm_bf16")
+        launch(a)
         e1.record()
     else:
-        _chk(lib().orbit2_gemm_bf16(C.byref(a), _stream()), "orbit2_gemm_bf16")
+        launch(a)
     return (out, parts) if want_colsum else out
 
 
@@ -293,23 +310,39 @@ GEMM_MAX_GROUP = 12
 
 def gemm_grouped(problems):
     """problems: list of (A, B, out, M, N, K, lda, ldb, ldc, kwargs) sharing one operand form; one launch
-    (include/orbit2_hip.h:orbit2_gemm_bf16_grouped)."""
+    (include/orbit2_hip.h:orbit2_gemm_bf16_grouped).  A problem's kwargs may hold kgate = (fp32 vector, rows of the contraction
+    per entry): the K gate of orbit2_gemm_bf16_grouped_gated -- ranges of the contraction whose entry is 0.0 hold zero rows in A."""
     n = len(problems)
     if not 0 < n <= GEMM_MAX_GROUP:
         raise HipBackendError("gemm_grouped takes 1..%d problems" % GEMM_MAX_GROUP)
     arr = (GemmArgs * n)()
+    kgates, kper, gated = (C.c_void_p * n)(), (C.c_int * n)(), False
     flops = nbytes = 0.0
     for i, (A, B, out, M, N, K, lda, ldb, ldc, kw) in enumerate(problems):
+        kw = dict(kw)
+        kg = kw.pop("kgate", None)
+        if kg is not None:
+            vec, per = kg
+            if per <= 0 or _dev(vec, F32, "kgate").numel() * per < K:
+                raise HipBackendError("gemm_grouped kgate needs one entry per k_per_gate rows of the contraction")
+            kgates[i], kper[i], gated = vec.data_ptr(), per, True
         f, b = _gemm_fill(arr[i], A, B, out, M, N, K, lda, ldb, ldc, **kw)
         flops += f
         nbytes += b
+
+    def launch():
+        if gated:
+            _chk(lib().orbit2_gemm_bf16_grouped_gated(arr, n, kgates, kper, _stream()), "orbit2_gemm_bf16_grouped_gated")
+        else:
+            _chk(lib().orbit2_gemm_bf16_grouped(arr, n, _stream()), "orbit2_gemm_bf16_grouped")
+
     if timer is not None:
         e0, e1 = timer.span("gemm_bf16", flops, nbytes)
         e0.record()
-        _chk(lib().orbit2_gemm_bf16_grouped(arr, n, _stream()), "orbit2_gemm_bf16_grouped")
+        launch()
         e1.record()
         return
-    _chk(lib().orbit2_gemm_bf16_grouped(arr, n, _stream()), "orbit2_gemm_bf16_grouped")
+    launch()
 
 
 def sgemm(A, B, out, M, N, K, lda, ldb, ldc, ta=False, tb=False, alpha=1.0, beta=0.0):
@@ -394,8 +427,16 @@ def mall_calibration():
     torch.cuda.synchronize()
 
 
-def attn_fwd(qkv, B, L, H, d, drop_p=0.0, seed=0, flags=0, out=None):
-    """out: optional [B * L, H * d] bf16 destination with any token-row pitch (orbit2_attn_fwd_ld); default [B, L, H * d]"""
+def _attn_gate(gate, B):
+    if gate is not None and _dev(gate, F32, "gate").numel() < B:
+        raise HipBackendError("attention gate needs one entry per sample")
+    return gate
+
+
+def attn_fwd(qkv, B, L, H, d, drop_p=0.0, seed=0, flags=0, out=None, gate=None):
+    """out: optional [B * L, H * d] bf16 destination with any token-row pitch (orbit2_attn_fwd_ld); default [B, L, H * d].
+    gate: fp32 [B] path gate (orbit2_attn_fwd_gated): out and lse of a sample whose entry is 0.0 may be stored as zeros"""
+    _attn_gate(gate, B)
     _dev_rows(qkv, BF, "qkv")
     ldq = qkv.stride(0) if qkv.dim() == 2 else 3 * H * d       # [B * L, 3 * H * d] with a token-row pitch, or contiguous
     if out is None:
@@ -408,8 +449,12 @@ def attn_fwd(qkv, B, L, H, d, drop_p=0.0, seed=0, flags=0, out=None):
         # algorithmic bytes: qkv read once, out + lse written once
         e0, e1 = timer.span("attn_fwd", 4.0 * B * H * L * L * d, 2.0 * 4 * B * L * H * d + 4.0 * B * H * L)
         e0.record()
-    _chk(lib().orbit2_attn_fwd_ld(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo),
-                                  _stream()), "orbit2_attn_fwd_ld")
+    if gate is None:
+        _chk(lib().orbit2_attn_fwd_ld(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo),
+                                      _stream()), "orbit2_attn_fwd_ld")
+    else:
+        _chk(lib().orbit2_attn_fwd_gated(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo),
+                                         _p(gate), _stream()), "orbit2_attn_fwd_gated")
     if timer is not None:
         e1.record()
     return out, lse
@@ -436,7 +481,9 @@ def attn_fwd_f32(qkv, B, L, H, d, drop_p=0.0, flags=0, out=None):
     return out, lse
 
 
-def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0):
+def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0, gate=None):
+    """gate: fp32 [B] path gate (orbit2_attn_bwd_gated): dqkv of a sample whose entry is 0.0 may be stored as zeros"""
+    _attn_gate(gate, B)
     _dev_rows(qkv, BF, "qkv"); _dev_rows(out, BF, "out"); _dev(dout, BF, "dout"); _dev(lse, F32, "lse")
     ldo = out.stride(0) if out.dim() == 2 else H * d           # [B * L, H * d] with a token-row pitch, or contiguous [B, L, H * d]
     ldq = qkv.stride(0) if qkv.dim() == 2 else 3 * H * d
@@ -449,8 +496,12 @@ def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0):
         # algorithmic: 2x the forward's FLOPs (recompute not credited); qkv, out, dout read once, dqkv written once
         e0, e1 = timer.span("attn_bwd", 8.0 * B * H * L * L * d, 2.0 * 8 * B * L * H * d + 8.0 * B * H * L)
         e0.record()
-    _chk(lib().orbit2_attn_bwd_ld(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, L, H, d,
-                                  drop_p, seed, int(flags), int(ldq), int(ldo), _stream()), "orbit2_attn_bwd_ld")
+    if gate is None:
+        _chk(lib().orbit2_attn_bwd_ld(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, L, H, d,
+                                      drop_p, seed, int(flags), int(ldq), int(ldo), _stream()), "orbit2_attn_bwd_ld")
+    else:
+        _chk(lib().orbit2_attn_bwd_gated(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, L, H, d,
+                                         drop_p, seed, int(flags), int(ldq), int(ldo), _p(gate), _stream()), "orbit2_attn_bwd_gated")
     if timer is not None:
         e1.record()
     return dqkv

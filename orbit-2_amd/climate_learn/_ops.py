@@ -220,6 +220,16 @@ def _dx(dy2d, W, M, N, K, pad=False, **kw):
     return _hip.gemm(dy2d, cw(W), out, M, K, N, _ld(dy2d, N), K, out.stride(0), a_kc=True, b_kc=False, **kw)
 
 
+# Path gate: the Block hands its per-sample DropPath scales to the kernels between the scale's two uses, which may
+# then skip the samples the branch dropped.  ORBIT2_PATH_GATE=0: no gate anywhere (A/B timing; the results are the same).
+_PATH_GATE = _os.environ.get("ORBIT2_PATH_GATE", "1") != "0"
+_PATH_GATE_DW = _os.environ.get("ORBIT2_PATH_GATE_DW", "1") != "0"      # the weight-gradient contraction skips dropped samples too
+
+
+def _gate_kw(dp, L):
+    return dict(gate=dp, rows_per_gate=L) if _PATH_GATE and dp is not None else {}
+
+
 _FUSE_COLSUM = True   # fc1's bias gradient from the factor-multiply GEMM's per-tile-row sums (bench.py --no-fused-colsum: A/B)
 _DW_SPLIT = 8     # K-split of a weight gradient whose output is too few tiles to fill the chip (0: off)
 
@@ -311,9 +321,12 @@ def _dw_balance(problems):
         if r0 > 0:                                   # the problem's first tile rows stay full-length
             full.append((dy[:, :n0], x, out[:n0], n0, K, M_, lda, ldb, ldc, kw))
         parts = torch.empty(S, n1 - n0, K, dtype=BF, device=dy.device)      # bf16 partials, summed in fp32 by orbit2_batch_sum
+        kg = kw.get("kgate")               # a slice of the tokens takes its own entries of the K gate (whole samples per slice only)
         for q in range(S):
-            split[q].append((dy[q * Mc:(q + 1) * Mc, n0:n1], x[q * Mc:(q + 1) * Mc], parts[q], n1 - n0, K, Mc, lda, ldb, K,
-                             dict(a_kc=False, b_kc=False)))
+            kwq = dict(a_kc=False, b_kc=False)
+            if kg is not None and Mc % kg[1] == 0:
+                kwq["kgate"] = (kg[0][q * (Mc // kg[1]):(q + 1) * (Mc // kg[1])], kg[1])
+            split[q].append((dy[q * Mc:(q + 1) * Mc, n0:n1], x[q * Mc:(q + 1) * Mc], parts[q], n1 - n0, K, Mc, lda, ldb, K, kwq))
         sums.append((parts, S, n1 - n0, K, out[n0:n1], kw.get("beta", 0.0)))
     probs = full + [u for q in range(S) for u in split[q]]       # full-length tiles first (whole rounds), then slice by slice
     if len(probs) > _hip.GEMM_MAX_GROUP:
@@ -329,11 +342,14 @@ class _DwBatch:
     def __init__(self):
         self.problems, self.sinks, self.keep = [], [], []
 
-    def add(self, dy2d, x2d, W, b, M, N, K, colsum_parts=None):
-        """queues dW[N,K] = dy^T . x; returns (index of the weight result, bias result)"""
+    def add(self, dy2d, x2d, W, b, M, N, K, colsum_parts=None, kgate=None):
+        """queues dW[N,K] = dy^T . x; returns (index of the weight result, bias result).  kgate = (per-sample scales, tokens per
+        sample): the rows of dy2d of a sample whose scale is 0.0 are zeros (the path gate left them so) and may be skipped"""
         sw = _GradSink(W)
-        self.problems.append((dy2d, x2d, sw.buf, N, K, M, _ld(dy2d, N), _ld(x2d, K), K,
-                              dict(a_kc=False, b_kc=False, beta=sw.beta)))
+        kw = dict(a_kc=False, b_kc=False, beta=sw.beta)
+        if kgate is not None and _PATH_GATE_DW:
+            kw["kgate"] = kgate
+        self.problems.append((dy2d, x2d, sw.buf, N, K, M, _ld(dy2d, N), _ld(x2d, K), K, kw))
         self.sinks.append(sw)
         self.keep.append((dy2d, x2d))
         gb = None
@@ -429,11 +445,14 @@ class BlockFn(torch.autograd.Function):
         h1, mean1, rstd1 = _hip.layernorm_fwd(x2d, cw(n1w), cw(n1b), out=_rows(M, D, x2d.device))
         # the q third leaves the GEMM epilogue as q * log2(e)/sqrt(d) (fp32 product, ONE rounding to bf16): the attention
         # kernels' scores are exp2 arguments with exact bf16 x bf16 products, as with the reference's fp32 scaling
-        qkv = _linear_fwd(h1, wqkv, bqkv, M, 3 * Dl, D, pad=True, colscale=(Dl, _Q_PRESCALE / math.sqrt(d)))
-        o2d, lse = _hip.attn_fwd(qkv, B, L, H, d, p_attn, sa, flags=_hip.ATTN_Q_PRESCALED, out=_rows(M, Dl, x2d.device))
+        # (path gate: single-rank Blocks only -- under tensor parallelism the row scale is applied behind the all-reduce)
+        g1, g2 = (_gate_kw(dp1, L), _gate_kw(dp2, L)) if grp is None else ({}, {})
+        qkv = _linear_fwd(h1, wqkv, bqkv, M, 3 * Dl, D, pad=True, colscale=(Dl, _Q_PRESCALE / math.sqrt(d)), **g1)
+        o2d, lse = _hip.attn_fwd(qkv, B, L, H, d, p_attn, sa, flags=_hip.ATTN_Q_PRESCALED, out=_rows(M, Dl, x2d.device),
+                                 gate=g1.get("gate"))
         if grp is None:
             x1 = _linear_fwd(o2d, wp, bp, M, D, Dl, drop_p=p_proj, seed=sp, rowscale=dp1, rows_per_scale=L,
-                             residual=x2d, ldr=D)
+                             residual=x2d, ldr=D, **g1)
         else:
             # row-parallel proj: bias + dropout on the partial product (identical masks on all ranks of the group),
             # SUM over the group, then DropPath scale + residual (reference attention.py:81-85, vit_blocks.py:77)
@@ -447,10 +466,10 @@ class BlockFn(torch.autograd.Function):
         # not the pre-activation itself: the fc2 input gradient then has a one-multiply epilogue (4-wave kernel) instead of
         # GELU' + the mask again (reference: autograd of mlp.py:64-65)
         gsaved = _rows(M, hid, x2d.device, _gelu_saved_dtype(p_mlp))      # the factor tensor (int16 q14) or the pre-activation
-        hm = _linear_fwd(h2, w1, b1, M, hid, D, pad=True, **_gelu_fwd_kw(gsaved, p_mlp, s1))
+        hm = _linear_fwd(h2, w1, b1, M, hid, D, pad=True, **_gelu_fwd_kw(gsaved, p_mlp, s1), **g2)
         if grp is None:
             x2 = _linear_fwd(hm, w2, b2, M, D, hid, drop_p=p_mlp, seed=s2, rowscale=dp2, rows_per_scale=L,
-                             residual=x1, ldr=D)
+                             residual=x1, ldr=D, **g2)
         else:
             part = _linear_fwd(hm, w2, b2, M, D, hid, drop_p=p_mlp, seed=s2)
             _tp.all_reduce_sum(part, grp)
@@ -470,36 +489,38 @@ class BlockFn(torch.autograd.Function):
         else:
             x2d, dp1, dp2, h1, mean1, rstd1, qkv, o2d, lse, x1, h2, mean2, rstd2, gsaved, hm = ctx.saved_tensors
         grp, Dl = ctx.grp, H * d
+        g1, g2 = (_gate_kw(dp1, L), _gate_kw(dp2, L)) if grp is None else ({}, {})
         dx2 = dx2.reshape(M, D)
         if dx2.dtype != BF or not dx2.is_contiguous():
             dx2 = dx2.contiguous().to(BF)
         # ---- MLP branch   (the four dW GEMMs are queued and issued as one grouped launch at the end)
         dws = _DwBatch()
         dym2, gb2, done2 = _drop_bwd_bias(dx2, M, D, p_mlp, s2, dp2, L, b2)      # fc2's bias gradient rides along
-        i2, gb2_ = dws.add(dym2, hm, w2, None if done2 else b2, M, D, hid)
+        k1, k2 = ((g1["gate"], L) if g1 else None), ((g2["gate"], L) if g2 else None)
+        i2, gb2_ = dws.add(dym2, hm, w2, None if done2 else b2, M, D, hid, kgate=k2)
         gb2 = gb2 if done2 else gb2_
         # (fc1's bias gradient = column sums of dpre: the factor-multiply epilogue of this GEMM leaves them per tile row when it can)
-        dpre, dpre_sums = _dx(dym2, w2, M, D, hid, pad=True, want_colsum=_FUSE_COLSUM, **_gelu_bwd_kw(gsaved, p_mlp, s1)), None
+        dpre, dpre_sums = _dx(dym2, w2, M, D, hid, pad=True, want_colsum=_FUSE_COLSUM, **_gelu_bwd_kw(gsaved, p_mlp, s1), **g2), None
         if _FUSE_COLSUM:
             dpre, dpre_sums = dpre
         del hm, gsaved, dym2
-        i1, gb1 = dws.add(dpre, h2, w1, b1, M, hid, D, colsum_parts=dpre_sums)
-        dh2 = _dx(dpre, w1, M, hid, D)
+        i1, gb1 = dws.add(dpre, h2, w1, b1, M, hid, D, colsum_parts=dpre_sums, kgate=k2)
+        dh2 = _dx(dpre, w1, M, hid, D, **g2)
         del dpre, h2
         _tp.all_reduce_sum(dh2, grp)        # column-parallel fc1: the input gradient is a partial sum per rank
         dx1, gn2w, gn2b = _ln_bwd(dh2, x1, n2w, n2b, mean2, rstd2, dx2)
         del dh2, x1
         # ---- attention branch
         dym1, gbp, donep = _drop_bwd_bias(dx1, M, D, p_proj, sp, dp1, L, bp)     # proj's bias gradient rides along
-        ip, gbp_ = dws.add(dym1, o2d, wp, None if donep else bp, M, D, Dl)
+        ip, gbp_ = dws.add(dym1, o2d, wp, None if donep else bp, M, D, Dl, kgate=k1)
         gbp = gbp if donep else gbp_
-        do = _dx(dym1, wp, M, D, Dl)
+        do = _dx(dym1, wp, M, D, Dl, **g1)
         del dym1
         # (dqkv is the gradient with respect to the UNSCALED q, k, v: the qkv GEMM's backward needs no column scale)
-        dqkv = _hip.attn_bwd(qkv, o2d, do, lse, B, L, H, d, p_attn, sa, flags=_hip.ATTN_Q_PRESCALED)
+        dqkv = _hip.attn_bwd(qkv, o2d, do, lse, B, L, H, d, p_attn, sa, flags=_hip.ATTN_Q_PRESCALED, gate=g1.get("gate"))
         del do, o2d, qkv
-        iq, gbqkv = dws.add(dqkv, h1, wqkv, bqkv, M, 3 * Dl, D)
-        dh1 = _dx(dqkv, wqkv, M, 3 * Dl, D)
+        iq, gbqkv = dws.add(dqkv, h1, wqkv, bqkv, M, 3 * Dl, D, kgate=k1)
+        dh1 = _dx(dqkv, wqkv, M, 3 * Dl, D, **g1)
         del dqkv, h1
         _tp.all_reduce_sum(dh1, grp)        # column-parallel qkv
         dx, gn1w, gn1b = _ln_bwd(dh1, x2d, n1w, n1b, mean1, rstd1, dx1)

@@ -115,6 +115,19 @@ __device__ __forceinline__ void attn_tile_coords(int nq, int H, int& qt, int& he
   b = grp / H;
 }
 
+// The walk of the GATED kernels (path gate, include/orbit2_hip.h: orbit2_attn_fwd_gated): the SAMPLE fastest among the (sample,
+// head) pairs, so that an XCD's contiguous range holds a few heads of EVERY sample instead of every head of a few samples.
+// Workgroup b runs on XCD b & 7 whatever the others are doing: with attn_tile_coords a dropped sample empties one XCD's queue and
+// the launch still lasts as long as the seven full ones (measured: profiles/r07_path_gate_ab.txt, the first gated build's attention
+// kernels did not shrink); here every XCD loses the same share.  What an XCD runs at a time is still consecutive tiles of one or
+// two (sample, head) pairs.  Any bijection gives the same results: a tile's arithmetic depends on its coordinates alone.
+__device__ __forceinline__ void attn_tile_coords_gated(int nq, int H, int& qt, int& head, int& b) {
+  attn_tile_coords(nq, H, qt, b, head);          // (b, head) = (grp % H, grp / H) ...
+  const int grp = head * H + b, B = gridDim.x / (nq * H);
+  b = grp % B;                                   // ... re-read as (grp % B, grp / B)
+  head = grp / B;
+}
+
 // =============================================================================================
 // forward
 // =============================================================================================
@@ -617,17 +630,36 @@ static inline bool attn_w4_range_ok(int L, int ldq, int ldo) {
   const uint64_t lim = 1ull << 31;
   return (uint64_t)(L + 64) * (uint64_t)ldq * 2ull < lim && (uint64_t)(L + 64) * (uint64_t)ldo * 2ull < lim;
 }
-template <bool DROP>
-__global__ __launch_bounds__(256, 1) void attn_fwd_w4_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
-                                                            float* __restrict__ lse, int L, int H, unsigned thr, float dscale,
-                                                            uint64_t seed_arg, int ldo, int ldq) {
+// Path gate of the generated kernels (include/orbit2_hip.h: orbit2_attn_fwd_gated): the zero-fill a workgroup of a dropped sample
+// makes in place of its work -- `rows` token rows of 128 elements (256 bytes: 16 lanes x 16 bytes per row, 16 rows per step) at
+// row pitch ld.
+__device__ __forceinline__ void attn_gate_zero_rows(bf16_t* __restrict__ p, int rows, size_t ld, int tid) {
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+  p += (size_t)(tid >> 4) * ld + 8 * (tid & 15);
+  for (int r = 0; r < rows; r += 16) *reinterpret_cast<u32x4*>(p + (size_t)r * ld) = zero;
+}
+
+// The body of the kernel: attn_fwd_w4_kernel is it without a gate, attn_fwd_w4_gated_kernel with one (GATED: the check is compiled
+// into the gated kernel only, the ungated one is instruction for instruction what it was).
+template <bool DROP, bool GATED>
+__device__ __forceinline__ void attn_fwd_w4_body(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+                                                 float* __restrict__ lse, int L, int H, unsigned thr, float dscale,
+                                                 uint64_t seed_arg, int ldo, int ldq, const float* __restrict__ gate) {
   constexpr int D = 128;
   __shared__ __attribute__((aligned(1024))) char smem[O2_AF_LDS_BYTES(O2_AF_MAX_L)];   // [2 slots][K 16 KiB | V 16 KiB] | key-group hashes
   const uint64_t seed = seed_arg ^ o2_seed_salt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int tile_i, head, b;
-  attn_tile_coords(L / 256, H, tile_i, head, b);
+  if constexpr (GATED) attn_tile_coords_gated(L / 256, H, tile_i, head, b);
+  else attn_tile_coords(L / 256, H, tile_i, head, b);
+  if constexpr (GATED) {
+    if (gate[b] == 0.0f) {                  // workgroup-uniform
+      attn_gate_zero_rows(out + ((size_t)b * L + tile_i * 256) * (size_t)ldo + (size_t)head * D, 256, (size_t)ldo, tid);
+      lse[((size_t)(b * H + head)) * L + tile_i * 256 + tid] = 0.f;
+      return;
+    }
+  }
   const int q0 = tile_i * 256 + wave * 64;
   const size_t tstride = (size_t)ldq;      // token-row pitch of qkv (and dqkv), >= 3 * H * D
   if (DROP) {
@@ -664,6 +696,18 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w4_kernel(const bf16_t* __res
                    [rhx] "v"(rhx), [rhy] "v"(rhy)
                  : O2_AF_CLOBBERS);
   }
+}
+template <bool DROP>
+__global__ __launch_bounds__(256, 1) void attn_fwd_w4_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+                                                            float* __restrict__ lse, int L, int H, unsigned thr, float dscale,
+                                                            uint64_t seed_arg, int ldo, int ldq) {
+  attn_fwd_w4_body<DROP, false>(qkv, out, lse, L, H, thr, dscale, seed_arg, ldo, ldq, nullptr);
+}
+template <bool DROP>
+__global__ __launch_bounds__(256, 1) void attn_fwd_w4_gated_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+                                                                  float* __restrict__ lse, int L, int H, unsigned thr, float dscale,
+                                                                  uint64_t seed_arg, int ldo, int ldq, const float* __restrict__ gate) {
+  attn_fwd_w4_body<DROP, true>(qkv, out, lse, L, H, thr, dscale, seed_arg, ldo, ldq, gate);
 }
 
 // =============================================================================================
@@ -873,18 +917,25 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_bwd_dq_kerne
 // Same construction as attn_fwd_w4_kernel (one wave per SIMD, two 32-row blocks per wave, every instruction placed by the
 // generator, the same text executed on the CPU by tests/test_attn_dq_asm_emu_cpu.py); the schedule is described in the
 // generator's header.  The compiler contributes the coordinates, the key-group hash table and the lane's two row hashes.
-template <bool DROP>
-__global__ __launch_bounds__(256, 1) void attn_bwd_dq_w4_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
-                                                               const float* __restrict__ nlse2, const float* __restrict__ ndelta,
-                                                               bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fs,
-                                                               uint64_t seed_arg, int Lp, int ldq) {
+template <bool DROP, bool GATED>
+__device__ __forceinline__ void attn_bwd_dq_w4_body(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
+                                                    const float* __restrict__ nlse2, const float* __restrict__ ndelta,
+                                                    bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fs,
+                                                    uint64_t seed_arg, int Lp, int ldq, const float* __restrict__ gate) {
   constexpr int D = 128;
   __shared__ __attribute__((aligned(1024))) char smem[O2_DQ_LDS_BYTES(O2_AF_MAX_L)];   // 4 x [K 16 KiB] | 4 x [V 16 KiB] | key-group hashes
   const uint64_t seed = seed_arg ^ o2_seed_salt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int tile_i, head, b;
-  attn_tile_coords(L / 256, H, tile_i, head, b);
+  if constexpr (GATED) attn_tile_coords_gated(L / 256, H, tile_i, head, b);
+  else attn_tile_coords(L / 256, H, tile_i, head, b);
+  if constexpr (GATED) {
+    if (gate[b] == 0.0f) {                  // workgroup-uniform: the tile's rows of the q third
+      attn_gate_zero_rows(dqkv + ((size_t)b * L + tile_i * 256) * (size_t)ldq + (size_t)head * D, 256, (size_t)ldq, tid);
+      return;
+    }
+  }
   const int q0 = tile_i * 256 + wave * 64;
   const size_t tstride = (size_t)ldq;      // token-row pitch of qkv (and dqkv), >= 3 * H * D
   if (DROP) {
@@ -916,6 +967,20 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq_w4_kernel(const bf16_t* __
     asm volatile(O2_DQ_ASM_NODROP : : O2_DQ_OPERANDS : O2_DQ_CLOBBERS);
   }
 #undef O2_DQ_OPERANDS
+}
+template <bool DROP>
+__global__ __launch_bounds__(256, 1) void attn_bwd_dq_w4_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
+                                                               const float* __restrict__ nlse2, const float* __restrict__ ndelta,
+                                                               bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fs,
+                                                               uint64_t seed_arg, int Lp, int ldq) {
+  attn_bwd_dq_w4_body<DROP, false>(qkv, dout, nlse2, ndelta, dqkv, L, H, thr, fs, seed_arg, Lp, ldq, nullptr);
+}
+template <bool DROP>
+__global__ __launch_bounds__(256, 1) void attn_bwd_dq_w4_gated_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
+                                                                     const float* __restrict__ nlse2, const float* __restrict__ ndelta,
+                                                                     bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fs,
+                                                                     uint64_t seed_arg, int Lp, int ldq, const float* __restrict__ gate) {
+  attn_bwd_dq_w4_body<DROP, true>(qkv, dout, nlse2, ndelta, dqkv, L, H, thr, fs, seed_arg, Lp, ldq, gate);
 }
 
 // =============================================================================================
@@ -1371,18 +1436,27 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv128_kernel(const bf16_t* _
 // statement is the whole kernel (schedule: the generator's header; CPU execution of the same text: tests/test_attn_dkv_asm_emu_cpu.py).
 // The compiler contributes the coordinates, the lane's key-group hash and the seed-dependent constant of the row hash
 // (o2_hash64 with a zero high index word: requires B * H * L < 2^32, checked by the launcher).
-template <bool DROP>
-__global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w4_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
-                                                                const float* __restrict__ nlse2, const float* __restrict__ ndelta,
-                                                                bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fk, float fv,
-                                                                uint64_t seed_arg, int Lp, int ldq) {
+template <bool DROP, bool GATED>
+__device__ __forceinline__ void attn_bwd_dkv_w4_body(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
+                                                     const float* __restrict__ nlse2, const float* __restrict__ ndelta,
+                                                     bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fk, float fv,
+                                                     uint64_t seed_arg, int Lp, int ldq, const float* __restrict__ gate) {
   constexpr int D = 128;
   __shared__ __attribute__((aligned(1024))) char smem[O2_KV_LDS_BYTES];   // 4 x [Q 16 KiB] | 4 x [dO 16 KiB] | 4 x 1 KiB of row statistics
   const uint64_t seed = seed_arg ^ o2_seed_salt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int tile_i, head, b;
-  attn_tile_coords(L / 128, H, tile_i, head, b);
+  if constexpr (GATED) attn_tile_coords_gated(L / 128, H, tile_i, head, b);
+  else attn_tile_coords(L / 128, H, tile_i, head, b);
+  if constexpr (GATED) {
+    if (gate[b] == 0.0f) {                  // workgroup-uniform: the tile's 128 rows of the k and of the v third
+      bf16_t* kz = dqkv + ((size_t)b * L + tile_i * 128) * (size_t)ldq + (size_t)H * D + (size_t)head * D;
+      attn_gate_zero_rows(kz, 128, (size_t)ldq, tid);
+      attn_gate_zero_rows(kz + (size_t)H * D, 128, (size_t)ldq, tid);
+      return;
+    }
+  }
   const int k0 = tile_i * 128 + wave * 32;
   const size_t tstride = (size_t)ldq;      // token-row pitch of qkv (and dqkv), >= 3 * H * D
   const char* kptr = reinterpret_cast<const char*>(qkv + ((size_t)b * L + k0) * tstride + (size_t)H * D + (size_t)head * D);
@@ -1410,6 +1484,21 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w4_kernel(const bf16_t* _
     asm volatile(O2_KV_ASM_NODROP : : O2_KV_OPERANDS : O2_KV_CLOBBERS);
   }
 #undef O2_KV_OPERANDS
+}
+template <bool DROP>
+__global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w4_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
+                                                                const float* __restrict__ nlse2, const float* __restrict__ ndelta,
+                                                                bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fk, float fv,
+                                                                uint64_t seed_arg, int Lp, int ldq) {
+  attn_bwd_dkv_w4_body<DROP, false>(qkv, dout, nlse2, ndelta, dqkv, L, H, thr, fk, fv, seed_arg, Lp, ldq, nullptr);
+}
+template <bool DROP>
+__global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w4_gated_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
+                                                                      const float* __restrict__ nlse2, const float* __restrict__ ndelta,
+                                                                      bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fk,
+                                                                      float fv, uint64_t seed_arg, int Lp, int ldq,
+                                                                      const float* __restrict__ gate) {
+  attn_bwd_dkv_w4_body<DROP, true>(qkv, dout, nlse2, ndelta, dqkv, L, H, thr, fk, fv, seed_arg, Lp, ldq, gate);
 }
 
 // =============================================================================================
@@ -1757,8 +1846,10 @@ template <class F> static void attn_with_variant(int d, int nw, bool drop, bool 
   }, drop, ragged);
 }
 
-extern "C" int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
-                                  uint64_t seed, int flags, int ldq, int ldo, void* stream) {
+// gate: the path gate of orbit2_attn_fwd_gated (nullptr: none).  The plan does not look at it: a gated call runs the gated twin
+// of the kernel the ungated call runs, on the same grid; the kernels without a twin ignore it.
+static int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
+                           uint64_t seed, int flags, int ldq, int ldo, const float* gate, void* stream) {
   int rc = attn_check(qkv, out, B, L, H, d, drop_p);
   if (rc) return rc;
   if (!lse || ldo < H * d || (ldo & 7) || ldq < 3 * H * d || (ldq & 7)) return O2_ERR_ARG;
@@ -1767,7 +1858,12 @@ extern "C" int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B,
   const bf16_t* q_ = (const bf16_t*)qkv;
   bf16_t* o_ = (bf16_t*)out;
 #define O2_FWD(KERN, ...) hipLaunchKernelGGL(KERN, p.fwd.grid, p.fwd.block, 0, s, q_, o_, lse, L, H, __VA_ARGS__, seed, ldo, ldq)
-  if (p.fwd_w4)
+  if (p.fwd_w4 && gate)
+    o2_with_flags([&](auto DR) {
+      hipLaunchKernelGGL((attn_fwd_w4_gated_kernel<DR>), p.fwd.grid, p.fwd.block, 0, s, q_, o_, lse, L, H, p.thr, p.dscale, seed,
+                         ldo, ldq, gate);
+    }, p.drop);
+  else if (p.fwd_w4)
     o2_with_flags([&](auto DR) { O2_FWD((attn_fwd_w4_kernel<DR>), p.thr, p.dscale); }, p.drop);
   else
     attn_with_variant(d, p.nw_fwd, p.drop, p.ragged_fwd, [&](auto DV, auto NW, auto DR, auto RG) {
@@ -1780,6 +1876,14 @@ extern "C" int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B,
   O2_CHECK_LAUNCH();
   return O2_OK;
 }
+extern "C" int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
+                                  uint64_t seed, int flags, int ldq, int ldo, void* stream) {
+  return attn_fwd_launch(qkv, out, lse, B, L, H, d, drop_p, seed, flags, ldq, ldo, nullptr, stream);
+}
+extern "C" int orbit2_attn_fwd_gated(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
+                                     uint64_t seed, int flags, int ldq, int ldo, const float* gate, void* stream) {
+  return attn_fwd_launch(qkv, out, lse, B, L, H, d, drop_p, seed, flags, ldq, ldo, gate, stream);
+}
 
 static int attn_lpad(int L) { return ((L + 63) / 64) * 64 + 64; }     // padded row stride of the statistics tables
 
@@ -1788,9 +1892,9 @@ extern "C" int64_t orbit2_attn_bwd_ws_floats(int B, int L, int H) {
   return (int64_t)2 * B * H * attn_lpad(L);
 }
 
-extern "C" int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
-                                  void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq,
-                                  int ldo, void* stream) {
+static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+                           void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq,
+                           int ldo, const float* gate, void* stream) {
   int rc = attn_check(qkv, out, B, L, H, d, drop_p);
   if (rc) return rc;
   if (!dout || !lse || !delta || !dqkv || ldo < H * d || (ldo & 7) || ldq < 3 * H * d || (ldq & 7)) return O2_ERR_ARG;
@@ -1808,15 +1912,26 @@ extern "C" int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* 
   // a backward launch: the operands every kernel takes, its own scalars, the table pitch and the row pitch
 #define O2_BWD(KERN, PASS, ...) \
   hipLaunchKernelGGL(KERN, p.PASS.grid, p.PASS.block, 0, s, q_, do_, ws0, ws1, dq_, L, H, __VA_ARGS__, Lp, ldq)
+#define O2_BWD_GATED(KERN, PASS, ...) \
+  hipLaunchKernelGGL(KERN, p.PASS.grid, p.PASS.block, 0, s, q_, do_, ws0, ws1, dq_, L, H, __VA_ARGS__, Lp, ldq, gate)
 #define O2_BWD_CS p.scale, p.thr, p.dscale, seed, p.opmul          /* scalars of the compiler-scheduled kernels */
-  if (p.dq_w4)
+  if (p.dq_w4 && gate)
+    o2_with_flags([&](auto DR) { O2_BWD_GATED((attn_bwd_dq_w4_gated_kernel<DR>), dq, p.thr, p.dq_w4_scale, seed); }, p.drop);
+  else if (p.dq_w4)
     o2_with_flags([&](auto DR) { O2_BWD((attn_bwd_dq_w4_kernel<DR>), dq, p.thr, p.dq_w4_scale, seed); }, p.drop);
   else
     attn_with_variant(d, p.nw, p.drop, p.ragged,
                       [&](auto DV, auto NW, auto DR, auto RG) { O2_BWD((attn_bwd_dq_kernel<DV, DR, RG, NW>), dq, O2_BWD_CS); });
   switch (p.dkv) {
     case DKV_W4:
-      o2_with_flags([&](auto DR) { O2_BWD((attn_bwd_dkv_w4_kernel<DR>), dkv_l, p.thr, p.dkv_w4_kgrad, p.dkv_w4_dscale, seed); }, p.drop);
+      if (gate)
+        o2_with_flags([&](auto DR) {
+          O2_BWD_GATED((attn_bwd_dkv_w4_gated_kernel<DR>), dkv_l, p.thr, p.dkv_w4_kgrad, p.dkv_w4_dscale, seed);
+        }, p.drop);
+      else
+        o2_with_flags([&](auto DR) {
+          O2_BWD((attn_bwd_dkv_w4_kernel<DR>), dkv_l, p.thr, p.dkv_w4_kgrad, p.dkv_w4_dscale, seed);
+        }, p.drop);
       break;
     case DKV_FUSED128:
       o2_with_flags([&](auto DR, auto RG) { O2_BWD((attn_bwd_dkv128_kernel<DR, RG>), dkv_l, O2_BWD_CS, p.kgrad); }, p.drop, p.ragged);
@@ -1834,7 +1949,18 @@ extern "C" int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* 
       break;
   }
 #undef O2_BWD
+#undef O2_BWD_GATED
 #undef O2_BWD_CS
   O2_CHECK_LAUNCH();
   return O2_OK;
+}
+extern "C" int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+                                  void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq,
+                                  int ldo, void* stream) {
+  return attn_bwd_launch(qkv, out, dout, lse, delta, dqkv, B, L, H, d, drop_p, seed, flags, ldq, ldo, nullptr, stream);
+}
+extern "C" int orbit2_attn_bwd_gated(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+                                     void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq,
+                                     int ldo, const float* gate, void* stream) {
+  return attn_bwd_launch(qkv, out, dout, lse, delta, dqkv, B, L, H, d, drop_p, seed, flags, ldq, ldo, gate, stream);
 }

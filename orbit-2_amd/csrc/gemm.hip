@@ -84,7 +84,12 @@ struct Epi {
   bf16_t* save_dact;   // GELU'(pre) x dropout factor of the element, for the backward (see include/orbit2_hip.h)
   const bf16_t* mul;   // elementwise multiplier: the q14 factor tensor written through save_dact
   float rs_tile;       // (kernel-internal) the tile's row scale when the epilogue kind is 2
+  int rows_per_gate;   // rows of one entry of `gate`
   float* colsum_ws;    // kind 3 only: fp32 [M / 256][N], row t = column sums of the bf16-rounded output over tile row t
+  // path gate (orbit2_gemm_bf16_gated; a hint): an output tile whose rows all lie in one entry with gate[entry] == 0.0f -- a
+  // sample whose branch DropPath dropped -- may skip its contraction and store what annihilated inputs give: zeros (C, save_pre,
+  // save_dact, its colsum_ws row), or the residual rows when the row scale is the gate.  A kernel that ignores it is correct.
+  const float* gate;
 };
 
 __device__ __forceinline__ void epilogue4(const Epi& e, int m, int n, f32x4 v) {
@@ -492,12 +497,18 @@ struct GProb {
   const bf16_t* B;
   int M, N, K, lda, ldb, tiles_m, tiles_n, tile_end;
   Epi epi;
+  // K gate of a weight gradient (orbit2_gemm_bf16_grouped_gated; a hint): entry e covers rows e * k_per_gate onwards of the
+  // CONTRACTION (the tokens of one sample); kgate[e] == 0.0f says that the dY rows of that range are zeros, and the 4-wave TN
+  // kernel sweeps the kept ranges only
+  const float* kgate;
+  int k_per_gate;
 };
 struct GArgs {
   int n;
   int pace;        // 4-wave kernel: cohort start barrier (w4_cohort_start) -- long contractions, round-major ids
   GProb p[ORBIT2_GEMM_MAX_GROUP];
 };
+static_assert(sizeof(GArgs) <= 4096, "GArgs travels by value as the grouped kernels' argument: the kernarg segment holds 4 KiB");
 
 template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(256, 2) void gemm128_grouped_kernel(GArgs g) {
@@ -913,12 +924,40 @@ __device__ __forceinline__ void w4_generic_finish(const Epi& epi, const char* sm
   }
 }
 
+// Path gate of the 4-wave kernel: the store a dropped tile makes in place of its contraction and epilogue (see Epi::gate).  A lane
+// owns 8 consecutive n of a row, 32 lanes one 512-byte row segment, 8 rows per step: whole-line 16-byte stores.
+__device__ __forceinline__ void w4_gate_fill(const Epi& epi, int m0, int n0, int tid) {
+  const int n = n0 + 8 * (tid & 31), r8 = tid >> 5;
+  const u32x4 zero = {0u, 0u, 0u, 0u};
+  if (epi.residual) {
+#pragma unroll 1
+    for (int g0 = 0; g0 < 32; g0 += 8) {
+      u32x4 r[8];
+#pragma unroll
+      for (int g = 0; g < 8; ++g) r[g] = *reinterpret_cast<const u32x4*>(epi.residual + (size_t)(m0 + (g0 + g) * 8 + r8) * epi.ldr + n);
+#pragma unroll
+      for (int g = 0; g < 8; ++g)
+        *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(epi.C) + (size_t)(m0 + (g0 + g) * 8 + r8) * epi.ldc + n) = r[g];
+    }
+    return;
+  }
+#pragma unroll 4
+  for (int g = 0; g < 32; ++g) {
+    const size_t off = (size_t)(m0 + g * 8 + r8) * epi.ldc + n;
+    *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(epi.C) + off) = zero;
+    if (epi.save_pre) *reinterpret_cast<u32x4*>(epi.save_pre + off) = zero;
+    if (epi.save_dact) *reinterpret_cast<u32x4*>(epi.save_dact + off) = zero;
+  }
+  if (epi.colsum_ws) epi.colsum_ws[(size_t)(m0 >> 8) * epi.N + n0 + tid] = 0.f;
+}
+
 // FORM: 0 = NT (A, B K-contiguous), 1 = NN (B K-strided: the stored weight in dX = dY.W), 2 = TN (both K-strided: dW = dY^T.X),
 // 3 = TT.  STAMP (diagnostic build only): per-segment cycle sums of the loop into o2_dbg_w4.
 template <int FORM, bool STAMP, int EK = 0>
 __device__ __forceinline__ void gemm256w_tile(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, int M, int N,
                                               int K, int lda, int ldb, int tiles_m, int tiles_n, const Epi& epi, int id,
-                                              char* smem, const unsigned int* pace_ctr = nullptr, int pace_n = 0) {
+                                              char* smem, const unsigned int* pace_ctr = nullptr, int pace_n = 0,
+                                              const float* kgate = nullptr, int k_per_gate = 0) {
   constexpr bool A_KC = (FORM == 0 || FORM == 1), B_KC = (FORM == 0 || FORM == 3);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -947,6 +986,14 @@ __device__ __forceinline__ void gemm256w_tile(const bf16_t* __restrict__ A, cons
   const int t_b = (id % per_group) / gsz;
   const int tm = tw ? t_b : t_a, tn = tw ? t_a : t_b;
   const int m0 = tm * BM2, n0 = tn * BN2;
+
+  if (epi.gate) {                                   // wave-uniform: one scalar load per tile
+    const int entry = m0 / epi.rows_per_gate;
+    if ((m0 + BM2 - 1) / epi.rows_per_gate == entry && epi.gate[entry] == 0.0f) {
+      w4_gate_fill(epi, m0, n0, tid);
+      return;
+    }
+  }
 
 #ifdef O2_W4_STAMP
   const unsigned ts0 = (unsigned)__builtin_amdgcn_s_memtime();
@@ -977,11 +1024,11 @@ __device__ __forceinline__ void gemm256w_tile(const bf16_t* __restrict__ A, cons
   else { vob = (uint32_t)((16 * (rr >> 1) + 4 * (rr & 1)) * ldb + cp * 8) * 2u; pb0 = (uint32_t)(sk0 * ldb) * 2u; psb = (uint32_t)ldb * 2u; phb = 256u; kb = (uint32_t)(64 * ldb) * 2u; }
   // descriptor bases (the statement builds the descriptors and advances their bases along K: every per-lane / per-piece
   // offset stays below 256 rows x row pitch)
-  const bf16_t* abase = A_KC ? A + (size_t)m0 * lda : A + m0;
+  const bf16_t* abase = A_KC ? A + (size_t)m0 * lda : A + m0;      // (the K gate moves both bases and nk from range to range)
   const bf16_t* bbase = B_KC ? B + (size_t)n0 * ldb : B + n0;
   const uint32_t ldswa = lds0 + wave * 4 * (A_KC ? 1024 : 1056);
   const uint32_t ldswb = lds0 + 2 * O2_W4_UNIT + wave * 4 * (B_KC ? 1024 : 1056);
-  const uint32_t nk = (uint32_t)(K / BK3);
+  uint32_t nk = (uint32_t)(K / BK3);
   // cohort pacing inside the sweep (the TN statement only reads these): the counter's address for the ONE wave that arrives and
   // polls on the workgroup's behalf, 0 for the others and for unpaced launches
   const uint64_t pc64 = (wave == 0) ? (uint64_t)(uintptr_t)pace_ctr : 0ull;
@@ -1001,7 +1048,42 @@ __device__ __forceinline__ void gemm256w_tile(const bf16_t* __restrict__ A, cons
                : O2_W4_CLOBBERS)
     if constexpr (FORM == 0) O2_W4_RUN(O2_W4_ASM_NT);
     if constexpr (FORM == 1) O2_W4_RUN(O2_W4_ASM_NN);
-    if constexpr (FORM == 2) O2_W4_RUN(O2_W4_ASM_TN);
+    if constexpr (FORM == 2) {
+      // K gate: the sweep in segments, one statement per run of kept entries -- the first clears the accumulators, the others
+      // continue (O2_W4_ASM_TN_CONT) behind a barrier (a wave's prologue refills the stages its neighbours may still be reading).
+      // Everything here is workgroup-uniform.  No kept entry at all: the plain sweep (its products are zeros, the epilogue runs).
+      int s = 0, ns = 0;
+      if (kgate) {
+        ns = K / k_per_gate;
+        while (s < ns && kgate[s] == 0.0f) ++s;
+        if (s == ns) ns = 0;
+      }
+      if (ns == 0) {
+        O2_W4_RUN(O2_W4_ASM_TN);
+      } else {
+        const bf16_t *abase0 = abase, *bbase0 = bbase;
+        const uint32_t voa0 = voa, vob0 = vob, ra00 = ra0, ra10 = ra1, rb00 = rb0, rb10 = rb1;
+        bool first = true;
+        while (s < ns) {
+          int e = s + 1;
+          while (e < ns && kgate[e] != 0.0f) ++e;
+          const size_t k0 = (size_t)__builtin_amdgcn_readfirstlane(s) * (size_t)k_per_gate;
+          abase = abase0 + k0 * (size_t)lda;
+          bbase = bbase0 + k0 * (size_t)ldb;
+          nk = (uint32_t)__builtin_amdgcn_readfirstlane((e - s) * (k_per_gate / BK3));
+          voa = voa0; vob = vob0; ra0 = ra00; ra1 = ra10; rb0 = rb00; rb1 = rb10;
+          if (first) {
+            O2_W4_RUN(O2_W4_ASM_TN);
+          } else {
+            __syncthreads();
+            O2_W4_RUN(O2_W4_ASM_TN_CONT);
+          }
+          first = false;
+          s = e;
+          while (s < ns && kgate[s] == 0.0f) ++s;
+        }
+      }
+    }
     if constexpr (FORM == 3) O2_W4_RUN(O2_W4_ASM_TT);
 #undef O2_W4_RUN
   }
@@ -1177,7 +1259,8 @@ __global__ __launch_bounds__(256, 1) void gemm256w_grouped_kernel(GArgs g) {
   const int first = pi ? g.p[pi - 1].tile_end : 0;
   const GProb& P = g.p[pi];
   const Epi epi = P.epi;
-  gemm256w_tile<FORM, false>(P.A, P.B, P.M, P.N, P.K, P.lda, P.ldb, P.tiles_m, P.tiles_n, epi, id - first, smem, pace_ctr, pace_n);
+  gemm256w_tile<FORM, false>(P.A, P.B, P.M, P.N, P.K, P.lda, P.ldb, P.tiles_m, P.tiles_n, epi, id - first, smem, pace_ctr, pace_n,
+                             P.kgate, P.k_per_gate);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1329,7 +1412,18 @@ static int gemm_make_epi(const orbit2_gemm_args* a, Epi& e) {
   e.beta = a->beta;
   e.rs_tile = 1.0f;
   e.colsum_ws = a->colsum_ws;
+  e.gate = nullptr;
+  e.rows_per_gate = 0;
   return O2_OK;
+}
+
+// the epilogues whose result for a dropped entry is known without the contraction: bf16 output that replaces C, and either no
+// residual (zeros) or the residual added behind a row scale that IS the gate (the residual rows).  Any other call ignores the gate.
+static bool gemm_gate_ok(const Epi& e, const float* gate, int rows_per_gate) {
+  if (!gate || rows_per_gate <= 0 || e.out_fp32 || e.beta != 0.f) return false;
+  if (e.residual) return !e.res_first && e.res_mod == 0 && e.rowscale == gate && e.rows_per_scale == rows_per_gate &&
+                         !e.save_pre && !e.save_dact && !e.colsum_ws && e.ldr % 8 == 0 && !((uintptr_t)e.residual & 15);
+  return !e.rowscale;
 }
 
 // ---- kernel selection.  gemm_plan / gemm_group_plan decide which kernel takes a call and on which grid; they launch nothing.
@@ -1452,6 +1546,7 @@ static int gemm_group_plan(const orbit2_gemm_args* args, int n, GemmFamily& fami
     GProb& P = g.p[i];
     P.A = (const bf16_t*)a->A; P.B = (const bf16_t*)a->B;
     P.M = a->M; P.N = a->N; P.K = a->K; P.lda = a->lda; P.ldb = a->ldb;
+    P.kgate = nullptr; P.k_per_gate = 0;
     P.tiles_m = (a->M + TB - 1) / TB; P.tiles_n = (a->N + TB - 1) / TB;
     total += P.tiles_m * P.tiles_n;
     P.tile_end = total;
@@ -1469,11 +1564,14 @@ static int gemm_group_plan(const orbit2_gemm_args* args, int n, GemmFamily& fami
   return O2_OK;
 }
 
-extern "C" int orbit2_gemm_bf16(const orbit2_gemm_args* a, void* stream) {
+// one launch; gate / rows_per_gate: the path gate of orbit2_gemm_bf16_gated (nullptr: none).  The plan does not look at the
+// gate: a gated call runs exactly the kernel, grid and block of the ungated call.
+static int gemm_launch(const orbit2_gemm_args* a, const float* gate, int rows_per_gate, void* stream) {
   Epi e;
   GemmPlan p;
   int rc = gemm_make_epi(a, e);
   if (rc) return rc;
+  if (gemm_gate_ok(e, gate, rows_per_gate)) { e.gate = gate; e.rows_per_gate = rows_per_gate; }
   rc = gemm_plan(a, e, p);
   if (a->colsum_ws && !p.fuses_colsum) return O2_ERR_UNSUPPORTED;   // ask orbit2_gemm_bf16_colsum_rows first
   if (rc) return rc;
@@ -1505,6 +1603,13 @@ extern "C" int orbit2_gemm_bf16(const orbit2_gemm_args* a, void* stream) {
   return O2_OK;
 }
 
+extern "C" int orbit2_gemm_bf16(const orbit2_gemm_args* a, void* stream) { return gemm_launch(a, nullptr, 0, stream); }
+
+extern "C" int orbit2_gemm_bf16_gated(const orbit2_gemm_args* a, const float* gate, int rows_per_gate, void* stream) {
+  if (gate && rows_per_gate <= 0) return O2_ERR_ARG;
+  return gemm_launch(a, gate, rows_per_gate, stream);
+}
+
 extern "C" int orbit2_gemm_bf16_colsum_rows(const orbit2_gemm_args* a) {
   Epi e;
   GemmPlan p;
@@ -1513,7 +1618,8 @@ extern "C" int orbit2_gemm_bf16_colsum_rows(const orbit2_gemm_args* a) {
   return p.fuses_colsum ? a->M / 256 : 0;
 }
 
-extern "C" int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, void* stream) {
+// kgates / k_per_gate: the K gates of orbit2_gemm_bf16_grouped_gated (nullptr: none); the plan does not look at them
+static int gemm_group_launch(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate, void* stream) {
   if (!args || n <= 0 || n > ORBIT2_GEMM_MAX_GROUP) return O2_ERR_ARG;
   if (n == 1) return orbit2_gemm_bf16(args, stream);
   for (int i = 0; i < n; ++i)
@@ -1522,6 +1628,12 @@ extern "C" int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, voi
   GArgs g;
   const int rc = gemm_group_plan(args, n, family, g);
   if (rc) return rc;
+  if (kgates && k_per_gate && family == GEMM_256W && !args[0].a_kc && !args[0].b_kc)
+    for (int i = 0; i < n; ++i)       // whole entries of whole K-tiles, or the problem ignores its gate
+      if (kgates[i] && k_per_gate[i] > 0 && k_per_gate[i] % BK3 == 0 && args[i].K % k_per_gate[i] == 0) {
+        g.p[i].kgate = kgates[i];
+        g.p[i].k_per_gate = k_per_gate[i];
+      }
   const dim3 grid(g.p[n - 1].tile_end), block(gemm_block(family));
   hipStream_t s = (hipStream_t)stream;
   o2_with_flags([&](auto AK, auto BK) {
@@ -1533,6 +1645,14 @@ extern "C" int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, voi
   }, args[0].a_kc != 0, args[0].b_kc != 0);
   O2_CHECK_LAUNCH();
   return O2_OK;
+}
+
+extern "C" int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, void* stream) {
+  return gemm_group_launch(args, n, nullptr, nullptr, stream);
+}
+extern "C" int orbit2_gemm_bf16_grouped_gated(const orbit2_gemm_args* args, int n, const float* const* kgates,
+                                              const int* k_per_gate, void* stream) {
+  return gemm_group_launch(args, n, kgates, k_per_gate, stream);
 }
 
 // split-K plan of the skinny table products: enough slabs to put >= ~1024 workgroups on the chip, >= 4 staged k-steps each

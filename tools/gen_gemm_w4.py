@@ -21,7 +21,9 @@ Shape of the loop (gfx950, one wave per SIMD, 4 waves = one 256 x 256 tile, a wa
       bar2       : vmcnt(pieces of t + 2 issued so far) + s_barrier: K-tile t + 1 has landed for every wave
       then       : X reads of K-tile t + 1; counted lgkmcnt in front of their first uses in the next K-tile
   * K-tiles past the end re-load the last one into a stage nobody reads again: constant vmcnt arithmetic, no branches.
-Operands of the statement are named (%[...]); scratch SGPRs s64-s99 and every register above are clobbers."""
+Operands of the statement are named (%[...]); scratch SGPRs s64-s99 and every register above are clobbers.
+O2_W4_ASM_TN_CONT is the weight-gradient statement without the accumulator clear: it adds a further range of the contraction to the
+accumulators an earlier statement of the same tile left in a[0:255]."""
 import os
 
 UNIT = 16896                       # 16 pieces x (1024 + 32): the K-strided image; the K-contiguous image uses 16384 of it
@@ -135,8 +137,9 @@ def gen(a_kc, b_kc, cfg):
             e(x)
         for x in flip_write_bases():
             e(x)
-    for r in range(256):
-        e("v_accvgpr_write_b32 a%d, 0" % r)
+    if not cfg.get("cont"):                                   # (cont: the statement continues a sweep -- the accumulators are live)
+        for r in range(256):
+            e("v_accvgpr_write_b32 a%d, 0" % r)
     e("s_waitcnt vmcnt(16)")
     e("s_barrier")
     xreads = frag_reads("b", b_kc, [XB(j) for j in range(8)], 0) + frag_reads("a", a_kc, [XA(i) for i in range(8)], 0)
@@ -339,6 +342,10 @@ def emit(path):
         if cfg.get("kwrap_tn"):                  # (ablation restricted to the weight-gradient form: a step's activations stay right)
             cfg["kwrap"] = cfg["kwrap_tn"] if name == "TN" else 0
         macro("O2_W4_ASM_%s" % name, gen(a_kc, b_kc, cfg))
+        if name == "TN":
+            # the weight-gradient sweep in segments (csrc/gemm.hip, the K gate): the same statement without the accumulator clear --
+            # a fresh prologue (descriptors, piece offsets, two K-tiles in flight) on the next kept range of the contraction
+            macro("O2_W4_ASM_TN_CONT", gen(a_kc, b_kc, dict(cfg, cont=True)))
         macro("O2_W4_ASM_%s_STAMP" % name, gen(a_kc, b_kc, dict(BASE, stamp=True, pace=0)))
     clob = ['"memory"', '"scc"', '"vcc"'] + ['"a%d"' % r for r in range(256)] + ['"v%d"' % r for r in range(128, 256)] + \
            ['"s%d"' % r for r in range(64, 100)]
