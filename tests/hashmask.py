@@ -32,6 +32,39 @@ def keep_mask(seed: int, n_elems: int, p: float):
     return (byte >= np.uint64(thr)).astype(np.float32), 256.0 / (256.0 - thr)
 
 
+DROPPATH_SALT = 0xD1B54A32D192ED03
+
+
+def droppath_scales(seed: int, B: int, p: float) -> np.ndarray:
+    """float32 [B] per-sample DropPath scales (csrc/norm_elem.hip: droppath_scales_kernel): u = (h >> 8) / 2^24 of the hash of
+    seed ^ DROPPATH_SALT at index b, kept iff u >= float32(p), scale 1 / (1 - p) in float32 arithmetic as the kernel computes it"""
+    h = o2_hash64((seed ^ DROPPATH_SALT) & 0xFFFFFFFFFFFFFFFF, np.arange(B, dtype=np.uint64))
+    u = (h >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    p32 = np.float32(p)
+    return np.where(u >= p32, np.float32(1.0) / (np.float32(1.0) - p32), np.float32(0.0)).astype(np.float32)
+
+
+def hash_mix(x: np.ndarray) -> np.ndarray:
+    """the two-multiply finaliser of o2_hash64 alone (no fold of the high words)"""
+    h = x.astype(np.uint64) & M32
+    h ^= h >> np.uint64(16)
+    h = (h * np.uint64(0x7FEB352D)) & M32
+    h ^= h >> np.uint64(15)
+    h = (h * np.uint64(0x846CA68B)) & M32
+    h ^= h >> np.uint64(16)
+    return h
+
+
+def dkv_w4_hseed(seed: int) -> int:
+    """the constant the generated d = 128 dK + dV kernel xors into a query-row index in place of calling o2_hash64
+    (csrc/attn.hip attn_bwd_dkv_w4: hseed = s_lo ^ rot16(s_hi) ^ (s_hi + (s_hi << 3))): o2_hash64(seed, idx) =
+    hash_mix(idx ^ hseed) for idx < 2^32"""
+    seed &= 0xFFFFFFFFFFFFFFFF
+    s_lo, s_hi = seed & 0xFFFFFFFF, seed >> 32
+    rot = ((s_hi << 16) | (s_hi >> 16)) & 0xFFFFFFFF
+    return s_lo ^ rot ^ ((s_hi + (s_hi << 3)) & 0xFFFFFFFF)
+
+
 ATTN_KEY_SALT = 0x85EBCA6B9E3779B9
 
 

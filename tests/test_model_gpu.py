@@ -346,7 +346,7 @@ def test_train_mode_step_matches_oracle_with_replicated_masks(p_drop):
     from climate_learn.metrics import Bayesian_TV
     from oracle.harness import build_pair, nerr
     from climate_learn.trainer import training_step
-    from tests.hashmask import attn_keep_mask, keep_mask, o2_hash64
+    from tests.hashmask import attn_keep_mask, droppath_scales, keep_mask
     D, depth, heads, grid, B = 128, 3, 2, (16, 32), 2
     p_path = 0.2
     model, sd, cfg, O, x, y, in_vars, out_vars = build_pair(D=D, depth=depth, heads=heads, grid=grid, B=B, seed=31)
@@ -370,9 +370,7 @@ def test_train_mode_step_matches_oracle_with_replicated_masks(p_drop):
         return (torch.from_numpy(m) * sc).view(B, L, n_cols)
 
     def droppath(seed, p):
-        h = o2_hash64(seed ^ 0xD1B54A32D192ED03, np.arange(B, dtype=np.uint64))
-        u = (h >> np.uint64(8)).astype(np.float64) / 16777216.0
-        return torch.from_numpy(np.where(u >= p, 1.0 / (1.0 - p), 0.0)).float()
+        return torch.from_numpy(droppath_scales(seed, B, p))
 
     masks = {"pos": flat(ss.next(), D)}
     for i in range(depth):
