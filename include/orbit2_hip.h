@@ -125,6 +125,27 @@ int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, void* stream);
 int orbit2_gemm_bf16_grouped_gated(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate,
                                    void* stream);
 
+/* ---- TAIL QUEUE (additive entries; csrc/tail_queue.h) ---------------------------
+ * The launches of the one-workgroup-per-CU kernels (the 4-wave 256 x 256 GEMM, single and grouped; the generated d = 128 attention
+ * kernels) with their LAST ROUNDS of tiles handed out by ticket instead of by workgroup number: workgroup b always runs on XCD
+ * b & 7, so a static walk ends when the slowest XCD ends; here an XCD that gets to the tail first takes more of it.  The first
+ * T - tail tiles keep the ids of the plain entries; 2 * tail further workgroups each draw one ticket (one relaxed agent-scope
+ * atomic) and either take one of the last `tail` tiles or return.  No workgroup waits.  Every tile computes what it computes in
+ * the plain entry: the results are bit-identical.
+ *   sched_ws: one 32-bit device word (4-byte aligned), ZERO before the call; the launch leaves it zero (the drawer of the last
+ *     ticket clears it), so back-to-back calls on one stream and replays of a captured graph reuse it as it is.  Calls that may run
+ *     at the same time (different streams) need different words.  A launch aborted half-way leaves the number of tickets drawn
+ *     so far: zero the word before it is used again.  NULL: O2_ERR_ARG.
+ *   tail: 0 = sized by the library per kernel family (0, 2 or 4 whole rounds of the device's 256 workgroup slots, from
+ *     profiles/r08_tail_idle.txt; a launch that would keep fewer than 4 static rounds in front of its tail, and any device that
+ *     is not 256 CUs on 8 XCDs, stay static); > 0 = that many tiles (tests: small problems with a queued part; more
+ *     than the launch has: static); < 0 = static.
+ * A call whose plan is another kernel family launches exactly what the plain entry launches.  gate / kgates may be NULL. */
+int orbit2_gemm_bf16_tq(const orbit2_gemm_args* args, const float* gate, int rows_per_gate, void* sched_ws, int tail,
+                        void* stream);
+int orbit2_gemm_bf16_grouped_tq(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate,
+                                void* sched_ws, int tail, void* stream);
+
 /* small fp32 GEMM (parameter-table algebra of the folded variable aggregation):
  * C[M,N] = alpha * op(A) * op(B) + beta*C, row-major fp32; ta/tb: 0 = as stored, 1 = transposed.
  * ws: caller-owned fp32 workspace of orbit2_sgemm_f32_ws_floats(M,N,K) floats: skinny problems (a few rows against a D x D
@@ -188,6 +209,12 @@ int orbit2_attn_fwd_gated(const void* qkv, void* out, float* lse, int B, int L, 
 int orbit2_attn_bwd_gated(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                           void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq, int ldo,
                           const float* gate, void* stream);
+/* The same with a tail queue (see orbit2_gemm_bf16_tq; the backward's dQ and dK + dV passes use the one word in turn) */
+int orbit2_attn_fwd_tq(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
+                       uint64_t seed, int flags, int ldq, int ldo, const float* gate, void* sched_ws, int tail, void* stream);
+int orbit2_attn_bwd_tq(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+                       void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq, int ldo,
+                       const float* gate, void* sched_ws, int tail, void* stream);
 /* orbit2_attn_fwd_ld with fp32 qkv / out (attention.py:54-78 under data_type float32, components/attention.py:66-70): streaming
  * softmax in fp32, both products on v_mfma_f32_32x32x2_f32.  ldq, ldo % 4 == 0.  No dropout: drop_p != 0 returns
  * O2_ERR_UNSUPPORTED, as does any flag other than ORBIT2_ATTN_Q_PRESCALED (honoured as above: without it the kernel multiplies

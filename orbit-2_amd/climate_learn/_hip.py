@@ -62,6 +62,8 @@ PROTOTYPES = {
     "orbit2_gemm_f32": (_I, (_G, _P)),
     "orbit2_gemm_bf16_grouped": (_I, (_G, _I, _P)),
     "orbit2_gemm_bf16_grouped_gated": (_I, (_G, _I, _P, _P, _P)),
+    "orbit2_gemm_bf16_tq": (_I, (_G, _P, _I, _P, _I, _P)),
+    "orbit2_gemm_bf16_grouped_tq": (_I, (_G, _I, _P, _P, _P, _I, _P)),
     "orbit2_sgemm_f32_ws_floats": (_I64, (_I, _I, _I)),
     "orbit2_sgemm_f32_ws": (_I, (_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _I64, _P)),
     "orbit2_layernorm_fwd_ld": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P)),
@@ -74,6 +76,8 @@ PROTOTYPES = {
     "orbit2_attn_bwd_ld": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P)),
     "orbit2_attn_fwd_gated": (_I, (_P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P, _P)),
     "orbit2_attn_bwd_gated": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P, _P)),
+    "orbit2_attn_fwd_tq": (_I, (_P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P, _P, _I, _P)),
+    "orbit2_attn_bwd_tq": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P, _P, _I, _P)),
     "orbit2_varagg_fwd": (_I, (_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P)),
     "orbit2_varagg_fwd_f32": (_I, (_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P)),
     "orbit2_varagg_bwd_ws_floats": (_I64, (_I, _I, _I, _I, _I, _I)),
@@ -180,6 +184,54 @@ def _dev(t: torch.Tensor, dtype, name: str):
 BF, F32 = torch.bfloat16, torch.float32
 
 
+# ---- tail queue (include/orbit2_hip.h: orbit2_gemm_bf16_tq) -------------------------------------------------------------------
+# One zeroed counter word per stream: launches on one stream run one after the other and each leaves its word zero, launches on
+# different streams may overlap and must not share one.  The words live 128 bytes apart in one buffer per device that is never
+# freed (a captured graph keeps the address), handed out in the order streams first ask.  A launch that was aborted half-way
+# leaves a count behind: sched_reset() zeroes everything.
+_SCHED_SLOTS, _SCHED_STRIDE = 256, 32           # words apart
+_sched_bufs, _sched_slots = {}, {}
+
+
+def sched_workspace(device=None):
+    """the device's counter buffer (int32 [_SCHED_SLOTS * _SCHED_STRIDE]); all zeros whenever no tail-queue launch is running"""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    if idx not in _sched_bufs:
+        _sched_bufs[idx] = torch.zeros(_SCHED_SLOTS * _SCHED_STRIDE, dtype=torch.int32, device=torch.device("cuda", idx))
+    return _sched_bufs[idx]
+
+
+def sched_reset():
+    for buf in _sched_bufs.values():
+        buf.zero_()
+
+
+def _sched_word(device) -> int:
+    """the address of the current stream's counter word on `device`"""
+    buf = sched_workspace(device)
+    key = (buf.device.index, torch.cuda.current_stream(buf.device).cuda_stream)
+    slot = _sched_slots.get(key)
+    if slot is None:
+        slot = len([k for k in _sched_slots if k[0] == key[0]])
+        if slot >= _SCHED_SLOTS:
+            raise HipBackendError("tail queue: more than %d streams asked for a counter word" % _SCHED_SLOTS)
+        _sched_slots[key] = slot
+    return buf.data_ptr() + 4 * _SCHED_STRIDE * slot
+
+
+def _tail_arg(tail_queue):
+    """tail_queue of the wrappers -> the entries' `tail`, or None for the plain entries: None / False = plain, True = sized by
+    the library, an int > 0 = that many tiles by ticket (tests)"""
+    if tail_queue is None or tail_queue is False:
+        return None
+    if tail_queue is True:
+        return 0
+    if int(tail_queue) <= 0:
+        raise HipBackendError("tail_queue: True, or a positive number of tiles")
+    return int(tail_queue)
+
+
 def _dev_rows(t: torch.Tensor, dtype, name: str):
     """a GEMM operand / epilogue tensor handed over with an explicit leading dimension: rows contiguous, any row pitch"""
     if t.dim() == 2 and t.stride(1) == 1 and t.is_cuda and t.dtype == dtype:
@@ -242,19 +294,24 @@ def _gemm_fill(a, A, B, out, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, bias=
     return 2.0 * M * N * K, 2.0 * (M * K + N * K) + M * N * (4.0 if out.dtype == F32 else 2.0)
 
 
-def gemm(A, B, out, M, N, K, lda, ldb, ldc, want_colsum=False, gate=None, rows_per_gate=0, **kw):
+def gemm(A, B, out, M, N, K, lda, ldb, ldc, want_colsum=False, gate=None, rows_per_gate=0, tail_queue=None, **kw):
     """out[M,N] = epilogue(A x B); see include/orbit2_hip.h:orbit2_gemm_bf16.
     want_colsum: returns (out, parts) -- parts = fp32 [M / 256, N] per-tile-row column sums of the stored output when this call
     can fuse them (orbit2_gemm_bf16_colsum_rows), else None: the caller then runs `colsum` on `out` itself.
     gate: fp32 [ceil(M / rows_per_gate)] path gate (orbit2_gemm_bf16_gated): rows of an entry that is 0.0 may be stored as zeros
-    (as the residual rows when `rowscale` is the gate) without being computed."""
+    (as the residual rows when `rowscale` is the gate) without being computed.
+    tail_queue: True = the launch's last rounds by ticket (orbit2_gemm_bf16_tq; _tail_arg); the results are the same bits."""
+    tail = _tail_arg(tail_queue)
     if gate is not None:
         _dev(gate, F32, "gate")
         if rows_per_gate <= 0 or gate.numel() * rows_per_gate < M:
             raise HipBackendError("gemm gate needs rows_per_gate > 0 and one entry per rows_per_gate rows")
 
     def launch(a):
-        if gate is None:
+        if tail is not None:
+            _chk(lib().orbit2_gemm_bf16_tq(C.byref(a), _p(gate), rows_per_gate if gate is not None else 0, _sched_word(out.device),
+                                           tail, _stream()), "orbit2_gemm_bf16_tq")
+        elif gate is None:
             _chk(lib().orbit2_gemm_bf16(C.byref(a), _stream()), "orbit2_gemm_bf16")
         else:
             _chk(lib().orbit2_gemm_bf16_gated(C.byref(a), gate.data_ptr(), rows_per_gate, _stream()), "orbit2_gemm_bf16_gated")
@@ -308,10 +365,12 @@ def gemm_f32(A, B, out, M, N, K, lda, ldb, ldc, bias=None, act=0, residual=None,
 GEMM_MAX_GROUP = 12
 
 
-def gemm_grouped(problems):
+def gemm_grouped(problems, tail_queue=None):
     """problems: list of (A, B, out, M, N, K, lda, ldb, ldc, kwargs) sharing one operand form; one launch
     (include/orbit2_hip.h:orbit2_gemm_bf16_grouped).  A problem's kwargs may hold kgate = (fp32 vector, rows of the contraction
-    per entry): the K gate of orbit2_gemm_bf16_grouped_gated -- ranges of the contraction whose entry is 0.0 hold zero rows in A."""
+    per entry): the K gate of orbit2_gemm_bf16_grouped_gated -- ranges of the contraction whose entry is 0.0 hold zero rows in A.
+    tail_queue: as in gemm (orbit2_gemm_bf16_grouped_tq)."""
+    tail = _tail_arg(tail_queue)
     n = len(problems)
     if not 0 < n <= GEMM_MAX_GROUP:
         raise HipBackendError("gemm_grouped takes 1..%d problems" % GEMM_MAX_GROUP)
@@ -331,7 +390,10 @@ def gemm_grouped(problems):
         nbytes += b
 
     def launch():
-        if gated:
+        if tail is not None:
+            _chk(lib().orbit2_gemm_bf16_grouped_tq(arr, n, kgates if gated else None, kper if gated else None,
+                                                   _sched_word(problems[0][2].device), tail, _stream()), "orbit2_gemm_bf16_grouped_tq")
+        elif gated:
             _chk(lib().orbit2_gemm_bf16_grouped_gated(arr, n, kgates, kper, _stream()), "orbit2_gemm_bf16_grouped_gated")
         else:
             _chk(lib().orbit2_gemm_bf16_grouped(arr, n, _stream()), "orbit2_gemm_bf16_grouped")
@@ -433,9 +495,11 @@ def _attn_gate(gate, B):
     return gate
 
 
-def attn_fwd(qkv, B, L, H, d, drop_p=0.0, seed=0, flags=0, out=None, gate=None):
+def attn_fwd(qkv, B, L, H, d, drop_p=0.0, seed=0, flags=0, out=None, gate=None, tail_queue=None):
     """out: optional [B * L, H * d] bf16 destination with any token-row pitch (orbit2_attn_fwd_ld); default [B, L, H * d].
-    gate: fp32 [B] path gate (orbit2_attn_fwd_gated): out and lse of a sample whose entry is 0.0 may be stored as zeros"""
+    gate: fp32 [B] path gate (orbit2_attn_fwd_gated): out and lse of a sample whose entry is 0.0 may be stored as zeros
+    tail_queue: as in gemm (orbit2_attn_fwd_tq)"""
+    tail = _tail_arg(tail_queue)
     _attn_gate(gate, B)
     _dev_rows(qkv, BF, "qkv")
     ldq = qkv.stride(0) if qkv.dim() == 2 else 3 * H * d       # [B * L, 3 * H * d] with a token-row pitch, or contiguous
@@ -449,7 +513,10 @@ def attn_fwd(qkv, B, L, H, d, drop_p=0.0, seed=0, flags=0, out=None, gate=None):
         # algorithmic bytes: qkv read once, out + lse written once
         e0, e1 = timer.span("attn_fwd", 4.0 * B * H * L * L * d, 2.0 * 4 * B * L * H * d + 4.0 * B * H * L)
         e0.record()
-    if gate is None:
+    if tail is not None:
+        _chk(lib().orbit2_attn_fwd_tq(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo),
+                                      _p(gate), _sched_word(qkv.device), tail, _stream()), "orbit2_attn_fwd_tq")
+    elif gate is None:
         _chk(lib().orbit2_attn_fwd_ld(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo),
                                       _stream()), "orbit2_attn_fwd_ld")
     else:
@@ -481,8 +548,10 @@ def attn_fwd_f32(qkv, B, L, H, d, drop_p=0.0, flags=0, out=None):
     return out, lse
 
 
-def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0, gate=None):
-    """gate: fp32 [B] path gate (orbit2_attn_bwd_gated): dqkv of a sample whose entry is 0.0 may be stored as zeros"""
+def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0, gate=None, tail_queue=None):
+    """gate: fp32 [B] path gate (orbit2_attn_bwd_gated): dqkv of a sample whose entry is 0.0 may be stored as zeros
+    tail_queue: as in gemm (orbit2_attn_bwd_tq)"""
+    tail = _tail_arg(tail_queue)
     _attn_gate(gate, B)
     _dev_rows(qkv, BF, "qkv"); _dev_rows(out, BF, "out"); _dev(dout, BF, "dout"); _dev(lse, F32, "lse")
     ldo = out.stride(0) if out.dim() == 2 else H * d           # [B * L, H * d] with a token-row pitch, or contiguous [B, L, H * d]
@@ -496,7 +565,10 @@ def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0, gate=
         # algorithmic: 2x the forward's FLOPs (recompute not credited); qkv, out, dout read once, dqkv written once
         e0, e1 = timer.span("attn_bwd", 8.0 * B * H * L * L * d, 2.0 * 8 * B * L * H * d + 8.0 * B * H * L)
         e0.record()
-    if gate is None:
+    if tail is not None:
+        _chk(lib().orbit2_attn_bwd_tq(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, L, H, d, drop_p, seed, int(flags),
+                                      int(ldq), int(ldo), _p(gate), _sched_word(qkv.device), tail, _stream()), "orbit2_attn_bwd_tq")
+    elif gate is None:
         _chk(lib().orbit2_attn_bwd_ld(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, L, H, d,
                                       drop_p, seed, int(flags), int(ldq), int(ldo), _stream()), "orbit2_attn_bwd_ld")
     else:

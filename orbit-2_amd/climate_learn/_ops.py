@@ -207,9 +207,15 @@ def _gelu_saved_dtype(p):
     return torch.int16 if _dact_ok(p) else BF
 
 
+# Tail queue: the one-workgroup-per-CU kernels hand the last rounds of their tiles out by ticket, so that an XCD that
+# is ahead takes more of them.  The library sizes the tail and leaves small launches, other kernel families and other devices
+# static.  ORBIT2_TAIL_QUEUE=0: the plain entries everywhere (A/B timing; the results are the same bits).
+_TQ = dict(tail_queue=True) if _os.environ.get("ORBIT2_TAIL_QUEUE", "1") != "0" else {}
+
+
 def _linear_fwd(x2d, W, b, M, N, K, pad=False, **kw):
     out = _rows(M, N, x2d.device) if pad else torch.empty(M, N, dtype=BF, device=x2d.device)
-    return _hip.gemm(x2d, cw(W), out, M, N, K, _ld(x2d, K), K, out.stride(0), bias=None if b is None else cw(b), **kw)
+    return _hip.gemm(x2d, cw(W), out, M, N, K, _ld(x2d, K), K, out.stride(0), bias=None if b is None else cw(b), **_TQ, **kw)
 
 
 def _dx(dy2d, W, M, N, K, pad=False, **kw):
@@ -217,7 +223,7 @@ def _dx(dy2d, W, M, N, K, pad=False, **kw):
     hardware-transposing LDS path of the 8-phase kernel (as fast as the K-contiguous form on a transposed copy --
     profiles/r02_gemm_t8_ab.txt -- so the per-step transposed weight copies of round 1 are gone)."""
     out = _rows(M, K, dy2d.device) if pad else torch.empty(M, K, dtype=BF, device=dy2d.device)
-    return _hip.gemm(dy2d, cw(W), out, M, K, N, _ld(dy2d, N), K, out.stride(0), a_kc=True, b_kc=False, **kw)
+    return _hip.gemm(dy2d, cw(W), out, M, K, N, _ld(dy2d, N), K, out.stride(0), a_kc=True, b_kc=False, **_TQ, **kw)
 
 
 # Path gate (DESIGN.md): the Block hands its per-sample DropPath scales to the kernels between the scale's two uses, which may
@@ -251,7 +257,7 @@ def _dw(dy2d, x2d, W, b, M, N, K):
         S, Mc = _DW_SPLIT, M // _DW_SPLIT
         parts = torch.empty(S, N, K, dtype=BF, device=dy2d.device)     # bf16 partials, summed in fp32 by orbit2_batch_sum
         _hip.gemm_grouped([(dy2d[i * Mc:(i + 1) * Mc], x2d[i * Mc:(i + 1) * Mc], parts[i], N, K, Mc, dy2d.stride(0), x2d.stride(0), K,
-                            dict(a_kc=False, b_kc=False)) for i in range(S)])
+                            dict(a_kc=False, b_kc=False)) for i in range(S)], **_TQ)
         _hip.batch_sum(parts, S, N, K, sw.buf, beta=sw.beta)
     else:
         _hip.gemm(dy2d, x2d, sw.buf, N, K, M, _ld(dy2d, N), _ld(x2d, K), K, a_kc=False, b_kc=False, beta=sw.beta)
@@ -366,7 +372,7 @@ class _DwBatch:
         """launches the group; returns the per-problem values backward must return for the weights"""
         probs, sums = _dw_balance(self.problems)
         for i in range(0, len(probs), _hip.GEMM_MAX_GROUP):     # the whole node as ONE grouped launch
-            _hip.gemm_grouped(probs[i:i + _hip.GEMM_MAX_GROUP])
+            _hip.gemm_grouped(probs[i:i + _hip.GEMM_MAX_GROUP], **_TQ)
         for parts, S, rows, K, dst, beta in sums:               # the split tiles' partial products, summed in a fixed order
             _hip.batch_sum(parts, S, rows, K, dst, beta=beta)
         out = [s.done() for s in self.sinks]
@@ -449,7 +455,7 @@ class BlockFn(torch.autograd.Function):
         g1, g2 = (_gate_kw(dp1, L), _gate_kw(dp2, L)) if grp is None else ({}, {})
         qkv = _linear_fwd(h1, wqkv, bqkv, M, 3 * Dl, D, pad=True, colscale=(Dl, _Q_PRESCALE / math.sqrt(d)), **g1)
         o2d, lse = _hip.attn_fwd(qkv, B, L, H, d, p_attn, sa, flags=_hip.ATTN_Q_PRESCALED, out=_rows(M, Dl, x2d.device),
-                                 gate=g1.get("gate"))
+                                 gate=g1.get("gate"), **_TQ)
         if grp is None:
             x1 = _linear_fwd(o2d, wp, bp, M, D, Dl, drop_p=p_proj, seed=sp, rowscale=dp1, rows_per_scale=L,
                              residual=x2d, ldr=D, **g1)
@@ -517,7 +523,8 @@ class BlockFn(torch.autograd.Function):
         do = _dx(dym1, wp, M, D, Dl, **g1)
         del dym1
         # (dqkv is the gradient with respect to the UNSCALED q, k, v: the qkv GEMM's backward needs no column scale)
-        dqkv = _hip.attn_bwd(qkv, o2d, do, lse, B, L, H, d, p_attn, sa, flags=_hip.ATTN_Q_PRESCALED, gate=g1.get("gate"))
+        dqkv = _hip.attn_bwd(qkv, o2d, do, lse, B, L, H, d, p_attn, sa, flags=_hip.ATTN_Q_PRESCALED, gate=g1.get("gate"),
+                             **_TQ)
         del do, o2d, qkv
         iq, gbqkv = dws.add(dqkv, h1, wqkv, bqkv, M, 3 * Dl, D, kgate=k1)
         dh1 = _dx(dqkv, wqkv, M, 3 * Dl, D, **g1)

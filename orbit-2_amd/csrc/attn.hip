@@ -19,11 +19,13 @@
 #define O2_DKV256_LA 2      /* k-steps of LDS operands in flight in the d = 256 fused dK+dV kernel */
 #endif
 #include "../../include/orbit2_hip.h"
+#include "tail_queue.h"
 #include "attn_fwd_asm.h"
 #include "attn_dq_asm.h"
 #include "attn_dkv_asm.h"
 
 namespace {
+O2_TQ_TRACE_DEFINE(o2_tq_trace_attn, orbit2_debug_read_tq_trace_attn)
 
 #ifdef O2_STAMP
 // Diagnostic build only (tools/stamp_build.sh): wave 0 of the first 64 workgroups of the forward / dK kernels sums the shader
@@ -105,14 +107,14 @@ __device__ __forceinline__ void stage_keyhash(uint32_t* skh, uint64_t seed, int 
 // CONTIGUOUS range of tile ids: the ~64 workgroups an XCD runs at a time are then consecutive tiles of one or two
 // (batch, head) pairs and share that pair's K/V (or Q/dO) through the XCD's L2, instead of every XCD streaming the
 // tiles of eight different heads.
-__device__ __forceinline__ void attn_tile_coords(int nq, int H, int& qt, int& head, int& b) {
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+__device__ __forceinline__ void attn_id_coords(int id, int nq, int H, int& qt, int& head, int& b) {
   qt = id % nq;
   const int grp = id / nq;
   head = grp % H;
   b = grp / H;
+}
+__device__ __forceinline__ void attn_tile_coords(int nq, int H, int& qt, int& head, int& b) {
+  attn_id_coords(o2_xcd_range_id((int)blockIdx.x, (int)gridDim.x), nq, H, qt, head, b);      // (tail_queue.h: the remap)
 }
 
 // The walk of the GATED kernels (path gate, include/orbit2_hip.h: orbit2_attn_fwd_gated): the SAMPLE fastest among the (sample,
@@ -121,11 +123,25 @@ __device__ __forceinline__ void attn_tile_coords(int nq, int H, int& qt, int& he
 // the launch still lasts as long as the seven full ones (measured: profiles/r07_path_gate_ab.txt, the first gated build's attention
 // kernels did not shrink); here every XCD loses the same share.  What an XCD runs at a time is still consecutive tiles of one or
 // two (sample, head) pairs.  Any bijection gives the same results: a tile's arithmetic depends on its coordinates alone.
-__device__ __forceinline__ void attn_tile_coords_gated(int nq, int H, int& qt, int& head, int& b) {
-  attn_tile_coords(nq, H, qt, b, head);          // (b, head) = (grp % H, grp / H) ...
-  const int grp = head * H + b, B = gridDim.x / (nq * H);
+__device__ __forceinline__ void attn_id_coords_gated(int id, int nq, int H, int B, int& qt, int& head, int& b) {
+  attn_id_coords(id, nq, H, qt, b, head);        // (b, head) = (grp % H, grp / H) ...
+  const int grp = head * H + b;
   b = grp % B;                                   // ... re-read as (grp % B, grp / B)
   head = grp / B;
+}
+__device__ __forceinline__ void attn_tile_coords_gated(int nq, int H, int& qt, int& head, int& b) {
+  attn_id_coords_gated(o2_xcd_range_id((int)blockIdx.x, (int)gridDim.x), nq, H, (int)gridDim.x / (nq * H), qt, head, b);
+}
+// The coordinates of a workgroup of a launch with a tail queue (tail_queue.h; TQ kernels): the same walks over the q.S static
+// workgroups, the last q.tail tile ids by ticket.  false: the workgroup has no tile and returns.  slot: see o2_tail_tile.
+template <bool GATED>
+__device__ __forceinline__ bool attn_tile_coords_tq(const O2TailQ& q, int* slot, int nq, int H, int& qt, int& head, int& b) {
+  bool is_tail;
+  const int id = o2_tail_tile(q, [](int wg, int nwg) { return o2_xcd_range_id(wg, nwg); }, slot, &is_tail);
+  if (id < 0) return false;
+  if constexpr (GATED) attn_id_coords_gated(id, nq, H, (q.S + q.tail) / (nq * H), qt, head, b);
+  else attn_id_coords(id, nq, H, qt, head, b);
+  return true;
 }
 
 // =============================================================================================
@@ -641,17 +657,20 @@ __device__ __forceinline__ void attn_gate_zero_rows(bf16_t* __restrict__ p, int 
 
 // The body of the kernel: attn_fwd_w4_kernel is it without a gate, attn_fwd_w4_gated_kernel with one (GATED: the check is compiled
 // into the gated kernel only, the ungated one is instruction for instruction what it was).
-template <bool DROP, bool GATED>
+template <bool DROP, bool GATED, bool TQ = false>
 __device__ __forceinline__ void attn_fwd_w4_body(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                  float* __restrict__ lse, int L, int H, unsigned thr, float dscale,
-                                                 uint64_t seed_arg, int ldo, int ldq, const float* __restrict__ gate) {
+                                                 uint64_t seed_arg, int ldo, int ldq, const float* __restrict__ gate,
+                                                 const O2TailQ q = O2TailQ{}) {
   constexpr int D = 128;
   __shared__ __attribute__((aligned(1024))) char smem[O2_AF_LDS_BYTES(O2_AF_MAX_L)];   // [2 slots][K 16 KiB | V 16 KiB] | key-group hashes
   const uint64_t seed = seed_arg ^ o2_seed_salt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int tile_i, head, b;
-  if constexpr (GATED) attn_tile_coords_gated(L / 256, H, tile_i, head, b);
+  if constexpr (TQ) {
+    if (!attn_tile_coords_tq<GATED>(q, reinterpret_cast<int*>(smem), L / 256, H, tile_i, head, b)) return;
+  } else if constexpr (GATED) attn_tile_coords_gated(L / 256, H, tile_i, head, b);
   else attn_tile_coords(L / 256, H, tile_i, head, b);
   if constexpr (GATED) {
     if (gate[b] == 0.0f) {                  // workgroup-uniform
@@ -701,13 +720,28 @@ template <bool DROP>
 __global__ __launch_bounds__(256, 1) void attn_fwd_w4_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                             float* __restrict__ lse, int L, int H, unsigned thr, float dscale,
                                                             uint64_t seed_arg, int ldo, int ldq) {
+  O2_TQ_TRACE_BEGIN();
   attn_fwd_w4_body<DROP, false>(qkv, out, lse, L, H, thr, dscale, seed_arg, ldo, ldq, nullptr);
+  O2_TQ_TRACE_END(o2_tq_trace_attn, 0);
 }
 template <bool DROP>
 __global__ __launch_bounds__(256, 1) void attn_fwd_w4_gated_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                                   float* __restrict__ lse, int L, int H, unsigned thr, float dscale,
                                                                   uint64_t seed_arg, int ldo, int ldq, const float* __restrict__ gate) {
+  O2_TQ_TRACE_BEGIN();
   attn_fwd_w4_body<DROP, true>(qkv, out, lse, L, H, thr, dscale, seed_arg, ldo, ldq, gate);
+  O2_TQ_TRACE_END(o2_tq_trace_attn, 0);
+}
+// with a tail queue (tail_queue.h), gated or not (GATED = false: gate is not read)
+template <bool DROP, bool GATED>
+__global__ __launch_bounds__(256, 1) void attn_fwd_w4_tq_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+                                                               float* __restrict__ lse, int L, int H, unsigned thr, float dscale,
+                                                               uint64_t seed_arg, int ldo, int ldq, const float* __restrict__ gate,
+                                                               unsigned int* tq_ctr, int tq_S, int tq_tail) {
+  const O2TailQ q = {tq_ctr, tq_S, tq_tail};
+  O2_TQ_TRACE_BEGIN();
+  attn_fwd_w4_body<DROP, GATED, true>(qkv, out, lse, L, H, thr, dscale, seed_arg, ldo, ldq, gate, q);
+  O2_TQ_TRACE_END(o2_tq_trace_attn, 0);
 }
 
 // =============================================================================================
@@ -917,18 +951,21 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_bwd_dq_kerne
 // Same construction as attn_fwd_w4_kernel (one wave per SIMD, two 32-row blocks per wave, every instruction placed by the
 // generator, the same text executed on the CPU by tests/test_attn_dq_asm_emu_cpu.py); the schedule is described in the
 // generator's header.  The compiler contributes the coordinates, the key-group hash table and the lane's two row hashes.
-template <bool DROP, bool GATED>
+template <bool DROP, bool GATED, bool TQ = false>
 __device__ __forceinline__ void attn_bwd_dq_w4_body(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                     const float* __restrict__ nlse2, const float* __restrict__ ndelta,
                                                     bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fs,
-                                                    uint64_t seed_arg, int Lp, int ldq, const float* __restrict__ gate) {
+                                                    uint64_t seed_arg, int Lp, int ldq, const float* __restrict__ gate,
+                                                    const O2TailQ q = O2TailQ{}) {
   constexpr int D = 128;
   __shared__ __attribute__((aligned(1024))) char smem[O2_DQ_LDS_BYTES(O2_AF_MAX_L)];   // 4 x [K 16 KiB] | 4 x [V 16 KiB] | key-group hashes
   const uint64_t seed = seed_arg ^ o2_seed_salt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int tile_i, head, b;
-  if constexpr (GATED) attn_tile_coords_gated(L / 256, H, tile_i, head, b);
+  if constexpr (TQ) {
+    if (!attn_tile_coords_tq<GATED>(q, reinterpret_cast<int*>(smem), L / 256, H, tile_i, head, b)) return;
+  } else if constexpr (GATED) attn_tile_coords_gated(L / 256, H, tile_i, head, b);
   else attn_tile_coords(L / 256, H, tile_i, head, b);
   if constexpr (GATED) {
     if (gate[b] == 0.0f) {                  // workgroup-uniform: the tile's rows of the q third
@@ -973,14 +1010,29 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq_w4_kernel(const bf16_t* __
                                                                const float* __restrict__ nlse2, const float* __restrict__ ndelta,
                                                                bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fs,
                                                                uint64_t seed_arg, int Lp, int ldq) {
+  O2_TQ_TRACE_BEGIN();
   attn_bwd_dq_w4_body<DROP, false>(qkv, dout, nlse2, ndelta, dqkv, L, H, thr, fs, seed_arg, Lp, ldq, nullptr);
+  O2_TQ_TRACE_END(o2_tq_trace_attn, 0);
 }
 template <bool DROP>
 __global__ __launch_bounds__(256, 1) void attn_bwd_dq_w4_gated_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                                      const float* __restrict__ nlse2, const float* __restrict__ ndelta,
                                                                      bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fs,
                                                                      uint64_t seed_arg, int Lp, int ldq, const float* __restrict__ gate) {
+  O2_TQ_TRACE_BEGIN();
   attn_bwd_dq_w4_body<DROP, true>(qkv, dout, nlse2, ndelta, dqkv, L, H, thr, fs, seed_arg, Lp, ldq, gate);
+  O2_TQ_TRACE_END(o2_tq_trace_attn, 0);
+}
+template <bool DROP, bool GATED>
+__global__ __launch_bounds__(256, 1) void attn_bwd_dq_w4_tq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
+                                                                  const float* __restrict__ nlse2, const float* __restrict__ ndelta,
+                                                                  bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fs,
+                                                                  uint64_t seed_arg, int Lp, int ldq, const float* __restrict__ gate,
+                                                                  unsigned int* tq_ctr, int tq_S, int tq_tail) {
+  const O2TailQ q = {tq_ctr, tq_S, tq_tail};
+  O2_TQ_TRACE_BEGIN();
+  attn_bwd_dq_w4_body<DROP, GATED, true>(qkv, dout, nlse2, ndelta, dqkv, L, H, thr, fs, seed_arg, Lp, ldq, gate, q);
+  O2_TQ_TRACE_END(o2_tq_trace_attn, 0);
 }
 
 // =============================================================================================
@@ -1436,18 +1488,21 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_dkv128_kernel(const bf16_t* _
 // statement is the whole kernel (schedule: the generator's header; CPU execution of the same text: tests/test_attn_dkv_asm_emu_cpu.py).
 // The compiler contributes the coordinates, the lane's key-group hash and the seed-dependent constant of the row hash
 // (o2_hash64 with a zero high index word: requires B * H * L < 2^32, checked by the launcher).
-template <bool DROP, bool GATED>
+template <bool DROP, bool GATED, bool TQ = false>
 __device__ __forceinline__ void attn_bwd_dkv_w4_body(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                      const float* __restrict__ nlse2, const float* __restrict__ ndelta,
                                                      bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fk, float fv,
-                                                     uint64_t seed_arg, int Lp, int ldq, const float* __restrict__ gate) {
+                                                     uint64_t seed_arg, int Lp, int ldq, const float* __restrict__ gate,
+                                                     const O2TailQ q = O2TailQ{}) {
   constexpr int D = 128;
   __shared__ __attribute__((aligned(1024))) char smem[O2_KV_LDS_BYTES];   // 4 x [Q 16 KiB] | 4 x [dO 16 KiB] | 4 x 1 KiB of row statistics
   const uint64_t seed = seed_arg ^ o2_seed_salt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int tile_i, head, b;
-  if constexpr (GATED) attn_tile_coords_gated(L / 128, H, tile_i, head, b);
+  if constexpr (TQ) {
+    if (!attn_tile_coords_tq<GATED>(q, reinterpret_cast<int*>(smem), L / 128, H, tile_i, head, b)) return;
+  } else if constexpr (GATED) attn_tile_coords_gated(L / 128, H, tile_i, head, b);
   else attn_tile_coords(L / 128, H, tile_i, head, b);
   if constexpr (GATED) {
     if (gate[b] == 0.0f) {                  // workgroup-uniform: the tile's 128 rows of the k and of the v third
@@ -1490,7 +1545,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w4_kernel(const bf16_t* _
                                                                 const float* __restrict__ nlse2, const float* __restrict__ ndelta,
                                                                 bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fk, float fv,
                                                                 uint64_t seed_arg, int Lp, int ldq) {
+  O2_TQ_TRACE_BEGIN();
   attn_bwd_dkv_w4_body<DROP, false>(qkv, dout, nlse2, ndelta, dqkv, L, H, thr, fk, fv, seed_arg, Lp, ldq, nullptr);
+  O2_TQ_TRACE_END(o2_tq_trace_attn, O2_TQ_TRACE_WGS / 2);
 }
 template <bool DROP>
 __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w4_gated_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
@@ -1498,7 +1555,20 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w4_gated_kernel(const bf1
                                                                       bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fk,
                                                                       float fv, uint64_t seed_arg, int Lp, int ldq,
                                                                       const float* __restrict__ gate) {
+  O2_TQ_TRACE_BEGIN();
   attn_bwd_dkv_w4_body<DROP, true>(qkv, dout, nlse2, ndelta, dqkv, L, H, thr, fk, fv, seed_arg, Lp, ldq, gate);
+  O2_TQ_TRACE_END(o2_tq_trace_attn, O2_TQ_TRACE_WGS / 2);
+}
+template <bool DROP, bool GATED>
+__global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w4_tq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
+                                                                   const float* __restrict__ nlse2, const float* __restrict__ ndelta,
+                                                                   bf16_t* __restrict__ dqkv, int L, int H, unsigned thr, float fk,
+                                                                   float fv, uint64_t seed_arg, int Lp, int ldq,
+                                                                   const float* __restrict__ gate, unsigned int* tq_ctr, int tq_S, int tq_tail) {
+  const O2TailQ q = {tq_ctr, tq_S, tq_tail};
+  O2_TQ_TRACE_BEGIN();
+  attn_bwd_dkv_w4_body<DROP, GATED, true>(qkv, dout, nlse2, ndelta, dqkv, L, H, thr, fk, fv, seed_arg, Lp, ldq, gate, q);
+  O2_TQ_TRACE_END(o2_tq_trace_attn, O2_TQ_TRACE_WGS / 2);
 }
 
 // =============================================================================================
@@ -1848,8 +1918,20 @@ template <class F> static void attn_with_variant(int d, int nw, bool drop, bool 
 
 // gate: the path gate of orbit2_attn_fwd_gated (nullptr: none).  The plan does not look at it: a gated call runs the gated twin
 // of the kernel the ungated call runs, on the same grid; the kernels without a twin ignore it.
+// Tail rounds of the generated kernels (o2_tail_auto; 0: static), sized from profiles/r08_tail_idle.txt: the backward (dQ and
+// dK + dV together) runs -1.0 ... -1.5 % shorter with 2 to 6 rounds, best at 4, gated or not; the forward within +-0.7 % at every
+// tail although its end idle halves: static.
+#define O2_TQ_ROUNDS_ATTN_FWD 0
+#define O2_TQ_ROUNDS_ATTN_BWD 4
+// sched / tail_arg: the tail queue of orbit2_attn_fwd_tq / _bwd_tq (nullptr: none) for a generated kernel's grid
+static O2TailPlan attn_tail_plan(const AttnLaunch& l, unsigned int* sched, int tail_arg, int rounds) {
+  if (!sched || tail_arg < 0) return o2_tail_plan(l.grid.x, 0);
+  return o2_tail_plan_arg(l.grid.x, tail_arg, rounds, tail_arg == 0 ? o2_tail_slots() : 0);
+}
+
 static int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
-                           uint64_t seed, int flags, int ldq, int ldo, const float* gate, void* stream) {
+                           uint64_t seed, int flags, int ldq, int ldo, const float* gate, void* stream,
+                           unsigned int* sched = nullptr, int tail_arg = -1) {
   int rc = attn_check(qkv, out, B, L, H, d, drop_p);
   if (rc) return rc;
   if (!lse || ldo < H * d || (ldo & 7) || ldq < 3 * H * d || (ldq & 7)) return O2_ERR_ARG;
@@ -1858,7 +1940,14 @@ static int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int L,
   const bf16_t* q_ = (const bf16_t*)qkv;
   bf16_t* o_ = (bf16_t*)out;
 #define O2_FWD(KERN, ...) hipLaunchKernelGGL(KERN, p.fwd.grid, p.fwd.block, 0, s, q_, o_, lse, L, H, __VA_ARGS__, seed, ldo, ldq)
-  if (p.fwd_w4 && gate)
+  const O2TailPlan tp = p.fwd_w4 ? attn_tail_plan(p.fwd, sched, tail_arg, O2_TQ_ROUNDS_ATTN_FWD) : o2_tail_plan(0, 0);
+  if (tp.tail > 0) {
+    const O2TailQ tq = {sched, tp.S, tp.tail};
+    o2_with_flags([&](auto DR, auto GT) {
+      hipLaunchKernelGGL((attn_fwd_w4_tq_kernel<DR, GT>), dim3((unsigned)tp.grid), p.fwd.block, 0, s, q_, o_, lse, L, H, p.thr,
+                         p.dscale, seed, ldo, ldq, gate, tq.ctr, tq.S, tq.tail);
+    }, p.drop, gate != nullptr);
+  } else if (p.fwd_w4 && gate)
     o2_with_flags([&](auto DR) {
       hipLaunchKernelGGL((attn_fwd_w4_gated_kernel<DR>), p.fwd.grid, p.fwd.block, 0, s, q_, o_, lse, L, H, p.thr, p.dscale, seed,
                          ldo, ldq, gate);
@@ -1894,7 +1983,7 @@ extern "C" int64_t orbit2_attn_bwd_ws_floats(int B, int L, int H) {
 
 static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                            void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq,
-                           int ldo, const float* gate, void* stream) {
+                           int ldo, const float* gate, void* stream, unsigned int* sched = nullptr, int tail_arg = -1) {
   int rc = attn_check(qkv, out, B, L, H, d, drop_p);
   if (rc) return rc;
   if (!dout || !lse || !delta || !dqkv || ldo < H * d || (ldo & 7) || ldq < 3 * H * d || (ldq & 7)) return O2_ERR_ARG;
@@ -1915,7 +2004,16 @@ static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, c
 #define O2_BWD_GATED(KERN, PASS, ...) \
   hipLaunchKernelGGL(KERN, p.PASS.grid, p.PASS.block, 0, s, q_, do_, ws0, ws1, dq_, L, H, __VA_ARGS__, Lp, ldq, gate)
 #define O2_BWD_CS p.scale, p.thr, p.dscale, seed, p.opmul          /* scalars of the compiler-scheduled kernels */
-  if (p.dq_w4 && gate)
+  // (the two passes run one after the other on the stream: they share the counter, which is zero again between them)
+  const O2TailPlan tq_dq = p.dq_w4 ? attn_tail_plan(p.dq, sched, tail_arg, O2_TQ_ROUNDS_ATTN_BWD) : o2_tail_plan(0, 0);
+  const O2TailPlan tq_kv = p.dkv == DKV_W4 ? attn_tail_plan(p.dkv_l, sched, tail_arg, O2_TQ_ROUNDS_ATTN_BWD) : o2_tail_plan(0, 0);
+  if (tq_dq.tail > 0) {
+    const O2TailQ tq = {sched, tq_dq.S, tq_dq.tail};
+    o2_with_flags([&](auto DR, auto GT) {
+      hipLaunchKernelGGL((attn_bwd_dq_w4_tq_kernel<DR, GT>), dim3((unsigned)tq_dq.grid), p.dq.block, 0, s, q_, do_, ws0, ws1, dq_, L,
+                         H, p.thr, p.dq_w4_scale, seed, Lp, ldq, gate, tq.ctr, tq.S, tq.tail);
+    }, p.drop, gate != nullptr);
+  } else if (p.dq_w4 && gate)
     o2_with_flags([&](auto DR) { O2_BWD_GATED((attn_bwd_dq_w4_gated_kernel<DR>), dq, p.thr, p.dq_w4_scale, seed); }, p.drop);
   else if (p.dq_w4)
     o2_with_flags([&](auto DR) { O2_BWD((attn_bwd_dq_w4_kernel<DR>), dq, p.thr, p.dq_w4_scale, seed); }, p.drop);
@@ -1924,7 +2022,13 @@ static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, c
                       [&](auto DV, auto NW, auto DR, auto RG) { O2_BWD((attn_bwd_dq_kernel<DV, DR, RG, NW>), dq, O2_BWD_CS); });
   switch (p.dkv) {
     case DKV_W4:
-      if (gate)
+      if (tq_kv.tail > 0) {
+        const O2TailQ tq = {sched, tq_kv.S, tq_kv.tail};
+        o2_with_flags([&](auto DR, auto GT) {
+          hipLaunchKernelGGL((attn_bwd_dkv_w4_tq_kernel<DR, GT>), dim3((unsigned)tq_kv.grid), p.dkv_l.block, 0, s, q_, do_, ws0, ws1,
+                             dq_, L, H, p.thr, p.dkv_w4_kgrad, p.dkv_w4_dscale, seed, Lp, ldq, gate, tq.ctr, tq.S, tq.tail);
+        }, p.drop, gate != nullptr);
+      } else if (gate)
         o2_with_flags([&](auto DR) {
           O2_BWD_GATED((attn_bwd_dkv_w4_gated_kernel<DR>), dkv_l, p.thr, p.dkv_w4_kgrad, p.dkv_w4_dscale, seed);
         }, p.drop);
@@ -1963,4 +2067,18 @@ extern "C" int orbit2_attn_bwd_gated(const void* qkv, const void* out, const voi
                                      void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq,
                                      int ldo, const float* gate, void* stream) {
   return attn_bwd_launch(qkv, out, dout, lse, delta, dqkv, B, L, H, d, drop_p, seed, flags, ldq, ldo, gate, stream);
+}
+
+// The same launches with a tail queue for the generated kernels (csrc/tail_queue.h); gate may be NULL
+extern "C" int orbit2_attn_fwd_tq(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p, uint64_t seed,
+                                  int flags, int ldq, int ldo, const float* gate, void* sched_ws, int tail, void* stream) {
+  if (!sched_ws || ((uintptr_t)sched_ws & 3)) return O2_ERR_ARG;
+  return attn_fwd_launch(qkv, out, lse, B, L, H, d, drop_p, seed, flags, ldq, ldo, gate, stream, (unsigned int*)sched_ws, tail);
+}
+extern "C" int orbit2_attn_bwd_tq(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                                  int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq, int ldo,
+                                  const float* gate, void* sched_ws, int tail, void* stream) {
+  if (!sched_ws || ((uintptr_t)sched_ws & 3)) return O2_ERR_ARG;
+  return attn_bwd_launch(qkv, out, dout, lse, delta, dqkv, B, L, H, d, drop_p, seed, flags, ldq, ldo, gate, stream,
+                         (unsigned int*)sched_ws, tail);
 }

@@ -12,6 +12,7 @@
 // ends up holding 4 consecutive n of one output row m -> 8-byte bf16 (16-byte fp32) row-major stores.
 #include "common.h"
 #include "../../include/orbit2_hip.h"
+#include "tail_queue.h"
 
 namespace {
 
@@ -326,12 +327,7 @@ __device__ __forceinline__ void epi8_finish(const Epi& e, int m, int n, float* v
 
 // XCD-aware remap (bijective for any grid size): blocks b, b+8, .. share an XCD -> give each XCD a
 // contiguous range of tile ids.
-__device__ __forceinline__ int xcd_tile_id() {
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-}
+__device__ __forceinline__ int xcd_tile_id() { return o2_xcd_range_id((int)blockIdx.x, (int)gridDim.x); }
 
 // Round-major form for the kernels that hold ONE workgroup per CU (the 4-wave 256 x 256 kernel): the 256 workgroups that run at
 // the same time (block b lands on XCD b & 7, in dispatch order) take 256 CONSECUTIVE tile ids -- a compact block of the output --
@@ -340,14 +336,10 @@ __device__ __forceinline__ int xcd_tile_id() {
 // round sweep K side by side and the second reader of a strip finds it in the Infinity Cache.  What that buys: the clock
 // (profiles/r06_dw_traffic_clock.txt, r06_dw_traffic_instep.txt: the weight-gradient launch with its panels served from the
 // Infinity Cache runs 13 % faster at the same MFMA-busy share).  Bijective for any grid size.
-__device__ __forceinline__ int xcd_round_tile_id() {
-  const int nwg = gridDim.x, b = blockIdx.x;
-  const int base = b & ~255;
-  const int cnt = (nwg - base) < 256 ? (nwg - base) : 256;          // workgroups of this round
-  const int x = b & 7, s = (b & 255) >> 3;
-  const int q8 = cnt >> 3, r8 = cnt & 7;
-  return base + (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + s;
-}
+// (both walks are o2_xcd_range_id / o2_xcd_round_id of tail_queue.h; nwg: the workgroups that walk statically -- the grid, or the
+// static part of a launch with a tail queue)
+__device__ __forceinline__ int xcd_round_tile_id(int b, int nwg) { return o2_xcd_round_id(b, nwg); }
+__device__ __forceinline__ int xcd_round_tile_id() { return xcd_round_tile_id((int)blockIdx.x, (int)gridDim.x); }
 // Start barrier of a round's XCD cohort (long contractions only: the weight-gradient launch, 2048 K-tiles per tile).  Within a
 // round the 32 workgroups of an XCD keep step by themselves -- same instruction stream, same clock -- and fetch every strip
 // K-tile ONCE beyond L2 (profiles/r06_l2_share_probe.txt: one round = 1.00-1.01 x the ideal bytes at any K).  What breaks the
@@ -361,8 +353,8 @@ __device__ __forceinline__ int xcd_round_tile_id() {
 #define O2_W4_SYNC_SLOTS 512
 static __device__ unsigned int o2_w4_sync[3 * O2_W4_SYNC_SLOTS];       // [slot] = arrivals, [SLOTS + slot] = generation,
                                                                         // [2 SLOTS + slot] = arrivals at the in-sweep check points
-__device__ __forceinline__ const unsigned int* w4_cohort_start(int& n_out) {
-  const int nwg = gridDim.x, b = blockIdx.x;
+__device__ __forceinline__ const unsigned int* w4_cohort_start(int& n_out, int nwg) {
+  const int b = blockIdx.x;
   const int base = b & ~255, x = b & 7;
   const int cnt = (nwg - base) < 256 ? (nwg - base) : 256;
   const int n = (cnt >> 3) + (x < (cnt & 7) ? 1 : 0);               // workgroups of this round on this XCD
@@ -399,6 +391,7 @@ __device__ __forceinline__ const unsigned int* w4_cohort_start(int& n_out) {
 #define O2_W4_WALK 1        // 1: round-major ids for the 4-wave kernels; 0: the contiguous-range-per-XCD ids of rounds 2-5 (A/B builds)
 #endif
 __device__ __forceinline__ int w4_tile_id() { return O2_W4_WALK ? xcd_round_tile_id() : xcd_tile_id(); }
+__device__ __forceinline__ int w4_tile_id(int b, int nwg) { return O2_W4_WALK ? xcd_round_tile_id(b, nwg) : o2_xcd_range_id(b, nwg); }
 
 // one 128x128 output tile (tile `id` of the problem; tiles are walked in groups of 8 tile-rows so neighbours
 // share panels)
@@ -825,6 +818,7 @@ __global__ __launch_bounds__(512, 2) void gemm256t_grouped_kernel(GArgs g) {
 // operand, a scalar offset per piece), rows are not clamped.
 // ==========================================================================================
 #include "gemm_w4_asm.h"
+O2_TQ_TRACE_DEFINE(o2_tq_trace_gemm, orbit2_debug_read_tq_trace_gemm)
 
 #ifdef O2_W4_STAMP
 __device__ unsigned int o2_dbg_w4[64 * 4 * 16];   // diagnostic build only: per-wave cycle sums of the loop's segments
@@ -1231,7 +1225,25 @@ __global__ __launch_bounds__(256, 1) void gemm256w_kernel(const bf16_t* __restri
                                                           int M, int N, int K, int lda, int ldb, int tiles_m,
                                                           int tiles_n, Epi epi) {
   __shared__ __attribute__((aligned(16))) char smem[8 * O2_W4_UNIT];
+  O2_TQ_TRACE_BEGIN();
   gemm256w_tile<FORM, STAMP, EK>(A, B, M, N, K, lda, ldb, tiles_m, tiles_n, epi, w4_tile_id(), smem);
+  O2_TQ_TRACE_END(o2_tq_trace_gemm, 0);
+}
+
+// The same kernel with a tail queue (tail_queue.h): workgroups below q.S walk as above with q.S in place of the grid size, the
+// others draw a ticket for one of the last q.tail tiles or return.  The ticket crosses the waves through the first word of smem,
+// which the sweep has not touched yet.
+template <int FORM, int EK = 0>
+__global__ __launch_bounds__(256, 1) void gemm256w_tq_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
+                                                             int M, int N, int K, int lda, int ldb, int tiles_m,
+                                                             int tiles_n, Epi epi, unsigned int* tq_ctr, int tq_S, int tq_tail) {
+  const O2TailQ q = {tq_ctr, tq_S, tq_tail};
+  __shared__ __attribute__((aligned(16))) char smem[8 * O2_W4_UNIT];
+  O2_TQ_TRACE_BEGIN();
+  bool is_tail;
+  const int id = o2_tail_tile(q, [](int b, int nwg) { return w4_tile_id(b, nwg); }, reinterpret_cast<int*>(smem), &is_tail);
+  if (id >= 0) gemm256w_tile<FORM, false, EK>(A, B, M, N, K, lda, ldb, tiles_m, tiles_n, epi, id, smem);
+  O2_TQ_TRACE_END(o2_tq_trace_gemm, 0);
 }
 
 // the epilogue kind of epi8_finish a whole-tile bf16 problem qualifies for (0: the runtime form)
@@ -1250,9 +1262,10 @@ static int w4_epi_kind(const Epi& e) {
 template <int FORM>
 __global__ __launch_bounds__(256, 1) void gemm256w_grouped_kernel(GArgs g) {
   __shared__ __attribute__((aligned(16))) char smem[8 * O2_W4_UNIT];
+  O2_TQ_TRACE_BEGIN();
   const int id = w4_tile_id();
   int pace_n = 0;
-  const unsigned int* pace_ctr = g.pace ? w4_cohort_start(pace_n) : nullptr;
+  const unsigned int* pace_ctr = g.pace ? w4_cohort_start(pace_n, (int)gridDim.x) : nullptr;
   if (g.pace < 2) pace_ctr = nullptr;                                   // pace 1: the start barrier only
   int pi = 0;
   while (pi + 1 < g.n && id >= g.p[pi].tile_end) ++pi;
@@ -1261,6 +1274,31 @@ __global__ __launch_bounds__(256, 1) void gemm256w_grouped_kernel(GArgs g) {
   const Epi epi = P.epi;
   gemm256w_tile<FORM, false>(P.A, P.B, P.M, P.N, P.K, P.lda, P.ldb, P.tiles_m, P.tiles_n, epi, id - first, smem, pace_ctr, pace_n,
                              P.kgate, P.k_per_gate);
+  O2_TQ_TRACE_END(o2_tq_trace_gemm, 0);
+}
+
+// with a tail queue: a ticket holder joins no cohort (its neighbours are whoever drew the next tickets), the static workgroups'
+// cohorts are those of a grid of q.S
+template <int FORM>
+__global__ __launch_bounds__(256, 1) void gemm256w_grouped_tq_kernel(GArgs g, unsigned int* tq_ctr, int tq_S, int tq_tail) {
+  const O2TailQ q = {tq_ctr, tq_S, tq_tail};
+  __shared__ __attribute__((aligned(16))) char smem[8 * O2_W4_UNIT];
+  O2_TQ_TRACE_BEGIN();
+  bool is_tail;
+  const int id = o2_tail_tile(q, [](int b, int nwg) { return w4_tile_id(b, nwg); }, reinterpret_cast<int*>(smem), &is_tail);
+  if (id < 0) {
+    O2_TQ_TRACE_END(o2_tq_trace_gemm, 0);
+    return;
+  }
+  int pace_n = 0;
+  const unsigned int* pace_ctr = (g.pace && !is_tail) ? w4_cohort_start(pace_n, q.S) : nullptr;
+  if (g.pace < 2) pace_ctr = nullptr;
+  int first;
+  const GProb& P = g.p[o2_group_problem(g, id, first)];
+  const Epi epi = P.epi;
+  gemm256w_tile<FORM, false>(P.A, P.B, P.M, P.N, P.K, P.lda, P.ldb, P.tiles_m, P.tiles_n, epi, id - first, smem, pace_ctr, pace_n,
+                             P.kgate, P.k_per_gate);
+  O2_TQ_TRACE_END(o2_tq_trace_gemm, 0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1564,9 +1602,26 @@ static int gemm_group_plan(const orbit2_gemm_args* args, int n, GemmFamily& fami
   return O2_OK;
 }
 
+// Tail rounds a family asks for by itself (o2_tail_auto; 0: the family stays static), sized from profiles/r08_tail_idle.txt:
+// the mean time of a launch at the bench shapes, static against tails of 1, 2, 4 and 6 rounds, ungated and gated.
+//   grouped weight gradients             -3.2 ... -5.3 %, flat from 2 rounds on: 4
+//   input-gradient form, plain epilogue  -0.7 ... -1.8 % at every tail, gated or not: 2
+//   forward form, kind 2 (proj, fc2)     -0.6 ... -1.1 % at 1 and 2 rounds, +0.7 ... +1.4 % at 4 and 6 when gated: 2
+//   forward form, kinds 0 and 1; input-gradient form, kind 3: within +-0.6 % ungated, +0.5 ... +1.6 % gated (a ticket
+//     holder's neighbours in L2 are whoever drew the next tickets, not its cohort): static
+#define O2_TQ_ROUNDS_GROUP 4
+constexpr int w4_tail_rounds(int form, int ek) { return (form == 1 && ek == 0) || (form == 0 && ek == 2) ? 2 : 0; }
+// the plan of a launch of T tiles that offers a counter (sched; nullptr: static) -- tail_arg as in o2_tail_plan_arg
+static O2TailPlan gemm_tail_plan(long T, unsigned int* sched, int tail_arg, int rounds) {
+  if (!sched || tail_arg < 0) return o2_tail_plan(T, 0);
+  return o2_tail_plan_arg(T, tail_arg, rounds, tail_arg == 0 ? o2_tail_slots() : 0);
+}
+
 // one launch; gate / rows_per_gate: the path gate of orbit2_gemm_bf16_gated (nullptr: none).  The plan does not look at the
-// gate: a gated call runs exactly the kernel, grid and block of the ungated call.
-static int gemm_launch(const orbit2_gemm_args* a, const float* gate, int rows_per_gate, void* stream) {
+// gate: a gated call runs exactly the kernel, grid and block of the ungated call.  sched / tail_arg: the tail queue of
+// orbit2_gemm_bf16_tq (nullptr: none) -- the 4-wave kernel's launches only, any other plan launches as without it.
+static int gemm_launch(const orbit2_gemm_args* a, const float* gate, int rows_per_gate, void* stream, unsigned int* sched = nullptr,
+                       int tail_arg = -1) {
   Epi e;
   GemmPlan p;
   int rc = gemm_make_epi(a, e);
@@ -1576,6 +1631,25 @@ static int gemm_launch(const orbit2_gemm_args* a, const float* gate, int rows_pe
   if (a->colsum_ws && !p.fuses_colsum) return O2_ERR_UNSUPPORTED;   // ask orbit2_gemm_bf16_colsum_rows first
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
+  if (sched && p.family == GEMM_256W && !p.stamped) {
+    const int form_of_plan = w4_form(p.a_kc, p.b_kc);
+    const O2TailPlan tp = gemm_tail_plan((long)p.grid, sched, tail_arg, w4_tail_rounds(form_of_plan, p.ek));
+    if (tp.tail > 0) {
+      const O2TailQ q = {sched, tp.S, tp.tail};
+      o2_with_flags([&](auto AK, auto BK) {
+        constexpr int FORM = w4_form(AK, BK);
+        auto kind = [&](auto EK) {
+          if constexpr (w4_compiled_kind(FORM, EK) == EK)
+            if (p.ek == EK)
+              hipLaunchKernelGGL((gemm256w_tq_kernel<FORM, EK>), dim3((unsigned)tp.grid), dim3(p.block), 0, s, (const bf16_t*)a->A,
+                                 (const bf16_t*)a->B, a->M, a->N, a->K, a->lda, a->ldb, p.tiles_m, p.tiles_n, e, q.ctr, q.S, q.tail);
+        };
+        kind(o2_int<0>{}); kind(o2_int<1>{}); kind(o2_int<2>{}); kind(o2_int<3>{});
+      }, p.a_kc, p.b_kc);
+      O2_CHECK_LAUNCH();
+      return O2_OK;
+    }
+  }
 #define O2_GEMM_LAUNCH(...)                                                                                              \
   hipLaunchKernelGGL((__VA_ARGS__), dim3(p.grid), dim3(p.block), 0, s, (const bf16_t*)a->A, (const bf16_t*)a->B, a->M, a->N, \
                      a->K, a->lda, a->ldb, p.tiles_m, p.tiles_n, e)
@@ -1610,6 +1684,12 @@ extern "C" int orbit2_gemm_bf16_gated(const orbit2_gemm_args* a, const float* ga
   return gemm_launch(a, gate, rows_per_gate, stream);
 }
 
+extern "C" int orbit2_gemm_bf16_tq(const orbit2_gemm_args* a, const float* gate, int rows_per_gate, void* sched_ws, int tail,
+                                   void* stream) {
+  if (!sched_ws || ((uintptr_t)sched_ws & 3) || (gate && rows_per_gate <= 0)) return O2_ERR_ARG;
+  return gemm_launch(a, gate, rows_per_gate, stream, (unsigned int*)sched_ws, tail);
+}
+
 extern "C" int orbit2_gemm_bf16_colsum_rows(const orbit2_gemm_args* a) {
   Epi e;
   GemmPlan p;
@@ -1619,9 +1699,10 @@ extern "C" int orbit2_gemm_bf16_colsum_rows(const orbit2_gemm_args* a) {
 }
 
 // kgates / k_per_gate: the K gates of orbit2_gemm_bf16_grouped_gated (nullptr: none); the plan does not look at them
-static int gemm_group_launch(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate, void* stream) {
+static int gemm_group_launch(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate, void* stream,
+                             unsigned int* sched = nullptr, int tail_arg = -1) {
   if (!args || n <= 0 || n > ORBIT2_GEMM_MAX_GROUP) return O2_ERR_ARG;
-  if (n == 1) return orbit2_gemm_bf16(args, stream);
+  if (n == 1) return gemm_launch(args, nullptr, 0, stream, sched, tail_arg);
   for (int i = 0; i < n; ++i)
     if (args[i].colsum_ws) return O2_ERR_UNSUPPORTED;      // single launches only (orbit2_gemm_bf16_colsum_rows)
   GemmFamily family;
@@ -1636,6 +1717,19 @@ static int gemm_group_launch(const orbit2_gemm_args* args, int n, const float* c
       }
   const dim3 grid(g.p[n - 1].tile_end), block(gemm_block(family));
   hipStream_t s = (hipStream_t)stream;
+  if (sched && family == GEMM_256W) {
+    const O2TailPlan tp = gemm_tail_plan((long)g.p[n - 1].tile_end, sched, tail_arg, O2_TQ_ROUNDS_GROUP);
+    if (tp.tail > 0) {
+      const O2TailQ q = {sched, tp.S, tp.tail};
+      // (the start barrier's rule "more than one round" is about the workgroups that walk statically)
+      if (tp.S <= 256) g.pace = 0;
+      o2_with_flags([&](auto AK, auto BK) {
+        hipLaunchKernelGGL((gemm256w_grouped_tq_kernel<w4_form(AK, BK)>), dim3((unsigned)tp.grid), block, 0, s, g, q.ctr, q.S, q.tail);
+      }, args[0].a_kc != 0, args[0].b_kc != 0);
+      O2_CHECK_LAUNCH();
+      return O2_OK;
+    }
+  }
   o2_with_flags([&](auto AK, auto BK) {
     switch (family) {
       case GEMM_256W: hipLaunchKernelGGL((gemm256w_grouped_kernel<w4_form(AK, BK)>), grid, block, 0, s, g); break;
@@ -1653,6 +1747,12 @@ extern "C" int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, voi
 extern "C" int orbit2_gemm_bf16_grouped_gated(const orbit2_gemm_args* args, int n, const float* const* kgates,
                                               const int* k_per_gate, void* stream) {
   return gemm_group_launch(args, n, kgates, k_per_gate, stream);
+}
+
+extern "C" int orbit2_gemm_bf16_grouped_tq(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate,
+                                           void* sched_ws, int tail, void* stream) {
+  if (!sched_ws || ((uintptr_t)sched_ws & 3)) return O2_ERR_ARG;
+  return gemm_group_launch(args, n, kgates, k_per_gate, stream, (unsigned int*)sched_ws, tail);
 }
 
 // split-K plan of the skinny table products: enough slabs to put >= ~1024 workgroups on the chip, >= 4 staged k-steps each
