@@ -6,6 +6,7 @@ pointers plus torch's current HIP stream across the ABI.  A missing library or a
 code raises immediately."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Optional
@@ -264,6 +265,31 @@ class KernelTimer:
 timer: Optional[KernelTimer] = None
 
 
+@contextlib.contextmanager
+def _timed(name, flops, nbytes=0.0):
+    """records the launches inside the block as one span of `timer`; does nothing when no timer is set"""
+    if timer is None:
+        yield
+        return
+    e0, e1 = timer.span(name, flops, nbytes)
+    e0.record()
+    yield
+    e1.record()
+
+
+def _call_entry(plain, gated, tq, args, gate_args, has_gate, tail, device):
+    """One launch through the entry its gate and tail select: `tq` when a tail queue is asked for (tail is not None: the gate
+    arguments, which say "none" when has_gate is false, the stream's counter word on `device` and the tail), else `gated` when the
+    call has a gate, else `plain`.  args: the leading arguments all three share; the stream is the last one of each."""
+    if tail is not None:
+        name, args = tq, args + gate_args + (_sched_word(device), tail)
+    elif has_gate:
+        name, args = gated, args + gate_args
+    else:
+        name = plain
+    _chk(getattr(lib(), name)(*args, _stream()), name)
+
+
 # ------------------------------------------------------------------------------------------------
 def _gemm_fill(a, A, B, out, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, bias=None, act=0, save_pre=None,
                dgelu_pre=None, drop_p=0.0, seed=0, rowscale=None, rows_per_scale=0, residual=None, ldr=0, res_mod=0,
@@ -307,15 +333,6 @@ def gemm(A, B, out, M, N, K, lda, ldb, ldc, want_colsum=False, gate=None, rows_p
         if rows_per_gate <= 0 or gate.numel() * rows_per_gate < M:
             raise HipBackendError("gemm gate needs rows_per_gate > 0 and one entry per rows_per_gate rows")
 
-    def launch(a):
-        if tail is not None:
-            _chk(lib().orbit2_gemm_bf16_tq(C.byref(a), _p(gate), rows_per_gate if gate is not None else 0, _sched_word(out.device),
-                                           tail, _stream()), "orbit2_gemm_bf16_tq")
-        elif gate is None:
-            _chk(lib().orbit2_gemm_bf16(C.byref(a), _stream()), "orbit2_gemm_bf16")
-        else:
-            _chk(lib().orbit2_gemm_bf16_gated(C.byref(a), gate.data_ptr(), rows_per_gate, _stream()), "orbit2_gemm_bf16_gated")
-
     a = GemmArgs()
     flops, nbytes = _gemm_fill(a, A, B, out, M, N, K, lda, ldb, ldc, **kw)
     parts = None
@@ -324,13 +341,9 @@ def gemm(A, B, out, M, N, K, lda, ldb, ldc, want_colsum=False, gate=None, rows_p
         if rows > 0:
             parts = torch.empty(rows, N, dtype=F32, device=out.device)
             a.colsum_ws = parts.data_ptr()
-    if timer is not None:
-        e0, e1 = timer.span("gemm_bf16", flops, nbytes)
-        e0.record()
-        launch(a)
-        e1.record()
-    else:
-        launch(a)
+    with _timed("gemm_bf16", flops, nbytes):
+        _call_entry("orbit2_gemm_bf16", "orbit2_gemm_bf16_gated", "orbit2_gemm_bf16_tq", (C.byref(a),),
+                    (_p(gate), rows_per_gate if gate is not None else 0), gate is not None, tail, out.device)
     return (out, parts) if want_colsum else out
 
 
@@ -352,12 +365,7 @@ def gemm_f32(A, B, out, M, N, K, lda, ldb, ldc, bias=None, act=0, residual=None,
     a.beta = float(beta)
     a.tile_hint = int(tile)
     a.colscale_n, a.colscale = (0, 1.0) if colscale is None else (int(colscale[0]), float(colscale[1]))
-    if timer is not None:
-        e0, e1 = timer.span("gemm_f32", 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N))
-        e0.record()
-        _chk(lib().orbit2_gemm_f32(C.byref(a), _stream()), "orbit2_gemm_f32")
-        e1.record()
-    else:
+    with _timed("gemm_f32", 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N)):
         _chk(lib().orbit2_gemm_f32(C.byref(a), _stream()), "orbit2_gemm_f32")
     return out
 
@@ -389,22 +397,9 @@ def gemm_grouped(problems, tail_queue=None):
         flops += f
         nbytes += b
 
-    def launch():
-        if tail is not None:
-            _chk(lib().orbit2_gemm_bf16_grouped_tq(arr, n, kgates if gated else None, kper if gated else None,
-                                                   _sched_word(problems[0][2].device), tail, _stream()), "orbit2_gemm_bf16_grouped_tq")
-        elif gated:
-            _chk(lib().orbit2_gemm_bf16_grouped_gated(arr, n, kgates, kper, _stream()), "orbit2_gemm_bf16_grouped_gated")
-        else:
-            _chk(lib().orbit2_gemm_bf16_grouped(arr, n, _stream()), "orbit2_gemm_bf16_grouped")
-
-    if timer is not None:
-        e0, e1 = timer.span("gemm_bf16", flops, nbytes)
-        e0.record()
-        launch()
-        e1.record()
-        return
-    launch()
+    with _timed("gemm_bf16", flops, nbytes):
+        _call_entry("orbit2_gemm_bf16_grouped", "orbit2_gemm_bf16_grouped_gated", "orbit2_gemm_bf16_grouped_tq", (arr, n),
+                    (kgates if gated else None, kper if gated else None), gated, tail, problems[0][2].device)
 
 
 def sgemm(A, B, out, M, N, K, lda, ldb, ldc, ta=False, tb=False, alpha=1.0, beta=0.0):
@@ -509,21 +504,11 @@ def attn_fwd(qkv, B, L, H, d, drop_p=0.0, seed=0, flags=0, out=None, gate=None, 
         out = _dev_rows(out, BF, "out")
         ldo = out.stride(0)
     lse = torch.empty(B, H, L, dtype=F32, device=qkv.device)
-    if timer is not None:
-        # algorithmic bytes: qkv read once, out + lse written once
-        e0, e1 = timer.span("attn_fwd", 4.0 * B * H * L * L * d, 2.0 * 4 * B * L * H * d + 4.0 * B * H * L)
-        e0.record()
-    if tail is not None:
-        _chk(lib().orbit2_attn_fwd_tq(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo),
-                                      _p(gate), _sched_word(qkv.device), tail, _stream()), "orbit2_attn_fwd_tq")
-    elif gate is None:
-        _chk(lib().orbit2_attn_fwd_ld(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo),
-                                      _stream()), "orbit2_attn_fwd_ld")
-    else:
-        _chk(lib().orbit2_attn_fwd_gated(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo),
-                                         _p(gate), _stream()), "orbit2_attn_fwd_gated")
-    if timer is not None:
-        e1.record()
+    # algorithmic bytes: qkv read once, out + lse written once
+    with _timed("attn_fwd", 4.0 * B * H * L * L * d, 2.0 * 4 * B * L * H * d + 4.0 * B * H * L):
+        _call_entry("orbit2_attn_fwd_ld", "orbit2_attn_fwd_gated", "orbit2_attn_fwd_tq",
+                    (_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo)), (_p(gate),),
+                    gate is not None, tail, qkv.device)
     return out, lse
 
 
@@ -538,13 +523,9 @@ def attn_fwd_f32(qkv, B, L, H, d, drop_p=0.0, flags=0, out=None):
         out = _dev_rows(out, F32, "out")
         ldo = out.stride(0)
     lse = torch.empty(B, H, L, dtype=F32, device=qkv.device)
-    if timer is not None:
-        e0, e1 = timer.span("attn_fwd_f32", 4.0 * B * H * L * L * d, 4.0 * 4 * B * L * H * d + 4.0 * B * H * L)
-        e0.record()
-    _chk(lib().orbit2_attn_fwd_f32(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, 0, int(flags), int(ldq), int(ldo),
-                                   _stream()), "orbit2_attn_fwd_f32")
-    if timer is not None:
-        e1.record()
+    with _timed("attn_fwd_f32", 4.0 * B * H * L * L * d, 4.0 * 4 * B * L * H * d + 4.0 * B * H * L):
+        _chk(lib().orbit2_attn_fwd_f32(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, 0, int(flags), int(ldq), int(ldo),
+                                       _stream()), "orbit2_attn_fwd_f32")
     return out, lse
 
 
@@ -561,21 +542,11 @@ def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0, gate=
     else:
         dqkv = torch.empty_like(qkv)
     delta = torch.empty(lib().orbit2_attn_bwd_ws_floats(B, L, H), dtype=F32, device=qkv.device)
-    if timer is not None:
-        # algorithmic: 2x the forward's FLOPs (recompute not credited); qkv, out, dout read once, dqkv written once
-        e0, e1 = timer.span("attn_bwd", 8.0 * B * H * L * L * d, 2.0 * 8 * B * L * H * d + 8.0 * B * H * L)
-        e0.record()
-    if tail is not None:
-        _chk(lib().orbit2_attn_bwd_tq(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, L, H, d, drop_p, seed, int(flags),
-                                      int(ldq), int(ldo), _p(gate), _sched_word(qkv.device), tail, _stream()), "orbit2_attn_bwd_tq")
-    elif gate is None:
-        _chk(lib().orbit2_attn_bwd_ld(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, L, H, d,
-                                      drop_p, seed, int(flags), int(ldq), int(ldo), _stream()), "orbit2_attn_bwd_ld")
-    else:
-        _chk(lib().orbit2_attn_bwd_gated(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, L, H, d,
-                                         drop_p, seed, int(flags), int(ldq), int(ldo), _p(gate), _stream()), "orbit2_attn_bwd_gated")
-    if timer is not None:
-        e1.record()
+    # algorithmic: 2x the forward's FLOPs (recompute not credited); qkv, out, dout read once, dqkv written once
+    with _timed("attn_bwd", 8.0 * B * H * L * L * d, 2.0 * 8 * B * L * H * d + 8.0 * B * H * L):
+        _call_entry("orbit2_attn_bwd_ld", "orbit2_attn_bwd_gated", "orbit2_attn_bwd_tq",
+                    (_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo)),
+                    (_p(gate),), gate is not None, tail, qkv.device)
     return dqkv
 
 

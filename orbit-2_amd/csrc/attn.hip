@@ -1841,8 +1841,10 @@ static int attn_check(const void* a, const void* b, int B, int L, int H, int d, 
   return O2_OK;
 }
 
-// ---- kernel selection.  attn_plan decides which kernel runs each pass of a call, on which grid and with which scalars; it
-// launches nothing, and the entry points below map it to instantiations.  The variant is an ARGUMENT of the entry points (flags):
+// ---- kernel selection.  attn_plan decides which kernel runs each pass of a call, on which grid and with which scalars, whether
+// the pass honours the caller's path gate and whether it has a queued tail and of what size (tail_queue.h); it launches nothing,
+// and the entry points below map it to instantiations and decide nothing.  Neither the gate nor the queue moves the selection: a
+// gated or queued pass runs the twin of the kernel the plain call runs, with the same block (tests/test_dispatch_cpu.py).  The variant is an ARGUMENT of the entry points (flags):
 // a forward / backward pair cannot disagree behind the caller's back, nothing is read from the environment on the launch path.
 enum AttnDkv {
   DKV_W4,         // the generated one-wave-per-SIMD dK + dV kernel: 128 keys per workgroup
@@ -1851,7 +1853,11 @@ enum AttnDkv {
   DKV_FUSED256,   // d = 256: one pass at one wave per SIMD (interm_10b)
   DKV_SPLIT       // dK and dV as two passes
 };
-struct AttnLaunch { dim3 grid, block; };
+struct AttnLaunch {              // one pass
+  dim3 grid, block;              // what is launched: the pass's workgroups, or tail.grid
+  bool gated;                    // a generated kernel and a gate: its gated twin runs (the kernels without a twin ignore the gate)
+  O2TailPlan tail;               // tail.tail > 0: the tail-queue twin of a generated kernel runs; 0: static
+};
 struct AttnPlan {
   bool fwd_w4, dq_w4;            // the generated one-wave-per-SIMD kernels (256-row workgroups) take the forward / the dQ pass
   bool fwd_lazy;                 // compiler-scheduled forward: the lazy-rescaling kernel (every call without dropout)
@@ -1872,7 +1878,15 @@ static bool attn_w4_ok(int d, int L, int flags, int ldq, int ldo) {
          attn_w4_range_ok(L, ldq, ldo);
 }
 
-static AttnPlan attn_plan(int d, int L, int B, int H, int flags, int ldq, int ldo, float drop_p) {
+// Tail rounds of the generated kernels (o2_tail_auto; 0: static), sized from profiles/r08_tail_idle.txt: the backward (dQ and
+// dK + dV together) runs -1.0 ... -1.5 % shorter with 2 to 6 rounds, best at 4, gated or not; the forward within +-0.7 % at every
+// tail although its end idle halves: static.
+#define O2_TQ_ROUNDS_ATTN_FWD 0
+#define O2_TQ_ROUNDS_ATTN_BWD 4
+
+// gate: the path gate of the _gated / _tq entries; sched / tail_arg: the counter and `tail` of the _tq entries (nullptr: none)
+static AttnPlan attn_plan(int d, int L, int B, int H, int flags, int ldq, int ldo, float drop_p, const float* gate,
+                          const void* sched, int tail_arg) {
   AttnPlan p;
   const bool pre = (flags & ORBIT2_ATTN_Q_PRESCALED) != 0, split = (flags & ORBIT2_ATTN_SPLIT_DKV) != 0;
   p.thr = (unsigned)(drop_p * 256.0f + 0.5f);
@@ -1898,10 +1912,21 @@ static AttnPlan attn_plan(int d, int L, int B, int H, int flags, int ldq, int ld
   // (the generated dK + dV kernel numbers query rows across the batch in 32 bits)
   p.dkv = (p.dq_w4 && !split && (uint64_t)B * (uint64_t)H * (uint64_t)L < (1ull << 32)) ? DKV_W4 : d == 64 ? DKV_FUSED64
           : split ? DKV_SPLIT : d == 256 ? DKV_FUSED256 : p.nw == 8 ? DKV_FUSED128 : DKV_SPLIT;
-  const auto rows = [&](int r, int threads) { return AttnLaunch{dim3((unsigned)(((L + r - 1) / r) * H * B)), dim3(threads)}; };
-  p.fwd = p.fwd_w4 ? rows(256, 256) : rows(p.nw_fwd * 32, p.nw_fwd * 64);
-  p.dq = p.dq_w4 ? rows(256, 256) : rows(p.nw * 32, p.nw * 64);
-  p.dkv_l = p.dkv == DKV_W4 ? rows(128, 256) : rows(p.nw * 32, p.nw * 64);
+  // a pass over r rows per workgroup; w4: of a generated kernel, which has the twins -- rounds: the tail it asks for by itself
+  // (the passes of a backward call are planned independently and run one after the other on the stream: they share the counter,
+  // which is zero again between them)
+  const auto rows = [&](int r, int threads, bool w4 = false, int rounds = 0) {
+    const unsigned wgs = (unsigned)(((L + r - 1) / r) * H * B);
+    AttnLaunch l;
+    l.block = dim3(threads);
+    l.gated = w4 && gate;
+    l.tail = o2_tail_plan_launch(wgs, w4 ? sched : nullptr, tail_arg, rounds);
+    l.grid = dim3(l.tail.tail > 0 ? (unsigned)l.tail.grid : wgs);
+    return l;
+  };
+  p.fwd = p.fwd_w4 ? rows(256, 256, true, O2_TQ_ROUNDS_ATTN_FWD) : rows(p.nw_fwd * 32, p.nw_fwd * 64);
+  p.dq = p.dq_w4 ? rows(256, 256, true, O2_TQ_ROUNDS_ATTN_BWD) : rows(p.nw * 32, p.nw * 64);
+  p.dkv_l = p.dkv == DKV_W4 ? rows(128, 256, true, O2_TQ_ROUNDS_ATTN_BWD) : rows(p.nw * 32, p.nw * 64);
   return p;
 }
 
@@ -1916,44 +1941,35 @@ template <class F> static void attn_with_variant(int d, int nw, bool drop, bool 
   }, drop, ragged);
 }
 
-// gate: the path gate of orbit2_attn_fwd_gated (nullptr: none).  The plan does not look at it: a gated call runs the gated twin
-// of the kernel the ungated call runs, on the same grid; the kernels without a twin ignore it.
-// Tail rounds of the generated kernels (o2_tail_auto; 0: static), sized from profiles/r08_tail_idle.txt: the backward (dQ and
-// dK + dV together) runs -1.0 ... -1.5 % shorter with 2 to 6 rounds, best at 4, gated or not; the forward within +-0.7 % at every
-// tail although its end idle halves: static.
-#define O2_TQ_ROUNDS_ATTN_FWD 0
-#define O2_TQ_ROUNDS_ATTN_BWD 4
-// sched / tail_arg: the tail queue of orbit2_attn_fwd_tq / _bwd_tq (nullptr: none) for a generated kernel's grid
-static O2TailPlan attn_tail_plan(const AttnLaunch& l, unsigned int* sched, int tail_arg, int rounds) {
-  if (!sched || tail_arg < 0) return o2_tail_plan(l.grid.x, 0);
-  return o2_tail_plan_arg(l.grid.x, tail_arg, rounds, tail_arg == 0 ? o2_tail_slots() : 0);
-}
+// A pass of a generated kernel, as its plan (PASS) says: the plain kernel, its gated twin or its tail-queue twin.  The arguments
+// behind the twins are the ones all three take; the gated twin adds the gate, the tail-queue twin the gate, the counter and the tail
+#define O2_W4_PASS(PASS, PLAIN, GATED, TQ, ...)                                                                                    \
+  do {                                                                                                                           \
+    if (PASS.tail.tail > 0)                                                                                                      \
+      o2_with_flags([&](auto DR, auto GT) {                                                                                      \
+        hipLaunchKernelGGL((TQ<DR, GT>), PASS.grid, PASS.block, 0, s, __VA_ARGS__, gate, sched, PASS.tail.S, PASS.tail.tail);    \
+      }, p.drop, PASS.gated);                                                                                                    \
+    else if (PASS.gated)                                                                                                         \
+      o2_with_flags([&](auto DR) { hipLaunchKernelGGL((GATED<DR>), PASS.grid, PASS.block, 0, s, __VA_ARGS__, gate); }, p.drop);  \
+    else                                                                                                                         \
+      o2_with_flags([&](auto DR) { hipLaunchKernelGGL((PLAIN<DR>), PASS.grid, PASS.block, 0, s, __VA_ARGS__); }, p.drop);        \
+  } while (0)
 
+// gate: the path gate of orbit2_attn_fwd_gated, sched / tail_arg: the tail queue of orbit2_attn_fwd_tq (nullptr: none)
 static int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
                            uint64_t seed, int flags, int ldq, int ldo, const float* gate, void* stream,
                            unsigned int* sched = nullptr, int tail_arg = -1) {
   int rc = attn_check(qkv, out, B, L, H, d, drop_p);
   if (rc) return rc;
   if (!lse || ldo < H * d || (ldo & 7) || ldq < 3 * H * d || (ldq & 7)) return O2_ERR_ARG;
-  const AttnPlan p = attn_plan(d, L, B, H, flags, ldq, ldo, drop_p);
+  const AttnPlan p = attn_plan(d, L, B, H, flags, ldq, ldo, drop_p, gate, sched, tail_arg);
   hipStream_t s = (hipStream_t)stream;
   const bf16_t* q_ = (const bf16_t*)qkv;
   bf16_t* o_ = (bf16_t*)out;
 #define O2_FWD(KERN, ...) hipLaunchKernelGGL(KERN, p.fwd.grid, p.fwd.block, 0, s, q_, o_, lse, L, H, __VA_ARGS__, seed, ldo, ldq)
-  const O2TailPlan tp = p.fwd_w4 ? attn_tail_plan(p.fwd, sched, tail_arg, O2_TQ_ROUNDS_ATTN_FWD) : o2_tail_plan(0, 0);
-  if (tp.tail > 0) {
-    const O2TailQ tq = {sched, tp.S, tp.tail};
-    o2_with_flags([&](auto DR, auto GT) {
-      hipLaunchKernelGGL((attn_fwd_w4_tq_kernel<DR, GT>), dim3((unsigned)tp.grid), p.fwd.block, 0, s, q_, o_, lse, L, H, p.thr,
-                         p.dscale, seed, ldo, ldq, gate, tq.ctr, tq.S, tq.tail);
-    }, p.drop, gate != nullptr);
-  } else if (p.fwd_w4 && gate)
-    o2_with_flags([&](auto DR) {
-      hipLaunchKernelGGL((attn_fwd_w4_gated_kernel<DR>), p.fwd.grid, p.fwd.block, 0, s, q_, o_, lse, L, H, p.thr, p.dscale, seed,
-                         ldo, ldq, gate);
-    }, p.drop);
-  else if (p.fwd_w4)
-    o2_with_flags([&](auto DR) { O2_FWD((attn_fwd_w4_kernel<DR>), p.thr, p.dscale); }, p.drop);
+  if (p.fwd_w4)
+    O2_W4_PASS(p.fwd, attn_fwd_w4_kernel, attn_fwd_w4_gated_kernel, attn_fwd_w4_tq_kernel, q_, o_, lse, L, H, p.thr, p.dscale, seed,
+               ldo, ldq);
   else
     attn_with_variant(d, p.nw_fwd, p.drop, p.ragged_fwd, [&](auto DV, auto NW, auto DR, auto RG) {
       if constexpr (!DR) {                  // (the lazy-rescaling kernel has no dropout form)
@@ -1987,7 +2003,7 @@ static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, c
   int rc = attn_check(qkv, out, B, L, H, d, drop_p);
   if (rc) return rc;
   if (!dout || !lse || !delta || !dqkv || ldo < H * d || (ldo & 7) || ldq < 3 * H * d || (ldq & 7)) return O2_ERR_ARG;
-  const AttnPlan p = attn_plan(d, L, B, H, flags, ldq, ldo, drop_p);
+  const AttnPlan p = attn_plan(d, L, B, H, flags, ldq, ldo, drop_p, gate, sched, tail_arg);
   hipStream_t s = (hipStream_t)stream;
   // per-row statistics tables (attn_delta_kernel): delta = workspace of orbit2_attn_bwd_ws_floats(B, L, H) floats
   const int Lp = attn_lpad(L);
@@ -2001,41 +2017,17 @@ static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, c
   // a backward launch: the operands every kernel takes, its own scalars, the table pitch and the row pitch
 #define O2_BWD(KERN, PASS, ...) \
   hipLaunchKernelGGL(KERN, p.PASS.grid, p.PASS.block, 0, s, q_, do_, ws0, ws1, dq_, L, H, __VA_ARGS__, Lp, ldq)
-#define O2_BWD_GATED(KERN, PASS, ...) \
-  hipLaunchKernelGGL(KERN, p.PASS.grid, p.PASS.block, 0, s, q_, do_, ws0, ws1, dq_, L, H, __VA_ARGS__, Lp, ldq, gate)
 #define O2_BWD_CS p.scale, p.thr, p.dscale, seed, p.opmul          /* scalars of the compiler-scheduled kernels */
-  // (the two passes run one after the other on the stream: they share the counter, which is zero again between them)
-  const O2TailPlan tq_dq = p.dq_w4 ? attn_tail_plan(p.dq, sched, tail_arg, O2_TQ_ROUNDS_ATTN_BWD) : o2_tail_plan(0, 0);
-  const O2TailPlan tq_kv = p.dkv == DKV_W4 ? attn_tail_plan(p.dkv_l, sched, tail_arg, O2_TQ_ROUNDS_ATTN_BWD) : o2_tail_plan(0, 0);
-  if (tq_dq.tail > 0) {
-    const O2TailQ tq = {sched, tq_dq.S, tq_dq.tail};
-    o2_with_flags([&](auto DR, auto GT) {
-      hipLaunchKernelGGL((attn_bwd_dq_w4_tq_kernel<DR, GT>), dim3((unsigned)tq_dq.grid), p.dq.block, 0, s, q_, do_, ws0, ws1, dq_, L,
-                         H, p.thr, p.dq_w4_scale, seed, Lp, ldq, gate, tq.ctr, tq.S, tq.tail);
-    }, p.drop, gate != nullptr);
-  } else if (p.dq_w4 && gate)
-    o2_with_flags([&](auto DR) { O2_BWD_GATED((attn_bwd_dq_w4_gated_kernel<DR>), dq, p.thr, p.dq_w4_scale, seed); }, p.drop);
-  else if (p.dq_w4)
-    o2_with_flags([&](auto DR) { O2_BWD((attn_bwd_dq_w4_kernel<DR>), dq, p.thr, p.dq_w4_scale, seed); }, p.drop);
+  if (p.dq_w4)
+    O2_W4_PASS(p.dq, attn_bwd_dq_w4_kernel, attn_bwd_dq_w4_gated_kernel, attn_bwd_dq_w4_tq_kernel, q_, do_, ws0, ws1, dq_, L, H,
+               p.thr, p.dq_w4_scale, seed, Lp, ldq);
   else
     attn_with_variant(d, p.nw, p.drop, p.ragged,
                       [&](auto DV, auto NW, auto DR, auto RG) { O2_BWD((attn_bwd_dq_kernel<DV, DR, RG, NW>), dq, O2_BWD_CS); });
   switch (p.dkv) {
     case DKV_W4:
-      if (tq_kv.tail > 0) {
-        const O2TailQ tq = {sched, tq_kv.S, tq_kv.tail};
-        o2_with_flags([&](auto DR, auto GT) {
-          hipLaunchKernelGGL((attn_bwd_dkv_w4_tq_kernel<DR, GT>), dim3((unsigned)tq_kv.grid), p.dkv_l.block, 0, s, q_, do_, ws0, ws1,
-                             dq_, L, H, p.thr, p.dkv_w4_kgrad, p.dkv_w4_dscale, seed, Lp, ldq, gate, tq.ctr, tq.S, tq.tail);
-        }, p.drop, gate != nullptr);
-      } else if (gate)
-        o2_with_flags([&](auto DR) {
-          O2_BWD_GATED((attn_bwd_dkv_w4_gated_kernel<DR>), dkv_l, p.thr, p.dkv_w4_kgrad, p.dkv_w4_dscale, seed);
-        }, p.drop);
-      else
-        o2_with_flags([&](auto DR) {
-          O2_BWD((attn_bwd_dkv_w4_kernel<DR>), dkv_l, p.thr, p.dkv_w4_kgrad, p.dkv_w4_dscale, seed);
-        }, p.drop);
+      O2_W4_PASS(p.dkv_l, attn_bwd_dkv_w4_kernel, attn_bwd_dkv_w4_gated_kernel, attn_bwd_dkv_w4_tq_kernel, q_, do_, ws0, ws1, dq_, L,
+                 H, p.thr, p.dkv_w4_kgrad, p.dkv_w4_dscale, seed, Lp, ldq);
       break;
     case DKV_FUSED128:
       o2_with_flags([&](auto DR, auto RG) { O2_BWD((attn_bwd_dkv128_kernel<DR, RG>), dkv_l, O2_BWD_CS, p.kgrad); }, p.drop, p.ragged);
@@ -2053,11 +2045,11 @@ static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, c
       break;
   }
 #undef O2_BWD
-#undef O2_BWD_GATED
 #undef O2_BWD_CS
   O2_CHECK_LAUNCH();
   return O2_OK;
 }
+#undef O2_W4_PASS
 extern "C" int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                                   void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq,
                                   int ldo, void* stream) {
@@ -2072,13 +2064,13 @@ extern "C" int orbit2_attn_bwd_gated(const void* qkv, const void* out, const voi
 // The same launches with a tail queue for the generated kernels (csrc/tail_queue.h); gate may be NULL
 extern "C" int orbit2_attn_fwd_tq(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p, uint64_t seed,
                                   int flags, int ldq, int ldo, const float* gate, void* sched_ws, int tail, void* stream) {
-  if (!sched_ws || ((uintptr_t)sched_ws & 3)) return O2_ERR_ARG;
+  if (!o2_sched_ok(sched_ws)) return O2_ERR_ARG;
   return attn_fwd_launch(qkv, out, lse, B, L, H, d, drop_p, seed, flags, ldq, ldo, gate, stream, (unsigned int*)sched_ws, tail);
 }
 extern "C" int orbit2_attn_bwd_tq(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                                   int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq, int ldo,
                                   const float* gate, void* sched_ws, int tail, void* stream) {
-  if (!sched_ws || ((uintptr_t)sched_ws & 3)) return O2_ERR_ARG;
+  if (!o2_sched_ok(sched_ws)) return O2_ERR_ARG;
   return attn_bwd_launch(qkv, out, dout, lse, delta, dqkv, B, L, H, d, drop_p, seed, flags, ldq, ldo, gate, stream,
                          (unsigned int*)sched_ws, tail);
 }

@@ -1411,7 +1411,18 @@ extern "C" int orbit2_debug_read(unsigned int* host_dst, int n) {   // diagnosti
 }
 #endif
 
-static int gemm_make_epi(const orbit2_gemm_args* a, Epi& e) {
+// The gate rule.  The epilogues whose result for a dropped entry is known without the contraction: bf16 output that
+// replaces C, and either no residual (zeros) or the residual added behind a row scale that IS the gate (the residual rows).  Any
+// other call ignores the gate.
+static bool gemm_gate_ok(const Epi& e, const float* gate, int rows_per_gate) {
+  if (!gate || rows_per_gate <= 0 || e.out_fp32 || e.beta != 0.f) return false;
+  if (e.residual) return !e.res_first && e.res_mod == 0 && e.rowscale == gate && e.rows_per_scale == rows_per_gate &&
+                         !e.save_pre && !e.save_dact && !e.colsum_ws && e.ldr % 8 == 0 && !((uintptr_t)e.residual & 15);
+  return !e.rowscale;
+}
+
+// gate / rows_per_gate: the call's path gate (nullptr: none); the epilogue carries it when gemm_gate_ok honours it
+static int gemm_make_epi(const orbit2_gemm_args* a, const float* gate, int rows_per_gate, Epi& e) {
   if (!a || !a->A || !a->B || !a->C) return O2_ERR_ARG;
   if (a->M <= 0 || a->N <= 0 || a->K <= 0) return O2_ERR_ARG;
   // rows of a K-contiguous operand are clamped at staging and masked at the store, so M is free there; an operand
@@ -1450,22 +1461,18 @@ static int gemm_make_epi(const orbit2_gemm_args* a, Epi& e) {
   e.beta = a->beta;
   e.rs_tile = 1.0f;
   e.colsum_ws = a->colsum_ws;
-  e.gate = nullptr;
-  e.rows_per_gate = 0;
+  const bool gated = gemm_gate_ok(e, gate, rows_per_gate);
+  e.gate = gated ? gate : nullptr;
+  e.rows_per_gate = gated ? rows_per_gate : 0;
   return O2_OK;
 }
 
-// the epilogues whose result for a dropped entry is known without the contraction: bf16 output that replaces C, and either no
-// residual (zeros) or the residual added behind a row scale that IS the gate (the residual rows).  Any other call ignores the gate.
-static bool gemm_gate_ok(const Epi& e, const float* gate, int rows_per_gate) {
-  if (!gate || rows_per_gate <= 0 || e.out_fp32 || e.beta != 0.f) return false;
-  if (e.residual) return !e.res_first && e.res_mod == 0 && e.rowscale == gate && e.rows_per_scale == rows_per_gate &&
-                         !e.save_pre && !e.save_dact && !e.colsum_ws && e.ldr % 8 == 0 && !((uintptr_t)e.residual & 15);
-  return !e.rowscale;
-}
-
-// ---- kernel selection.  gemm_plan / gemm_group_plan decide which kernel takes a call and on which grid; they launch nothing.
-// The entry points below make the epilogue, plan, and map the plan to an instantiation.
+// ---- kernel selection.  gemm_plan / gemm_group_plan decide everything about a launch and launch nothing: which kernel takes the
+// call and on which grid, whether the launch has a queued tail and of what size (tail_queue.h), and for a group which problems'
+// K gates are honoured and the final pacing mode.  The path gate of a single call is decided where its epilogue is made
+// (gemm_make_epi, gemm_gate_ok).  Neither the gate nor the queue moves the selection: family, form, kind, tiles and block are those
+// of the plain call (tests/test_dispatch_cpu.py).  The entry points below make the epilogue, plan, and map the plan to an
+// instantiation; they decide nothing.
 enum GemmFamily {
   GEMM_128,        // 128 x 128 tiles, 2 workgroups/CU, ragged K: small or ragged problems
   GEMM_128_HALF,   // the same kernel on 64-row tiles (A K-contiguous)
@@ -1478,7 +1485,8 @@ struct GemmPlan {
   int ek;                   // GEMM_256W: compile-time epilogue kind (0: the runtime epilogue)
   bool stamped;             // GEMM_256W: the stamped diagnostic form (hint 261)
   int tiles_m, tiles_n;
-  unsigned grid, block;
+  O2TailPlan tail;          // tail.tail > 0: the tail-queue twin takes the launch (GEMM_256W, not stamped); 0: static
+  unsigned grid, block;     // what is launched: the tiles, or tail.grid
   bool fuses_colsum;        // this launch fills colsum_ws (orbit2_gemm_bf16_colsum_rows)
 };
 static unsigned gemm_block(GemmFamily f) { return f == GEMM_256T ? 512 : 256; }
@@ -1501,7 +1509,18 @@ static bool gemm_fills_chip(long t256) {
 // balances the group's own last round (climate_learn/_ops.py: _dw_balance_plan), so only the tile count matters
 static bool gemm_group_fills_chip(long t256) { return t256 >= 192; }
 
-static int gemm_plan(const orbit2_gemm_args* a, const Epi& e, GemmPlan& p) {
+// Tail rounds a family asks for by itself (o2_tail_auto; 0: the family stays static), sized from profiles/r08_tail_idle.txt:
+// the mean time of a launch at the bench shapes, static against tails of 1, 2, 4 and 6 rounds, ungated and gated.
+//   grouped weight gradients             -3.2 ... -5.3 %, flat from 2 rounds on: 4
+//   input-gradient form, plain epilogue  -0.7 ... -1.8 % at every tail, gated or not: 2
+//   forward form, kind 2 (proj, fc2)     -0.6 ... -1.1 % at 1 and 2 rounds, +0.7 ... +1.4 % at 4 and 6 when gated: 2
+//   forward form, kinds 0 and 1; input-gradient form, kind 3: within +-0.6 % ungated, +0.5 ... +1.6 % gated (a ticket
+//     holder's neighbours in L2 are whoever drew the next tickets, not its cohort): static
+#define O2_TQ_ROUNDS_GROUP 4
+constexpr int w4_tail_rounds(int form, int ek) { return (form == 1 && ek == 0) || (form == 0 && ek == 2) ? 2 : 0; }
+
+// sched / tail_arg: the counter and the `tail` of orbit2_gemm_bf16_tq (nullptr: no queue; o2_tail_plan_launch)
+static int gemm_plan(const orbit2_gemm_args* a, const Epi& e, const void* sched, int tail_arg, GemmPlan& p) {
   p = GemmPlan{};
   p.a_kc = a->a_kc != 0;
   p.b_kc = a->b_kc != 0;
@@ -1553,11 +1572,21 @@ static int gemm_plan(const orbit2_gemm_args* a, const Epi& e, GemmPlan& p) {
   }
   p.grid = (unsigned)(p.tiles_m * p.tiles_n);
   p.block = gemm_block(p.family);
+  // the tail queue: the 4-wave kernel's launches only, any other plan launches as without a counter
+  p.tail = o2_tail_plan_launch((long)p.grid, p.family == GEMM_256W && !p.stamped ? sched : nullptr, tail_arg, w4_tail_rounds(form, p.ek));
+  if (p.tail.tail > 0) p.grid = (unsigned)p.tail.grid;
   return O2_OK;
 }
 
-// a group (n >= 2): the kernel family for all of it, and in g every problem with its tile range and the pacing mode
-static int gemm_group_plan(const orbit2_gemm_args* args, int n, GemmFamily& family, GArgs& g) {
+// a group (n >= 2): the kernel family for all of it, its tail and grid, and in g every problem with its tile range, its K gate
+// where it is honoured (kgates / k_per_gate of orbit2_gemm_bf16_grouped_gated; nullptr: none) and the pacing mode
+struct GemmGroupPlan {
+  GemmFamily family;
+  O2TailPlan tail;          // tail.tail > 0: gemm256w_grouped_tq_kernel takes the launch (GEMM_256W); 0: static
+  unsigned grid, block;
+};
+static int gemm_group_plan(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate, const void* sched,
+                           int tail_arg, GemmGroupPlan& p, GArgs& g) {
   g.n = n;
   g.pace = 0;
   // 256-tile kernels when every problem of the group can take them and the group fills the chip -- the 4-wave kernel when all
@@ -1573,22 +1602,30 @@ static int gemm_group_plan(const orbit2_gemm_args* args, int n, GemmFamily& fami
     kmin = a->K < kmin ? a->K : kmin;
   }
   if (args[0].tile_hint < 256 && !gemm_group_fills_chip(t256)) big = false;
-  family = !big ? GEMM_128 : whole ? GEMM_256W : GEMM_256T;
+  const GemmFamily family = p.family = !big ? GEMM_128 : whole ? GEMM_256W : GEMM_256T;
   const int TB = big ? 256 : 128;
+  // K gates: the 4-wave kernel in the weight-gradient form (neither operand K-contiguous)
+  const bool kgate_form = kgates && k_per_gate && family == GEMM_256W && !args[0].a_kc && !args[0].b_kc;
   int total = 0;
   for (int i = 0; i < n; ++i) {
     const orbit2_gemm_args* a = args + i;
     if (a->a_kc != args[0].a_kc || a->b_kc != args[0].b_kc) return O2_ERR_ARG;   // one operand form per group
-    const int rc = gemm_make_epi(a, g.p[i].epi);
+    const int rc = gemm_make_epi(a, nullptr, 0, g.p[i].epi);
     if (rc) return rc;
     GProb& P = g.p[i];
     P.A = (const bf16_t*)a->A; P.B = (const bf16_t*)a->B;
     P.M = a->M; P.N = a->N; P.K = a->K; P.lda = a->lda; P.ldb = a->ldb;
-    P.kgate = nullptr; P.k_per_gate = 0;
+    // whole entries of whole K-tiles, or the problem ignores its gate
+    const bool gated = kgate_form && kgates[i] && k_per_gate[i] > 0 && k_per_gate[i] % BK3 == 0 && a->K % k_per_gate[i] == 0;
+    P.kgate = gated ? kgates[i] : nullptr;
+    P.k_per_gate = gated ? k_per_gate[i] : 0;
     P.tiles_m = (a->M + TB - 1) / TB; P.tiles_n = (a->N + TB - 1) / TB;
     total += P.tiles_m * P.tiles_n;
     P.tile_end = total;
   }
+  p.block = gemm_block(family);
+  p.tail = o2_tail_plan_launch(total, family == GEMM_256W ? sched : nullptr, tail_arg, O2_TQ_ROUNDS_GROUP);
+  p.grid = (unsigned)p.tail.grid;
   if (family == GEMM_256W) {
     // cohort start barrier: every problem's tiles sweep >= 512 K-tiles (a round lasts >= 0.6 ms: the bounded wait is noise
     // against it, and a lost cohort costs a whole sweep of re-fetched strips)
@@ -1597,76 +1634,45 @@ static int gemm_group_plan(const orbit2_gemm_args* args, int n, GemmFamily& fami
     // SAME time in the step (166.6 vs 166.6 ms per step, profiles/r06_pace2b_instep.txt): every column group then sweeps at the
     // slowest group's rate, which is what a round takes anyway.  Kept selectable, not default.
     static const int pace_env = [] { const char* e = getenv("ORBIT2_W4_PACE"); return e ? atoi(e) : 1; }();
-    g.pace = (O2_W4_WALK && pace_env && kmin >= 512 * BK3 && total > 256) ? pace_env : 0;
+    // ("more than one round" is about the workgroups that walk statically: all of them, or the ones in front of the tail)
+    g.pace = (O2_W4_WALK && pace_env && kmin >= 512 * BK3 && p.tail.S > 256) ? pace_env : 0;
   }
   return O2_OK;
 }
 
-// Tail rounds a family asks for by itself (o2_tail_auto; 0: the family stays static), sized from profiles/r08_tail_idle.txt:
-// the mean time of a launch at the bench shapes, static against tails of 1, 2, 4 and 6 rounds, ungated and gated.
-//   grouped weight gradients             -3.2 ... -5.3 %, flat from 2 rounds on: 4
-//   input-gradient form, plain epilogue  -0.7 ... -1.8 % at every tail, gated or not: 2
-//   forward form, kind 2 (proj, fc2)     -0.6 ... -1.1 % at 1 and 2 rounds, +0.7 ... +1.4 % at 4 and 6 when gated: 2
-//   forward form, kinds 0 and 1; input-gradient form, kind 3: within +-0.6 % ungated, +0.5 ... +1.6 % gated (a ticket
-//     holder's neighbours in L2 are whoever drew the next tickets, not its cohort): static
-#define O2_TQ_ROUNDS_GROUP 4
-constexpr int w4_tail_rounds(int form, int ek) { return (form == 1 && ek == 0) || (form == 0 && ek == 2) ? 2 : 0; }
-// the plan of a launch of T tiles that offers a counter (sched; nullptr: static) -- tail_arg as in o2_tail_plan_arg
-static O2TailPlan gemm_tail_plan(long T, unsigned int* sched, int tail_arg, int rounds) {
-  if (!sched || tail_arg < 0) return o2_tail_plan(T, 0);
-  return o2_tail_plan_arg(T, tail_arg, rounds, tail_arg == 0 ? o2_tail_slots() : 0);
-}
-
-// one launch; gate / rows_per_gate: the path gate of orbit2_gemm_bf16_gated (nullptr: none).  The plan does not look at the
-// gate: a gated call runs exactly the kernel, grid and block of the ungated call.  sched / tail_arg: the tail queue of
-// orbit2_gemm_bf16_tq (nullptr: none) -- the 4-wave kernel's launches only, any other plan launches as without it.
+// one launch; gate / rows_per_gate: the path gate of orbit2_gemm_bf16_gated, sched / tail_arg: the tail queue of orbit2_gemm_bf16_tq
+// (nullptr: none)
 static int gemm_launch(const orbit2_gemm_args* a, const float* gate, int rows_per_gate, void* stream, unsigned int* sched = nullptr,
                        int tail_arg = -1) {
   Epi e;
   GemmPlan p;
-  int rc = gemm_make_epi(a, e);
+  int rc = gemm_make_epi(a, gate, rows_per_gate, e);
   if (rc) return rc;
-  if (gemm_gate_ok(e, gate, rows_per_gate)) { e.gate = gate; e.rows_per_gate = rows_per_gate; }
-  rc = gemm_plan(a, e, p);
+  rc = gemm_plan(a, e, sched, tail_arg, p);
   if (a->colsum_ws && !p.fuses_colsum) return O2_ERR_UNSUPPORTED;   // ask orbit2_gemm_bf16_colsum_rows first
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (sched && p.family == GEMM_256W && !p.stamped) {
-    const int form_of_plan = w4_form(p.a_kc, p.b_kc);
-    const O2TailPlan tp = gemm_tail_plan((long)p.grid, sched, tail_arg, w4_tail_rounds(form_of_plan, p.ek));
-    if (tp.tail > 0) {
-      const O2TailQ q = {sched, tp.S, tp.tail};
-      o2_with_flags([&](auto AK, auto BK) {
-        constexpr int FORM = w4_form(AK, BK);
-        auto kind = [&](auto EK) {
-          if constexpr (w4_compiled_kind(FORM, EK) == EK)
-            if (p.ek == EK)
-              hipLaunchKernelGGL((gemm256w_tq_kernel<FORM, EK>), dim3((unsigned)tp.grid), dim3(p.block), 0, s, (const bf16_t*)a->A,
-                                 (const bf16_t*)a->B, a->M, a->N, a->K, a->lda, a->ldb, p.tiles_m, p.tiles_n, e, q.ctr, q.S, q.tail);
-        };
-        kind(o2_int<0>{}); kind(o2_int<1>{}); kind(o2_int<2>{}); kind(o2_int<3>{});
-      }, p.a_kc, p.b_kc);
-      O2_CHECK_LAUNCH();
-      return O2_OK;
-    }
-  }
-#define O2_GEMM_LAUNCH(...)                                                                                              \
-  hipLaunchKernelGGL((__VA_ARGS__), dim3(p.grid), dim3(p.block), 0, s, (const bf16_t*)a->A, (const bf16_t*)a->B, a->M, a->N, \
-                     a->K, a->lda, a->ldb, p.tiles_m, p.tiles_n, e)
+  // (KERN in parentheses; further arguments: those of the tail-queue twin)
+#define O2_GEMM_LAUNCH(KERN, ...)                                                                                           \
+  hipLaunchKernelGGL(KERN, dim3(p.grid), dim3(p.block), 0, s, (const bf16_t*)a->A, (const bf16_t*)a->B, a->M, a->N, a->K, a->lda, \
+                     a->ldb, p.tiles_m, p.tiles_n, e, ##__VA_ARGS__)
   o2_with_flags([&](auto AK, auto BK) {
     constexpr int FORM = w4_form(AK, BK);
     switch (p.family) {
-      case GEMM_128: O2_GEMM_LAUNCH(gemm128_kernel<AK, BK>); break;
-      case GEMM_128_HALF: if constexpr (AK) O2_GEMM_LAUNCH(gemm128_kernel<true, BK, 64>); break;
-      case GEMM_256T: O2_GEMM_LAUNCH(gemm256t_kernel<AK, BK>); break;
+      case GEMM_128: O2_GEMM_LAUNCH((gemm128_kernel<AK, BK>)); break;
+      case GEMM_128_HALF: if constexpr (AK) O2_GEMM_LAUNCH((gemm128_kernel<true, BK, 64>)); break;
+      case GEMM_256T: O2_GEMM_LAUNCH((gemm256t_kernel<AK, BK>)); break;
       case GEMM_256W: {
-        auto kind = [&](auto EK) {        // one instantiation per compiled (form, kind) pair; p.ek names exactly one of them
+        auto kind = [&](auto EK) {        // one instantiation per compiled (form, kind) pair and twin; p.ek names exactly one pair
           if constexpr (w4_compiled_kind(FORM, EK) == EK)
-            if (p.ek == EK) O2_GEMM_LAUNCH(gemm256w_kernel<FORM, false, EK>);
+            if (p.ek == EK) {
+              if (p.tail.tail > 0) O2_GEMM_LAUNCH((gemm256w_tq_kernel<FORM, EK>), sched, p.tail.S, p.tail.tail);
+              else O2_GEMM_LAUNCH((gemm256w_kernel<FORM, false, EK>));
+            }
         };
         if (!p.stamped) { kind(o2_int<0>{}); kind(o2_int<1>{}); kind(o2_int<2>{}); kind(o2_int<3>{}); }
 #ifdef O2_W4_STAMP
-        else O2_GEMM_LAUNCH(gemm256w_kernel<FORM, true>);
+        else O2_GEMM_LAUNCH((gemm256w_kernel<FORM, true>));
 #endif
         break;
       }
@@ -1686,53 +1692,38 @@ extern "C" int orbit2_gemm_bf16_gated(const orbit2_gemm_args* a, const float* ga
 
 extern "C" int orbit2_gemm_bf16_tq(const orbit2_gemm_args* a, const float* gate, int rows_per_gate, void* sched_ws, int tail,
                                    void* stream) {
-  if (!sched_ws || ((uintptr_t)sched_ws & 3) || (gate && rows_per_gate <= 0)) return O2_ERR_ARG;
+  if (!o2_sched_ok(sched_ws) || (gate && rows_per_gate <= 0)) return O2_ERR_ARG;
   return gemm_launch(a, gate, rows_per_gate, stream, (unsigned int*)sched_ws, tail);
 }
 
 extern "C" int orbit2_gemm_bf16_colsum_rows(const orbit2_gemm_args* a) {
   Epi e;
   GemmPlan p;
-  if (!a || gemm_make_epi(a, e)) return 0;
-  gemm_plan(a, e, p);                       // (a refused call leaves the flag clear)
+  if (!a || gemm_make_epi(a, nullptr, 0, e)) return 0;
+  gemm_plan(a, e, nullptr, -1, p);          // (a refused call leaves the flag clear)
   return p.fuses_colsum ? a->M / 256 : 0;
 }
 
-// kgates / k_per_gate: the K gates of orbit2_gemm_bf16_grouped_gated (nullptr: none); the plan does not look at them
+// kgates / k_per_gate: the K gates of orbit2_gemm_bf16_grouped_gated, sched / tail_arg: the tail queue of
+// orbit2_gemm_bf16_grouped_tq (nullptr: none).  One problem is the single launch (with the counter, without a gate)
 static int gemm_group_launch(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate, void* stream,
                              unsigned int* sched = nullptr, int tail_arg = -1) {
   if (!args || n <= 0 || n > ORBIT2_GEMM_MAX_GROUP) return O2_ERR_ARG;
   if (n == 1) return gemm_launch(args, nullptr, 0, stream, sched, tail_arg);
   for (int i = 0; i < n; ++i)
     if (args[i].colsum_ws) return O2_ERR_UNSUPPORTED;      // single launches only (orbit2_gemm_bf16_colsum_rows)
-  GemmFamily family;
+  GemmGroupPlan p;
   GArgs g;
-  const int rc = gemm_group_plan(args, n, family, g);
+  const int rc = gemm_group_plan(args, n, kgates, k_per_gate, sched, tail_arg, p, g);
   if (rc) return rc;
-  if (kgates && k_per_gate && family == GEMM_256W && !args[0].a_kc && !args[0].b_kc)
-    for (int i = 0; i < n; ++i)       // whole entries of whole K-tiles, or the problem ignores its gate
-      if (kgates[i] && k_per_gate[i] > 0 && k_per_gate[i] % BK3 == 0 && args[i].K % k_per_gate[i] == 0) {
-        g.p[i].kgate = kgates[i];
-        g.p[i].k_per_gate = k_per_gate[i];
-      }
-  const dim3 grid(g.p[n - 1].tile_end), block(gemm_block(family));
+  const dim3 grid(p.grid), block(p.block);
   hipStream_t s = (hipStream_t)stream;
-  if (sched && family == GEMM_256W) {
-    const O2TailPlan tp = gemm_tail_plan((long)g.p[n - 1].tile_end, sched, tail_arg, O2_TQ_ROUNDS_GROUP);
-    if (tp.tail > 0) {
-      const O2TailQ q = {sched, tp.S, tp.tail};
-      // (the start barrier's rule "more than one round" is about the workgroups that walk statically)
-      if (tp.S <= 256) g.pace = 0;
-      o2_with_flags([&](auto AK, auto BK) {
-        hipLaunchKernelGGL((gemm256w_grouped_tq_kernel<w4_form(AK, BK)>), dim3((unsigned)tp.grid), block, 0, s, g, q.ctr, q.S, q.tail);
-      }, args[0].a_kc != 0, args[0].b_kc != 0);
-      O2_CHECK_LAUNCH();
-      return O2_OK;
-    }
-  }
   o2_with_flags([&](auto AK, auto BK) {
-    switch (family) {
-      case GEMM_256W: hipLaunchKernelGGL((gemm256w_grouped_kernel<w4_form(AK, BK)>), grid, block, 0, s, g); break;
+    switch (p.family) {
+      case GEMM_256W:
+        if (p.tail.tail > 0) hipLaunchKernelGGL((gemm256w_grouped_tq_kernel<w4_form(AK, BK)>), grid, block, 0, s, g, sched, p.tail.S, p.tail.tail);
+        else hipLaunchKernelGGL((gemm256w_grouped_kernel<w4_form(AK, BK)>), grid, block, 0, s, g);
+        break;
       case GEMM_256T: hipLaunchKernelGGL((gemm256t_grouped_kernel<AK, BK>), grid, block, 0, s, g); break;
       default: hipLaunchKernelGGL((gemm128_grouped_kernel<AK, BK>), grid, block, 0, s, g); break;
     }
@@ -1751,7 +1742,7 @@ extern "C" int orbit2_gemm_bf16_grouped_gated(const orbit2_gemm_args* args, int 
 
 extern "C" int orbit2_gemm_bf16_grouped_tq(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate,
                                            void* sched_ws, int tail, void* stream) {
-  if (!sched_ws || ((uintptr_t)sched_ws & 3)) return O2_ERR_ARG;
+  if (!o2_sched_ok(sched_ws)) return O2_ERR_ARG;
   return gemm_group_launch(args, n, kgates, k_per_gate, stream, (unsigned int*)sched_ws, tail);
 }
 

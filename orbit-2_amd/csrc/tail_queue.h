@@ -152,4 +152,12 @@ static inline int o2_tail_slots() {
   }
   return cached[dev] > 0 ? cached[dev] : 0;
 }
+// the tail plan of a launch of T tiles whose caller offers a counter (sched; nullptr: static) -- tail_arg as in o2_tail_plan_arg,
+// rounds: what the kernel family asks for by itself; the device is asked only when the launch sizes its own tail
+static inline O2TailPlan o2_tail_plan_launch(long long T, const void* sched, int tail_arg, int rounds) {
+  if (!sched || tail_arg < 0) return o2_tail_plan(T, 0);
+  return o2_tail_plan_arg(T, tail_arg, rounds, tail_arg == 0 ? o2_tail_slots() : 0);
+}
+// the counter the _tq entry points take: one 4-byte aligned word
+static inline bool o2_sched_ok(const void* sched_ws) { return sched_ws && !((uintptr_t)sched_ws & 3); }
 #endif

@@ -65,6 +65,27 @@ template <class... A> void launch(const std::type_info& k, dim3 grid, dim3 block
 #undef O2_CHECK_LAUNCH
 #define O2_CHECK_LAUNCH() do { } while (0)
 
+namespace rec {
+struct Device { int cus, xccs; };
+inline const Device& device() {
+  static const Device d = [] {
+    Device v = {256, 8};
+    const char* e = getenv("ORBIT2_RECORDER_DEVICE");
+    if (e && sscanf(e, "%dx%d", &v.cus, &v.xccs) != 2) { fprintf(stderr, "ORBIT2_RECORDER_DEVICE: CUSxXCCS\n"); exit(2); }
+    return v;
+  }();
+  return d;
+}
+inline hipError_t get_device(int* dev) { *dev = 0; return hipSuccess; }
+inline hipError_t device_attribute(int* v, hipDeviceAttribute_t attr, int) {
+  if (attr == hipDeviceAttributeMultiprocessorCount) { *v = device().cus; return hipSuccess; }
+  if (attr == hipDeviceAttributeNumberOfXccs) { *v = device().xccs; return hipSuccess; }
+  return hipErrorInvalidValue;
+}
+}  // namespace rec
+#define hipGetDevice rec::get_device
+#define hipDeviceGetAttribute rec::device_attribute
+
 #include "gemm.hip"
 #include "attn.hip"
 
@@ -76,7 +97,7 @@ void log_struct(std::ostream& os, const Epi& e) {
   for (int v : {e.M, e.N, e.ldc, e.ldr, e.res_mod, e.res_first, e.rows_per_scale, e.act, e.out_fp32}) rec::log_arg(os, v);
   rec::log_arg(os, e.thr); rec::log_arg(os, e.dscale); rec::log_arg(os, e.beta); rec::log_arg(os, e.colscale_n);
   rec::log_arg(os, e.colscale); rec::log_arg(os, e.save_dact); rec::log_arg(os, e.mul); rec::log_arg(os, e.rs_tile);
-  rec::log_arg(os, e.colsum_ws);
+  rec::log_arg(os, e.colsum_ws); rec::log_arg(os, e.gate); rec::log_arg(os, e.rows_per_gate);
   os << " }";
 }
 void log_struct(std::ostream& os, const GArgs& g) {
@@ -87,6 +108,7 @@ void log_struct(std::ostream& os, const GArgs& g) {
     rec::log_arg(os, P.A); rec::log_arg(os, P.B);
     for (int v : {P.M, P.N, P.K, P.lda, P.ldb, P.tiles_m, P.tiles_n, P.tile_end}) rec::log_arg(os, v);
     log_struct(os, P.epi);
+    rec::log_arg(os, P.kgate); rec::log_arg(os, P.k_per_gate);
     os << " ]";
   }
 }
@@ -135,6 +157,11 @@ orbit2_gemm_args gemm_args(const KV& kv) {          // pointers are fake address
 //                             colsum_ws is set when the first call returned rows)
 // group n=N lines=L [null=1]: the next L lines ("g K=V...") are the problems; orbit2_gemm_bf16_grouped(args, N)
 // afwd / abwd K=V...        : orbit2_attn_fwd_ld / orbit2_attn_bwd_ld
+// Each of them takes the path gate and the tail queue, and calls the entry climate_learn/_hip.py calls for that combination:
+//   gate=ADDR rows_per_gate=N : the _gated entry (attention: gate=ADDR alone); a "g" line: kgate=ADDR k_per_gate=N, and the group
+//                               goes to orbit2_gemm_bf16_grouped_gated when any of its lines names one (the others: NULL, 0)
+//   sched=ADDR tail=N         : the _tq entry, with the gate or NULL (tail: 0 sized by the library, > 0 that many tiles, < 0 static)
+// A key that is present selects the entry, whatever its value (sched=0: the _tq entry with a NULL counter).
 int main() {
   std::string line;
   while (std::getline(std::cin, line)) {
@@ -143,6 +170,10 @@ int main() {
     if (!(in >> cmd) || cmd[0] == '#') continue;
     const KV kv = parse(in);
     printf("> %s\n", line.c_str());
+    const bool gated = kv.count("gate") != 0, queued = kv.count("sched") != 0;
+    const float* gate = getp<const float>(kv, "gate", 0);
+    const int rows_per_gate = (int)geti(kv, "rows_per_gate", 0), tail = (int)geti(kv, "tail", 0);
+    void* sched = getp(kv, "sched", 0);
     int rc = 0;
     if (cmd == "gemm") {
       orbit2_gemm_args a = gemm_args(kv);
@@ -150,25 +181,49 @@ int main() {
       const int rows = orbit2_gemm_bf16_colsum_rows(pa);
       printf("colsum_rows=%d\n", rows);
       if (geti(kv, "want_colsum", 0) && rows > 0) a.colsum_ws = (float*)0x70000;   // as climate_learn/_hip.py:gemm does
-      rc = orbit2_gemm_bf16(pa, nullptr);
+      rc = queued ? orbit2_gemm_bf16_tq(pa, gate, gated ? rows_per_gate : 0, sched, tail, nullptr)
+           : gated ? orbit2_gemm_bf16_gated(pa, gate, rows_per_gate, nullptr) : orbit2_gemm_bf16(pa, nullptr);
     } else if (cmd == "group") {
       std::vector<orbit2_gemm_args> v(16);
+      const float* kgates[16] = {};
+      int kper[16] = {};
+      bool kgated = false;
       const int lines = (int)geti(kv, "lines", 0);
       for (int i = 0; i < lines && std::getline(std::cin, line); ++i) {
         std::istringstream gin(line);
         gin >> cmd;
-        if (i < 16) v[i] = gemm_args(parse(gin));
+        const KV gkv = parse(gin);
+        if (i >= 16) continue;
+        v[i] = gemm_args(gkv);
+        kgates[i] = getp<const float>(gkv, "kgate", 0);
+        kper[i] = (int)geti(gkv, "k_per_gate", 0);
+        kgated = kgated || gkv.count("kgate") != 0;
       }
-      rc = orbit2_gemm_bf16_grouped(geti(kv, "null", 0) ? nullptr : v.data(), (int)geti(kv, "n", 0), nullptr);
+      const orbit2_gemm_args* pv = geti(kv, "null", 0) ? nullptr : v.data();
+      const int n = (int)geti(kv, "n", 0);
+      rc = queued ? orbit2_gemm_bf16_grouped_tq(pv, n, kgated ? kgates : nullptr, kgated ? kper : nullptr, sched, tail, nullptr)
+           : kgated ? orbit2_gemm_bf16_grouped_gated(pv, n, kgates, kper, nullptr) : orbit2_gemm_bf16_grouped(pv, n, nullptr);
     } else if (cmd == "afwd") {
-      rc = orbit2_attn_fwd_ld(getp(kv, "qkv", 0x10000), getp(kv, "out", 0x20000), getp<float>(kv, "lse", 0x30000),
-                              geti(kv, "B", 1), geti(kv, "L", 1), geti(kv, "H", 1), geti(kv, "d", 64), (float)getf(kv, "drop_p", 0.0),
-                              (uint64_t)geti(kv, "seed", 0), geti(kv, "flags", 0), geti(kv, "ldq", 0), geti(kv, "ldo", 0), nullptr);
+      void *qkv = getp(kv, "qkv", 0x10000), *out = getp(kv, "out", 0x20000);
+      float* lse = getp<float>(kv, "lse", 0x30000);
+      const int B = geti(kv, "B", 1), L = geti(kv, "L", 1), H = geti(kv, "H", 1), d = geti(kv, "d", 64), flags = geti(kv, "flags", 0),
+                ldq = geti(kv, "ldq", 0), ldo = geti(kv, "ldo", 0);
+      const float p = (float)getf(kv, "drop_p", 0.0);
+      const uint64_t seed = (uint64_t)geti(kv, "seed", 0);
+      rc = queued ? orbit2_attn_fwd_tq(qkv, out, lse, B, L, H, d, p, seed, flags, ldq, ldo, gate, sched, tail, nullptr)
+           : gated ? orbit2_attn_fwd_gated(qkv, out, lse, B, L, H, d, p, seed, flags, ldq, ldo, gate, nullptr)
+                   : orbit2_attn_fwd_ld(qkv, out, lse, B, L, H, d, p, seed, flags, ldq, ldo, nullptr);
     } else if (cmd == "abwd") {
-      rc = orbit2_attn_bwd_ld(getp(kv, "qkv", 0x10000), getp(kv, "out", 0x20000), getp(kv, "dout", 0x40000),
-                              getp<float>(kv, "lse", 0x30000), getp<float>(kv, "delta", 0x50000), getp(kv, "dqkv", 0x60000),
-                              geti(kv, "B", 1), geti(kv, "L", 1), geti(kv, "H", 1), geti(kv, "d", 64), (float)getf(kv, "drop_p", 0.0),
-                              (uint64_t)geti(kv, "seed", 0), geti(kv, "flags", 0), geti(kv, "ldq", 0), geti(kv, "ldo", 0), nullptr);
+      void *qkv = getp(kv, "qkv", 0x10000), *out = getp(kv, "out", 0x20000), *dout = getp(kv, "dout", 0x40000),
+           *dqkv = getp(kv, "dqkv", 0x60000);
+      float *lse = getp<float>(kv, "lse", 0x30000), *delta = getp<float>(kv, "delta", 0x50000);
+      const int B = geti(kv, "B", 1), L = geti(kv, "L", 1), H = geti(kv, "H", 1), d = geti(kv, "d", 64), flags = geti(kv, "flags", 0),
+                ldq = geti(kv, "ldq", 0), ldo = geti(kv, "ldo", 0);
+      const float p = (float)getf(kv, "drop_p", 0.0);
+      const uint64_t seed = (uint64_t)geti(kv, "seed", 0);
+      rc = queued ? orbit2_attn_bwd_tq(qkv, out, dout, lse, delta, dqkv, B, L, H, d, p, seed, flags, ldq, ldo, gate, sched, tail, nullptr)
+           : gated ? orbit2_attn_bwd_gated(qkv, out, dout, lse, delta, dqkv, B, L, H, d, p, seed, flags, ldq, ldo, gate, nullptr)
+                   : orbit2_attn_bwd_ld(qkv, out, dout, lse, delta, dqkv, B, L, H, d, p, seed, flags, ldq, ldo, nullptr);
     } else {
       fprintf(stderr, "unknown command: %s\n", cmd.c_str());
       return 2;

@@ -1,9 +1,12 @@
 """Which kernel runs: the selection in csrc/gemm.hip and csrc/attn.hip for the product's own calls, pinned on the CPU.
 
 tests/dispatch_recorder.hip includes both sources with hipLaunchKernelGGL redefined to print the kernel instantiation, grid, block
-and launch arguments (host-only build, no GPU).  The expected lines in tests/dispatch_expected.txt were recorded from the sources of
-the commit named in that file's header, never from the code under test: a product shape that falls from the 4-wave kernel to the
-128-tile kernel, or from a generated attention kernel to a compiler-scheduled one, passes every parity test and fails here.
+and launch arguments (host-only build, no GPU).  Pinned are the entries the product calls under default settings -- the tail-queue
+entries (orbit2_*_tq) with a library-sized tail, the Block's calls with their path gate or K gate -- on the recorder's own device
+shape (256 CUs on 8 XCCs), so the lines say which twin of a kernel runs, on which grid, with which gate and which tail.  The
+expected lines in tests/dispatch_expected.txt were recorded from the sources of the commit named in that file's header, never from
+the code under test: a product shape that falls from the 4-wave kernel to the 128-tile kernel, or from a generated attention kernel
+to a compiler-scheduled one, a mis-sized tail or an ignored gate passes every parity test and fails here.
 
 Run as a script, the module is also the A/B driver for a change of the dispatch code itself:
     python tests/test_dispatch_cpu.py CSRC_DIR [LOG]      # product calls + the sweep below against CSRC_DIR; prints count, sha256
@@ -34,6 +37,10 @@ CONFIGS = {
 ATTN_Q_PRESCALED = 4
 P = dict(bias="0x1000", residual="0x2000", rowscale="0x3000", save_dact="0x4000", mul="0x5000", save_pre="0x6000",
          dgelu_pre="0x7000")      # fake addresses, 16-byte aligned; never dereferenced
+SCHED = "0x9000"                  # the counter word of a tail-queue call
+OTHER_GATE = "0x3100"             # a gate that is no call's row scale
+TQ = dict(sched=SCHED, tail=0)    # _ops._TQ: the library sizes the tail
+OTHER_DEVICE = {"ORBIT2_RECORDER_DEVICE": "304x8"}      # not the part the tail queue is sized for: auto tails stay static
 
 
 def build_recorder(csrc, out):
@@ -43,7 +50,7 @@ def build_recorder(csrc, out):
 
 
 def record(exe, lines, env=None):
-    e = {k: v for k, v in os.environ.items() if k != "ORBIT2_W4_PACE"}
+    e = {k: v for k, v in os.environ.items() if k not in ("ORBIT2_W4_PACE", "ORBIT2_RECORDER_DEVICE")}
     e.update(env or {})
     r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=e, check=True)
     return r.stdout
@@ -63,20 +70,23 @@ def group(problems, n=None, **kw):
 
 
 # ---- the product's calls (climate_learn/_ops.py: BlockFn, ChainFn under res_slimvit's head, EmbedFn) ------------------------
-def _dw_group(problems):
+def _dw_group(problems, kgate=None):
     """the grouped weight-gradient launch of _ops._DwBatch.flush for problems (N, K, M, lda, ldb) = dW[N, K] over M tokens:
-    _ops._dw_balance's slicing on shapes alone"""
+    _ops._dw_balance's slicing on shapes alone.  kgate = (address, tokens per entry): the K gate of every problem; a slice of the
+    tokens takes its own entries (fp32: 4 bytes each) when it holds whole samples"""
     from climate_learn import _ops
     S = _ops._DW_BALANCE
     M = problems[0][2]
-    full = [dict(M=n, N=k, K=m, lda=lda, ldb=ldb, ldc=k, a_kc=0, b_kc=0) for n, k, m, lda, ldb in problems]
+    kg = {} if kgate is None else dict(kgate=kgate[0], k_per_gate=kgate[1])
+    full = [dict(M=n, N=k, K=m, lda=lda, ldb=ldb, ldc=k, a_kc=0, b_kc=0, **kg) for n, k, m, lda, ldb in problems]
     ok = len(problems) >= 2 and all(p[2] == M and p[0] % 256 == 0 and p[1] % 256 == 0 for p in problems) and \
         M % (S * 64) == 0 and M // S >= 32768
     plan = _ops._dw_balance_plan([(p[0] // 256, p[1] // 256) for p in problems], S) if ok else None
     if plan is None:
-        return group(full)
+        return group(full, **TQ)
     cut = {i: (r0, r) for i, r0, r in plan}
     keep, split = [], [[] for _ in range(S)]
+    Mc = M // S
     for i, (n, k, m, lda, ldb) in enumerate(problems):
         if i not in cut:
             keep.append(full[i])
@@ -85,9 +95,12 @@ def _dw_group(problems):
         if r0 > 0:
             keep.append(dict(full[i], M=256 * r0))
         for q in range(S):
-            split[q].append(dict(M=256 * r, N=k, K=M // S, lda=lda, ldb=ldb, ldc=k, a_kc=0, b_kc=0))
+            kq = {}
+            if kgate is not None and Mc % kgate[1] == 0:
+                kq = dict(kgate=hex(int(kgate[0], 16) + 4 * q * (Mc // kgate[1])), k_per_gate=kgate[1])
+            split[q].append(dict(M=256 * r, N=k, K=Mc, lda=lda, ldb=ldb, ldc=k, a_kc=0, b_kc=0, **kq))
     probs = keep + [u for q in range(S) for u in split[q]]
-    return group(probs) if len(probs) <= 12 else group(full)
+    return group(probs if len(probs) <= 12 else full, **TQ)
 
 
 def _dw_single(N, K, M, lda, ldb):
@@ -95,11 +108,13 @@ def _dw_single(N, K, M, lda, ldb):
     from climate_learn import _ops
     if _ops._dw_split_ok(M, N, K):
         S = _ops._DW_SPLIT
-        return group([dict(M=N, N=K, K=M // S, lda=lda, ldb=ldb, ldc=K, a_kc=0, b_kc=0)] * S)
-    return [gemm(N, K, M, lda, ldb, K, a_kc=0, b_kc=0)]
+        return group([dict(M=N, N=K, K=M // S, lda=lda, ldb=ldb, ldc=K, a_kc=0, b_kc=0)] * S, **TQ)
+    return [gemm(N, K, M, lda, ldb, K, a_kc=0, b_kc=0)]                 # (the one call _ops makes without the tail queue)
 
 
 def product_calls(name, drop):
+    """what _ops passes under default settings: every call but a lone unsplit weight gradient through the tail-queue entry, and in
+    the dropout configurations (DropPath on) the Block's GEMMs and attention calls with the branch's scales as their gate"""
     from climate_learn import _ops
     D, heads, B, (h, w) = CONFIGS[name]
     L, d, hid = (h // 2) * (w // 2), D // heads, 4 * D
@@ -108,32 +123,35 @@ def product_calls(name, drop):
     ldD, ldq, ldh = _ops._ld_pad(D), _ops._ld_pad(3 * D), _ops._ld_pad(hid)
     dp = dict(drop_p=p, seed=7) if drop else {}
     path = dict(rowscale=P["rowscale"], rows_per_scale=L) if drop else {}
+    gate = dict(gate=P["rowscale"], rows_per_gate=L) if drop else {}      # _ops._gate_kw
+    agate = dict(gate=P["rowscale"]) if drop else {}
+    kgate = (P["rowscale"], L) if drop else None
     gelu = dict(act=1, save_dact=P["save_dact"], **dp)
     out = ["# %s %s dropout: embedding" % (name, "with" if drop else "without")]
-    out.append(gemm(M, D, D, D, D, D, bias=P["bias"], residual=P["residual"], ldr=D, res_mod=L, res_first=1, **dp))
+    out.append(gemm(M, D, D, D, D, D, bias=P["bias"], residual=P["residual"], ldr=D, res_mod=L, res_first=1, **dp, **TQ))
     out += _dw_single(D, D, M, D, D)
-    out.append(gemm(M, D, D, D, D, D, b_kc=0))
+    out.append(gemm(M, D, D, D, D, D, b_kc=0, **TQ))
     out.append("# Block forward: qkv, attention, proj, fc1, fc2")
-    out.append(gemm(M, 3 * D, D, ldD, D, ldq, bias=P["bias"], colscale_n=D, colscale=math.log2(math.e) / math.sqrt(d)))
-    attn = dict(B=B, L=L, H=heads, d=d, drop_p=p, seed=7, flags=ATTN_Q_PRESCALED, ldq=ldq, ldo=ldD)
+    out.append(gemm(M, 3 * D, D, ldD, D, ldq, bias=P["bias"], colscale_n=D, colscale=math.log2(math.e) / math.sqrt(d), **gate, **TQ))
+    attn = dict(B=B, L=L, H=heads, d=d, drop_p=p, seed=7, flags=ATTN_Q_PRESCALED, ldq=ldq, ldo=ldD, **agate, **TQ)
     out.append(call("afwd", **attn))
-    out.append(gemm(M, D, D, ldD, D, D, bias=P["bias"], residual=P["residual"], ldr=D, **dp, **path))
-    out.append(gemm(M, hid, D, ldD, D, ldh, bias=P["bias"], **gelu))
-    out.append(gemm(M, D, hid, ldh, hid, D, bias=P["bias"], residual=P["residual"], ldr=D, **dp, **path))
+    out.append(gemm(M, D, D, ldD, D, D, bias=P["bias"], residual=P["residual"], ldr=D, **dp, **path, **gate, **TQ))
+    out.append(gemm(M, hid, D, ldD, D, ldh, bias=P["bias"], **gelu, **gate, **TQ))
+    out.append(gemm(M, D, hid, ldh, hid, D, bias=P["bias"], residual=P["residual"], ldr=D, **dp, **path, **gate, **TQ))
     out.append("# Block backward: fc2 dx (fused column sums), fc1 dx, proj dx, attention, qkv dx, the grouped weight gradients")
-    out.append(gemm(M, hid, D, D, hid, ldh, b_kc=0, mul=P["mul"], want_colsum=1))
-    out.append(gemm(M, D, hid, ldh, D, D, b_kc=0))
-    out.append(gemm(M, D, D, D, D, D, b_kc=0))
+    out.append(gemm(M, hid, D, D, hid, ldh, b_kc=0, mul=P["mul"], want_colsum=1, **gate, **TQ))
+    out.append(gemm(M, D, hid, ldh, D, D, b_kc=0, **gate, **TQ))
+    out.append(gemm(M, D, D, D, D, D, b_kc=0, **gate, **TQ))
     out.append(call("abwd", **attn))
-    out.append(gemm(M, D, 3 * D, ldq, D, D, b_kc=0))
-    out += _dw_group([(D, hid, M, D, ldh), (hid, D, M, ldh, ldD), (D, D, M, D, ldD), (3 * D, D, M, ldq, ldD)])
+    out.append(gemm(M, D, 3 * D, ldq, D, D, b_kc=0, **gate, **TQ))
+    out += _dw_group([(D, hid, M, D, ldh), (hid, D, M, ldh, ldD), (D, D, M, D, ldD), (3 * D, D, M, ldq, ldD)], kgate)
     out.append("# head chain: 4 x (Linear + GELU), Linear to 192; backward")
-    out += [gemm(M, D, D, D, D, D, bias=P["bias"], act=1, save_dact=P["save_dact"])] * 4
-    out.append(gemm(M, 192, D, D, D, 192, bias=P["bias"]))
+    out += [gemm(M, D, D, D, D, D, bias=P["bias"], act=1, save_dact=P["save_dact"], **TQ)] * 4
+    out.append(gemm(M, 192, D, D, D, 192, bias=P["bias"], **TQ))
     out += _dw_single(192, D, M, 192, D)
-    out.append(gemm(M, D, 192, 192, D, D, b_kc=0, mul=P["mul"]))
-    out += [gemm(M, D, D, D, D, D, b_kc=0, mul=P["mul"])] * 3
-    out.append(gemm(M, D, D, D, D, D, b_kc=0))
+    out.append(gemm(M, D, 192, 192, D, D, b_kc=0, mul=P["mul"], **TQ))
+    out += [gemm(M, D, D, D, D, D, b_kc=0, mul=P["mul"], **TQ)] * 3
+    out.append(gemm(M, D, D, D, D, D, b_kc=0, **TQ))
     out += _dw_group([(D, D, M, D, D)] * 4)
     return out
 
@@ -185,6 +203,56 @@ def sweep_gemm():
     return out
 
 
+FORMS = tuple(itertools.product((1, 0), (1, 0)))
+TAILS = ({}, dict(sched=SCHED, tail=0), dict(sched=SCHED, tail=-1), dict(sched=SCHED, tail=64))
+
+
+def sweep_gemm_gate_queue():
+    """the path gate and the tail queue of the single GEMM: a reduced cross of shapes x forms x epilogues at hints 0 / 260 / 262"""
+    big, small = (131072, 12288, 3072), (3072, 4096, 1024)          # 24576 tiles of 256 x 256; 192
+    out = []
+
+    def add(shape, form, **kw):
+        (M, N, K), (akc, bkc) = shape, form
+        out.append(gemm(M, N, K, K if akc else M, K if bkc else N, N, a_kc=akc, b_kc=bkc, **kw))
+
+    # every clause of the gate rule, honoured and as a near-miss
+    G, rows = P["rowscale"], 8192
+    res = dict(bias=P["bias"], residual=P["residual"], ldr=12288, rowscale=G, rows_per_scale=rows)
+    epis = [{}, dict(bias=P["bias"]), res, dict(out_fp32=1), dict(res, out_fp32=1), dict(beta=1.0), dict(res, beta=1.0),
+            dict(res, res_first=1), dict(res, res_mod=4096), dict(res, rowscale=OTHER_GATE), dict(res, rows_per_scale=4096),
+            dict(res, save_pre=P["save_pre"]), dict(res, act=1, save_dact=P["save_dact"]), dict(res, colsum_ws="0x8000"),
+            dict(res, ldr=12292), dict(res, residual="0x2008"), dict(rowscale=G, rows_per_scale=rows),
+            dict(res, drop_p=0.1, seed=3), dict(mul=P["mul"]), dict(mul=P["mul"], colsum_ws="0x8000")]
+    for form, hint, epi, tq in itertools.product(FORMS, (0, 260, 262), epis, TAILS):
+        add(big, form, tile_hint=hint, gate=G, rows_per_gate=rows, **epi, **tq)
+    for form, tq, bad in itertools.product(((1, 1), (1, 0)), TAILS[:2], (dict(rows_per_gate=0), dict(rows_per_gate=-8),
+                                                                       dict(gate=0, rows_per_gate=rows), dict(gate=0, rows_per_gate=0))):
+        add(big, form, **dict(dict(res, gate=G), **bad), **tq)
+    # the tail of every (form, kind) pair, auto and forced (1, 64, T, T + 1 tiles), gated or not
+    k1 = dict(bias=P["bias"], act=1, save_dact=P["save_dact"])
+    k2 = dict(bias=P["bias"], residual=P["residual"], ldr=12288)
+    drop = dict(drop_p=0.1, seed=3)
+    for shape, form, hint, epi, gate in itertools.product((big, small), FORMS, (0, 260, 262),
+                                                          ({}, k1, dict(k1, **drop), k2, dict(k2, **drop), dict(mul=P["mul"])),
+                                                          ({}, dict(gate=G, rows_per_gate=rows))):
+        T = (shape[0] // 256) * (shape[1] // 256)
+        for tail in (0, -1, 1, 64, T, T + 1):
+            add(shape, form, tile_hint=hint, sched=SCHED, tail=tail, **epi, **gate)
+    # O2_TQ_MIN_STATIC_ROUNDS: a two-round family asks for its tail from 6 rounds of 256 tiles on
+    for shape, (form, epi), hint in itertools.product(((1280, 78592, 1024), (1536, 65536, 1024), (1536, 65792, 1024)),
+                                                      (((1, 0), {}), ((1, 1), k2), ((1, 1), {}), ((0, 0), {})), (0, 260)):
+        add(shape, form, tile_hint=hint, sched=SCHED, tail=0, **epi)
+    # the other families and the stamped form stay static with a counter; a counter the entry refuses
+    for shape, form, hint, tail in itertools.product((big, small, (131000, 12288, 3072)), FORMS, (0, 64, 128, 256, 261), (0, 64)):
+        add(shape, form, tile_hint=hint, sched=SCHED, tail=tail)
+    for sched, gate, hint in itertools.product((0, "0x9002", "0x9001"), ({}, dict(gate=G, rows_per_gate=rows)), (0, 128)):
+        add(big, (1, 0), tile_hint=hint, sched=sched, tail=0, **gate)
+    out.append(call("gemm", null=1, sched=SCHED, tail=0))
+    out.append(call("gemm", null=1, gate=G, rows_per_gate=rows))
+    return out
+
+
 def sweep_grouped():
     def prob(M, N, K, akc=0, bkc=0, **kw):
         return dict(M=M, N=N, K=K, lda=K if akc else M, ldb=K if bkc else N, ldc=N, a_kc=akc, b_kc=bkc, **kw)
@@ -205,6 +273,37 @@ def sweep_grouped():
     out += group([prob(256, 256 * t, 65536) for t in (100, 91)])                  # 191 tiles: under the grouped fill rule
     out += group([prob(256, 256 * t, 65536) for t in (100, 92)])                  # 192
     out += group(base, null=1)
+    # ---- the K gates and the tail queue (576 tiles; the pacing start barrier is on: K = 512 K-tiles, more than a round)
+    G = P["rowscale"]
+    ok = dict(kgate=G, k_per_gate=4096)
+    tails = ({}, dict(sched=SCHED, tail=0), dict(sched=SCHED, tail=-1), dict(sched=SCHED, tail=64))
+    for tq in tails:
+        out += group([dict(p, **ok) for p in base], **tq)
+        out += group([dict(p, kgate=G, k_per_gate=4000) for p in base], **tq)          # not whole K-tiles
+        out += group([dict(p, kgate=G, k_per_gate=5120) for p in base], **tq)          # K is not whole entries
+        out += group([dict(p, kgate=G, k_per_gate=0) for p in base], **tq)
+        out += group([dict(p, **(ok if i % 2 else {})) for i, p in enumerate(base)], **tq)      # NULL entries among the gates
+        out += group([dict(p, **(ok if i % 2 else dict(kgate=0, k_per_gate=4096))) for i, p in enumerate(base)], **tq)
+        for akc, bkc in ((1, 1), (1, 0), (0, 1)):                                      # a form other than TN
+            out += group([dict(prob(3072, 3072, 32768, akc, bkc), **ok) for _ in range(4)], **tq)
+        for hint in (128, 256):                                                        # a family other than the 4-wave one
+            out += group([dict(p, **ok, **({"tile_hint": hint} if i == 0 else {})) for i, p in enumerate(base)], **tq)
+        out += group([dict(p, **ok) for p in base[:3]] + [dict(prob(3072, 3000, 32768), **ok)], **tq)
+        out += group([dict(base[0], **ok)], **tq)                                      # n = 1: the single launch, with the counter
+        out += group([dict(prob(131072, 12288, 3072, 1, 0), **ok)], **tq)              # ... on a shape whose single launch has a tail
+        out += group(base, **tq)
+    for tail in (1, 64, 319, 320, 321, 575, 576, 577):      # 320 leaves S = 256 static workgroups (no start barrier), 319 S = 257
+        out += group(base, sched=SCHED, tail=tail)
+        out += group([dict(p, **ok) for p in base], sched=SCHED, tail=tail)
+    # O2_TQ_MIN_STATIC_ROUNDS: the four-round grouped family asks for its tail from 8 rounds of 256 tiles on
+    for last in (47, 48, 49):
+        out += group([prob(256, 256 * t, 32768) for t in (1000, 1000, last)], sched=SCHED, tail=0)
+    for sched in (0, "0x9002"):
+        out += group(base, sched=sched, tail=0)
+        out += group(base[:1], sched=sched, tail=0)
+    out += group(base, null=1, sched=SCHED, tail=0)
+    out += group(base, n=0, sched=SCHED, tail=0)
+    out += group(base, n=13, sched=SCHED, tail=0)
     return out
 
 
@@ -227,14 +326,38 @@ def sweep_attn():
     return out
 
 
+def sweep_attn_gate_queue():
+    """the gate and the tail queue of the attention entries: the generated kernels (d = 128, flags 4) against the
+    compiler-scheduled ones (other d, NO_W4, q not pre-scaled), the split dK + dV pass, launches large and small"""
+    out = []
+    G = P["rowscale"]
+    for (B, H, L), d, flags, p, cmd, gate in itertools.product(((16, 24, 8192), (2, 4, 512)), (64, 128, 256), (0, 4, 6, 12),
+                                                               (0.0, 0.1), ("afwd", "abwd"), ({}, dict(gate=G))):
+        base = dict(B=B, L=L, H=H, d=d, drop_p=p, seed=5, flags=flags, ldq=3 * H * d, ldo=H * d, **gate)
+        out.append(call(cmd, **base))
+        T = (L // 256) * H * B                  # 256-row workgroups of the forward and of dQ; dK + dV has twice as many
+        for tail in (0, -1, 1, 64, T, T + 1, 2 * T, 2 * T + 1):
+            out.append(call(cmd, sched=SCHED, tail=tail, **base))
+    for cmd, flags, tail, gate in itertools.product(("afwd", "abwd"), (4, 6), (0, 64), ({}, dict(gate=G))):
+        for B in (10923, 10922):                # B * H * L >= 2^32: dQ stays on the generated kernel, dK + dV leaves it
+            out.append(call(cmd, B=B, L=16384, H=24, d=128, flags=flags, ldq=9216, ldo=3072, sched=SCHED, tail=tail, **gate))
+    for cmd, sched in itertools.product(("afwd", "abwd"), (0, "0x9002")):
+        out.append(call(cmd, B=2, L=512, H=4, d=128, flags=4, ldq=1536, ldo=512, sched=sched, tail=0))
+        out.append(call(cmd, B=2, L=512, H=4, d=64, flags=0, ldq=768, ldo=256, sched=sched, tail=0, gate=G))
+    return out
+
+
 def sweep_log(exe):
-    """(number of calls, the whole log): the product's calls and the three sweeps; the grouped sweep once per ORBIT2_W4_PACE setting
-    (the library reads it once per process)"""
-    fixed = all_product_calls() + sweep_gemm() + sweep_attn()
+    """(number of calls, the whole log): the product's calls and the sweeps; the grouped sweep once per ORBIT2_W4_PACE setting
+    (the library reads it once per process), the gate / tail-queue sweeps also on a device the tail queue is not sized for"""
+    queue = sweep_gemm_gate_queue() + sweep_attn_gate_queue()
+    fixed = all_product_calls() + sweep_gemm() + sweep_attn() + queue
     grouped = sweep_grouped() + [ln for name in CONFIGS for ln in product_calls(name, True) if ln.startswith(("group", "g "))]
     log = record(exe, fixed)
     for pace in (None, "0", "2"):
         log += "== ORBIT2_W4_PACE %s\n" % pace + record(exe, grouped, {} if pace is None else {"ORBIT2_W4_PACE": pace})
+    log += "== ORBIT2_RECORDER_DEVICE %s\n" % OTHER_DEVICE["ORBIT2_RECORDER_DEVICE"]
+    log += record(exe, all_product_calls() + queue + grouped, OTHER_DEVICE)
     return log.count("\nrc=") + log.startswith("rc="), log
 
 
@@ -246,6 +369,118 @@ def test_product_calls_select_the_pinned_kernels(tmp_path):
     want = [ln for ln in open(EXPECTED).read().splitlines() if not ln.startswith("#")]
     assert len(want) > 300                                   # 8 runs of ~30 calls, two or more lines each
     assert got == want, "\n".join(itertools.islice(difflib.unified_diff(want, got, "pinned", "this tree", lineterm="", n=2), 80))
+
+
+# ---- the gate and the queue do not move the selection ---------------------------------------------------
+OWN = ("gate", "rows_per_gate", "sched", "tail", "kgate", "k_per_gate")     # the keys of the gate and the queue
+
+
+def _blocks(lines):
+    """the calls of a list of lines, each with its "g" lines and without the gate / queue keys and the comments"""
+    out = []
+    for ln in lines:
+        if ln.startswith("#"):
+            continue
+        ln = " ".join(t for t in ln.split() if t.split("=")[0] not in OWN)
+        if ln.startswith("g "):
+            out[-1].append(ln)
+        else:
+            out.append([ln])
+    return out
+
+
+def _with(block, head=None, member=None):
+    return [block[0] + (" " + head if head else "")] + [g + (" " + member if member else "") for g in block[1:]]
+
+
+def _parse(log):
+    """per call: (return code, [(kernel name, grid, block, the rest of the launch line)])"""
+    out = []
+    for rec in ("\n" + log).split("\n> ")[1:]:
+        lines = rec.splitlines()
+        launches = [ln.split(" ", 3) for ln in lines[1:] if " grid=" in ln]
+        out.append((lines[-1], [(k, g, b, rest) for k, g, b, rest in launches]))
+    return out
+
+
+def _untwinned(kernel):
+    """the name of the plain kernel a gated or tail-queue twin stands for"""
+    name, args = kernel.rstrip(">").split("<") if "<" in kernel else (kernel, "")
+    a = [x.strip() for x in args.split(",")]
+    if name == "gemm256w_tq_kernel":
+        return "gemm256w_kernel<%s, false, %s>" % (a[0], a[1])
+    if name == "gemm256w_grouped_tq_kernel":
+        return "gemm256w_grouped_kernel<%s>" % a[0]
+    for twin in ("_w4_gated_kernel", "_w4_tq_kernel"):
+        if name.endswith(twin):
+            return "%s_w4_kernel<%s>" % (name[:-len(twin)], a[0])
+    return kernel
+
+
+def no_move_inputs():
+    """every product call, and sweep lines that reach the four GEMM families (single and grouped) and both attention classes"""
+    shapes = ((131072, 12288, 3072), (3072, 4096, 1024), (131000, 12288, 3072), (768, 512, 192))
+    k2 = dict(bias=P["bias"], residual=P["residual"], ldr=12288, rowscale=P["rowscale"], rows_per_scale=8192)
+    lines = all_product_calls()
+    for (M, N, K), (akc, bkc), epi in itertools.product(shapes, ((1, 1), (1, 0), (0, 0)), ({}, k2)):
+        lines.append(gemm(M, N, K, K if akc else M, K if bkc else N, N, a_kc=akc, b_kc=bkc, **epi))
+    lines.append(gemm(768, 512, 192, 192, 192, 512, tile_hint=128))
+    for hint, K in itertools.product((0, 128, 256), (32768, 32704)):
+        lines += group([dict(M=3072, N=3072, K=K, lda=3072, ldb=3072, ldc=3072, a_kc=0, b_kc=0,
+                             **({"tile_hint": hint} if i == 0 else {})) for i in range(4)])
+    for d, flags, p, cmd in itertools.product((64, 128, 256), (4, 6, 12), (0.0, 0.1), ("afwd", "abwd")):
+        lines.append(call(cmd, B=16, L=8192, H=24, d=d, drop_p=p, seed=5, flags=flags, ldq=3 * 24 * d, ldo=24 * d))
+    return _blocks(lines)
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+def test_the_gate_and_the_queue_do_not_move_the_selection(tmp_path):
+    """Each call plain, gated, queued with tail < 0 and queued with an auto tail on a device the queue is not sized for: the same
+    return code, grid and block, the same kernel up to its documented twin (gemm256w_kernel<F, false, E> / gemm256w_tq_kernel<F, E>,
+    ..._w4_kernel<D> / ..._w4_gated_kernel<D> / ..._w4_tq_kernel<D, G>); a queued call whose plan has no tail launches exactly what
+    the unqueued call launches; so does a gated call whose gate the rule of DESIGN 4.11 ignores (a residual behind a row scale
+    that is not the gate).  A grouped launch whose tail leaves no more than one round of static workgroups has no start barrier."""
+    exe = build_recorder(CSRC, str(tmp_path / "dispatch_recorder"))
+    blocks = no_move_inputs()
+    kv = lambda ln: dict(t.split("=") for t in ln.split()[1:])
+
+    def gated(b):
+        if b[0].startswith("a"):
+            return _with(b, "gate=" + OTHER_GATE)
+        if b[0].startswith("gemm"):
+            return _with(b, "gate=%s rows_per_gate=%s" % (OTHER_GATE, kv(b[0]).get("rows_per_scale", 256)))
+        return _with(b, member="kgate=%s k_per_gate=64" % OTHER_GATE)
+
+    flat = lambda bs: [ln for b in bs for ln in b]
+    plain = _parse(record(exe, flat(blocks)))
+    gate = _parse(record(exe, flat(gated(b) for b in blocks)))
+    static = _parse(record(exe, flat(_with(b, "sched=%s tail=-1" % SCHED) for b in blocks)))
+    other = _parse(record(exe, flat(_with(b, "sched=%s tail=0" % SCHED) for b in blocks), OTHER_DEVICE))
+    assert len(plain) == len(gate) == len(static) == len(other) == len(blocks) > 150
+    kernels = set()
+    for b, p, g, s, o in zip(blocks, plain, gate, static, other):
+        assert s == p and o == p, b                              # no tail: the unqueued launch, argument by argument
+        assert g[0] == p[0] and [(_untwinned(k), gr, bl) for k, gr, bl, _ in g[1]] == [(k, gr, bl) for k, gr, bl, _ in p[1]], b
+        a = kv(b[0])
+        if b[0].startswith("gemm") and "residual" in a and "rowscale" in a:
+            assert g == p, b                                     # the row scale is not the gate: the gate is ignored
+        kernels.update(k.split("<")[0] for k, _, _, _ in p[1])
+    assert {"gemm128_kernel", "gemm256t_kernel", "gemm256w_kernel", "gemm128_grouped_kernel", "gemm256t_grouped_kernel",
+            "gemm256w_grouped_kernel", "attn_fwd_w4_kernel", "attn_bwd_dq_w4_kernel", "attn_bwd_dkv_w4_kernel", "attn_fwd_kernel",
+            "attn_fwd_lazy_kernel", "attn_bwd_dq_kernel", "attn_bwd_dkv_kernel"} <= kernels
+    assert any(_untwinned(k) != k for _, ls in gate for k, _, _, _ in ls)      # some gated twin did run
+    # grouped launches with a forced tail: T + tail workgroups of the twin; the start barrier only with more than a round static
+    groups = [(b, p) for b, p in zip(blocks, plain) if b[0].startswith("group") and p[1] and
+              p[1][0][0].startswith("gemm256w_grouped_kernel") and int(p[1][0][1].split("=")[1]) > 257]
+    assert any(" pace=1 " in p[1][0][3] for _, p in groups)
+    for static_wgs in (256, 257):
+        tails = [int(p[1][0][1].split("=")[1]) - static_wgs for _, p in groups]
+        queued = _parse(record(exe, flat(_with(b, "sched=%s tail=%d" % (SCHED, t)) for (b, _), t in zip(groups, tails))))
+        for (b, p), t, q in zip(groups, tails, queued):
+            (k, gr, bl, rest), (pk, pgr, pbl, prest) = q[1][0], p[1][0]
+            assert q[0] == p[0] and _untwinned(k) == pk and k != pk and bl == pbl and gr == "grid=%d" % (static_wgs + 2 * t), b
+            want = prest.replace(" pace=1 ", " pace=0 ").replace(" pace=2 ", " pace=0 ") if static_wgs == 256 else prest
+            assert rest == "%s 0x%x %d %d" % (want, int(SCHED, 16), static_wgs, t), b
 
 
 if __name__ == "__main__":
