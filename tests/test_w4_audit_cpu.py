@@ -24,8 +24,10 @@ def test_compiler_keeps_out_of_the_named_registers():
     import audit_w4_asm
     found, bad = audit_w4_asm.audit()
     assert found >= 8 and not bad, bad
-    found, bad = audit_w4_asm.audit_attention()          # the generated attention kernels: one statement = the whole kernel
-    assert found == 6 and not bad, bad
+    # the generated attention kernels, gated and tail-queue twins included: one statement = the whole body; in the 12 without
+    # the gate check it also ends the kernel
+    found, ends, bad = audit_w4_asm.audit_attention()
+    assert found == 24 and ends == 12 and not bad, bad
 
 
 def test_generated_attention_streams_are_current(tmp_path):

@@ -5,8 +5,10 @@ across three statements, so OUTSIDE the statements (1) no compiler-generated v_a
 register operand at all -- on gfx950 loads, stores and LDS instructions take a[...] operands without any v_accvgpr_* -- (the fragment
 registers v128..v255 are dead behind the main loop: the compiler may use them between the statements), (3) no scratch,
 (4) 256 + 256 registers in the descriptor.
-Generated attention kernels (csrc/attn.hip, attn_fwd_w4_kernel / attn_bwd_dq_w4_kernel / attn_bwd_dkv_w4_kernel): the whole body is ONE statement that
-ends the kernel: no scratch, 256 + 256 registers, nothing but s_endpgm behind the statement.
+Generated attention kernels (csrc/attn.hip, attn_fwd_w4 / attn_bwd_dq_w4 / attn_bwd_dkv_w4: the plain kernels, their _gated twins and
+their tail-queue (_tq) twins, 24 instantiations): the whole body is ONE statement: no scratch, 256 + 256 registers.  In the 12 compiled
+without the gate check (the plain kernels and the _tq twins at GATED = false) the statement ends the kernel: nothing but s_endpgm
+behind it; the other 12 have the gate's zero-fill block laid out there.
 Compiles the sources to gfx950 assembly.  Exit code 0 = clean."""
 import os, re, subprocess, sys, tempfile
 
@@ -53,18 +55,20 @@ def audit(hipcc="/opt/rocm/bin/hipcc"):
 
 def audit_attention(hipcc="/opt/rocm/bin/hipcc"):
     t = _asm_of("attn.hip", hipcc)
-    found, bad = 0, []
-    for m in re.finditer(r"^(_ZN12_GLOBAL__N_1\d+attn_(?:fwd|bwd_dq|bwd_dkv)_w4_kernel\w+):", t, re.M):
+    found, ends, bad = 0, 0, []            # ends: the kernels held to the trailing-code rule
+    for m in re.finditer(r"^(_ZN12_GLOBAL__N_1\d+attn_(?:fwd|bwd_dq|bwd_dkv)_w4(_gated|_tq|)_kernelILb[01]E(?:Lb([01])E)?E\w+):", t, re.M):
         name, i = m.group(1), m.start()
+        gate_check = m.group(2) == "_gated" or (m.group(2) == "_tq" and m.group(3) == "1")
         j = t.index(".Lfunc_end", i)
         fn = t[i:j]
         after = fn[fn.rfind(";;#ASMEND"):].split("\n")[1:]
         trailing = [l.strip() for l in after if l.startswith("\t") and not l.strip().startswith((".", ";"))]
         scratch, agpr, vgpr = _resources(t[j:j + 8000])
         found += 1
-        if trailing != ["s_endpgm"] or fn.count(";;#ASMSTART") != 1 or scratch or agpr != 256 or vgpr != 256:
+        ends += not gate_check
+        if (not gate_check and trailing != ["s_endpgm"]) or fn.count(";;#ASMSTART") != 1 or scratch or agpr != 256 or vgpr != 256:
             bad.append((name, trailing[:3], fn.count(";;#ASMSTART"), scratch, agpr, vgpr))
-    return found, bad
+    return found, ends, bad
 
 
 if __name__ == "__main__":
@@ -72,8 +76,8 @@ if __name__ == "__main__":
     print("%d gemm256w kernels audited" % found)
     for b in bad:
         print("VIOLATION %s: compiler accvgpr %d, accumulator operands outside the statements %d, scratch %d B, agprs %d, vgprs %d" % b)
-    fa, ba = audit_attention()
-    print("%d generated attention kernels audited" % fa)
+    fa, ea, ba = audit_attention()
+    print("%d generated attention kernels audited, %d of them for code behind the statement" % (fa, ea))
     for b in ba:
         print("VIOLATION %s: code behind the statement %s, statements %d, scratch %d B, agprs %d, vgprs %d" % b)
-    sys.exit(1 if bad or ba or not found or fa != 6 else 0)
+    sys.exit(1 if bad or ba or not found or fa != 24 or ea != 12 else 0)

@@ -26,8 +26,9 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import gen_attn_fwd as F  # noqa: E402
-from gen_attn_fwd import A, S, V  # noqa: E402
+import w4asm  # noqa: E402
+from w4asm import A, S, V, insert_lgkm_waits, place  # noqa: E402
+from w4asm import mfma32 as mfma  # noqa: E402
 
 DK, DV, KF, VF, QROW, DOROW = 0, 64, 128, 160, 192, 224
 S_ = [32, 64]
@@ -46,10 +47,6 @@ S_X, S_Y2, S_LDS, S_H2, S_OFS, S_RB, S_DL, S_DN, S_OP = 62, 63, 64, 65, 66, 67, 
 
 STAT_OFF = 131072
 LDS_BYTES = STAT_OFF + 4096
-
-
-def mfma(d, a, b, c):
-    return "v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (d, a, b, c)
 
 
 def acc_mfmas(par):
@@ -145,18 +142,14 @@ def stream_gaps(par, drop, g0=4):
     return gaps
 
 
-def dma_piece(which, j, slot):
+def piece(which, j, slot):
     sof, desc, base, pc, vde, vdo = (S_OFQ, S_DQ, 0, S_PCQ, VDEQ, VDOQ) if which == "Q" else (S_OFD, S_DD, 65536, S_PCD, VDED, VDOD)
-    return ["s_add_u32 %s, %s, %s" % (S(S_TMP), S(sof), S(pc + j)),
-            "s_add_u32 m0, %s, %d" % (S(S_LW), base + slot * 16384 + j * 1024),
-            "s_nop 0",
-            "buffer_load_dwordx4 %s, %s, %s offen lds" % (V(vdo if j >= 2 else vde), S(desc, 4), S(S_TMP))]
+    return w4asm.dma_piece(desc, sof, pc + j, S_LW, base + slot * 16384 + j * 1024, S_TMP, vdo if j >= 2 else vde)
 
 
 def tile_offsets(dt):
-    return ["s_add_u32 %s, %s, %d" % (S(S_X), S(S_T), dt), "s_min_u32 %s, %s, %s" % (S(S_X), S(S_X), S(S_NT1)),
-            "s_mul_i32 %s, %s, %s" % (S(S_OFQ), S(S_X), S(S_TBQ)), "s_mul_i32 %s, %s, %s" % (S(S_OFD), S(S_X), S(S_TBD)),
-            "s_lshl_b32 %s, %s, 8" % (S(S_OFS), S(S_X)), "s_lshl_b32 %s, %s, 6" % (S(S_RB), S(S_X))]
+    return w4asm.tile_offset(S_X, S_T, dt, S_NT1, [(S_OFQ, S_TBQ), (S_OFD, S_TBD)]) + \
+           ["s_lshl_b32 %s, %s, 8" % (S(S_OFS), S(S_X)), "s_lshl_b32 %s, %s, 6" % (S(S_RB), S(S_X))]
 
 
 def stats_stage(slot, label, drop):
@@ -185,25 +178,12 @@ def stats_stage(slot, label, drop):
     return out
 
 
-def place(mf, gaps, fixed):
-    out = []
-    for m, ins in enumerate(mf):
-        out.append(ins)
-        out += fixed.get(m, [])
-        if m < len(gaps):
-            out += gaps[m]
-    return out
-
-
 def phase(u, drop, cfg):
     """phase of unit u (0..7 within the unrolled body of 4 tiles): slot = u >> 1, half = u & 1"""
     slot, half, par = (u >> 1) & 3, u & 1, u & 1
     mf = acc_mfmas(par) + sdp_mfmas(par)               # unit u - 2 has u's parity
-    fixed = {}
-
-    def add(g, ins):
-        fixed.setdefault(g, []).extend(ins if isinstance(ins, list) else [ins])
-
+    fixed = w4asm.Fixed()
+    add = fixed.add
     # stream: unit u - 1 (other parity); its tile slot / half
     su = (u - 1) % 8
     s_slot, s_half = (su >> 1) & 3, su & 1
@@ -220,7 +200,7 @@ def phase(u, drop, cfg):
         g = 4
         for w_ in ("Q", "D"):
             for j in range(4):
-                add(g, dma_piece(w_, j, (slot + 2) & 3))
+                add(g, piece(w_, j, (slot + 2) & 3))
                 g += cfg["dstride"]
         add(g, stats_stage((slot + 2) & 3, "u%d" % u, drop))
     # re-fills: Q^T / dO^T of unit u - 1 behind the dV / dK MFMAs (slots 0..15), Q / dO rows of unit u + 1 behind the chains
@@ -237,48 +217,13 @@ def phase(u, drop, cfg):
 
 
 def lane_addresses(e, L):
-    """prologue part shared in spirit with gen_attn_fwd.prologue: lane-constant LDS and DMA addresses"""
-    e("v_mbcnt_lo_u32_b32 %s, -1, 0" % V(VLANE))
-    e("v_mbcnt_hi_u32_b32 %s, -1, %s" % (V(VLANE), V(VLANE)))
+    """lane-constant LDS and DMA addresses (w4asm: r = lane & 31 stays in T0, h = lane >> 5 in T1); the dO image is 64 KiB up"""
+    L += w4asm.lane_id(VLANE)
     e("s_mov_b32 %s, %%[ldsb]" % S(S_LDS))
-    e("v_and_b32 %s, 31, %s" % (V(T0), V(VLANE)))
-    e("v_lshrrev_b32 %s, 5, %s" % (V(T1), V(VLANE)))
-    e("v_lshrrev_b32 %s, 3, %s" % (V(T2), V(T0)))
-    e("v_lshlrev_b32 %s, 11, %s" % (V(VRE), V(T2)))
-    e("v_and_b32 %s, 7, %s" % (V(T2), V(T0)))
-    e("v_lshl_add_u32 %s, %s, 6, %s" % (V(VRE), V(T2), V(VRE)))
-    e("v_bfe_u32 %s, %s, 2, 2" % (V(T2), V(T0)))
-    e("v_xor_b32 %s, %s, %s" % (V(T2), V(T2), V(T1)))
-    e("v_lshl_add_u32 %s, %s, 4, %s" % (V(VRE), V(T2), V(VRE)))
-    e("v_add_u32 %s, %s, %s" % (V(VRE), S(S_LDS), V(VRE)))
-    e("v_xor_b32 %s, 32, %s" % (V(VRO), V(VRE)))
-    e("v_add_u32 %s, 0x10000, %s" % (V(VRE2), V(VRE)))
-    e("v_add_u32 %s, 0x10000, %s" % (V(VRO2), V(VRO)))
-    e("v_bfe_u32 %s, %s, 2, 2" % (V(T2), V(VLANE)))
-    e("v_lshl_add_u32 %s, %s, 2, %s" % (V(T2), V(T1), V(T2)))
-    e("v_lshlrev_b32 %s, 6, %s" % (V(VT1), V(T2)))
-    e("v_bfe_u32 %s, %s, 4, 1" % (V(T2), V(VLANE)))
-    e("v_bfe_u32 %s, %s, 1, 1" % (V(T3), V(VLANE)))
-    e("v_lshl_add_u32 %s, %s, 1, %s" % (V(T2), V(T2), V(T3)))
-    e("v_xor_b32 %s, %s, %s" % (V(T2), V(T2), V(T1)))
-    e("v_lshl_add_u32 %s, %s, 4, %s" % (V(VT1), V(T2), V(VT1)))
-    e("v_and_b32 %s, 1, %s" % (V(T2), V(VLANE)))
-    e("v_lshl_add_u32 %s, %s, 3, %s" % (V(VT1), V(T2), V(VT1)))
-    e("v_add_u32 %s, %s, %s" % (V(VT1), S(S_LDS), V(VT1)))
-    e("v_xor_b32 %s, 32, %s" % (V(VT2), V(VT1)))
-    e("v_add_u32 %s, 0x800, %s" % (V(VT2), V(VT2)))
-    e("v_add_u32 %s, 0x10000, %s" % (V(VT1B), V(VT1)))
-    e("v_add_u32 %s, 0x10000, %s" % (V(VT2B), V(VT2)))
-    # DMA source offsets: ((lane >> 2) & 7) * pitch + 16 (4 (lane >> 5) + ((lane & 3) ^ ((lane >> 4) & 1))), odd pieces ^ 32
+    L += w4asm.row_read_base(VLANE, S_LDS, T0, T1, T2, VRE, VRO, second=(VRE2, VRO2))
+    L += w4asm.tr_read_base(VLANE, S_LDS, T1, T2, T3, VT1, VT2, second=(VT1B, VT2B))
     for pitch, vde, vdo in (("%[strideb]", VDEQ, VDOQ), ("%[dorowb]", VDED, VDOD)):
-        e("v_bfe_u32 %s, %s, 2, 3" % (V(T2), V(VLANE)))
-        e("v_mul_lo_u32 %s, %s, %s" % (V(vde), V(T2), pitch))
-        e("v_bfe_u32 %s, %s, 4, 1" % (V(T2), V(VLANE)))
-        e("v_and_b32 %s, 3, %s" % (V(T3), V(VLANE)))
-        e("v_xor_b32 %s, %s, %s" % (V(T2), V(T2), V(T3)))
-        e("v_lshl_add_u32 %s, %s, 2, %s" % (V(T2), V(T1), V(T2)))
-        e("v_lshl_add_u32 %s, %s, 4, %s" % (V(vde), V(T2), V(vde)))
-        e("v_xor_b32 %s, 32, %s" % (V(vdo), V(vde)))
+        L += w4asm.dma_source_offsets(VLANE, T1, T2, T3, vde, vdo, pitch)
     # statistics: 16-byte rows at + 16 h; the quad's row hash at + 4 (4 h + (lane & 3))
     e("v_lshlrev_b32 %s, 4, %s" % (V(VST), V(T1)))
     e("v_add_u32 %s, 0x%x, %s" % (V(VST), STAT_OFF, V(VST)))
@@ -307,39 +252,26 @@ def prologue(drop):
     e("s_mov_b32 %s, 0x7FEB352D" % S(S_Y2))
     e("s_mov_b32 %s, 0x846CA68B" % S(S_H2))
     for desc, ptr in ((S_DQ, "%[qptr]"), (S_DD, "%[doptr]"), (S_DL, "%[lseptr]"), (S_DN, "%[dltptr]")):
-        e("s_mov_b64 %s, %s" % (S(desc, 2), ptr))
-        e("s_mov_b32 %s, 0x7fffffff" % S(desc + 2))
-        e("s_mov_b32 %s, 0x00020000" % S(desc + 3))
+        L += w4asm.descriptor(desc, ptr)
     e("s_lshl_b32 %s, %%[strideb], 6" % S(S_TBQ))
     e("s_lshl_b32 %s, %%[dorowb], 6" % S(S_TBD))
     e("s_sub_u32 %s, %%[nt], 1" % S(S_NT1))
     for pc, pitch in ((S_PCQ, "%[strideb]"), (S_PCD, "%[dorowb]")):
-        e("s_lshl_b32 %s, %%[wave], 4" % S(S_X))
-        e("s_mul_i32 %s, %s, %s" % (S(pc), S(S_X), pitch))
-        e("s_add_u32 %s, %s, 128" % (S(pc + 1), S(pc)))
-        e("s_lshl_b32 %s, %s, 3" % (S(S_X), pitch))
-        e("s_add_u32 %s, %s, %s" % (S(pc + 2), S(pc), S(S_X)))
-        e("s_add_u32 %s, %s, 128" % (S(pc + 3), S(pc + 2)))
-    e("s_lshl_b32 %s, %%[wave], 12" % S(S_X))
-    e("s_add_u32 %s, %s, %s" % (S(S_LW), S(S_LDS), S(S_X)))
+        L += w4asm.piece_offsets(pc, S_X, pitch)
+    L += w4asm.wave_lds_base(S_LW, S_LDS, S_X)
     # tiles 0, 1 -> slots 0, 1 (+ tile 0 once more into slot 3: the stand-in for "tile -1" of the first re-fills)
     for tile, slot in ((0, 0), (1, 1), (0, 3)):
         e("s_mov_b32 %s, %d" % (S(S_T), tile))
         L.extend(tile_offsets(0))
         for w_ in ("Q", "D"):
             for j in range(4):
-                L.extend(dma_piece(w_, j, slot))
+                L.extend(piece(w_, j, slot))
         L.extend(stats_stage(slot, "p%d" % slot, drop))
     # the wave's K / V rows as MFMA B operands (key on the lane): lane (key r, h) holds elements 16 ds + 8 h .. + 7
     e("v_and_b32 %s, 31, %s" % (V(T0), V(VLANE)))
     e("v_lshrrev_b32 %s, 5, %s" % (V(T1), V(VLANE)))
-    e("v_lshlrev_b32 %s, 4, %s" % (V(T2), V(T1)))
-    e("v_mul_lo_u32 %s, %s, %%[strideb]" % (V(T3), V(T0)))
-    e("v_add_u32 %s, %s, %s" % (V(T3), V(T3), V(T2)))
-    for ds in range(8):
-        e("global_load_dwordx4 %s, %s, %%[kptr] offset:%d" % (A(KF + 4 * ds, 4), V(T3), ds * 32))
-    for ds in range(8):
-        e("global_load_dwordx4 %s, %s, %%[vptr] offset:%d" % (A(VF + 4 * ds, 4), V(T3), ds * 32))
+    L += w4asm.frag_offset(T3, T0, T1, T2, "%[strideb]")
+    L += w4asm.frag_loads(KF, T3, "%[kptr]") + w4asm.frag_loads(VF, T3, "%[vptr]")
     for r in range(128):
         e("v_accvgpr_write_b32 %s, 0" % A(r))
     for par in range(2):
@@ -433,66 +365,33 @@ def gen(drop, cfg=None):
     body = []
     for u in range(8):
         body += phase(u, drop, cfg)
-    _, carry = F.insert_lgkm_waits(body, ())
-    body, pend = F.insert_lgkm_waits(body, carry)
+    _, carry = insert_lgkm_waits(body, ())
+    body, pend = insert_lgkm_waits(body, carry)
     assert pend == carry, "the LDS reads outstanding at the end of the loop body differ from those at its entry"
     L += body
     L += ["s_cmp_lt_u32 %s, %%[nt]" % S(S_T), "s_cbranch_scc1 o2kv_loop_%="]
     # tail (units 2 nt - 2 in set 0 ... wait for its packs; 2 nt - 1 in set 1): phase 2 nt = dV / dK of unit 2 nt - 2 with the
     # stream of unit 2 nt - 1 in its gaps and that unit's transposed fragments re-filled; then dV / dK of unit 2 nt - 1
-    fixed = {}
+    fixed = w4asm.Fixed()
     for j in range(8):
         tr = tr_reads(j, 3, 1)
-        fixed.setdefault(2 * j + 1, []).extend(tr[:2])
-        fixed.setdefault(min(15, 2 * j + 2), []).extend(tr[2:])
+        fixed.add(2 * j + 1, tr[:2])
+        fixed.add(min(15, 2 * j + 2), tr[2:])
     g = stream_gaps(1, drop)
     t0 = place(acc_mfmas(0), g[:16], fixed)
     t0 += [x for gg in g[16:] for x in gg + ["s_nop 0"]] + ["s_nop 3"]      # (no MFMA between these gaps: keep exp2 results one slot apart)
     t0 += acc_mfmas(1)
-    t0, pend = F.insert_lgkm_waits(t0, carry)
+    t0, pend = insert_lgkm_waits(t0, carry)
     assert not pend
     L += t0
     L += epilogue()
     return L
 
 
-def emit(path):
-    out = ["// GENERATED by tools/gen_attn_dkv.py -- do not edit; the schedule lives in that script.", "#pragma once",
-           "#define O2_KV_STAT_OFF %d" % STAT_OFF, "#define O2_KV_LDS_BYTES %d" % LDS_BYTES]
-
-    def macro(name, lines):
-        out.append("#define %s \\" % name)
-        for k, s in enumerate(lines):
-            if s.endswith(":"):
-                out.append('  "%s\\n"%s' % (s, " \\" if k + 1 < len(lines) else ""))
-            else:
-                out.append('  "%s\\n\\t"%s' % (s, " \\" if k + 1 < len(lines) else ""))
-
-    macro("O2_KV_ASM_DROP", gen(True))
-    macro("O2_KV_ASM_NODROP", gen(False))
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"a%d"' % r for r in range(256)] + ['"v%d"' % r for r in range(8, 256)] + \
-           ['"s%d"' % r for r in range(36, 78)]
-    out.append("#define O2_KV_CLOBBERS \\")
-    for k in range(0, len(clob), 16):
-        chunk = ", ".join(clob[k:k + 16])
-        out.append("  %s%s" % (chunk, ", \\" if k + 16 < len(clob) else ""))
-    open(path, "w").write("\n".join(out) + "\n")
+def header():
+    return dict(prefix="O2_KV", defines=["#define O2_KV_STAT_OFF %d" % STAT_OFF, "#define O2_KV_LDS_BYTES %d" % LDS_BYTES],
+                macros=[("O2_KV_ASM_DROP", gen(True)), ("O2_KV_ASM_NODROP", gen(False))], vregs=8, sregs=(36, 78))
 
 
 if __name__ == "__main__":
-    if "--cfg" in sys.argv:
-        for kv in sys.argv[sys.argv.index("--cfg") + 1].split(","):
-            k, v = kv.split("=")
-            BASE[k] = int(v)
-    if len(sys.argv) > 1 and sys.argv[1] == "show":
-        lines = gen("nodrop" not in sys.argv)
-        slot = -1
-        for l in lines:
-            if l.startswith("v_mfma"):
-                slot += 1
-            print(slot, l)
-    else:
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(root, "orbit-2_amd", "csrc", "attn_dkv_asm.h")
-        emit(out)
-        print("wrote %s" % out, BASE)
+    w4asm.main(sys.modules[__name__], "attn_dkv_asm.h")

@@ -23,8 +23,9 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import gen_attn_fwd as F  # noqa: E402
-from gen_attn_fwd import A, S, V  # noqa: E402
+import w4asm  # noqa: E402
+from w4asm import A, S, V, insert_lgkm_waits, place  # noqa: E402
+from w4asm import mfma32 as mfma  # noqa: E402
 
 DQ = {"X": 0, "Y": 64}
 Q_ = {"X": 128, "Y": 160}
@@ -44,10 +45,6 @@ S_DK, S_DV, S_PC, S_LW, S_T, S_TB, S_NT1, S_OFK, S_OFV, S_TMP, S_M0, S_MIX = 36,
 S_QP, S_OP, S_X, S_Y2, S_EX, S_LDS, S_DP2 = 60, 62, 64, 65, 66, 68, 70
 
 KH_OFF = 131072           # 4 K slots + 4 V slots of 16 KiB
-
-
-def mfma(d, a, b, c):
-    return "v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (d, a, b, c)
 
 
 def unit_mfmas(blk):
@@ -86,22 +83,13 @@ def kt_reads(i, slot, kb):
             "ds_read_b64_tr_b16 %s, %s offset:%d" % (V(KT + 4 * i + 2, 2), V(VT2), off)]
 
 
-def kh_reads(par):
-    return ["ds_read_b128 %s, %s" % (V(KH[par], 4), V(VKH)), "ds_read_b128 %s, %s offset:16" % (V(KH[par] + 4, 4), V(VKH)),
-            "v_add_u32 %s, 64, %s" % (V(VKH), V(VKH))]
-
-
-def dma_piece(which, j, slot):
+def piece(which, j, slot):
     sof, desc, base = (S_OFK, S_DK, 0) if which == "K" else (S_OFV, S_DV, 65536)
-    return ["s_add_u32 %s, %s, %s" % (S(S_TMP), S(sof), S(S_PC + j)),
-            "s_add_u32 m0, %s, %d" % (S(S_LW), base + slot * 16384 + j * 1024),
-            "s_nop 0",
-            "buffer_load_dwordx4 %s, %s, %s offen lds" % (V(VDO if j >= 2 else VDE), S(desc, 4), S(S_TMP))]
+    return w4asm.dma_piece(desc, sof, S_PC + j, S_LW, base + slot * 16384 + j * 1024, S_TMP, VDO if j >= 2 else VDE)
 
 
 def tile_offset(dt):
-    return ["s_add_u32 %s, %s, %d" % (S(S_X), S(S_T), dt), "s_min_u32 %s, %s, %s" % (S(S_X), S(S_X), S(S_NT1)),
-            "s_mul_i32 %s, %s, %s" % (S(S_OFK), S(S_X), S(S_TB)), "s_mov_b32 %s, %s" % (S(S_OFV), S(S_OFK))]
+    return w4asm.tile_offset(S_X, S_T, dt, S_NT1, [(S_OFK, S_TB)]) + ["s_mov_b32 %s, %s" % (S(S_OFV), S(S_OFK))]
 
 
 def hashg(blk, khreg, slot):
@@ -142,26 +130,13 @@ def stream_gaps(blk, drop, kh, nxt):
     return gaps
 
 
-def place(mf, gaps, fixed):
-    out = []
-    for m, ins in enumerate(mf):
-        out.append(ins)
-        out += fixed.get(m, [])
-        if m < len(gaps):
-            out += gaps[m]
-    return out
-
-
 def phase(ph, q, drop, cfg):
     """phase ph (0..3 = A0..A3) of the tile in ring slot q (= t & 3).  Returns the flat instruction list."""
     blk_m = "X" if ph % 2 == 0 else "Y"
     blk_v = "Y" if ph % 2 == 0 else "X"
     mf = unit_mfmas(blk_m)
-    fixed = {}
-
-    def add(g, ins):
-        fixed.setdefault(g, []).extend(ins if isinstance(ins, list) else [ins])
-
+    fixed = w4asm.Fixed()
+    add = fixed.add
     # the stream's unit: A0 -> Y(t-1,1), A1 -> X(t,0), A2 -> Y(t,0), A3 -> X(t,1); kh registers by tile parity
     par = q & 1
     unit_kh = {0: KH[par ^ 1] + 4, 1: KH[par], 2: KH[par], 3: KH[par] + 4}[ph]
@@ -175,11 +150,11 @@ def phase(ph, q, drop, cfg):
         pieces = [("K", j) for j in range(4)] + [("V", j) for j in range(4)]
         g = 2
         for w, j in pieces:
-            add(g, dma_piece(w, j, (q + 2) & 3))
+            add(g, piece(w, j, (q + 2) & 3))
             g += cfg["dstride"]
         assert g - cfg["dstride"] <= 23
     if ph == 2 and drop:
-        add(1, kh_reads(par ^ 1))                      # key-group hashes of tile t + 1
+        add(1, w4asm.kh_reads(KH[par ^ 1], VKH))                      # key-group hashes of tile t + 1
     if ph in (1, 3):
         # Y's unit is the second user of every fragment: re-fill in place for the next key half
         kb_n, slot_n = (1, q) if ph == 1 else (0, (q + 1) & 3)     # K / V rows: (t, 1) in A1, (t + 1, 0) in A3
@@ -198,99 +173,34 @@ def prologue(drop):
     e = L.append
     e("s_nop 4")
     e("s_mov_b32 %s, m0" % S(S_M0))
-    e("v_mbcnt_lo_u32_b32 %s, -1, 0" % V(VLANE))
-    e("v_mbcnt_hi_u32_b32 %s, -1, %s" % (V(VLANE), V(VLANE)))
+    L += w4asm.lane_id(VLANE)
     e("s_mov_b32 %s, %%[ldsb]" % S(S_LDS))
-    # row reads (K and V images are the same: V's base is 64 KiB up)
-    e("v_and_b32 %s, 31, %s" % (V(T0), V(VLANE)))
-    e("v_lshrrev_b32 %s, 5, %s" % (V(T1), V(VLANE)))
-    e("v_lshrrev_b32 %s, 3, %s" % (V(T2), V(T0)))
-    e("v_lshlrev_b32 %s, 11, %s" % (V(VKE), V(T2)))
-    e("v_and_b32 %s, 7, %s" % (V(T2), V(T0)))
-    e("v_lshl_add_u32 %s, %s, 6, %s" % (V(VKE), V(T2), V(VKE)))
-    e("v_bfe_u32 %s, %s, 2, 2" % (V(T2), V(T0)))
-    e("v_xor_b32 %s, %s, %s" % (V(T2), V(T2), V(T1)))
-    e("v_lshl_add_u32 %s, %s, 4, %s" % (V(VKE), V(T2), V(VKE)))
-    e("v_add_u32 %s, %s, %s" % (V(VKE), S(S_LDS), V(VKE)))
-    e("v_xor_b32 %s, 32, %s" % (V(VKO), V(VKE)))
-    e("v_add_u32 %s, 0x10000, %s" % (V(VVE), V(VKE)))
-    e("v_add_u32 %s, 0x10000, %s" % (V(VVO), V(VKO)))
-    # transposed reads of K
-    e("v_bfe_u32 %s, %s, 2, 2" % (V(T2), V(VLANE)))
-    e("v_lshl_add_u32 %s, %s, 2, %s" % (V(T2), V(T1), V(T2)))
-    e("v_lshlrev_b32 %s, 6, %s" % (V(VT1), V(T2)))
-    e("v_bfe_u32 %s, %s, 4, 1" % (V(T2), V(VLANE)))
-    e("v_bfe_u32 %s, %s, 1, 1" % (V(T3), V(VLANE)))
-    e("v_lshl_add_u32 %s, %s, 1, %s" % (V(T2), V(T2), V(T3)))
-    e("v_xor_b32 %s, %s, %s" % (V(T2), V(T2), V(T1)))
-    e("v_lshl_add_u32 %s, %s, 4, %s" % (V(VT1), V(T2), V(VT1)))
-    e("v_and_b32 %s, 1, %s" % (V(T2), V(VLANE)))
-    e("v_lshl_add_u32 %s, %s, 3, %s" % (V(VT1), V(T2), V(VT1)))
-    e("v_add_u32 %s, %s, %s" % (V(VT1), S(S_LDS), V(VT1)))
-    e("v_xor_b32 %s, 32, %s" % (V(VT2), V(VT1)))
-    e("v_add_u32 %s, 0x800, %s" % (V(VT2), V(VT2)))
-    # LDS-DMA source offsets
-    e("v_bfe_u32 %s, %s, 2, 3" % (V(T2), V(VLANE)))
-    e("v_mul_lo_u32 %s, %s, %%[strideb]" % (V(VDE), V(T2)))
-    e("v_bfe_u32 %s, %s, 4, 1" % (V(T2), V(VLANE)))
-    e("v_and_b32 %s, 3, %s" % (V(T3), V(VLANE)))
-    e("v_xor_b32 %s, %s, %s" % (V(T2), V(T2), V(T3)))
-    e("v_lshl_add_u32 %s, %s, 2, %s" % (V(T2), V(T1), V(T2)))
-    e("v_lshl_add_u32 %s, %s, 4, %s" % (V(VDE), V(T2), V(VDE)))
-    e("v_xor_b32 %s, 32, %s" % (V(VDO), V(VDE)))
-    e("v_lshlrev_b32 %s, 5, %s" % (V(VKH), V(T1)))
-    e("v_add_u32 %s, %s, %s" % (V(VKH), S(S_LDS), V(VKH)))
-    e("v_add_u32 %s, 0x%x, %s" % (V(VKH), KH_OFF, V(VKH)))
+    # (w4asm: r = lane & 31 stays in T0, h = lane >> 5 in T1)  K and V images are the same: V's base is 64 KiB up
+    L += w4asm.row_read_base(VLANE, S_LDS, T0, T1, T2, VKE, VKO, second=(VVE, VVO))
+    L += w4asm.tr_read_base(VLANE, S_LDS, T1, T2, T3, VT1, VT2)              # transposed reads of K
+    L += w4asm.dma_source_offsets(VLANE, T1, T2, T3, VDE, VDO, "%[strideb]")
+    L += w4asm.kh_base(VKH, T1, S_LDS, KH_OFF)
     e("v_mov_b32 %s, %%[rhx]" % V(RH["X"]))
     e("v_mov_b32 %s, %%[rhy]" % V(RH["Y"]))
     e("v_mov_b32 %s, %%[thr]" % V(VTHR))
     e("s_mov_b32 %s, 0x9E3779B1" % S(S_MIX))
-    e("s_mov_b64 %s, %%[kptr]" % S(S_DK, 2))
-    e("s_mov_b32 %s, 0x7fffffff" % S(S_DK + 2))
-    e("s_mov_b32 %s, 0x00020000" % S(S_DK + 3))
-    e("s_add_u32 %s, %s, %%[hd2]" % (S(S_DV), S(S_DK)))
-    e("s_addc_u32 %s, %s, 0" % (S(S_DV + 1), S(S_DK + 1)))
-    e("s_mov_b32 %s, 0x7fffffff" % S(S_DV + 2))
-    e("s_mov_b32 %s, 0x00020000" % S(S_DV + 3))
+    L += w4asm.descriptor(S_DK, "%[kptr]", second=(S_DV, "%[hd2]"))
     e("s_lshl_b32 %s, %%[strideb], 6" % S(S_TB))
     e("s_sub_u32 %s, %%[nt], 1" % S(S_NT1))
-    e("s_lshl_b32 %s, %%[wave], 4" % S(S_X))
-    e("s_mul_i32 %s, %s, %%[strideb]" % (S(S_PC), S(S_X)))
-    e("s_add_u32 %s, %s, 128" % (S(S_PC + 1), S(S_PC)))
-    e("s_lshl_b32 %s, %%[strideb], 3" % S(S_X))
-    e("s_add_u32 %s, %s, %s" % (S(S_PC + 2), S(S_PC), S(S_X)))
-    e("s_add_u32 %s, %s, 128" % (S(S_PC + 3), S(S_PC + 2)))
-    e("s_lshl_b32 %s, %%[wave], 12" % S(S_X))
-    e("s_add_u32 %s, %s, %s" % (S(S_LW), S(S_LDS), S(S_X)))
+    L += w4asm.piece_offsets(S_PC, S_X, "%[strideb]")
+    L += w4asm.wave_lds_base(S_LW, S_LDS, S_X)
     # tiles 0, 1 -> slots 0, 1
     for tile in range(2):
         e("s_mov_b32 %s, 0" % S(S_T))
         L.extend(tile_offset(tile))
         for w in ("K", "V"):
             for j in range(4):
-                L.extend(dma_piece(w, j, tile))
+                L.extend(piece(w, j, tile))
     # Q / dO fragments, row statistics
-    e("v_lshlrev_b32 %s, 4, %s" % (V(T2), V(T1)))
-    e("v_mul_lo_u32 %s, %s, %%[strideb]" % (V(T3), V(T0)))
-    e("v_add_u32 %s, %s, %s" % (V(T3), V(T3), V(T2)))                 # Q: r stride + 16 h
-    e("s_lshl_b32 %s, %%[strideb], 5" % S(S_X))
-    e("s_mov_b64 %s, %%[qptr]" % S(S_QP, 2))
-    e("s_add_u32 %s, %s, %s" % (S(S_QP), S(S_QP), S(S_X)))
-    e("s_addc_u32 %s, %s, 0" % (S(S_QP + 1), S(S_QP + 1)))
-    for ds in range(8):
-        e("global_load_dwordx4 %s, %s, %%[qptr] offset:%d" % (A(Q_["X"] + 4 * ds, 4), V(T3), ds * 32))
-    for ds in range(8):
-        e("global_load_dwordx4 %s, %s, %s offset:%d" % (A(Q_["Y"] + 4 * ds, 4), V(T3), S(S_QP, 2), ds * 32))
-    e("v_mul_lo_u32 %s, %s, %%[dorowb]" % (V(T3), V(T0)))
-    e("v_add_u32 %s, %s, %s" % (V(T3), V(T3), V(T2)))                 # dO: r pitch + 16 h
-    e("s_lshl_b32 %s, %%[dorowb], 5" % S(S_X))
-    e("s_mov_b64 %s, %%[doptr]" % S(S_DP2, 2))
-    e("s_add_u32 %s, %s, %s" % (S(S_DP2), S(S_DP2), S(S_X)))
-    e("s_addc_u32 %s, %s, 0" % (S(S_DP2 + 1), S(S_DP2 + 1)))
-    for ds in range(8):
-        e("global_load_dwordx4 %s, %s, %%[doptr] offset:%d" % (A(DO["X"] + 4 * ds, 4), V(T3), ds * 32))
-    for ds in range(8):
-        e("global_load_dwordx4 %s, %s, %s offset:%d" % (A(DO["Y"] + 4 * ds, 4), V(T3), S(S_DP2, 2), ds * 32))
+    L += w4asm.frag_offset(T3, T0, T1, T2, "%[strideb]")
+    L += w4asm.block_frag_loads(Q_["X"], Q_["Y"], T3, "%[qptr]", S_QP, S_X, "%[strideb]")
+    L += w4asm.frag_offset(T3, T0, T1, T2, "%[dorowb]", with_h=False)
+    L += w4asm.block_frag_loads(DO["X"], DO["Y"], T3, "%[doptr]", S_DP2, S_X, "%[dorowb]")
     e("v_lshlrev_b32 %s, 2, %s" % (V(T2), V(T0)))                     # 4 r: the lane's entry of the statistics tables
     e("global_load_dword %s, %s, %%[lseptr]" % (V(NL["X"]), V(T2)))
     e("global_load_dword %s, %s, %%[lseptr] offset:128" % (V(NL["Y"]), V(T2)))
@@ -317,7 +227,7 @@ def prologue(drop):
         L.extend(kt_reads(i, 0, 0))                                    # K^T(-1, 1) stands in: any finite operand (dS = 0)
     e("s_mov_b32 %s, 0" % S(S_T))
     if drop:
-        L.extend(kh_reads(0))                                          # tile 0's; tile t + 1's are read in phase A2 of tile t
+        L.extend(w4asm.kh_reads(KH[0], VKH))                           # tile 0's; tile t + 1's are read in phase A2 of tile t
     e("s_waitcnt lgkmcnt(0)")
     e("s_nop 3")
     return L
@@ -386,8 +296,8 @@ BASE = dict(lag=1, dstride=3)
 
 def gen(drop, cfg=None):
     cfg = BASE if cfg is None else cfg
-    if cfg.get("abl_1616") and not cfg.get("_in1616"):      # timing only, see gen_attn_fwd.to1616
-        return F.to1616(gen(drop, dict(cfg, _in1616=1)))
+    if cfg.get("abl_1616") and not cfg.get("_in1616"):      # timing only, see w4asm.to1616
+        return w4asm.to1616(gen(drop, dict(cfg, _in1616=1)))
     L = prologue(drop)
     L.append("o2dq_loop_%=:")
     body = []
@@ -396,8 +306,8 @@ def gen(drop, cfg=None):
             body += phase(ph, q, drop, cfg)
     # the re-fills of the last phase are outstanding when the body is entered again: the waits are placed for that state (the
     # first entry, from the prologue, has nothing outstanding: every wait is then trivially satisfied)
-    _, carry = F.insert_lgkm_waits(body, ())
-    body, pend = F.insert_lgkm_waits(body, carry)
+    _, carry = insert_lgkm_waits(body, ())
+    body, pend = insert_lgkm_waits(body, carry)
     assert pend == carry, "the LDS reads outstanding at the end of the loop body differ from those at its entry"
     L += body
     L += ["s_cmp_lt_u32 %s, %%[nt]" % S(S_T), "s_cbranch_scc1 o2dq_loop_%="]
@@ -407,50 +317,17 @@ def gen(drop, cfg=None):
     gl = stream_gaps("Y", drop, KH[1] + 4, ("X", KH[0]))
     tail += [x for g in gl[8:] for x in g]
     tail += ["s_nop 3"] + dq_only("Y")
-    tail, pend = F.insert_lgkm_waits(tail, carry)
+    tail, pend = insert_lgkm_waits(tail, carry)
     assert not pend
     L += tail
     L += epilogue(drop)
     return L
 
 
-def emit(path):
-    out = ["// GENERATED by tools/gen_attn_dq.py -- do not edit; the schedule lives in that script.", "#pragma once",
-           "#define O2_DQ_KH_OFF %d" % KH_OFF, "#define O2_DQ_LDS_BYTES(L) (%d + (L) + 64)" % KH_OFF]
-
-    def macro(name, lines):
-        out.append("#define %s \\" % name)
-        for k, s in enumerate(lines):
-            if s.endswith(":"):
-                out.append('  "%s\\n"%s' % (s, " \\" if k + 1 < len(lines) else ""))
-            else:
-                out.append('  "%s\\n\\t"%s' % (s, " \\" if k + 1 < len(lines) else ""))
-
-    macro("O2_DQ_ASM_DROP", gen(True))
-    macro("O2_DQ_ASM_NODROP", gen(False))
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"a%d"' % r for r in range(256)] + ['"v%d"' % r for r in range(8, 256)] + \
-           ['"s%d"' % r for r in range(36, 72)]
-    out.append("#define O2_DQ_CLOBBERS \\")
-    for k in range(0, len(clob), 16):
-        chunk = ", ".join(clob[k:k + 16])
-        out.append("  %s%s" % (chunk, ", \\" if k + 16 < len(clob) else ""))
-    open(path, "w").write("\n".join(out) + "\n")
+def header():
+    return dict(prefix="O2_DQ", defines=["#define O2_DQ_KH_OFF %d" % KH_OFF, "#define O2_DQ_LDS_BYTES(L) (%d + (L) + 64)" % KH_OFF],
+                macros=[("O2_DQ_ASM_DROP", gen(True)), ("O2_DQ_ASM_NODROP", gen(False))], vregs=8, sregs=(36, 72))
 
 
 if __name__ == "__main__":
-    if "--cfg" in sys.argv:
-        for kv in sys.argv[sys.argv.index("--cfg") + 1].split(","):
-            k, v = kv.split("=")
-            BASE[k] = int(v)
-    if len(sys.argv) > 1 and sys.argv[1] == "show":
-        lines = gen("nodrop" not in sys.argv)
-        slot = -1
-        for l in lines:
-            if l.startswith("v_mfma"):
-                slot += 1
-            print(slot, l)
-    else:
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(root, "orbit-2_amd", "csrc", "attn_dq_asm.h")
-        emit(out)
-        print("wrote %s" % out, BASE)
+    w4asm.main(sys.modules[__name__], "attn_dq_asm.h")

@@ -28,13 +28,18 @@ Shape (gfx950, one wave per SIMD, 512 registers per lane):
     table of the whole sequence written by the kernel's prologue; l sums the un-dropped p, O the dropped ones, 1/(1-p) folded
     into the final scale.
   * K / V tiles arrive by LDS-DMA (buffer_load_dwordx4 ... lds) into a 2-slot ring of [K 16 KiB | V 16 KiB]; LDS image of a tile
-    = 8-row x 32-column subtiles of 512 B (off = 2048 (row >> 3) + 512 (ch >> 2) + 64 (row & 7) + 16 ((ch & 3) ^ ((row >> 2) & 3))):
-    every row read and every transposed read is one of 2 + 2 lane-constant address registers plus an immediate.  One barrier
+    = 8-row x 32-column subtiles of 512 B with a bank swizzle (tools/w4asm.py, with the address set-up all three attention
+    generators share): every row read and every transposed read is one of 2 + 2 lane-constant address registers plus an immediate.  One barrier
     per tile (phase 2): behind it K(t+3) and V(t+2) are put in flight one piece every few MFMAs; they are waited for at the
     next barrier, one tile before their first read.
 """
 import os
 import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import w4asm  # noqa: E402
+from w4asm import A, S, V, cost, insert_lgkm_waits, place, regs_of, to1616  # noqa: E402
+from w4asm import mfma32 as mfma  # noqa: E402
 
 # ---- registers -------------------------------------------------------------------------------------------------------
 O_ = {"X": 0, "Y": 64}
@@ -59,28 +64,6 @@ S_QP, S_OP, S_X, S_Y2, S_EX, S_LDS = 60, 62, 64, 65, 66, 68
 
 KH_OFF = 65536            # byte offset of the key-group hash table behind the 2 x 32 KiB ring
 LIMIT = "0x53800000"      # 2^40
-
-
-def V(b, n=1):
-    return "v%d" % b if n == 1 else "v[%d:%d]" % (b, b + n - 1)
-
-
-def A(b, n=1):
-    return "a%d" % b if n == 1 else "a[%d:%d]" % (b, b + n - 1)
-
-
-def S(b, n=1):
-    return "s%d" % b if n == 1 else "s[%d:%d]" % (b, b + n - 1)
-
-
-COST = {"v_exp_f32": 8, "v_mul_lo_u32": 8, "v_log_f32": 8, "v_rcp_f32": 8}
-
-
-def cost(text):
-    op = text.split()[0]
-    if op.startswith("ds_") or op.startswith("s_"):
-        return 1
-    return COST.get(op, 4)
 
 
 # ---- the vector stream of one block's tile: S -> p, row sums, dropout, P^T fragments --------------------------------------
@@ -153,10 +136,6 @@ def guard(blk, site):
 
 
 # ---- MFMA sequences ------------------------------------------------------------------------------------------------------
-def mfma(d, a, b, c):
-    return "v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (d, a, b, c)
-
-
 def s_chain(blk, cinit=None):
     """16 MFMAs S^T[kb] = K[kb] Q^T (+ C); K fragment f = 2 ds + kb in a[AK + 4 f]"""
     out = []
@@ -191,51 +170,32 @@ def v_reads(j, slot):
             "ds_read_b64_tr_b16 %s, %s offset:%d" % (V(VV + 4 * j + 2, 2), V(VV2), off)]
 
 
-def kh_reads(par):
-    return ["ds_read_b128 %s, %s" % (V(KH[par], 4), V(VKH)), "ds_read_b128 %s, %s offset:16" % (V(KH[par] + 4, 4), V(VKH)),
-            "v_add_u32 %s, 64, %s" % (V(VKH), V(VKH))]
-
-
-def dma_piece(which, j, slot):
+def piece(which, j, slot):
     """piece j (0..3) of this wave's share of a K ('K') or V ('V') tile into ring slot `slot`; soffset in S_TMP"""
     sof, desc, half = (S_OFK, S_DK, 0) if which == "K" else (S_OFV, S_DV, 16384)
-    return ["s_add_u32 %s, %s, %s" % (S(S_TMP), S(sof), S(S_PC + j)),
-            "s_add_u32 m0, %s, %d" % (S(S_LW), slot * 32768 + half + j * 1024),
-            "s_nop 0",
-            "buffer_load_dwordx4 %s, %s, %s offen lds" % (V(VDO if j >= 2 else VDE), S(desc, 4), S(S_TMP))]
+    return w4asm.dma_piece(desc, sof, S_PC + j, S_LW, slot * 32768 + half + j * 1024, S_TMP, VDO if j >= 2 else VDE)
 
 
 def tile_offsets(dk, dv):
     """S_OFK / S_OFV = byte offset of tile min(t + dk, nt - 1) / min(t + dv, nt - 1)"""
-    return ["s_add_u32 %s, %s, %d" % (S(S_X), S(S_T), dk), "s_min_u32 %s, %s, %s" % (S(S_X), S(S_X), S(S_NT1)),
-            "s_mul_i32 %s, %s, %s" % (S(S_OFK), S(S_X), S(S_TB)),
-            "s_add_u32 %s, %s, %d" % (S(S_X), S(S_T), dv), "s_min_u32 %s, %s, %s" % (S(S_X), S(S_X), S(S_NT1)),
-            "s_mul_i32 %s, %s, %s" % (S(S_OFV), S(S_X), S(S_TB))]
+    return w4asm.tile_offset(S_X, S_T, dk, S_NT1, [(S_OFK, S_TB)]) + w4asm.tile_offset(S_X, S_T, dv, S_NT1, [(S_OFV, S_TB)])
 
 
 # ---- one phase: 32 MFMAs with everything else placed in the gaps ----------------------------------------------------------
-def place(mf, valu, fixed, cfg):
-    """mf: 32 MFMA texts; valu: ordered vector stream; fixed: {gap: [instructions]} -> flat list.  The vector stream is spread
-    over gaps g0..g1 in proportion to its issue cost, fixed instructions go first in their gap."""
-    if valu and isinstance(valu[0], list):
-        gaps = valu                              # already one list per gap
-    else:
-        g0, g1 = cfg.get("valu_first", 0), cfg.get("valu_last", 31)
-        total = sum(cost(x) for x in valu if not x.endswith(":"))
-        per = total / float(g1 - g0 + 1)
-        gaps = [[] for _ in range(32)]
-        acc = 0.0
-        for x in valu:
-            g = min(g1, g0 + int(acc / per)) if per > 0 else g0
-            gaps[g].append(x)
-            if not x.endswith(":"):
-                acc += cost(x)
-    out = []
-    for m in range(32):
-        out.append(mf[m])
-        out += fixed.get(m, [])
-        out += gaps[m]
-    return out
+def spread(valu, cfg):
+    """an ordered flat vector stream -> 32 per-gap lists: spread over gaps valu_first..valu_last in proportion to its issue cost
+    (cfg spread; the default stream comes as per-gap lists from softmax_gaps)"""
+    g0, g1 = cfg.get("valu_first", 0), cfg.get("valu_last", 31)
+    total = sum(cost(x) for x in valu if not x.endswith(":"))
+    per = total / float(g1 - g0 + 1)
+    gaps = [[] for _ in range(32)]
+    acc = 0.0
+    for x in valu:
+        g = min(g1, g0 + int(acc / per)) if per > 0 else g0
+        gaps[g].append(x)
+        if not x.endswith(":"):
+            acc += cost(x)
+    return gaps
 
 
 def phase(which, par, drop, site, cfg, first=False):
@@ -244,11 +204,8 @@ def phase(which, par, drop, site, cfg, first=False):
     blk_m, blk_v = ("Y", "X") if which == 1 else ("X", "Y")
     sc, pv = s_chain(blk_m), pv_chain(blk_m)
     mf = [x for x, _ in sc] + [x for x, _ in pv]
-    fixed = {}
-
-    def add(g, ins):
-        fixed.setdefault(g, []).extend(ins if isinstance(ins, list) else [ins])
-
+    fixed = w4asm.Fixed()
+    add = fixed.add
     if cfg.get("spread"):
         valu = softmax_stream(blk_v, drop, KH[par]) + guard(blk_v, site)
     else:
@@ -267,8 +224,9 @@ def phase(which, par, drop, site, cfg, first=False):
         mf = [x.replace("v[%d:%d]" % (S_[blk_m], S_[blk_m] + 15), "a[%d:%d]" % (O_[blk_m], O_[blk_m] + 15))
                .replace("v[%d:%d]" % (S_[blk_m] + 16, S_[blk_m] + 31), "a[%d:%d]" % (O_[blk_m] + 16, O_[blk_m] + 31))
                .replace("v[%d:%d]" % (NR[blk_m], NR[blk_m] + 15), "a[%d:%d]" % (O_[blk_m] + 32, O_[blk_m] + 47)) for x in mf]
+    gaps = spread(valu, cfg) if cfg.get("spread") else valu
     if which == 1 and cfg.get("abl_lds"):
-        return place(mf, valu, fixed, cfg)
+        return place(mf, gaps, fixed)
     if which == 1:
         for f in range(16):                      # K(t+1) into the fragment registers, each right behind its last use (slot f)
             add(f + cfg["klag"], k_read(f, par ^ 1))
@@ -282,79 +240,16 @@ def phase(which, par, drop, site, cfg, first=False):
         b = cfg["bar"]
         add(b, ["s_waitcnt vmcnt(0) lgkmcnt(0)"] + ([] if cfg.get("abl_bar") else ["s_barrier"]) + tile_offsets(3, 2))
         if drop:                                  # key-group hashes of tile t + 1 into the other register set
-            add(b + 1, kh_reads(par ^ 1))
+            add(b + 1, w4asm.kh_reads(KH[par ^ 1], VKH))
         pieces = [("K", j, par ^ 1) for j in range(4)] + [("V", j, par) for j in range(4)]
         g = b + 2
         for k, (w, j, sl) in enumerate(pieces):
             if not cfg.get("abl_dma"):
-                add(g, dma_piece(w, j, sl))
+                add(g, piece(w, j, sl))
             g += cfg["dstride"]
         assert g - cfg["dstride"] <= 31, "pieces run past the phase"
         add(31, ["s_add_u32 %s, %s, 1" % (S(S_T), S(S_T))])
-    return place(mf, valu, fixed, cfg)
-
-
-# ---- counted LDS waits ---------------------------------------------------------------------------------------------------
-def regs_of(tok):
-    """registers named by an operand token -> set of ('v' | 'a' | 's', index)"""
-    tok = tok.strip()
-    out = set()
-    if not tok or tok[0] not in "vas" or tok in ("vcc", "scc", "s_nop"):
-        return out
-    kind = tok[0]
-    body = tok[1:]
-    if body.startswith("["):
-        lo, hi = body[1:-1].split(":")
-        for r in range(int(lo), int(hi) + 1):
-            out.add((kind, r))
-    elif body.isdigit():
-        out.add((kind, int(body)))
-    return out
-
-
-def operands(text):
-    parts = text.split(None, 1)
-    if len(parts) < 2:
-        return parts[0], []
-    ops = [x.strip() for x in parts[1].split(",")]
-    last = ops[-1].split()
-    if last:
-        ops[-1] = last[0]
-    return parts[0], ops
-
-
-def insert_lgkm_waits(seq, carry=()):
-    """seq: flat instruction list entered with the LDS reads `carry` (destination-register sets, oldest first) outstanding.  Inserts the minimal counted s_waitcnt lgkmcnt(n) in front of every instruction that
-    touches a register an outstanding LDS read will still write (reads return in issue order; counts above 15 clamp)."""
-    out, pend = [], [set(x) for x in carry]          # pend: list of destination-register sets, oldest first
-    for ins in seq:
-        op, ops = operands(ins)
-        if op == "s_waitcnt":
-            if "lgkmcnt(0)" in ins:
-                pend = []
-            out.append(ins)
-            continue
-        if op.endswith(":"):
-            out.append(ins)
-            continue
-        touched = set()
-        for o in ops:
-            touched |= regs_of(o)
-        need = None
-        for k, dst in enumerate(pend):
-            if dst & touched:
-                need = k
-        if need is not None:
-            n = len(pend) - 1 - need
-            n = min(n, 15)
-            out.append("s_waitcnt lgkmcnt(%d)" % n)
-            pend = pend[len(pend) - n:] if n > 0 else []
-        if op.startswith("ds_read"):
-            pend.append(regs_of(ops[0]))
-        elif op.startswith("ds_write"):
-            pend.append(set())                      # an LDS store occupies a slot of the same counter
-        out.append(ins)
-    return out, pend
+    return place(mf, gaps, fixed)
 
 
 # ---- prologue / tail / epilogue / fix-ups ------------------------------------------------------------------------------------
@@ -377,73 +272,23 @@ def prologue(drop):
     e = L.append
     e("s_nop 4")
     e("s_mov_b32 %s, m0" % S(S_M0))
-    # ---- lane-constant addresses ----
-    e("v_mbcnt_lo_u32_b32 %s, -1, 0" % V(VLANE))
-    e("v_mbcnt_hi_u32_b32 %s, -1, %s" % (V(VLANE), V(VLANE)))
+    # ---- lane-constant addresses (w4asm: r = lane & 31 stays in T0, h = lane >> 5 in T1) ----
+    L += w4asm.lane_id(VLANE)
     e("s_mov_b32 %s, %%[ldsb]" % S(S_LDS))
-    # K row reads: r = lane & 31, h = lane >> 5: base = 2048 (r >> 3) + 64 (r & 7) + 16 (h ^ ((r >> 2) & 3)), odd k-steps ^ 32
-    e("v_and_b32 %s, 31, %s" % (V(T0), V(VLANE)))                  # r
-    e("v_lshrrev_b32 %s, 5, %s" % (V(T1), V(VLANE)))               # h
-    e("v_lshrrev_b32 %s, 3, %s" % (V(T2), V(T0)))
-    e("v_lshlrev_b32 %s, 11, %s" % (V(VKE), V(T2)))
-    e("v_and_b32 %s, 7, %s" % (V(T2), V(T0)))
-    e("v_lshl_add_u32 %s, %s, 6, %s" % (V(VKE), V(T2), V(VKE)))
-    e("v_bfe_u32 %s, %s, 2, 2" % (V(T2), V(T0)))                   # (r >> 2) & 3
-    e("v_xor_b32 %s, %s, %s" % (V(T2), V(T2), V(T1)))
-    e("v_lshl_add_u32 %s, %s, 4, %s" % (V(VKE), V(T2), V(VKE)))
-    e("v_add_u32 %s, %s, %s" % (V(VKE), S(S_LDS), V(VKE)))
-    e("v_xor_b32 %s, 32, %s" % (V(VKO), V(VKE)))
-    # V transposed reads: g1 = (lane >> 4) & 1, q = (lane & 15) >> 2, p = lane & 3:
-    #   first block 64 (4 h + q) + 16 ((2 g1 + (p >> 1)) ^ h) + 8 (p & 1); second block (first ^ 32) + 2048
-    e("v_bfe_u32 %s, %s, 2, 2" % (V(T2), V(VLANE)))                # q
-    e("v_lshl_add_u32 %s, %s, 2, %s" % (V(T2), V(T1), V(T2)))      # 4 h + q
-    e("v_lshlrev_b32 %s, 6, %s" % (V(VV1), V(T2)))
-    e("v_bfe_u32 %s, %s, 4, 1" % (V(T2), V(VLANE)))                # g1
-    e("v_bfe_u32 %s, %s, 1, 1" % (V(T3), V(VLANE)))                # p >> 1
-    e("v_lshl_add_u32 %s, %s, 1, %s" % (V(T2), V(T2), V(T3)))      # 2 g1 + (p >> 1)
-    e("v_xor_b32 %s, %s, %s" % (V(T2), V(T2), V(T1)))
-    e("v_lshl_add_u32 %s, %s, 4, %s" % (V(VV1), V(T2), V(VV1)))
-    e("v_and_b32 %s, 1, %s" % (V(T2), V(VLANE)))
-    e("v_lshl_add_u32 %s, %s, 3, %s" % (V(VV1), V(T2), V(VV1)))
-    e("v_add_u32 %s, %s, %s" % (V(VV1), S(S_LDS), V(VV1)))
-    e("v_xor_b32 %s, 32, %s" % (V(VV2), V(VV1)))
-    e("v_add_u32 %s, 0x800, %s" % (V(VV2), V(VV2)))
-    # LDS-DMA source offsets of a piece: ((lane >> 2) & 7) stride + 16 (4 (lane >> 5) + ((lane & 3) ^ (2 f + ((lane >> 4) & 1)))), f = 0 / 1
-    e("v_bfe_u32 %s, %s, 2, 3" % (V(T2), V(VLANE)))
-    e("v_mul_lo_u32 %s, %s, %%[strideb]" % (V(VDE), V(T2)))
-    e("v_bfe_u32 %s, %s, 4, 1" % (V(T2), V(VLANE)))
-    e("v_and_b32 %s, 3, %s" % (V(T3), V(VLANE)))
-    e("v_xor_b32 %s, %s, %s" % (V(T2), V(T2), V(T3)))
-    e("v_lshl_add_u32 %s, %s, 2, %s" % (V(T2), V(T1), V(T2)))      # 4 h + x
-    e("v_lshl_add_u32 %s, %s, 4, %s" % (V(VDE), V(T2), V(VDE)))
-    e("v_xor_b32 %s, 32, %s" % (V(VDO), V(VDE)))
-    # key-group hash table: half h reads its 8 values of tile t at KH_OFF + 64 t + 32 h
-    e("v_lshlrev_b32 %s, 5, %s" % (V(VKH), V(T1)))
-    e("v_add_u32 %s, %s, %s" % (V(VKH), S(S_LDS), V(VKH)))
-    e("v_add_u32 %s, 0x%x, %s" % (V(VKH), KH_OFF, V(VKH)))
+    L += w4asm.row_read_base(VLANE, S_LDS, T0, T1, T2, VKE, VKO)             # K row reads
+    L += w4asm.tr_read_base(VLANE, S_LDS, T1, T2, T3, VV1, VV2)              # V transposed reads
+    L += w4asm.dma_source_offsets(VLANE, T1, T2, T3, VDE, VDO, "%[strideb]")
+    L += w4asm.kh_base(VKH, T1, S_LDS, KH_OFF)
     e("v_mov_b32 %s, %%[rhx]" % V(RH["X"]))
     e("v_mov_b32 %s, %%[rhy]" % V(RH["Y"]))
     e("v_mov_b32 %s, %%[thr]" % V(VTHR))
     e("s_mov_b32 %s, 0x9E3779B1" % S(S_MIX))
     # ---- scalars: descriptors, piece offsets, tile size ----
-    e("s_mov_b64 %s, %%[kptr]" % S(S_DK, 2))
-    e("s_mov_b32 %s, 0x7fffffff" % S(S_DK + 2))
-    e("s_mov_b32 %s, 0x00020000" % S(S_DK + 3))
-    e("s_add_u32 %s, %s, %%[hd2]" % (S(S_DV), S(S_DK)))
-    e("s_addc_u32 %s, %s, 0" % (S(S_DV + 1), S(S_DK + 1)))
-    e("s_mov_b32 %s, 0x7fffffff" % S(S_DV + 2))
-    e("s_mov_b32 %s, 0x00020000" % S(S_DV + 3))
+    L += w4asm.descriptor(S_DK, "%[kptr]", second=(S_DV, "%[hd2]"))
     e("s_lshl_b32 %s, %%[strideb], 6" % S(S_TB))                    # bytes of a 64-token tile
     e("s_sub_u32 %s, %%[nt], 1" % S(S_NT1))
-    # piece j of wave w: tile piece i = 4 w + j: rows 8 (i >> 1) .., column half i & 1
-    e("s_lshl_b32 %s, %%[wave], 4" % S(S_X))                        # 16 w = 8 * (2 w)
-    e("s_mul_i32 %s, %s, %%[strideb]" % (S(S_PC), S(S_X)))
-    e("s_add_u32 %s, %s, 128" % (S(S_PC + 1), S(S_PC)))
-    e("s_lshl_b32 %s, %%[strideb], 3" % S(S_X))
-    e("s_add_u32 %s, %s, %s" % (S(S_PC + 2), S(S_PC), S(S_X)))
-    e("s_add_u32 %s, %s, 128" % (S(S_PC + 3), S(S_PC + 2)))
-    e("s_lshl_b32 %s, %%[wave], 12" % S(S_X))
-    e("s_add_u32 %s, %s, %s" % (S(S_LW), S(S_LDS), S(S_X)))
+    L += w4asm.piece_offsets(S_PC, S_X, "%[strideb]")
+    L += w4asm.wave_lds_base(S_LW, S_LDS, S_X)
     # ---- tiles 0 and 1 -> slots 0 and 1; Q fragments -> accumulator registers ----
     for tile in range(2):
         e("s_mov_b32 %s, %d" % (S(S_T), tile))
@@ -451,18 +296,9 @@ def prologue(drop):
                   "s_mov_b32 %s, %s" % (S(S_OFV), S(S_OFK))])
         for w in ("K", "V"):
             for j in range(4):
-                L.extend(dma_piece(w, j, tile))
-    e("v_lshlrev_b32 %s, 4, %s" % (V(T2), V(T1)))                   # 16 h
-    e("v_mul_lo_u32 %s, %s, %%[strideb]" % (V(T3), V(T0)))          # r stride
-    e("v_add_u32 %s, %s, %s" % (V(T3), V(T3), V(T2)))
-    e("s_lshl_b32 %s, %%[strideb], 5" % S(S_X))
-    e("s_mov_b64 %s, %%[qptr]" % S(S_QP, 2))
-    e("s_add_u32 %s, %s, %s" % (S(S_QP), S(S_QP), S(S_X)))
-    e("s_addc_u32 %s, %s, 0" % (S(S_QP + 1), S(S_QP + 1)))
-    for ds in range(8):
-        e("global_load_dwordx4 %s, %s, %%[qptr] offset:%d" % (A(Q_["X"] + 4 * ds, 4), V(T3), ds * 32))
-    for ds in range(8):
-        e("global_load_dwordx4 %s, %s, %s offset:%d" % (A(Q_["Y"] + 4 * ds, 4), V(T3), S(S_QP, 2), ds * 32))
+                L.extend(piece(w, j, tile))
+    L += w4asm.frag_offset(T3, T0, T1, T2, "%[strideb]")
+    L += w4asm.block_frag_loads(Q_["X"], Q_["Y"], T3, "%[qptr]", S_QP, S_X, "%[strideb]")
     for r in range(128):
         e("v_accvgpr_write_b32 %s, 0" % A(r))
     for blk in "XY":
@@ -481,7 +317,7 @@ def prologue(drop):
     L.extend(["s_mov_b32 %s, 2" % S(S_T), "s_min_u32 %s, %s, %s" % (S(S_X), S(S_T), S(S_NT1)),
               "s_mul_i32 %s, %s, %s" % (S(S_OFK), S(S_X), S(S_TB))])
     for j in range(4):
-        L.extend(dma_piece("K", j, 0))
+        L.extend(piece("K", j, 0))
     for blk in "XY":
         L.extend(x for x, _ in s_chain(blk, cinit="0"))
     e("s_nop 15")
@@ -498,7 +334,7 @@ def prologue(drop):
     e("s_nop 3")
     e("s_mov_b32 %s, 0" % S(S_T))
     if drop:
-        L.extend(kh_reads(0))                                        # outstanding at the loop's entry, as at every iteration's
+        L.extend(w4asm.kh_reads(KH[0], VKH))                         # outstanding at the loop's entry, as at every iteration's
     return L
 
 
@@ -606,28 +442,6 @@ def epilogue(drop):
 BASE = dict(klag=1, vlag=1, bar=6, dstride=3, valu_first=0, valu_last=31)
 
 
-def to1616(lines):
-    """TIMING ONLY (cfg abl_1616; results are garbage): every v_mfma_f32_32x32x16_bf16 becomes two v_mfma_f32_16x16x32_bf16 of the same
-    FLOPs on the first eight registers of its accumulator block, same operand registers, same place in the stream, and the
-    softmax guard never branches -- what this schedule would run at on the other MFMA shape (profiles/r04_attn_1616_probe.txt)"""
-    import re
-    out = []
-    for l in lines:
-        m = re.match(r"v_mfma_f32_32x32x16_bf16 ([av])\[(\d+):\d+\], (\S+), (\S+), (?:([av])\[(\d+):\d+\]|0)$", l)
-        if m:
-            dk, d0, a, b, ck = m.group(1), int(m.group(2)), m.group(3), m.group(4), m.group(5)
-            for h in range(2):
-                c = "0" if ck is None else "%s[%d:%d]" % (ck, int(m.group(6)) + 4 * h, int(m.group(6)) + 4 * h + 3)
-                out.append("v_mfma_f32_16x16x32_bf16 %s[%d:%d], %s, %s, %s" % (dk, d0 + 4 * h, d0 + 4 * h + 3, a, b, c))
-        elif l.startswith("v_mfma"):
-            raise ValueError("to1616: " + l)
-        elif l.startswith("s_cbranch_vccnz o2af_fix") or l.startswith("s_cbranch_vccnz o2dq_fix"):
-            out.append("s_nop 0")
-        else:
-            out.append(l)
-    return out
-
-
 def gen(drop, cfg=None):
     cfg = BASE if cfg is None else cfg
     if cfg.get("abl_1616") and not cfg.get("_in1616"):
@@ -652,43 +466,10 @@ def gen(drop, cfg=None):
     return L
 
 
-def emit(path):
-    out = ["// GENERATED by tools/gen_attn_fwd.py -- do not edit; the schedule lives in that script.", "#pragma once",
-           "#define O2_AF_KH_OFF %d" % KH_OFF, "#define O2_AF_LDS_BYTES(L) (%d + (L) + 64)" % KH_OFF]
-
-    def macro(name, lines):
-        out.append("#define %s \\" % name)
-        for k, s in enumerate(lines):
-            if s.endswith(":"):
-                out.append('  "%s\\n"%s' % (s, " \\" if k + 1 < len(lines) else ""))
-            else:
-                out.append('  "%s\\n\\t"%s' % (s, " \\" if k + 1 < len(lines) else ""))
-
-    macro("O2_AF_ASM_DROP", gen(True))
-    macro("O2_AF_ASM_NODROP", gen(False))
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"a%d"' % r for r in range(256)] + ['"v%d"' % r for r in range(8, 256)] + \
-           ['"s%d"' % r for r in range(36, 70)]
-    out.append("#define O2_AF_CLOBBERS \\")
-    for k in range(0, len(clob), 16):
-        chunk = ", ".join(clob[k:k + 16])
-        out.append("  %s%s" % (chunk, ", \\" if k + 16 < len(clob) else ""))
-    open(path, "w").write("\n".join(out) + "\n")
+def header():
+    return dict(prefix="O2_AF", defines=["#define O2_AF_KH_OFF %d" % KH_OFF, "#define O2_AF_LDS_BYTES(L) (%d + (L) + 64)" % KH_OFF],
+                macros=[("O2_AF_ASM_DROP", gen(True)), ("O2_AF_ASM_NODROP", gen(False))], vregs=8, sregs=(36, 70))
 
 
 if __name__ == "__main__":
-    if "--cfg" in sys.argv:
-        for kv in sys.argv[sys.argv.index("--cfg") + 1].split(","):
-            k, v = kv.split("=")
-            BASE[k] = int(v)
-    if len(sys.argv) > 1 and sys.argv[1] == "show":
-        lines = gen("nodrop" not in sys.argv)
-        slot = -1
-        for l in lines:
-            if l.startswith("v_mfma"):
-                slot += 1
-            print(slot, l)
-    else:
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(root, "orbit-2_amd", "csrc", "attn_fwd_asm.h")
-        emit(out)
-        print("wrote %s" % out, BASE)
+    w4asm.main(sys.modules[__name__], "attn_fwd_asm.h")

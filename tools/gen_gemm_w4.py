@@ -25,6 +25,10 @@ Operands of the statement are named (%[...]); scratch SGPRs s64-s99 and every re
 O2_W4_ASM_TN_CONT is the weight-gradient statement without the accumulator clear: it adds a further range of the contraction to the
 accumulators an earlier statement of the same tile left in a[0:255]."""
 import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import w4asm  # noqa: E402
 
 UNIT = 16896                       # 16 pieces x (1024 + 32): the K-strided image; the K-contiguous image uses 16384 of it
 STAGE = 4 * UNIT
@@ -115,10 +119,7 @@ def gen(a_kc, b_kc, cfg):
             e("s_add_u32 s%d, s%d, %s" % (S + t, S + t - 1, ps))
         for t in range(4):
             e("s_add_u32 s%d, s%d, %s" % (S + 4 + t, S + t, ph))
-    for S, base in ((S_DA, "%[abase]"), (S_DB, "%[bbase]")):          # raw buffer descriptors: base, stride 0, 2^31 - 1 bytes
-        e("s_mov_b64 s[%d:%d], %s" % (S, S + 1, base))
-        e("s_mov_b32 s%d, 0x7fffffff" % (S + 2))
-        e("s_mov_b32 s%d, 0x00020000" % (S + 3))
+    L += w4asm.descriptor(S_DA, "%[abase]") + w4asm.descriptor(S_DB, "%[bbase]")
     if cfg.get("pace"):
         e("s_mov_b32 s97, 0")
     e("s_mov_b32 s%d, %%[ldswa]" % S_WA)
@@ -323,17 +324,8 @@ BASE = dict(bar1_lag=6, lstride=6, bar2=90, xstride_kc=2, pace=64)
 FORMS = {"NT": (True, True), "NN": (True, False), "TN": (False, False), "TT": (False, True)}
 
 
-def emit(path):
-    out = ["// GENERATED by tools/gen_gemm_w4.py -- do not edit; the schedule lives in that script.", "#pragma once",
-           "#define O2_W4_UNIT %d" % UNIT]
-
-    def macro(name, lines):
-        out.append("#define %s \\" % name)
-        for k, s in enumerate(lines):
-            out.append('  "%s\\n\\t"%s' % (s, " \\" if k + 1 < len(lines) else ""))
-
-    for hh in range(2):
-        macro("O2_W4_CSTAGE%d" % hh, gen_cstage(hh))
+def header():
+    macros = [("O2_W4_CSTAGE%d" % hh, gen_cstage(hh)) for hh in range(2)]
     for name, (a_kc, b_kc) in FORMS.items():
         cfg = dict(BASE)
         if name != "TN" or cfg.get("kwrap") or cfg.get("kwrap_tn"):
@@ -341,43 +333,22 @@ def emit(path):
                                                  #  registers s96 / s97, so the two never share a loop)
         if cfg.get("kwrap_tn"):                  # (ablation restricted to the weight-gradient form: a step's activations stay right)
             cfg["kwrap"] = cfg["kwrap_tn"] if name == "TN" else 0
-        macro("O2_W4_ASM_%s" % name, gen(a_kc, b_kc, cfg))
+        macros.append(("O2_W4_ASM_%s" % name, gen(a_kc, b_kc, cfg)))
         if name == "TN":
             # the weight-gradient sweep in segments (csrc/gemm.hip, the K gate): the same statement without the accumulator clear --
             # a fresh prologue (descriptors, piece offsets, two K-tiles in flight) on the next kept range of the contraction
-            macro("O2_W4_ASM_TN_CONT", gen(a_kc, b_kc, dict(cfg, cont=True)))
-        macro("O2_W4_ASM_%s_STAMP" % name, gen(a_kc, b_kc, dict(BASE, stamp=True, pace=0)))
-    clob = ['"memory"', '"scc"', '"vcc"'] + ['"a%d"' % r for r in range(256)] + ['"v%d"' % r for r in range(128, 256)] + \
-           ['"s%d"' % r for r in range(64, 100)]
-    out.append("#define O2_W4_CLOBBERS \\")
-    for k in range(0, len(clob), 16):
-        chunk = ", ".join(clob[k:k + 16])
-        out.append("  %s%s" % (chunk, ", \\" if k + 16 < len(clob) else ""))
-    open(path, "w").write("\n".join(out) + "\n")
+            macros.append(("O2_W4_ASM_TN_CONT", gen(a_kc, b_kc, dict(cfg, cont=True))))
+        macros.append(("O2_W4_ASM_%s_STAMP" % name, gen(a_kc, b_kc, dict(BASE, stamp=True, pace=0))))
+    return dict(prefix="O2_W4", defines=["#define O2_W4_UNIT %d" % UNIT], macros=macros, vregs=128, sregs=(64, 100), labels=False)
 
 
-def show(name):
-    a_kc, b_kc = FORMS[name]
+def show(args):
+    """`show NT`: what sits in the gaps of one K-tile of that operand form (the MFMAs themselves are left out)"""
+    a_kc, b_kc = FORMS[args[0]]
     lines = gen(a_kc, b_kc, BASE)
-    slot = -1
-    for l in lines[lines.index("o2w4_loop_%=:") + 1:]:
-        if l.startswith("v_mfma"):
-            slot += 1
-            continue
-        print(slot, l)
+    w4asm.show(lines[lines.index("o2w4_loop_%=:") + 1:], mfmas=False)
 
 
+# tuning: --cfg "lstride=5,bar2=88" overrides BASE, --out PATH writes the header elsewhere (tools/mkvar_w4.sh)
 if __name__ == "__main__":
-    import sys
-    # tuning: --cfg "lstride=5,bar2=88" overrides BASE, --out PATH writes the header elsewhere (tools/mkvar_w4.sh)
-    if "--cfg" in sys.argv:
-        for kv in sys.argv[sys.argv.index("--cfg") + 1].split(","):
-            k, v = kv.split("=")
-            BASE[k] = int(v)
-    if len(sys.argv) > 2 and sys.argv[1] == "show":
-        show(sys.argv[2])
-    else:
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(root, "orbit-2_amd", "csrc", "gemm_w4_asm.h")
-        emit(out)
-        print("wrote %s:" % out, ", ".join(FORMS), BASE)
+    w4asm.main(sys.modules[__name__], "gemm_w4_asm.h")
