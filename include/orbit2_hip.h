@@ -25,10 +25,13 @@
 extern "C" {
 #endif
 
-#define ORBIT2_ABI_VERSION 7
-/* The fp32 forward entries (orbit2_gemm_f32, orbit2_attn_fwd_f32, orbit2_layernorm_fwd_f32, orbit2_varagg_fwd_f32,
- * orbit2_unpatchify_fwd_f32) were ADDED at version 7: no existing entry, structure or constant changed, so the number stays.  A
- * binding that declares them refuses an older build of version 7 by name ("lacks orbit2_gemm_f32, ..."). */
+#define ORBIT2_ABI_VERSION 8
+/* Version 8: orbit2_gemm_bf16, orbit2_gemm_bf16_grouped, orbit2_attn_fwd_ld and orbit2_attn_bwd_ld take the path gate and the tail
+ * queue as ARGUMENTS; the _gated and _tq entries that version 7 had beside them are gone.  A version-7 build exports the same
+ * four names with shorter argument lists, so the number had to change: a binding of one version refuses a build of the other.
+ * Everything else is as at version 7, the entries that were added during it included (the fp32 forward entries orbit2_gemm_f32,
+ * orbit2_attn_fwd_f32, orbit2_layernorm_fwd_f32, orbit2_varagg_fwd_f32, orbit2_unpatchify_fwd_f32; orbit2_ensemble_update and
+ * orbit2_gaussian_scores). */
 int orbit2_abi_version(void);
 
 /* ---- bf16 MFMA GEMM with fused epilogue ------------------------------------------------
@@ -79,18 +82,34 @@ typedef struct {
                               workspace).  Only the multiply-by-factor input gradient on whole tiles fills it: a call for which
                               orbit2_gemm_bf16_colsum_rows returns 0 is refused with O2_ERR_UNSUPPORTED when colsum_ws is set */
 } orbit2_gemm_args;
-int orbit2_gemm_bf16(const orbit2_gemm_args* args, void* stream);
+/* gate / rows_per_gate, the PATH GATE: gate = fp32 [ceil(M / rows_per_gate)] or NULL (none, whatever rows_per_gate is; a gate
+ * with rows_per_gate <= 0: O2_ERR_ARG), entry e covering rows e * rows_per_gate onwards (the per-sample DropPath scales of a Block
+ * and its token count: vit_blocks.py:77,80 / timm DropPath).  gate[e] == 0.0f says that everything computed from these rows is
+ * multiplied by 0 further down the branch.  The gate is a HINT: an output tile whose rows all lie in one such entry MAY skip its
+ * contraction and epilogue and store what annihilated inputs give -- zeros in C, save_pre, save_dact and its colsum_ws row; the
+ * residual rows when rowscale == gate and rows_per_scale == rows_per_gate (the row scale would have multiplied the product by 0)
+ * -- so nothing a later kernel reads is left unwritten.  A tile that straddles entries, a kernel family without the check (today
+ * every family but the 4-wave 256 x 256 kernel) and an epilogue outside that list (fp32 output, beta, another row scale) compute
+ * as without a gate; kept rows are bit-identical, and the kernel, grid and block are those of the ungated call
+ * (orbit2_gemm_bf16_colsum_rows answers for both).
+ * sched_ws / tail, the TAIL QUEUE (csrc/tail_queue.h) of the one-workgroup-per-CU kernels (the 4-wave 256 x 256 GEMM,
+ * single and grouped; the generated d = 128 attention kernels): their LAST ROUNDS of tiles handed out by ticket instead of by
+ * workgroup number.  Workgroup b always runs on XCD b & 7, so a static walk ends when the slowest XCD ends; here an XCD that gets
+ * to the tail first takes more of it.  The first T - tail tiles keep their static ids; 2 * tail further workgroups each draw one
+ * ticket (one relaxed agent-scope atomic) and either take one of the last `tail` tiles or return.  No workgroup waits.  Every tile
+ * computes what it computes in a static launch: the results are bit-identical.
+ *   tail: < 0 = static, sched_ws is not read and may be NULL -- the plain call is (gate = NULL, 0, sched_ws = NULL, tail = -1);
+ *     0 = sized by the library per kernel family (0, 2 or 4 whole rounds of the device's 256 workgroup slots, from
+ *     profiles/r08_tail_idle.txt; a launch that would keep fewer than 4 static rounds in front of its tail, and any device that
+ *     is not 256 CUs on 8 XCDs, stay static); > 0 = that many tiles (tests: small problems with a queued part; more than the
+ *     launch has: static).
+ *   sched_ws: one 32-bit device word (4-byte aligned, or O2_ERR_ARG at any tail), ZERO before the call; the launch leaves it zero
+ *     (the drawer of the last ticket clears it), so back-to-back calls on one stream and replays of a captured graph reuse it as
+ *     it is.  Calls that may run at the same time (different streams) need different words.  A launch aborted half-way leaves the
+ *     number of tickets drawn so far: zero the word before it is used again.  NULL with tail >= 0: O2_ERR_ARG before any launch.
+ * A call whose plan is another kernel family launches exactly what the static call launches. */
+int orbit2_gemm_bf16(const orbit2_gemm_args* args, const float* gate, int rows_per_gate, void* sched_ws, int tail, void* stream);
 int orbit2_gemm_bf16_colsum_rows(const orbit2_gemm_args* args);   /* 0: this call cannot fuse the column sums (colsum_ws must be NULL) */
-/* orbit2_gemm_bf16 with a PATH GATE: gate = fp32 [ceil(M / rows_per_gate)], entry e covering rows e * rows_per_gate onwards (the
- * per-sample DropPath scales of a Block and its token count: vit_blocks.py:77,80 / timm DropPath).  gate[e] == 0.0f says that
- * everything computed from these rows is multiplied by 0 further down the branch.  The gate is a HINT: an output tile whose rows
- * all lie in one such entry MAY skip its contraction and epilogue and store what annihilated inputs give -- zeros in C, save_pre,
- * save_dact and its colsum_ws row; the residual rows when rowscale == gate and rows_per_scale == rows_per_gate (the row scale
- * would have multiplied the product by 0) -- so nothing a later kernel reads is left unwritten.  A tile that straddles entries, a
- * kernel family without the check (today every family but the 4-wave 256 x 256 kernel) and an epilogue outside that list
- * (fp32 output, beta, another row scale) compute as orbit2_gemm_bf16 does; kept rows are bit-identical, and the kernel, grid and
- * block are those of the ungated call (orbit2_gemm_bf16_colsum_rows answers for both).  gate == NULL: orbit2_gemm_bf16. */
-int orbit2_gemm_bf16_gated(const orbit2_gemm_args* args, const float* gate, int rows_per_gate, void* stream);
 
 /* ---- fp32 GEMM with fused epilogue (the fp32 forward path) ---------------------------------
  * The same argument block with EVERY tensor pointer (A, B, C, bias, residual) read as fp32; out_fp32 must be 1.  fp32 operands,
@@ -108,43 +127,22 @@ int orbit2_gemm_f32(const orbit2_gemm_args* args, void* stream);
  * 8-phase kernel when every problem has K % 64 == 0, M, N >= 256 and the group fills the chip; the 128x128 kernel
  * otherwise): the partially filled last round of each problem is filled with the next one's tiles.  Used for
  * the four weight-gradient GEMMs of a Block (reference: autograd of attention.py:36,40 + mlp.py:50,54).
- * Up to 12 problems (the limit of ABI 7), so that a caller can hand over the tiles beyond the group's last whole round of 256 as
+ * Up to 12 problems (since ABI 7), so that a caller can hand over the tiles beyond the group's last whole round of 256 as
  * part-length problems over slices of the contraction (the Python layer's balanced weight-gradient launch: 3 full problems +
  * 2 x 4 quarter-length ones, partial products summed by orbit2_batch_sum).  When every problem sweeps >= 512 K-tiles of 64 the
  * workgroups of an XCD start their tiles together
  * (a bounded wait on a self-cleaning counter in a static device array: a pacing hint, never needed for correctness;
- * ORBIT2_W4_PACE = 0 / 1 / 2: off / on (default) / plus check points inside the sweep). */
+ * ORBIT2_W4_PACE = 0 / 1 / 2: off / on (default) / plus check points inside the sweep).
+ * kgates / k_per_gate, a K GATE per problem (weight gradients dW = dY^T . X, a_kc = b_kc = 0); either NULL: none.  kgates[i] =
+ * fp32 [K_i / k_per_gate[i]] or NULL, entry e covering rows e * k_per_gate[i] onwards of problem i's contraction (the tokens of
+ * one sample; for a problem over a slice of the tokens, the entries of that slice).  kgates[i][e] == 0.0f says that those rows of
+ * dY are ZEROS (the path gate of orbit2_gemm_bf16 left them so): the 4-wave kernel sweeps the kept ranges only.  A hint like the
+ * path gate: other kernel families, other operand forms and entries that are not whole 64-deep K-tiles ignore it; the products
+ * are the same (a skipped range adds zeros).
+ * sched_ws / tail: the tail queue, as in orbit2_gemm_bf16 (the plain call: kgates = k_per_gate = sched_ws = NULL, tail = -1). */
 #define ORBIT2_GEMM_MAX_GROUP 12
-int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, void* stream);
-/* The same with a K GATE per problem (weight gradients dW = dY^T . X, a_kc = b_kc = 0): kgates[i] = fp32 [K_i / k_per_gate[i]] or
- * NULL, entry e covering rows e * k_per_gate[i] onwards of problem i's contraction (the tokens of one sample; for a problem over a
- * slice of the tokens, the entries of that slice).  kgates[i][e] == 0.0f says that those rows of dY are ZEROS (the path gate of
- * orbit2_gemm_bf16_gated left them so): the 4-wave kernel sweeps the kept ranges only.  A hint like the path gate: other kernel
- * families, other operand forms and entries that are not whole 64-deep K-tiles ignore it; the products are the same (a skipped
- * range adds zeros).  kgates == NULL: orbit2_gemm_bf16_grouped. */
-int orbit2_gemm_bf16_grouped_gated(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate,
-                                   void* stream);
-
-/* ---- TAIL QUEUE (additive entries; csrc/tail_queue.h) ---------------------------
- * The launches of the one-workgroup-per-CU kernels (the 4-wave 256 x 256 GEMM, single and grouped; the generated d = 128 attention
- * kernels) with their LAST ROUNDS of tiles handed out by ticket instead of by workgroup number: workgroup b always runs on XCD
- * b & 7, so a static walk ends when the slowest XCD ends; here an XCD that gets to the tail first takes more of it.  The first
- * T - tail tiles keep the ids of the plain entries; 2 * tail further workgroups each draw one ticket (one relaxed agent-scope
- * atomic) and either take one of the last `tail` tiles or return.  No workgroup waits.  Every tile computes what it computes in
- * the plain entry: the results are bit-identical.
- *   sched_ws: one 32-bit device word (4-byte aligned), ZERO before the call; the launch leaves it zero (the drawer of the last
- *     ticket clears it), so back-to-back calls on one stream and replays of a captured graph reuse it as it is.  Calls that may run
- *     at the same time (different streams) need different words.  A launch aborted half-way leaves the number of tickets drawn
- *     so far: zero the word before it is used again.  NULL: O2_ERR_ARG.
- *   tail: 0 = sized by the library per kernel family (0, 2 or 4 whole rounds of the device's 256 workgroup slots, from
- *     profiles/r08_tail_idle.txt; a launch that would keep fewer than 4 static rounds in front of its tail, and any device that
- *     is not 256 CUs on 8 XCDs, stay static); > 0 = that many tiles (tests: small problems with a queued part; more
- *     than the launch has: static); < 0 = static.
- * A call whose plan is another kernel family launches exactly what the plain entry launches.  gate / kgates may be NULL. */
-int orbit2_gemm_bf16_tq(const orbit2_gemm_args* args, const float* gate, int rows_per_gate, void* sched_ws, int tail,
-                        void* stream);
-int orbit2_gemm_bf16_grouped_tq(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate,
-                                void* sched_ws, int tail, void* stream);
+int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate,
+                             void* sched_ws, int tail, void* stream);
 
 /* small fp32 GEMM (parameter-table algebra of the folded variable aggregation):
  * C[M,N] = alpha * op(A) * op(B) + beta*C, row-major fp32; ta/tb: 0 = as stored, 1 = transposed.
@@ -196,23 +194,15 @@ int64_t orbit2_attn_bwd_ws_floats(int B, int L, int H);
  * out[b, l] at (b * L + l) * ldo (ldo >= H * d); the natural pitches ldq = 3 * H * d, ldo = H * d are the contiguous layouts
  * above.  These tensors are GEMM operands on the other side, and rows a multiple of 8 KiB apart put every row's k-offset on one
  * memory channel (see orbit2_layernorm_fwd_ld).  dout stays [B, L, H, d]. */
-int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
-                       uint64_t seed, int flags, int ldq, int ldo, void* stream);
-int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
-                       void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq, int ldo, void* stream);
-/* The same with a path gate (see orbit2_gemm_bf16_gated): gate = fp32 [B], one entry per sample.  A workgroup of a sample with
+/* gate, the path gate (see orbit2_gemm_bf16): fp32 [B], one entry per sample, or NULL.  A workgroup of a sample with
  * gate[b] == 0.0f MAY skip its work and zero-fill what it owns: its rows of out and lse (forward), of the q third (dQ pass), of
  * the k and v thirds (dK + dV pass) of dqkv.  The generated d = 128 kernels implement it; every other kernel (and the statistics
- * pass) ignores the gate.  gate == NULL: the _ld entries. */
-int orbit2_attn_fwd_gated(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
-                          uint64_t seed, int flags, int ldq, int ldo, const float* gate, void* stream);
-int orbit2_attn_bwd_gated(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
-                          void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq, int ldo,
-                          const float* gate, void* stream);
-/* The same with a tail queue (see orbit2_gemm_bf16_tq; the backward's dQ and dK + dV passes use the one word in turn) */
-int orbit2_attn_fwd_tq(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
+ * pass) ignores the gate.
+ * sched_ws / tail: the tail queue, as in orbit2_gemm_bf16 (the backward's dQ and dK + dV passes use the one word in turn); the
+ * plain call is (gate = NULL, sched_ws = NULL, tail = -1). */
+int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
                        uint64_t seed, int flags, int ldq, int ldo, const float* gate, void* sched_ws, int tail, void* stream);
-int orbit2_attn_bwd_tq(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                        void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq, int ldo,
                        const float* gate, void* sched_ws, int tail, void* stream);
 /* orbit2_attn_fwd_ld with fp32 qkv / out (attention.py:54-78 under data_type float32, components/attention.py:66-70): streaming
@@ -335,7 +325,6 @@ int orbit2_eval_moments(const float* pred, const float* target, int Ht, int Wt, 
                         double* out, int B, int C, int H, int W, void* stream);
 
 /* ---- MC-dropout ensembles (utils/mc_dropout.py) and the Gaussian scores (metrics/functional.py:340-386) ------
- * Both entries were ADDED at version 7 (nothing existing changed; a binding that declares them refuses an older build by name).
  * orbit2_ensemble_update: the k-th (1-based) Welford step over n fp32 elements, in place:
  *   d = member - mean; mean += d / k; m2 += d * (member - mean).   k = 1 initialises (mean = member, m2 = 0; neither is read).
  * After N steps m2 / (N - 1) is the unbiased variance.  The three buffers must be distinct; 16-byte aligned bases take the

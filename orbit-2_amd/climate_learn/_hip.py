@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # $ORBIT2_HIP_LIB: another build of the same ABI (A/B timing of kernel variants on one box; tools/ab_build.sh)
 LIB_PATH = os.environ.get("ORBIT2_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "liborbit2_hip.so")
 _lib = None
-ABI_VERSION = 7                 # ORBIT2_ABI_VERSION: load() refuses a build of any other version
+ABI_VERSION = 8                 # ORBIT2_ABI_VERSION: load() refuses a build of any other version
 
 
 class HipBackendError(RuntimeError):
@@ -57,14 +57,10 @@ class GemmArgs(C.Structure):
 _I, _I64, _U64, _F, _P, _G = C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_void_p, C.POINTER(GemmArgs)
 PROTOTYPES = {
     "orbit2_abi_version": (_I, ()),
-    "orbit2_gemm_bf16": (_I, (_G, _P)),
+    "orbit2_gemm_bf16": (_I, (_G, _P, _I, _P, _I, _P)),
     "orbit2_gemm_bf16_colsum_rows": (_I, (_G,)),
-    "orbit2_gemm_bf16_gated": (_I, (_G, _P, _I, _P)),
     "orbit2_gemm_f32": (_I, (_G, _P)),
-    "orbit2_gemm_bf16_grouped": (_I, (_G, _I, _P)),
-    "orbit2_gemm_bf16_grouped_gated": (_I, (_G, _I, _P, _P, _P)),
-    "orbit2_gemm_bf16_tq": (_I, (_G, _P, _I, _P, _I, _P)),
-    "orbit2_gemm_bf16_grouped_tq": (_I, (_G, _I, _P, _P, _P, _I, _P)),
+    "orbit2_gemm_bf16_grouped": (_I, (_G, _I, _P, _P, _P, _I, _P)),
     "orbit2_sgemm_f32_ws_floats": (_I64, (_I, _I, _I)),
     "orbit2_sgemm_f32_ws": (_I, (_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _I64, _P)),
     "orbit2_layernorm_fwd_ld": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P)),
@@ -72,13 +68,9 @@ PROTOTYPES = {
     "orbit2_layernorm_bwd": (_I, (_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P, _I, _I, _I, _P)),
     "orbit2_layernorm_bwd_ws_floats": (_I, (_I, _I)),
     "orbit2_attn_bwd_ws_floats": (_I64, (_I, _I, _I)),
-    "orbit2_attn_fwd_ld": (_I, (_P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P)),
+    "orbit2_attn_fwd_ld": (_I, (_P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P, _P, _I, _P)),
     "orbit2_attn_fwd_f32": (_I, (_P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P)),
-    "orbit2_attn_bwd_ld": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P)),
-    "orbit2_attn_fwd_gated": (_I, (_P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P, _P)),
-    "orbit2_attn_bwd_gated": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P, _P)),
-    "orbit2_attn_fwd_tq": (_I, (_P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P, _P, _I, _P)),
-    "orbit2_attn_bwd_tq": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P, _P, _I, _P)),
+    "orbit2_attn_bwd_ld": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _U64, _I, _I, _I, _P, _P, _I, _P)),
     "orbit2_varagg_fwd": (_I, (_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P)),
     "orbit2_varagg_fwd_f32": (_I, (_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P)),
     "orbit2_varagg_bwd_ws_floats": (_I64, (_I, _I, _I, _I, _I, _I)),
@@ -185,7 +177,7 @@ def _dev(t: torch.Tensor, dtype, name: str):
 BF, F32 = torch.bfloat16, torch.float32
 
 
-# ---- tail queue (include/orbit2_hip.h: orbit2_gemm_bf16_tq) -------------------------------------------------------------------
+# ---- tail queue (include/orbit2_hip.h: orbit2_gemm_bf16) ----------------------------------------------------------------------
 # One zeroed counter word per stream: launches on one stream run one after the other and each leaves its word zero, launches on
 # different streams may overlap and must not share one.  The words live 128 bytes apart in one buffer per device that is never
 # freed (a captured graph keeps the address), handed out in the order streams first ask.  A launch that was aborted half-way
@@ -222,10 +214,10 @@ def _sched_word(device) -> int:
 
 
 def _tail_arg(tail_queue):
-    """tail_queue of the wrappers -> the entries' `tail`, or None for the plain entries: None / False = plain, True = sized by
-    the library, an int > 0 = that many tiles by ticket (tests)"""
+    """tail_queue of the wrappers -> the entries' `tail`: None / False = -1 (static: the plain call), True = 0 (sized by the
+    library), an int > 0 = that many tiles by ticket (tests)"""
     if tail_queue is None or tail_queue is False:
-        return None
+        return -1
     if tail_queue is True:
         return 0
     if int(tail_queue) <= 0:
@@ -277,17 +269,10 @@ def _timed(name, flops, nbytes=0.0):
     e1.record()
 
 
-def _call_entry(plain, gated, tq, args, gate_args, has_gate, tail, device):
-    """One launch through the entry its gate and tail select: `tq` when a tail queue is asked for (tail is not None: the gate
-    arguments, which say "none" when has_gate is false, the stream's counter word on `device` and the tail), else `gated` when the
-    call has a gate, else `plain`.  args: the leading arguments all three share; the stream is the last one of each."""
-    if tail is not None:
-        name, args = tq, args + gate_args + (_sched_word(device), tail)
-    elif has_gate:
-        name, args = gated, args + gate_args
-    else:
-        name = plain
-    _chk(getattr(lib(), name)(*args, _stream()), name)
+def _queue(tail, device):
+    """the (sched_ws, tail, stream) that end a GEMM or attention entry's arguments: the stream's counter word on `device` when a
+    tail queue is asked for (tail >= 0), NULL for a static call -- which so never allocates the counter buffer or claims a slot"""
+    return (_sched_word(device) if tail >= 0 else None), tail, _stream()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -324,9 +309,9 @@ def gemm(A, B, out, M, N, K, lda, ldb, ldc, want_colsum=False, gate=None, rows_p
     """out[M,N] = epilogue(A x B); see include/orbit2_hip.h:orbit2_gemm_bf16.
     want_colsum: returns (out, parts) -- parts = fp32 [M / 256, N] per-tile-row column sums of the stored output when this call
     can fuse them (orbit2_gemm_bf16_colsum_rows), else None: the caller then runs `colsum` on `out` itself.
-    gate: fp32 [ceil(M / rows_per_gate)] path gate (orbit2_gemm_bf16_gated): rows of an entry that is 0.0 may be stored as zeros
+    gate: fp32 [ceil(M / rows_per_gate)] path gate: rows of an entry that is 0.0 may be stored as zeros
     (as the residual rows when `rowscale` is the gate) without being computed.
-    tail_queue: True = the launch's last rounds by ticket (orbit2_gemm_bf16_tq; _tail_arg); the results are the same bits."""
+    tail_queue: True = the launch's last rounds by ticket (_tail_arg); the results are the same bits."""
     tail = _tail_arg(tail_queue)
     if gate is not None:
         _dev(gate, F32, "gate")
@@ -342,8 +327,8 @@ def gemm(A, B, out, M, N, K, lda, ldb, ldc, want_colsum=False, gate=None, rows_p
             parts = torch.empty(rows, N, dtype=F32, device=out.device)
             a.colsum_ws = parts.data_ptr()
     with _timed("gemm_bf16", flops, nbytes):
-        _call_entry("orbit2_gemm_bf16", "orbit2_gemm_bf16_gated", "orbit2_gemm_bf16_tq", (C.byref(a),),
-                    (_p(gate), rows_per_gate if gate is not None else 0), gate is not None, tail, out.device)
+        _chk(lib().orbit2_gemm_bf16(C.byref(a), _p(gate), rows_per_gate if gate is not None else 0, *_queue(tail, out.device)),
+             "orbit2_gemm_bf16")
     return (out, parts) if want_colsum else out
 
 
@@ -376,8 +361,8 @@ GEMM_MAX_GROUP = 12
 def gemm_grouped(problems, tail_queue=None):
     """problems: list of (A, B, out, M, N, K, lda, ldb, ldc, kwargs) sharing one operand form; one launch
     (include/orbit2_hip.h:orbit2_gemm_bf16_grouped).  A problem's kwargs may hold kgate = (fp32 vector, rows of the contraction
-    per entry): the K gate of orbit2_gemm_bf16_grouped_gated -- ranges of the contraction whose entry is 0.0 hold zero rows in A.
-    tail_queue: as in gemm (orbit2_gemm_bf16_grouped_tq)."""
+    per entry): the K gate -- ranges of the contraction whose entry is 0.0 hold zero rows in A.
+    tail_queue: as in gemm."""
     tail = _tail_arg(tail_queue)
     n = len(problems)
     if not 0 < n <= GEMM_MAX_GROUP:
@@ -398,8 +383,8 @@ def gemm_grouped(problems, tail_queue=None):
         nbytes += b
 
     with _timed("gemm_bf16", flops, nbytes):
-        _call_entry("orbit2_gemm_bf16_grouped", "orbit2_gemm_bf16_grouped_gated", "orbit2_gemm_bf16_grouped_tq", (arr, n),
-                    (kgates if gated else None, kper if gated else None), gated, tail, problems[0][2].device)
+        _chk(lib().orbit2_gemm_bf16_grouped(arr, n, kgates if gated else None, kper if gated else None,
+                                            *_queue(tail, problems[0][2].device)), "orbit2_gemm_bf16_grouped")
 
 
 def sgemm(A, B, out, M, N, K, lda, ldb, ldc, ta=False, tb=False, alpha=1.0, beta=0.0):
@@ -492,8 +477,8 @@ def _attn_gate(gate, B):
 
 def attn_fwd(qkv, B, L, H, d, drop_p=0.0, seed=0, flags=0, out=None, gate=None, tail_queue=None):
     """out: optional [B * L, H * d] bf16 destination with any token-row pitch (orbit2_attn_fwd_ld); default [B, L, H * d].
-    gate: fp32 [B] path gate (orbit2_attn_fwd_gated): out and lse of a sample whose entry is 0.0 may be stored as zeros
-    tail_queue: as in gemm (orbit2_attn_fwd_tq)"""
+    gate: fp32 [B] path gate: out and lse of a sample whose entry is 0.0 may be stored as zeros
+    tail_queue: as in gemm"""
     tail = _tail_arg(tail_queue)
     _attn_gate(gate, B)
     _dev_rows(qkv, BF, "qkv")
@@ -506,9 +491,8 @@ def attn_fwd(qkv, B, L, H, d, drop_p=0.0, seed=0, flags=0, out=None, gate=None, 
     lse = torch.empty(B, H, L, dtype=F32, device=qkv.device)
     # algorithmic bytes: qkv read once, out + lse written once
     with _timed("attn_fwd", 4.0 * B * H * L * L * d, 2.0 * 4 * B * L * H * d + 4.0 * B * H * L):
-        _call_entry("orbit2_attn_fwd_ld", "orbit2_attn_fwd_gated", "orbit2_attn_fwd_tq",
-                    (_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo)), (_p(gate),),
-                    gate is not None, tail, qkv.device)
+        _chk(lib().orbit2_attn_fwd_ld(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo), _p(gate),
+                                      *_queue(tail, qkv.device)), "orbit2_attn_fwd_ld")
     return out, lse
 
 
@@ -530,8 +514,8 @@ def attn_fwd_f32(qkv, B, L, H, d, drop_p=0.0, flags=0, out=None):
 
 
 def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0, gate=None, tail_queue=None):
-    """gate: fp32 [B] path gate (orbit2_attn_bwd_gated): dqkv of a sample whose entry is 0.0 may be stored as zeros
-    tail_queue: as in gemm (orbit2_attn_bwd_tq)"""
+    """gate: fp32 [B] path gate (orbit2_attn_bwd_ld): dqkv of a sample whose entry is 0.0 may be stored as zeros
+    tail_queue: as in gemm"""
     tail = _tail_arg(tail_queue)
     _attn_gate(gate, B)
     _dev_rows(qkv, BF, "qkv"); _dev_rows(out, BF, "out"); _dev(dout, BF, "dout"); _dev(lse, F32, "lse")
@@ -544,9 +528,8 @@ def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0, gate=
     delta = torch.empty(lib().orbit2_attn_bwd_ws_floats(B, L, H), dtype=F32, device=qkv.device)
     # algorithmic: 2x the forward's FLOPs (recompute not credited); qkv, out, dout read once, dqkv written once
     with _timed("attn_bwd", 8.0 * B * H * L * L * d, 2.0 * 8 * B * L * H * d + 8.0 * B * H * L):
-        _call_entry("orbit2_attn_bwd_ld", "orbit2_attn_bwd_gated", "orbit2_attn_bwd_tq",
-                    (_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo)),
-                    (_p(gate),), gate is not None, tail, qkv.device)
+        _chk(lib().orbit2_attn_bwd_ld(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, L, H, d, drop_p, seed, int(flags),
+                                      int(ldq), int(ldo), _p(gate), *_queue(tail, qkv.device)), "orbit2_attn_bwd_ld")
     return dqkv
 
 

@@ -209,7 +209,7 @@ def _gelu_saved_dtype(p):
 
 # Tail queue: the one-workgroup-per-CU kernels hand the last rounds of their tiles out by ticket, so that an XCD that
 # is ahead takes more of them.  The library sizes the tail and leaves small launches, other kernel families and other devices
-# static.  ORBIT2_TAIL_QUEUE=0: the plain entries everywhere (A/B timing; the results are the same bits).
+# static.  ORBIT2_TAIL_QUEUE=0: the plain calls everywhere (A/B timing; the results are the same bits).
 _TQ = dict(tail_queue=True) if _os.environ.get("ORBIT2_TAIL_QUEUE", "1") != "0" else {}
 
 
@@ -301,43 +301,64 @@ def _dw_balance_plan(shapes, S, slots=256):
     return plan if need == 0 else None
 
 
-def _dw_balance(problems):
-    """(problems for ONE grouped launch, [(parts, S, rows, K, destination rows, beta)] to sum afterwards): see _dw_balance_plan.
-    Applies to whole-tile bf16 problems over one long token range; anything else is returned unchanged."""
-    S = _DW_BALANCE
-    if S < 2 or len(problems) < 2:
-        return problems, []
-    M = problems[0][5]
-    ok = all(p[5] == M and p[3] % 256 == 0 and p[4] % 256 == 0 and p[2].dtype == BF and p[0].dim() == 2 and p[1].dim() == 2
-             for p in problems) and M % (S * 64) == 0 and M // S >= 32768
-    if not ok:
-        return problems, []
-    plan = _dw_balance_plan([(p[3] // 256, p[4] // 256) for p in problems], S)
+def _dw_balance_units(shapes, S, gate_rows=None):
+    """The grouped weight-gradient launch on integers alone.  shapes: [(N, K, M)] = dW[N, K] over M tokens; S: the token split of
+    the tail tiles (see _dw_balance_plan); gate_rows: tokens per entry of the problems' K gates (one number for all, one per
+    problem, or None: no gate).  Returns the launch's problems in launch order as units (i, n0, n1, m0, m1, g0): rows [n0, n1) of
+    problem i's output over tokens [m0, m1), with the K gate from entry g0 on (None: without a gate).  Full-length units come
+    first (they fill whole rounds), then the part-length ones slice by slice.  A slice of the tokens takes its own entries of the
+    gate when it holds whole entries, else none.  The group stays unsplit -- one whole unit per problem -- unless it is at least
+    2 whole-tile problems over one token range that S slices of >= 32768 tokens divide into whole K-tiles, _dw_balance_plan
+    finds a cut, and the result is no more than GEMM_MAX_GROUP problems."""
+    per = list(gate_rows) if isinstance(gate_rows, (list, tuple)) else [gate_rows] * len(shapes)
+    whole = [(i, 0, N, 0, M, 0 if per[i] else None) for i, (N, K, M) in enumerate(shapes)]
+    if S < 2 or len(shapes) < 2:
+        return whole
+    M = shapes[0][2]
+    if not (all(m == M and N % 256 == 0 and K % 256 == 0 for N, K, m in shapes) and M % (S * 64) == 0 and M // S >= 32768):
+        return whole
+    plan = _dw_balance_plan([(N // 256, K // 256) for N, K, _ in shapes], S)
     if plan is None:
-        return problems, []
-    full, split, sums = [], [[] for _ in range(S)], []
-    cut = {i: (r0, r) for i, r0, r in plan}
+        return whole
+    cut = {i: (256 * r0, 256 * (r0 + r)) for i, r0, r in plan}
     Mc = M // S
-    for i, (dy, x, out, N, K, M_, lda, ldb, ldc, kw) in enumerate(problems):
+    full, split = [], [[] for _ in range(S)]
+    for i, unit in enumerate(whole):
         if i not in cut:
-            full.append(problems[i])
+            full.append(unit)
             continue
-        r0, r = cut[i]
-        n0, n1 = 256 * r0, 256 * (r0 + r)
-        if r0 > 0:                                   # the problem's first tile rows stay full-length
-            full.append((dy[:, :n0], x, out[:n0], n0, K, M_, lda, ldb, ldc, kw))
-        parts = torch.empty(S, n1 - n0, K, dtype=BF, device=dy.device)      # bf16 partials, summed in fp32 by orbit2_batch_sum
-        kg = kw.get("kgate")               # a slice of the tokens takes its own entries of the K gate (whole samples per slice only)
+        n0, n1 = cut[i]
+        if n0 > 0:                                   # the problem's first tile rows stay full-length
+            full.append((i, 0, n0) + unit[3:])
         for q in range(S):
-            kwq = dict(a_kc=False, b_kc=False)
-            if kg is not None and Mc % kg[1] == 0:
-                kwq["kgate"] = (kg[0][q * (Mc // kg[1]):(q + 1) * (Mc // kg[1])], kg[1])
-            split[q].append((dy[q * Mc:(q + 1) * Mc, n0:n1], x[q * Mc:(q + 1) * Mc], parts[q], n1 - n0, K, Mc, lda, ldb, K, kwq))
-        sums.append((parts, S, n1 - n0, K, out[n0:n1], kw.get("beta", 0.0)))
-    probs = full + [u for q in range(S) for u in split[q]]       # full-length tiles first (whole rounds), then slice by slice
-    if len(probs) > _hip.GEMM_MAX_GROUP:
+            split[q].append((i, n0, n1, q * Mc, (q + 1) * Mc, q * (Mc // per[i]) if per[i] and Mc % per[i] == 0 else None))
+    units = full + [u for q in range(S) for u in split[q]]
+    return units if len(units) <= _hip.GEMM_MAX_GROUP else whole
+
+
+def _dw_balance(problems):
+    """(problems for ONE grouped launch, [(parts, S, rows, K, destination rows, beta)] to sum afterwards): the units of
+    _dw_balance_units on the problems' tensors.  Applies to bf16 problems on 2-D operands; anything else is returned unchanged."""
+    S = _DW_BALANCE
+    if not all(p[2].dtype == BF and p[0].dim() == 2 and p[1].dim() == 2 for p in problems):
         return problems, []
-    return probs, sums
+    kgs = [p[9].get("kgate") for p in problems]
+    units = _dw_balance_units([(p[3], p[4], p[5]) for p in problems], S, [kg and kg[1] for kg in kgs])
+    probs, parts = [], {}
+    for i, n0, n1, m0, m1, g0 in units:
+        dy, x, out, N, K, M, lda, ldb, ldc, kw = problems[i]
+        if (n0, n1, m0, m1) == (0, N, 0, M):
+            probs.append(problems[i])
+        elif (m0, m1) == (0, M):
+            probs.append((dy[:, n0:n1], x, out[n0:n1], n1 - n0, K, M, lda, ldb, ldc, kw))
+        else:
+            if i not in parts:                       # bf16 partials, summed in fp32 by orbit2_batch_sum
+                parts[i] = (torch.empty(S, n1 - n0, K, dtype=BF, device=dy.device), S, n1 - n0, K, out[n0:n1], kw.get("beta", 0.0))
+            kwq = dict(a_kc=False, b_kc=False)
+            if g0 is not None:
+                kwq["kgate"] = (kgs[i][0][g0:g0 + (m1 - m0) // kgs[i][1]], kgs[i][1])
+            probs.append((dy[m0:m1, n0:n1], x[m0:m1], parts[i][0][m0 // (m1 - m0)], n1 - n0, K, m1 - m0, lda, ldb, K, kwq))
+    return probs, list(parts.values())
 
 
 class _DwBatch:

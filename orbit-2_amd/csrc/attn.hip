@@ -117,7 +117,7 @@ __device__ __forceinline__ void attn_tile_coords(int nq, int H, int& qt, int& he
   attn_id_coords(o2_xcd_range_id((int)blockIdx.x, (int)gridDim.x), nq, H, qt, head, b);      // (tail_queue.h: the remap)
 }
 
-// The walk of the GATED kernels (path gate, include/orbit2_hip.h: orbit2_attn_fwd_gated): the SAMPLE fastest among the (sample,
+// The walk of the GATED kernels (path gate, include/orbit2_hip.h: orbit2_attn_fwd_ld): the SAMPLE fastest among the (sample,
 // head) pairs, so that an XCD's contiguous range holds a few heads of EVERY sample instead of every head of a few samples.
 // Workgroup b runs on XCD b & 7 whatever the others are doing: with attn_tile_coords a dropped sample empties one XCD's queue and
 // the launch still lasts as long as the seven full ones (measured: profiles/r07_path_gate_ab.txt, the first gated build's attention
@@ -646,7 +646,7 @@ static inline bool attn_w4_range_ok(int L, int ldq, int ldo) {
   const uint64_t lim = 1ull << 31;
   return (uint64_t)(L + 64) * (uint64_t)ldq * 2ull < lim && (uint64_t)(L + 64) * (uint64_t)ldo * 2ull < lim;
 }
-// Path gate of the generated kernels (include/orbit2_hip.h: orbit2_attn_fwd_gated): the zero-fill a workgroup of a dropped sample
+// Path gate of the generated kernels (include/orbit2_hip.h: orbit2_attn_fwd_ld): the zero-fill a workgroup of a dropped sample
 // makes in place of its work -- `rows` token rows of 128 elements (256 bytes: 16 lanes x 16 bytes per row, 16 rows per step) at
 // row pitch ld.
 __device__ __forceinline__ void attn_gate_zero_rows(bf16_t* __restrict__ p, int rows, size_t ld, int tid) {
@@ -1884,7 +1884,7 @@ static bool attn_w4_ok(int d, int L, int flags, int ldq, int ldo) {
 #define O2_TQ_ROUNDS_ATTN_FWD 0
 #define O2_TQ_ROUNDS_ATTN_BWD 4
 
-// gate: the path gate of the _gated / _tq entries; sched / tail_arg: the counter and `tail` of the _tq entries (nullptr: none)
+// gate: the path gate of the entries; sched / tail_arg: their counter and `tail` (nullptr or tail_arg < 0: no queue)
 static AttnPlan attn_plan(int d, int L, int B, int H, int flags, int ldq, int ldo, float drop_p, const float* gate,
                           const void* sched, int tail_arg) {
   AttnPlan p;
@@ -1955,10 +1955,10 @@ template <class F> static void attn_with_variant(int d, int nw, bool drop, bool 
       o2_with_flags([&](auto DR) { hipLaunchKernelGGL((PLAIN<DR>), PASS.grid, PASS.block, 0, s, __VA_ARGS__); }, p.drop);        \
   } while (0)
 
-// gate: the path gate of orbit2_attn_fwd_gated, sched / tail_arg: the tail queue of orbit2_attn_fwd_tq (nullptr: none)
+// gate: the path gate, sched / tail_arg: the tail queue of orbit2_attn_fwd_ld (nullptr: none)
 static int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
-                           uint64_t seed, int flags, int ldq, int ldo, const float* gate, void* stream,
-                           unsigned int* sched = nullptr, int tail_arg = -1) {
+                           uint64_t seed, int flags, int ldq, int ldo, const float* gate, unsigned int* sched, int tail_arg,
+                           void* stream) {
   int rc = attn_check(qkv, out, B, L, H, d, drop_p);
   if (rc) return rc;
   if (!lse || ldo < H * d || (ldo & 7) || ldq < 3 * H * d || (ldq & 7)) return O2_ERR_ARG;
@@ -1981,13 +1981,10 @@ static int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int L,
   O2_CHECK_LAUNCH();
   return O2_OK;
 }
-extern "C" int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
-                                  uint64_t seed, int flags, int ldq, int ldo, void* stream) {
-  return attn_fwd_launch(qkv, out, lse, B, L, H, d, drop_p, seed, flags, ldq, ldo, nullptr, stream);
-}
-extern "C" int orbit2_attn_fwd_gated(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p,
-                                     uint64_t seed, int flags, int ldq, int ldo, const float* gate, void* stream) {
-  return attn_fwd_launch(qkv, out, lse, B, L, H, d, drop_p, seed, flags, ldq, ldo, gate, stream);
+extern "C" int orbit2_attn_fwd_ld(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p, uint64_t seed,
+                                  int flags, int ldq, int ldo, const float* gate, void* sched_ws, int tail, void* stream) {
+  if (!o2_sched_ok(sched_ws, tail)) return O2_ERR_ARG;
+  return attn_fwd_launch(qkv, out, lse, B, L, H, d, drop_p, seed, flags, ldq, ldo, gate, (unsigned int*)sched_ws, tail, stream);
 }
 
 static int attn_lpad(int L) { return ((L + 63) / 64) * 64 + 64; }     // padded row stride of the statistics tables
@@ -1999,7 +1996,7 @@ extern "C" int64_t orbit2_attn_bwd_ws_floats(int B, int L, int H) {
 
 static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                            void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq,
-                           int ldo, const float* gate, void* stream, unsigned int* sched = nullptr, int tail_arg = -1) {
+                           int ldo, const float* gate, unsigned int* sched, int tail_arg, void* stream) {
   int rc = attn_check(qkv, out, B, L, H, d, drop_p);
   if (rc) return rc;
   if (!dout || !lse || !delta || !dqkv || ldo < H * d || (ldo & 7) || ldq < 3 * H * d || (ldq & 7)) return O2_ERR_ARG;
@@ -2050,27 +2047,10 @@ static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, c
   return O2_OK;
 }
 #undef O2_W4_PASS
-extern "C" int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
-                                  void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq,
-                                  int ldo, void* stream) {
-  return attn_bwd_launch(qkv, out, dout, lse, delta, dqkv, B, L, H, d, drop_p, seed, flags, ldq, ldo, nullptr, stream);
-}
-extern "C" int orbit2_attn_bwd_gated(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
-                                     void* dqkv, int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq,
-                                     int ldo, const float* gate, void* stream) {
-  return attn_bwd_launch(qkv, out, dout, lse, delta, dqkv, B, L, H, d, drop_p, seed, flags, ldq, ldo, gate, stream);
-}
-
-// The same launches with a tail queue for the generated kernels (csrc/tail_queue.h); gate may be NULL
-extern "C" int orbit2_attn_fwd_tq(const void* qkv, void* out, float* lse, int B, int L, int H, int d, float drop_p, uint64_t seed,
-                                  int flags, int ldq, int ldo, const float* gate, void* sched_ws, int tail, void* stream) {
-  if (!o2_sched_ok(sched_ws)) return O2_ERR_ARG;
-  return attn_fwd_launch(qkv, out, lse, B, L, H, d, drop_p, seed, flags, ldq, ldo, gate, stream, (unsigned int*)sched_ws, tail);
-}
-extern "C" int orbit2_attn_bwd_tq(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+extern "C" int orbit2_attn_bwd_ld(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                                   int B, int L, int H, int d, float drop_p, uint64_t seed, int flags, int ldq, int ldo,
                                   const float* gate, void* sched_ws, int tail, void* stream) {
-  if (!o2_sched_ok(sched_ws)) return O2_ERR_ARG;
-  return attn_bwd_launch(qkv, out, dout, lse, delta, dqkv, B, L, H, d, drop_p, seed, flags, ldq, ldo, gate, stream,
-                         (unsigned int*)sched_ws, tail);
+  if (!o2_sched_ok(sched_ws, tail)) return O2_ERR_ARG;
+  return attn_bwd_launch(qkv, out, dout, lse, delta, dqkv, B, L, H, d, drop_p, seed, flags, ldq, ldo, gate,
+                         (unsigned int*)sched_ws, tail, stream);
 }

@@ -87,7 +87,7 @@ struct Epi {
   float rs_tile;       // (kernel-internal) the tile's row scale when the epilogue kind is 2
   int rows_per_gate;   // rows of one entry of `gate`
   float* colsum_ws;    // kind 3 only: fp32 [M / 256][N], row t = column sums of the bf16-rounded output over tile row t
-  // path gate (orbit2_gemm_bf16_gated; a hint): an output tile whose rows all lie in one entry with gate[entry] == 0.0f -- a
+  // path gate (orbit2_gemm_bf16; a hint): an output tile whose rows all lie in one entry with gate[entry] == 0.0f -- a
   // sample whose branch DropPath dropped -- may skip its contraction and store what annihilated inputs give: zeros (C, save_pre,
   // save_dact, its colsum_ws row), or the residual rows when the row scale is the gate.  A kernel that ignores it is correct.
   const float* gate;
@@ -490,7 +490,7 @@ struct GProb {
   const bf16_t* B;
   int M, N, K, lda, ldb, tiles_m, tiles_n, tile_end;
   Epi epi;
-  // K gate of a weight gradient (orbit2_gemm_bf16_grouped_gated; a hint): entry e covers rows e * k_per_gate onwards of the
+  // K gate of a weight gradient (orbit2_gemm_bf16_grouped; a hint): entry e covers rows e * k_per_gate onwards of the
   // CONTRACTION (the tokens of one sample); kgate[e] == 0.0f says that the dY rows of that range are zeros, and the 4-wave TN
   // kernel sweeps the kept ranges only
   const float* kgate;
@@ -1519,7 +1519,7 @@ static bool gemm_group_fills_chip(long t256) { return t256 >= 192; }
 #define O2_TQ_ROUNDS_GROUP 4
 constexpr int w4_tail_rounds(int form, int ek) { return (form == 1 && ek == 0) || (form == 0 && ek == 2) ? 2 : 0; }
 
-// sched / tail_arg: the counter and the `tail` of orbit2_gemm_bf16_tq (nullptr: no queue; o2_tail_plan_launch)
+// sched / tail_arg: the counter and the `tail` of orbit2_gemm_bf16 (nullptr or tail_arg < 0: no queue; o2_tail_plan_launch)
 static int gemm_plan(const orbit2_gemm_args* a, const Epi& e, const void* sched, int tail_arg, GemmPlan& p) {
   p = GemmPlan{};
   p.a_kc = a->a_kc != 0;
@@ -1579,7 +1579,7 @@ static int gemm_plan(const orbit2_gemm_args* a, const Epi& e, const void* sched,
 }
 
 // a group (n >= 2): the kernel family for all of it, its tail and grid, and in g every problem with its tile range, its K gate
-// where it is honoured (kgates / k_per_gate of orbit2_gemm_bf16_grouped_gated; nullptr: none) and the pacing mode
+// where it is honoured (kgates / k_per_gate of orbit2_gemm_bf16_grouped; nullptr: none) and the pacing mode
 struct GemmGroupPlan {
   GemmFamily family;
   O2TailPlan tail;          // tail.tail > 0: gemm256w_grouped_tq_kernel takes the launch (GEMM_256W); 0: static
@@ -1640,10 +1640,9 @@ static int gemm_group_plan(const orbit2_gemm_args* args, int n, const float* con
   return O2_OK;
 }
 
-// one launch; gate / rows_per_gate: the path gate of orbit2_gemm_bf16_gated, sched / tail_arg: the tail queue of orbit2_gemm_bf16_tq
-// (nullptr: none)
-static int gemm_launch(const orbit2_gemm_args* a, const float* gate, int rows_per_gate, void* stream, unsigned int* sched = nullptr,
-                       int tail_arg = -1) {
+// one launch; gate / rows_per_gate: the path gate, sched / tail_arg: the tail queue of orbit2_gemm_bf16 (nullptr: none)
+static int gemm_launch(const orbit2_gemm_args* a, const float* gate, int rows_per_gate, unsigned int* sched, int tail_arg,
+                       void* stream) {
   Epi e;
   GemmPlan p;
   int rc = gemm_make_epi(a, gate, rows_per_gate, e);
@@ -1683,17 +1682,10 @@ static int gemm_launch(const orbit2_gemm_args* a, const float* gate, int rows_pe
   return O2_OK;
 }
 
-extern "C" int orbit2_gemm_bf16(const orbit2_gemm_args* a, void* stream) { return gemm_launch(a, nullptr, 0, stream); }
-
-extern "C" int orbit2_gemm_bf16_gated(const orbit2_gemm_args* a, const float* gate, int rows_per_gate, void* stream) {
-  if (gate && rows_per_gate <= 0) return O2_ERR_ARG;
-  return gemm_launch(a, gate, rows_per_gate, stream);
-}
-
-extern "C" int orbit2_gemm_bf16_tq(const orbit2_gemm_args* a, const float* gate, int rows_per_gate, void* sched_ws, int tail,
-                                   void* stream) {
-  if (!o2_sched_ok(sched_ws) || (gate && rows_per_gate <= 0)) return O2_ERR_ARG;
-  return gemm_launch(a, gate, rows_per_gate, stream, (unsigned int*)sched_ws, tail);
+extern "C" int orbit2_gemm_bf16(const orbit2_gemm_args* a, const float* gate, int rows_per_gate, void* sched_ws, int tail,
+                                void* stream) {
+  if (!o2_sched_ok(sched_ws, tail) || (gate && rows_per_gate <= 0)) return O2_ERR_ARG;
+  return gemm_launch(a, gate, rows_per_gate, (unsigned int*)sched_ws, tail, stream);
 }
 
 extern "C" int orbit2_gemm_bf16_colsum_rows(const orbit2_gemm_args* a) {
@@ -1704,12 +1696,12 @@ extern "C" int orbit2_gemm_bf16_colsum_rows(const orbit2_gemm_args* a) {
   return p.fuses_colsum ? a->M / 256 : 0;
 }
 
-// kgates / k_per_gate: the K gates of orbit2_gemm_bf16_grouped_gated, sched / tail_arg: the tail queue of
-// orbit2_gemm_bf16_grouped_tq (nullptr: none).  One problem is the single launch (with the counter, without a gate)
-static int gemm_group_launch(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate, void* stream,
-                             unsigned int* sched = nullptr, int tail_arg = -1) {
+// kgates / k_per_gate: the K gates, sched / tail_arg: the tail queue of orbit2_gemm_bf16_grouped (nullptr: none).  One problem
+// is the single launch (with the counter, without a gate)
+static int gemm_group_launch(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate,
+                             unsigned int* sched, int tail_arg, void* stream) {
   if (!args || n <= 0 || n > ORBIT2_GEMM_MAX_GROUP) return O2_ERR_ARG;
-  if (n == 1) return gemm_launch(args, nullptr, 0, stream, sched, tail_arg);
+  if (n == 1) return gemm_launch(args, nullptr, 0, sched, tail_arg, stream);
   for (int i = 0; i < n; ++i)
     if (args[i].colsum_ws) return O2_ERR_UNSUPPORTED;      // single launches only (orbit2_gemm_bf16_colsum_rows)
   GemmGroupPlan p;
@@ -1732,18 +1724,10 @@ static int gemm_group_launch(const orbit2_gemm_args* args, int n, const float* c
   return O2_OK;
 }
 
-extern "C" int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, void* stream) {
-  return gemm_group_launch(args, n, nullptr, nullptr, stream);
-}
-extern "C" int orbit2_gemm_bf16_grouped_gated(const orbit2_gemm_args* args, int n, const float* const* kgates,
-                                              const int* k_per_gate, void* stream) {
-  return gemm_group_launch(args, n, kgates, k_per_gate, stream);
-}
-
-extern "C" int orbit2_gemm_bf16_grouped_tq(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate,
-                                           void* sched_ws, int tail, void* stream) {
-  if (!o2_sched_ok(sched_ws)) return O2_ERR_ARG;
-  return gemm_group_launch(args, n, kgates, k_per_gate, stream, (unsigned int*)sched_ws, tail);
+extern "C" int orbit2_gemm_bf16_grouped(const orbit2_gemm_args* args, int n, const float* const* kgates, const int* k_per_gate,
+                                        void* sched_ws, int tail, void* stream) {
+  if (!o2_sched_ok(sched_ws, tail)) return O2_ERR_ARG;
+  return gemm_group_launch(args, n, kgates, k_per_gate, (unsigned int*)sched_ws, tail, stream);
 }
 
 // split-K plan of the skinny table products: enough slabs to put >= ~1024 workgroups on the chip, >= 4 staged k-steps each

@@ -158,6 +158,6 @@ static inline O2TailPlan o2_tail_plan_launch(long long T, const void* sched, int
   if (!sched || tail_arg < 0) return o2_tail_plan(T, 0);
   return o2_tail_plan_arg(T, tail_arg, rounds, tail_arg == 0 ? o2_tail_slots() : 0);
 }
-// the counter the _tq entry points take: one 4-byte aligned word
-static inline bool o2_sched_ok(const void* sched_ws) { return sched_ws && !((uintptr_t)sched_ws & 3); }
+// the counter and `tail` the entry points take: one 4-byte aligned word, which only a static call (tail < 0) may leave out
+static inline bool o2_sched_ok(const void* sched_ws, int tail) { return sched_ws ? !((uintptr_t)sched_ws & 3) : tail < 0; }
 #endif

@@ -157,11 +157,13 @@ orbit2_gemm_args gemm_args(const KV& kv) {          // pointers are fake address
 //                             colsum_ws is set when the first call returned rows)
 // group n=N lines=L [null=1]: the next L lines ("g K=V...") are the problems; orbit2_gemm_bf16_grouped(args, N)
 // afwd / abwd K=V...        : orbit2_attn_fwd_ld / orbit2_attn_bwd_ld
-// Each of them takes the path gate and the tail queue, and calls the entry climate_learn/_hip.py calls for that combination:
-//   gate=ADDR rows_per_gate=N : the _gated entry (attention: gate=ADDR alone); a "g" line: kgate=ADDR k_per_gate=N, and the group
-//                               goes to orbit2_gemm_bf16_grouped_gated when any of its lines names one (the others: NULL, 0)
-//   sched=ADDR tail=N         : the _tq entry, with the gate or NULL (tail: 0 sized by the library, > 0 that many tiles, < 0 static)
-// A key that is present selects the entry, whatever its value (sched=0: the _tq entry with a NULL counter).
+// Each of them takes the path gate and the tail queue as climate_learn/_hip.py passes them:
+//   gate=ADDR rows_per_gate=N : the path gate (attention: gate=ADDR alone); without the key: NULL.  A "g" line: kgate=ADDR
+//                               k_per_gate=N, and the group gets the two arrays when any of its lines names one (the others:
+//                               NULL, 0); otherwise NULL, NULL
+//   sched=ADDR tail=N         : the counter and the tail (0 sized by the library, > 0 that many tiles, < 0 static); without the
+//                               sched key: NULL, -1, the plain call
+// The sched key decides, whatever its value (sched=0 tail=0: a NULL counter with a tail, which the entries refuse).
 int main() {
   std::string line;
   while (std::getline(std::cin, line)) {
@@ -170,9 +172,8 @@ int main() {
     if (!(in >> cmd) || cmd[0] == '#') continue;
     const KV kv = parse(in);
     printf("> %s\n", line.c_str());
-    const bool gated = kv.count("gate") != 0, queued = kv.count("sched") != 0;
     const float* gate = getp<const float>(kv, "gate", 0);
-    const int rows_per_gate = (int)geti(kv, "rows_per_gate", 0), tail = (int)geti(kv, "tail", 0);
+    const int rows_per_gate = (int)geti(kv, "rows_per_gate", 0), tail = kv.count("sched") ? (int)geti(kv, "tail", 0) : -1;
     void* sched = getp(kv, "sched", 0);
     int rc = 0;
     if (cmd == "gemm") {
@@ -181,8 +182,7 @@ int main() {
       const int rows = orbit2_gemm_bf16_colsum_rows(pa);
       printf("colsum_rows=%d\n", rows);
       if (geti(kv, "want_colsum", 0) && rows > 0) a.colsum_ws = (float*)0x70000;   // as climate_learn/_hip.py:gemm does
-      rc = queued ? orbit2_gemm_bf16_tq(pa, gate, gated ? rows_per_gate : 0, sched, tail, nullptr)
-           : gated ? orbit2_gemm_bf16_gated(pa, gate, rows_per_gate, nullptr) : orbit2_gemm_bf16(pa, nullptr);
+      rc = orbit2_gemm_bf16(pa, gate, rows_per_gate, sched, tail, nullptr);
     } else if (cmd == "group") {
       std::vector<orbit2_gemm_args> v(16);
       const float* kgates[16] = {};
@@ -201,8 +201,7 @@ int main() {
       }
       const orbit2_gemm_args* pv = geti(kv, "null", 0) ? nullptr : v.data();
       const int n = (int)geti(kv, "n", 0);
-      rc = queued ? orbit2_gemm_bf16_grouped_tq(pv, n, kgated ? kgates : nullptr, kgated ? kper : nullptr, sched, tail, nullptr)
-           : kgated ? orbit2_gemm_bf16_grouped_gated(pv, n, kgates, kper, nullptr) : orbit2_gemm_bf16_grouped(pv, n, nullptr);
+      rc = orbit2_gemm_bf16_grouped(pv, n, kgated ? kgates : nullptr, kgated ? kper : nullptr, sched, tail, nullptr);
     } else if (cmd == "afwd") {
       void *qkv = getp(kv, "qkv", 0x10000), *out = getp(kv, "out", 0x20000);
       float* lse = getp<float>(kv, "lse", 0x30000);
@@ -210,9 +209,7 @@ int main() {
                 ldq = geti(kv, "ldq", 0), ldo = geti(kv, "ldo", 0);
       const float p = (float)getf(kv, "drop_p", 0.0);
       const uint64_t seed = (uint64_t)geti(kv, "seed", 0);
-      rc = queued ? orbit2_attn_fwd_tq(qkv, out, lse, B, L, H, d, p, seed, flags, ldq, ldo, gate, sched, tail, nullptr)
-           : gated ? orbit2_attn_fwd_gated(qkv, out, lse, B, L, H, d, p, seed, flags, ldq, ldo, gate, nullptr)
-                   : orbit2_attn_fwd_ld(qkv, out, lse, B, L, H, d, p, seed, flags, ldq, ldo, nullptr);
+      rc = orbit2_attn_fwd_ld(qkv, out, lse, B, L, H, d, p, seed, flags, ldq, ldo, gate, sched, tail, nullptr);
     } else if (cmd == "abwd") {
       void *qkv = getp(kv, "qkv", 0x10000), *out = getp(kv, "out", 0x20000), *dout = getp(kv, "dout", 0x40000),
            *dqkv = getp(kv, "dqkv", 0x60000);
@@ -221,9 +218,7 @@ int main() {
                 ldq = geti(kv, "ldq", 0), ldo = geti(kv, "ldo", 0);
       const float p = (float)getf(kv, "drop_p", 0.0);
       const uint64_t seed = (uint64_t)geti(kv, "seed", 0);
-      rc = queued ? orbit2_attn_bwd_tq(qkv, out, dout, lse, delta, dqkv, B, L, H, d, p, seed, flags, ldq, ldo, gate, sched, tail, nullptr)
-           : gated ? orbit2_attn_bwd_gated(qkv, out, dout, lse, delta, dqkv, B, L, H, d, p, seed, flags, ldq, ldo, gate, nullptr)
-                   : orbit2_attn_bwd_ld(qkv, out, dout, lse, delta, dqkv, B, L, H, d, p, seed, flags, ldq, ldo, nullptr);
+      rc = orbit2_attn_bwd_ld(qkv, out, dout, lse, delta, dqkv, B, L, H, d, p, seed, flags, ldq, ldo, gate, sched, tail, nullptr);
     } else {
       fprintf(stderr, "unknown command: %s\n", cmd.c_str());
       return 2;

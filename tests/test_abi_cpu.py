@@ -11,9 +11,11 @@ import pytest
 from tests.conftest import ROOT
 
 HEADER = os.path.join(ROOT, "include", "orbit2_hip.h")
-# the forwarding entries ABI 7 removed: each was a one-line call of the entry that replaced it
+# the forwarding entries ABI 7 and ABI 8 removed: each was a one-line call of the entry that replaced it
 REMOVED = ("orbit2_attn_fwd", "orbit2_attn_fwd_ex", "orbit2_attn_bwd", "orbit2_attn_bwd_ex", "orbit2_layernorm_fwd",
-           "orbit2_sgemm_f32")
+           "orbit2_sgemm_f32",
+           "orbit2_gemm_bf16_gated", "orbit2_gemm_bf16_tq", "orbit2_gemm_bf16_grouped_gated", "orbit2_gemm_bf16_grouped_tq",
+           "orbit2_attn_fwd_gated", "orbit2_attn_fwd_tq", "orbit2_attn_bwd_gated", "orbit2_attn_bwd_tq")
 
 
 def _header():
@@ -60,7 +62,7 @@ def test_library_exports_exactly_the_declared_symbols():
     assert len(names) >= 25
     for n in names:
         assert hasattr(lib, n), "missing export " + n
-    assert lib.orbit2_abi_version() == 7
+    assert lib.orbit2_abi_version() == 8
     # ... and the other way: the library exports nothing the header does not declare, none of the removed entries among it
     exported = _exports(_hip.LIB_PATH)
     assert exported == set(_prototypes()), "exported, not declared: %s; declared, not exported: %s" % (
@@ -88,11 +90,11 @@ def test_binding_declares_every_prototype_as_the_header_does():
 def test_binding_constants_match_the_header():
     from climate_learn import _hip
     defines = dict(re.findall(r"^#define\s+ORBIT2_(\w+)\s+(\d+)", _header(), flags=re.M))
-    assert int(defines["ABI_VERSION"]) == _hip.ABI_VERSION == 7
+    assert int(defines["ABI_VERSION"]) == _hip.ABI_VERSION == 8
     assert int(defines["GEMM_MAX_GROUP"]) == _hip.GEMM_MAX_GROUP
     flags = {k: int(v) for k, v in defines.items() if k.startswith("ATTN_")}
     assert flags and flags == {k: getattr(_hip, k) for k in dir(_hip) if k.startswith("ATTN_")}
-    assert _hip.lib().orbit2_abi_version() == 7
+    assert _hip.lib().orbit2_abi_version() == 8
 
 
 def test_load_refuses_another_abi_version(tmp_path):
@@ -169,4 +171,4 @@ def test_gemm_colsum_dispatch_is_host_logic():
                 args(131072, 12288, 3072, bias=True), args(131072, 12288, 3072, tile=256), args(131000, 12288, 3072)):
         assert lib.orbit2_gemm_bf16_colsum_rows(ctypes.byref(bad)) == 0
         bad.colsum_ws = 0x60000
-        assert lib.orbit2_gemm_bf16(ctypes.byref(bad), None) == -3
+        assert lib.orbit2_gemm_bf16(ctypes.byref(bad), None, 0, None, -1, None) == -3

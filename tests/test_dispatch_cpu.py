@@ -1,8 +1,8 @@
 """Which kernel runs: the selection in csrc/gemm.hip and csrc/attn.hip for the product's own calls, pinned on the CPU.
 
 tests/dispatch_recorder.hip includes both sources with hipLaunchKernelGGL redefined to print the kernel instantiation, grid, block
-and launch arguments (host-only build, no GPU).  Pinned are the entries the product calls under default settings -- the tail-queue
-entries (orbit2_*_tq) with a library-sized tail, the Block's calls with their path gate or K gate -- on the recorder's own device
+and launch arguments (host-only build, no GPU).  Pinned are the calls the product makes under default settings -- with a counter
+word and a library-sized tail, the Block's calls with their path gate or K gate -- on the recorder's own device
 shape (256 CUs on 8 XCCs), so the lines say which twin of a kernel runs, on which grid, with which gate and which tail.  The
 expected lines in tests/dispatch_expected.txt were recorded from the sources of the commit named in that file's header, never from
 the code under test: a product shape that falls from the 4-wave kernel to the 128-tile kernel, or from a generated attention kernel
@@ -71,36 +71,17 @@ def group(problems, n=None, **kw):
 
 # ---- the product's calls (climate_learn/_ops.py: BlockFn, ChainFn under res_slimvit's head, EmbedFn) ------------------------
 def _dw_group(problems, kgate=None):
-    """the grouped weight-gradient launch of _ops._DwBatch.flush for problems (N, K, M, lda, ldb) = dW[N, K] over M tokens:
-    _ops._dw_balance's slicing on shapes alone.  kgate = (address, tokens per entry): the K gate of every problem; a slice of the
-    tokens takes its own entries (fp32: 4 bytes each) when it holds whole samples"""
+    """the grouped weight-gradient launch of _ops._DwBatch.flush for problems (N, K, M, lda, ldb) = dW[N, K] over M tokens: the
+    units of _ops._dw_balance_units as recorder lines.  kgate = (address, tokens per entry): the K gate of every problem; a unit
+    that takes the gate from entry g0 on gets the address of that entry (fp32: 4 bytes each)"""
     from climate_learn import _ops
-    S = _ops._DW_BALANCE
-    M = problems[0][2]
-    kg = {} if kgate is None else dict(kgate=kgate[0], k_per_gate=kgate[1])
-    full = [dict(M=n, N=k, K=m, lda=lda, ldb=ldb, ldc=k, a_kc=0, b_kc=0, **kg) for n, k, m, lda, ldb in problems]
-    ok = len(problems) >= 2 and all(p[2] == M and p[0] % 256 == 0 and p[1] % 256 == 0 for p in problems) and \
-        M % (S * 64) == 0 and M // S >= 32768
-    plan = _ops._dw_balance_plan([(p[0] // 256, p[1] // 256) for p in problems], S) if ok else None
-    if plan is None:
-        return group(full, **TQ)
-    cut = {i: (r0, r) for i, r0, r in plan}
-    keep, split = [], [[] for _ in range(S)]
-    Mc = M // S
-    for i, (n, k, m, lda, ldb) in enumerate(problems):
-        if i not in cut:
-            keep.append(full[i])
-            continue
-        r0, r = cut[i]
-        if r0 > 0:
-            keep.append(dict(full[i], M=256 * r0))
-        for q in range(S):
-            kq = {}
-            if kgate is not None and Mc % kgate[1] == 0:
-                kq = dict(kgate=hex(int(kgate[0], 16) + 4 * q * (Mc // kgate[1])), k_per_gate=kgate[1])
-            split[q].append(dict(M=256 * r, N=k, K=Mc, lda=lda, ldb=ldb, ldc=k, a_kc=0, b_kc=0, **kq))
-    probs = keep + [u for q in range(S) for u in split[q]]
-    return group(probs if len(probs) <= 12 else full, **TQ)
+    units = _ops._dw_balance_units([p[:3] for p in problems], _ops._DW_BALANCE, kgate and kgate[1])
+    probs = []
+    for i, n0, n1, m0, m1, g0 in units:
+        n, k, m, lda, ldb = problems[i]
+        kg = {} if g0 is None else dict(kgate=hex(int(kgate[0], 16) + 4 * g0), k_per_gate=kgate[1])
+        probs.append(dict(M=n1 - n0, N=k, K=m1 - m0, lda=lda, ldb=ldb, ldc=k, a_kc=0, b_kc=0, **kg))
+    return group(probs, **TQ)
 
 
 def _dw_single(N, K, M, lda, ldb):
@@ -113,7 +94,7 @@ def _dw_single(N, K, M, lda, ldb):
 
 
 def product_calls(name, drop):
-    """what _ops passes under default settings: every call but a lone unsplit weight gradient through the tail-queue entry, and in
+    """what _ops passes under default settings: every call but a lone unsplit weight gradient with the tail queue, and in
     the dropout configurations (DropPath on) the Block's GEMMs and attention calls with the branch's scales as their gate"""
     from climate_learn import _ops
     D, heads, B, (h, w) = CONFIGS[name]
@@ -481,6 +462,24 @@ def test_the_gate_and_the_queue_do_not_move_the_selection(tmp_path):
             assert q[0] == p[0] and _untwinned(k) == pk and k != pk and bl == pbl and gr == "grid=%d" % (static_wgs + 2 * t), b
             want = prest.replace(" pace=1 ", " pace=0 ").replace(" pace=2 ", " pace=0 ") if static_wgs == 256 else prest
             assert rest == "%s 0x%x %d %d" % (want, int(SCHED, 16), static_wgs, t), b
+
+
+# ---- a counter and a tail go together --------------------------------------------------------------------------------------
+@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+def test_a_tail_without_a_counter_and_a_misaligned_counter_are_refused(tmp_path):
+    """every folded entry: tail >= 0 with a NULL counter, and a counter that is not 4-byte aligned at any tail (static included),
+    return O2_ERR_ARG (-1) before any launch"""
+    exe = build_recorder(CSRC, str(tmp_path / "dispatch_recorder"))
+    member = dict(M=3072, N=3072, K=32768, lda=3072, ldb=3072, ldc=3072, a_kc=0, b_kc=0)
+    attn = dict(B=2, L=512, H=4, d=128, flags=ATTN_Q_PRESCALED, ldq=1536, ldo=512)
+    for bad in (dict(sched=0, tail=0), dict(sched="0x9002", tail=-1)):
+        lines = [gemm(131072, 12288, 3072, 3072, 12288, 12288, b_kc=0, **bad)] + group([member] * 4, **bad) + \
+            [call("afwd", **attn, **bad), call("abwd", **attn, **bad)]
+        calls = _parse(record(exe, lines))
+        assert len(calls) == 4
+        assert all(rc == "rc=-1" and not launches for rc, launches in calls), bad
+    plain = [ln for b in _blocks(lines) for ln in b]             # the same four calls without the queue's keys do launch
+    assert all(rc == "rc=0" and launches for rc, launches in _parse(record(exe, plain)))
 
 
 if __name__ == "__main__":

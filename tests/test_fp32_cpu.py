@@ -53,10 +53,16 @@ def test_fp32_entries_are_declared_in_header_and_binding():
     for name in F32_ENTRIES:
         assert re.search(r"\bint %s\(" % name, hdr), name
         assert name in _hip.PROTOTYPES and hasattr(_hip.lib(), name), name
-    assert _hip.PROTOTYPES["orbit2_gemm_f32"] == _hip.PROTOTYPES["orbit2_gemm_bf16"]
-    assert _hip.PROTOTYPES["orbit2_attn_fwd_f32"] == _hip.PROTOTYPES["orbit2_attn_fwd_ld"]
+    # the fp32 entries keep the argument lists they were added with; each bf16 entry's list is the fp32 one with the hint
+    # parameters (gate, rows_per_gate, sched_ws, tail / gate, sched_ws, tail) inserted in front of the stream
+    I, F, U64, P, G = _hip._I, _hip._F, _hip._U64, _hip._P, _hip._G
+    gemm_f32, attn_f32 = (I, (G, P)), (I, (P, P, P, I, I, I, I, F, U64, I, I, I, P))
+    assert _hip.PROTOTYPES["orbit2_gemm_f32"] == gemm_f32
+    assert _hip.PROTOTYPES["orbit2_attn_fwd_f32"] == attn_f32
+    assert _hip.PROTOTYPES["orbit2_gemm_bf16"] == (I, gemm_f32[1][:-1] + (P, I, P, I) + gemm_f32[1][-1:])
+    assert _hip.PROTOTYPES["orbit2_attn_fwd_ld"] == (I, attn_f32[1][:-1] + (P, P, I) + attn_f32[1][-1:])
     assert _hip.PROTOTYPES["orbit2_layernorm_fwd_f32"] == _hip.PROTOTYPES["orbit2_layernorm_fwd_ld"]
-    assert _hip.ABI_VERSION == 7                                   # additive entries: the version did not move
+    assert _hip.ABI_VERSION == 8                                   # (the fp32 entries were additive at 7; 8 folded the bf16 entries)
 
 
 def test_fp32_wrappers_refuse_cpu_and_wrong_dtype():

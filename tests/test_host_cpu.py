@@ -181,6 +181,36 @@ def test_weight_gradient_group_balance_plan():
     assert _dw_balance_plan([(36, 12), (12, 12), (48, 12), (12, 48)], 0) is None
 
 
+def test_weight_gradient_group_units():
+    """the grouped weight-gradient launch on integers (_ops._dw_balance_units): which rows of which problem over which tokens, in
+    launch order, and which entries of the K gate a slice of the tokens takes"""
+    from climate_learn._ops import _dw_balance_plan, _dw_balance_units
+
+    def block(D, M):                                              # (N, K, M) of fc2, fc1, proj, qkv: the order BlockFn queues them in
+        return [(D, 4 * D, M), (4 * D, D, M), (D, D, M), (3 * D, D, M)]
+
+    shapes, M, S = block(3072, 131072), 131072, 4                 # interm_1b: 1728 tiles = 6.75 rounds
+    assert _dw_balance_plan([(n // 256, k // 256) for n, k, _ in shapes], S) == [(2, 0, 12), (3, 32, 4)]
+    units = _dw_balance_units(shapes, S)
+    assert len(units) == 11
+    assert units[:3] == [(0, 0, 3072, 0, M, None), (1, 0, 12288, 0, M, None), (3, 0, 8192, 0, M, None)]      # full-length first
+    for q in range(S):                                            # then slice by slice: all of proj, the last 4 tile rows of qkv
+        m0, m1 = 32768 * q, 32768 * (q + 1)
+        assert units[3 + 2 * q:5 + 2 * q] == [(2, 0, 3072, m0, m1, None), (3, 8192, 9216, m0, m1, None)]
+    # 8192 tokens per gate entry: a slice holds 4 whole entries and takes its own; 49152: no whole entries, no gate in the slices
+    gated = _dw_balance_units(shapes, S, 8192)
+    assert [u[:5] for u in gated] == [u[:5] for u in units]
+    assert [u[5] for u in gated] == [0, 0, 0] + [4 * q for q in range(S) for _ in range(2)]
+    assert gated == _dw_balance_units(shapes, S, [8192] * 4)
+    assert [u[5] for u in _dw_balance_units(shapes, S, 49152)] == [0, 0, 0] + [None] * 8
+    # too few tokens per slice: the group stays as it is, one whole unit per problem
+    for D, M in ((1024, 4096), (8192, 16384)):                    # interm_117m, interm_10b
+        shapes = block(D, M)
+        assert _dw_balance_plan([(n // 256, k // 256) for n, k, _ in shapes], S) is None
+        assert _dw_balance_units(shapes, S) == [(i, 0, n, 0, M, None) for i, (n, _, _) in enumerate(shapes)]
+        assert _dw_balance_units(shapes, S, M // 8) == [(i, 0, n, 0, M, 0) for i, (n, _, _) in enumerate(shapes)]
+
+
 def test_round_major_tile_ids_are_a_bijection():
     """mirror of csrc/gemm.hip:xcd_round_tile_id (block b runs on XCD b & 7; the 256 blocks of a round take 256 consecutive ids,
     each XCD a consecutive run of them) and of gemm256w_tile's id -> (tm, tn) walk incl. the column-major form of wide problems:

@@ -156,10 +156,7 @@ def _attn_call(fwd, gate, *args):
     from climate_learn import _hip
     lib = _hip.lib()
     stream = torch.cuda.current_stream().cuda_stream
-    if gate is None:
-        rc = (lib.orbit2_attn_fwd_ld if fwd else lib.orbit2_attn_bwd_ld)(*args, stream)
-    else:
-        rc = (lib.orbit2_attn_fwd_gated if fwd else lib.orbit2_attn_bwd_gated)(*args, gate.data_ptr(), stream)
+    rc = (lib.orbit2_attn_fwd_ld if fwd else lib.orbit2_attn_bwd_ld)(*args, None if gate is None else gate.data_ptr(), None, -1, stream)
     assert rc == 0
 
 

@@ -143,6 +143,29 @@ def test_grouped_weight_gradients_with_a_queued_tail():
     assert _ws_is_zero()
 
 
+def test_plain_calls_leave_the_counter_storage_alone():
+    """a call without tail_queue passes no counter: it neither allocates the device's counter buffer nor claims a word for its
+    stream -- a fresh stream here, whose claim would show"""
+    from climate_learn import _hip
+    rnd = _dev(34)
+    bufs, slots = dict(_hip._sched_bufs), dict(_hip._sched_slots)
+    blank = lambda: torch.full((256, 256), NAN, device="cuda", dtype=BF)
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        c = _hip.gemm(rnd(256, 64), rnd(256, 64), blank(), 256, 256, 64, 64, 64, 256, tile=260)
+        a, b, outs = rnd(256, 128), rnd(256, 128), [blank(), blank()]
+        _hip.gemm_grouped([(a, b, o, 256, 256, 128, 128, 128, 256, {}) for o in outs])
+        qkv = rnd(256, 3 * 128)
+        out, lse = _hip.attn_fwd(qkv, 1, 256, 1, 128, flags=_hip.ATTN_Q_PRESCALED)
+        dqkv = _hip.attn_bwd(qkv, out, rnd(256, 128), lse, 1, 256, 1, 128, flags=_hip.ATTN_Q_PRESCALED)
+    stream.synchronize()
+    for t in (c, outs[0], outs[1], out, lse, dqkv):
+        assert not torch.isnan(t.float()).any()                   # every call did launch
+    assert _hip._sched_slots == slots
+    assert _hip._sched_bufs.keys() == bufs.keys() and all(_hip._sched_bufs[k] is v for k, v in bufs.items())
+
+
 @pytest.fixture(scope="module")
 def attn_data():
     rnd = _dev(33)

@@ -35,14 +35,14 @@ for p in (0.1, 0.0):
     for name, lib in libs:
         st[name] = (torch.empty(B, L, H * d, dtype=BF, device="cuda"), torch.empty(B, H, L, dtype=F32, device="cuda"))
     def fwd(lib, s):
-        assert lib.orbit2_attn_fwd_ld(P(qkv), P(s[0]), P(s[1]), B, L, H, d, p, 11, flags, 3 * H * d, H * d, S()) == 0
+        assert lib.orbit2_attn_fwd_ld(P(qkv), P(s[0]), P(s[1]), B, L, H, d, p, 11, flags, 3 * H * d, H * d, None, None, -1, S()) == 0
     if BWD:      # time the backward (statistics + dQ + dK/dV) instead; the printed difference is over dqkv
         for name, lib in libs:
             fwd(lib, st[name])
             ws = torch.empty(lib.orbit2_attn_bwd_ws_floats(B, L, H), dtype=F32, device="cuda")
             st[name] = (torch.empty_like(qkv), st[name][1], st[name][0], ws)
         def fwd(lib, s):
-            assert lib.orbit2_attn_bwd_ld(P(qkv), P(s[2]), P(do), P(s[1]), P(s[3]), P(s[0]), B, L, H, d, p, 11, flags, 3 * H * d, H * d, S()) == 0
+            assert lib.orbit2_attn_bwd_ld(P(qkv), P(s[2]), P(do), P(s[1]), P(s[3]), P(s[0]), B, L, H, d, p, 11, flags, 3 * H * d, H * d, None, None, -1, S()) == 0
     for name, lib in libs:
         fwd(lib, st[name]); fwd(lib, st[name])
     torch.cuda.synchronize()

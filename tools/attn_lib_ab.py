@@ -15,9 +15,9 @@ P = lambda t: t.data_ptr()
 S = lambda: torch.cuda.current_stream().cuda_stream
 
 def fwd(lib, qkv, out, lse, Bx, L, H, d, p):
-    assert lib.orbit2_attn_fwd_ld(P(qkv), P(out), P(lse), Bx, L, H, d, p, 11, 0, 3 * H * d, H * d, S()) == 0
+    assert lib.orbit2_attn_fwd_ld(P(qkv), P(out), P(lse), Bx, L, H, d, p, 11, 0, 3 * H * d, H * d, None, None, -1, S()) == 0
 def bwd(lib, qkv, out, do, lse, delta, dqkv, Bx, L, H, d, p):
-    assert lib.orbit2_attn_bwd_ld(P(qkv), P(out), P(do), P(lse), P(delta), P(dqkv), Bx, L, H, d, p, 11, 0, 3 * H * d, H * d, S()) == 0
+    assert lib.orbit2_attn_bwd_ld(P(qkv), P(out), P(do), P(lse), P(delta), P(dqkv), Bx, L, H, d, p, 11, 0, 3 * H * d, H * d, None, None, -1, S()) == 0
 def t(f, n=4):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()

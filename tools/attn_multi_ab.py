@@ -31,8 +31,8 @@ for p in (0.1, 0.0):
         out = torch.empty(B, L, H * d, dtype=BF, device="cuda"); lse = torch.empty(B, H, L, dtype=F32, device="cuda")
         delta = torch.empty(2 * B * H * ((L + 63) // 64 * 64 + 64), dtype=F32, device="cuda"); dq = torch.empty_like(qkv)   # >= orbit2_attn_bwd_ws_floats
         st[name] = (out, lse, delta, dq)
-    def fwd(lib, s): assert lib.orbit2_attn_fwd_ld(P(qkv), P(s[0]), P(s[1]), B, L, H, d, p, 11, 0, 3 * H * d, H * d, S()) == 0
-    def bwd(lib, s): assert lib.orbit2_attn_bwd_ld(P(qkv), P(s[0]), P(do), P(s[1]), P(s[2]), P(s[3]), B, L, H, d, p, 11, 0, 3 * H * d, H * d, S()) == 0
+    def fwd(lib, s): assert lib.orbit2_attn_fwd_ld(P(qkv), P(s[0]), P(s[1]), B, L, H, d, p, 11, 0, 3 * H * d, H * d, None, None, -1, S()) == 0
+    def bwd(lib, s): assert lib.orbit2_attn_bwd_ld(P(qkv), P(s[0]), P(do), P(s[1]), P(s[2]), P(s[3]), B, L, H, d, p, 11, 0, 3 * H * d, H * d, None, None, -1, S()) == 0
     for name, lib in libs:
         fwd(lib, st[name]); bwd(lib, st[name])
     torch.cuda.synchronize()

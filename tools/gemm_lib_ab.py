@@ -43,7 +43,7 @@ for name, kind, N, K, kw in cases:
         _hip._gemm_fill(a, x, w, out, M, N, K, K, K if kind == "nt" else N, N, a_kc=True, b_kc=(kind == "nt"), bias=bias,
                         residual=res, ldr=N if res is not None else 0, save_pre=pre if kw.get("save_pre") else None,
                         save_dact=pre if kw.get("save_dact") else None, seed=5, **k2)
-        assert lib.orbit2_gemm_bf16(C.byref(a), S()) == 0
+        assert lib.orbit2_gemm_bf16(C.byref(a), None, 0, None, -1, S()) == 0
     tm = {k: [] for k in libs}
     for k, lib in libs.items():
         side = torch.empty(M, N, dtype=BF, device="cuda") if kw.get("save_pre") else (torch.empty(M, N, dtype=torch.int16, device="cuda") if kw.get("save_dact") else None)
@@ -66,7 +66,7 @@ def grouped(lib, outs):
     arr = (_hip.GemmArgs * 4)()
     for i, (dy, x, N, K) in enumerate(probs):
         _hip._gemm_fill(arr[i], dy, x, outs[i], N, K, M, N, K, K, a_kc=False, b_kc=False)
-    assert lib.orbit2_gemm_bf16_grouped(arr, 4, S()) == 0
+    assert lib.orbit2_gemm_bf16_grouped(arr, 4, None, None, None, -1, S()) == 0
 outs = {k: [torch.empty(N, K, dtype=BF, device="cuda") for (_, _, N, K) in probs] for k in libs}
 tm = {k: [] for k in libs}
 for k, lib in libs.items(): grouped(lib, outs[k])
