@@ -33,8 +33,18 @@ O2_TQ_TRACE_DEFINE(o2_tq_trace_attn, orbit2_debug_read_tq_trace_attn)
 __device__ unsigned int o2_dbg_attn[64 * 8];
 #define O2_T() ((unsigned)__builtin_amdgcn_s_memtime())
 #define O2_SEG(acc) { t1_ = O2_T(); acc += t1_ - t0_; t0_ = t1_; }
+#define O2_STAMP_BEGIN                                                              \
+  unsigned tS = 0, tQK = 0, tSM = 0, tPV = 0, tW = 0, tB = 0, t0_ = O2_T(), t1_; \
+  const unsigned tstart_ = t0_;
+#define O2_STAMP_DUMP(nt)                                                                                                     \
+  if (blockIdx.x < 64 && wave == 0 && lane == 0) {                                                                            \
+    unsigned* dd_ = o2_dbg_attn + blockIdx.x * 8;                                                                             \
+    dd_[0] = tS; dd_[1] = tQK; dd_[2] = tSM; dd_[3] = tPV; dd_[4] = tW; dd_[5] = tB; dd_[6] = O2_T() - tstart_; dd_[7] = (unsigned)(nt); \
+  }
 #else
 #define O2_SEG(acc)
+#define O2_STAMP_BEGIN
+#define O2_STAMP_DUMP(nt)
 #endif
 
 __device__ __forceinline__ bf16x8 pack_frag(const f32x16& x, int s) {
@@ -144,6 +154,12 @@ __device__ __forceinline__ bool attn_tile_coords_tq(const O2TailQ& q, int* slot,
   return true;
 }
 
+// Register r of a 32x32 accumulator whose registers run along KEYS (column = query on the lane) is key
+// kbase + (r & 3) + 8 (r >> 2) + 4 hq: is that key past the end of a ragged sequence?
+__device__ __forceinline__ bool attn_key_past_end(int kbase, int r, int hq, int L) {
+  return kbase + (r & 3) + 8 * (r >> 2) + 4 * hq >= L;
+}
+
 // =============================================================================================
 // forward
 // =============================================================================================
@@ -158,10 +174,12 @@ __device__ __forceinline__ bool attn_tile_coords_tq(const O2TailQ& q, int* slot,
 // half the LDS-DMA pieces per wave and per MFMA of the 4-wave / two-workgroups-per-CU form (the stamps of that form,
 // profiles/r02_attn_fwd_stamps_4wave.txt, show 8 pieces per wave and tile costing 700-970 of ~3200-5100 cycles: the CU's
 // LDS write path is busy ~11 cycles per 1-KiB piece and all 8 resident waves queue on it).
+//
+// This is the forward WITH dropout, always: every call without dropout runs attn_fwd_lazy_kernel below (attn_fwd_launch).
 #ifndef O2_FWD256_LA
 #define O2_FWD256_LA 3
 #endif
-template <int D, bool DROP, bool RAGGED, int NW>
+template <int D, bool RAGGED, int NW>
 __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                           float* __restrict__ lse, int L, int H, float sc_log2,
                                                           unsigned thr, float dscale, uint64_t seed_arg, int ldo, int ldq) {
@@ -194,19 +212,16 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_kernel(c
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
   float m_run = -1e30f, l_run = 0.f;
-  const uint32_t rowhash = DROP ? o2_attn_rowhash(seed, (uint64_t)(b * H + head) * L + (uint64_t)qrow) : 0u;
+  const uint32_t rowhash = o2_attn_rowhash(seed, (uint64_t)(b * H + head) * L + (uint64_t)qrow);
 
   const int nt = (L + 63) / 64;
   stage64<D, RAGGED, NW>(kbase, tstride, smem, wave, lane, L);
   stage64<D, RAGGED, NW>(vbase, tstride, smem + C::TILE, wave, lane, L);
-  if (DROP) stage_keyhash(skh[0], seed, 0, tid);
+  stage_keyhash(skh[0], seed, 0, tid);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   int cur = 0;
-#ifdef O2_STAMP
-  unsigned tS = 0, tQK = 0, tSM = 0, tPV = 0, tW = 0, tB = 0, t0_ = O2_T(), t1_;
-  const unsigned tstart_ = t0_;
-#endif
+  O2_STAMP_BEGIN
   for (int t = 0; t < nt; ++t) {
     const char* sk = smem + cur * 2 * C::TILE;
     const char* sv = sk + C::TILE;
@@ -214,7 +229,7 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_kernel(c
       char* nk = smem + (cur ^ 1) * 2 * C::TILE;
       stage64<D, RAGGED, NW>(kbase + (size_t)(t + 1) * 64 * tstride, tstride, nk, wave, lane, L - (t + 1) * 64);
       stage64<D, RAGGED, NW>(vbase + (size_t)(t + 1) * 64 * tstride, tstride, nk + C::TILE, wave, lane, L - (t + 1) * 64);
-      if (DROP) stage_keyhash(skh[cur ^ 1], seed, t + 1, tid);
+      stage_keyhash(skh[cur ^ 1], seed, t + 1, tid);
     }
     O2_SEG(tS)
     // S^T[kb] = K_kb . Q^T   (rows = keys in registers, column = query on the lane)
@@ -259,7 +274,7 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_kernel(c
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (t * 64 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hq >= L) s[kb][r] = -1e30f;
+          if (attn_key_past_end(t * 64 + kb * 32, r, hq, L)) s[kb][r] = -1e30f;
     }
     O2_SEG(tQK)
     // online softmax over this lane's query row (its 32 keys + the partner half's 32)
@@ -294,11 +309,9 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_kernel(c
         psum += p;
       }
     l_run = l_run * alpha + psum;
-    if (DROP) {
 #pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-        drop_keys_in_regs<true>(s[kb], rowhash, *reinterpret_cast<const u32x4*>(&skh[cur][hq * 8 + kb * 4]), thr);
-    }
+    for (int kb = 0; kb < 2; ++kb)
+      drop_keys_in_regs<true>(s[kb], rowhash, *reinterpret_cast<const u32x4*>(&skh[cur][hq * 8 + kb * 4]), thr);
     O2_SEG(tSM)
     // O^T[db] += V^T . P^T
     if constexpr (D == 256) {
@@ -334,14 +347,9 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_kernel(c
     O2_SEG(tB)
     cur ^= 1;
   }
-#ifdef O2_STAMP
-  if (blockIdx.x < 64 && wave == 0 && lane == 0) {
-    unsigned* dd_ = o2_dbg_attn + blockIdx.x * 8;
-    dd_[0] = tS; dd_[1] = tQK; dd_[2] = tSM; dd_[3] = tPV; dd_[4] = tW; dd_[5] = tB; dd_[6] = O2_T() - tstart_; dd_[7] = (unsigned)nt;
-  }
-#endif
+  O2_STAMP_DUMP(nt)
   const float l_tot = l_run + __shfl_xor(l_run, 32);
-  const float inv = (DROP ? dscale : 1.0f) / l_tot;   // dropout scale folded out of the inner loop
+  const float inv = dscale / l_tot;   // dropout scale folded out of the inner loop
   if (!q_ok) return;
   if (hq == 0) lse[((size_t)(b * H + head)) * L + qrow] = (m_run + log2f(l_tot)) * 0.6931471805599453f;
   bf16_t* orow = out + ((size_t)b * L + qrow) * (size_t)ldo + (size_t)head * D;   // ldo: token-row pitch of out (>= H * D)
@@ -364,22 +372,20 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_kernel(c
 // leave the matrix pipe as exp2 arguments.  The reference is the row's maximum over the first tile and stays FIXED while no
 // probability relative to it leaves [0, 2^40]: P, O and l share it and fp32 / bf16 keep their relative precision at any scale,
 // so the result is exact, and a score element costs one exp2, one add and its share of the bf16 conversion (124 vector
-// instructions per 64-key tile against 200 in attn_fwd_kernel<.., DROP = false, ..>: +6 % at the interm_1b shape,
-// profiles/r03_attn_fwd_variants.txt).  The row sums are the guard: a wave in which one leaves the range continues in an
-// online-softmax loop.  With dropout the same formulation is 6-16 % SLOWER than attn_fwd_kernel in five variants (guard
-// placement, priority, pinned / free select, subtract instead of accumulator start): hipcc's schedule of that loop, not its
-// instruction count (243 against 306), decides -- the dropout forward stays as it was.
+// instructions per 64-key tile against 200 in the no-dropout form attn_fwd_kernel once had -- that form is gone, this
+// kernel takes every call without dropout: +6 % at the interm_1b shape, profiles/r03_attn_fwd_variants.txt).  The row sums
+// are the guard: a wave in which one leaves the range continues in an online-softmax loop.  With dropout the same formulation
+// is 6-16 % SLOWER than attn_fwd_kernel in five variants (guard placement, priority, pinned / free select, subtract instead of
+// accumulator start): hipcc's schedule of that loop, not its instruction count (243 against 306), decides -- the dropout forward
+// stays as it was.
 template <int D, bool RAGGED, int NW>
 __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_lazy_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                           float* __restrict__ lse, int L, int H, float sc_log2,
                                                           unsigned thr, float dscale, uint64_t seed_arg, int ldo, int ldq) {
-  constexpr bool DROP = false;                      // (the dropout forward is attn_fwd_kernel above)
-  const uint64_t seed = seed_arg ^ o2_seed_salt;
+  // (thr, dscale, seed_arg: the dropout forward is attn_fwd_kernel above; one launch form serves both kernels)
   using C = Cfg<D>;
-  constexpr int KT = 1;      // 64-key tiles per stage and per workgroup barrier (2 was measured: no gain)
-  constexpr int STAGE = KT * 2 * C::TILE;
-  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];        // [2 stages][KT][K | V]
-  __shared__ __attribute__((aligned(16))) uint32_t skh[2][KT * 16];    // [stage][tile] key-group hashes of the tile (dropout)
+  // one 64-key tile per stage and per workgroup barrier (two were measured: no gain)
+  __shared__ __attribute__((aligned(16))) char smem[4 * C::TILE];  // [2 stages][K | V]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hq = lane >> 5;  // MFMA half
@@ -408,30 +414,26 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_lazy_ker
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
   float m_run = 0.f, l_run = 0.f;
-  const uint32_t rowhash = DROP ? o2_attn_rowhash(seed, (uint64_t)(b * H + head) * L + (uint64_t)qrow) : 0u;
 
   const int nt = (L + 63) / 64;
   int cur = 0;
-  // stage the KT tiles of super-tile T into buffer `buf` (tiles past the end of the sequence are not staged, nor read)
-  auto stage_super = [&](int T, int buf) {
-#pragma unroll
-    for (int j = 0; j < KT; ++j) {
-      const int tt = T * KT + j;
-      if (tt < nt) {
-        char* nk = smem + buf * STAGE + j * 2 * C::TILE;
-        stage64<D, RAGGED, NW, (D >= 128)>(kbase + (size_t)tt * 64 * tstride, tstride, nk, wave, lane, L - tt * 64);
-        stage64<D, RAGGED, NW, (D >= 128)>(vbase + (size_t)tt * 64 * tstride, tstride, nk + C::TILE, wave, lane, L - tt * 64);
-        if (DROP) stage_keyhash(skh[buf] + j * 16, seed, tt, tid);
-      }
+  // stage tile tt into buffer `buf` (a tile past the end of the sequence is not staged, nor read)
+  auto stage_tile = [&](int tt, int buf) {
+    if (tt < nt) {
+      char* nk = smem + buf * 2 * C::TILE;
+      stage64<D, RAGGED, NW, (D >= 128)>(kbase + (size_t)tt * 64 * tstride, tstride, nk, wave, lane, L - tt * 64);
+      stage64<D, RAGGED, NW, (D >= 128)>(vbase + (size_t)tt * 64 * tstride, tstride, nk + C::TILE, wave, lane, L - tt * 64);
     }
   };
-  stage_super(0, 0);
+  // put the next tile in flight (the check here and the one in stage_tile are the text that was compared with the two-level
+  // staging this loop once had and timed against it: profiles/attn_shared_parts_equivalence.txt)
+  auto stage_next = [&](int t) {
+    if (t + 1 < nt) stage_tile(t + 1, cur ^ 1);
+  };
+  stage_tile(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-#ifdef O2_STAMP
-  unsigned tS = 0, tQK = 0, tSM = 0, tPV = 0, tW = 0, tB = 0, t0_ = O2_T(), t1_;
-  const unsigned tstart_ = t0_;
-#endif
+  O2_STAMP_BEGIN
   // scores of tile t relative to `ref` (exp2 domain): S^T[kb] = K_kb . Q~^T - ref  (rows = keys in registers, column =
   // query on the lane).  The two key blocks' chains are interleaved: a K fragment is consumed two MFMAs after the
   // previous one of its chain, so its LDS read has twice the time to land.
@@ -468,7 +470,7 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_lazy_ker
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (t * 64 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hq >= L) s[kb][r] = -1e30f;
+          if (attn_key_past_end(t * 64 + kb * 32, r, hq, L)) s[kb][r] = -1e30f;
     }
   };
   auto rowmax = [&](const f32x16 (&s)[2]) {
@@ -486,17 +488,8 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_lazy_ker
     scores(smem, 0, zero, s0);
     m_run = rowmax(s0);
   }
-  // first tile of a super-tile: put the next super-tile in flight
-  auto stage_next = [&](int t) {
-    if (t % KT == 0 && (t / KT + 1) * KT < nt) stage_super(t / KT + 1, cur ^ 1);
-  };
-  // O^T[db] += V^T . (dropout(P))^T, then (last tile of a super-tile) the hand-over: next super-tile landed, everybody done
-  auto drop_pv_sync = [&](int t, const char* sv, f32x16 (&s)[2]) {
-    if (DROP) {
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-        drop_keys_in_regs<true>(s[kb], rowhash, *reinterpret_cast<const u32x4*>(&skh[cur][(t % KT) * 16 + hq * 8 + kb * 4]), thr);
-    }
+  // O^T[db] += V^T . P^T, then the hand-over: next tile landed, everybody done
+  auto pv_sync = [&](const char* sv, f32x16 (&s)[2]) {
     O2_SEG(tSM)
     if constexpr (D == 256) {
       bf16x8 pf[4];
@@ -525,13 +518,11 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_lazy_ker
         }
     }
     O2_SEG(tPV)
-    if (t % KT == KT - 1 || t == nt - 1) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      O2_SEG(tW)
-      __syncthreads();
-      O2_SEG(tB)
-      cur ^= 1;
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    O2_SEG(tW)
+    __syncthreads();
+    O2_SEG(tB)
+    cur ^= 1;
   };
   // ---- fast loop: FIXED reference (the row's maximum over the first tile).  P, O and l share that one reference per row and
   // fp32 / bf16 keep their relative precision at any scale, so as long as no probability relative to it overflows the result
@@ -545,7 +536,7 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_lazy_ker
   int t = 0;
   bool fast_ok = true;
   for (; t < nt; ++t) {
-    const char* sk = smem + cur * STAGE + (t % KT) * 2 * C::TILE;
+    const char* sk = smem + cur * 2 * C::TILE;
     stage_next(t);
     O2_SEG(tS)
     f32x16 s[2];
@@ -562,7 +553,7 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_lazy_ker
       }
     if (__any(!(psum <= FAST_LIMIT))) { fast_ok = false; break; }     // wave-uniform; tile t is redone by the safe loop
     l_run += psum;
-    drop_pv_sync(t, sk + C::TILE, s);
+    pv_sync(sk + C::TILE, s);
   }
   // ---- safe loop (only after the guard tripped; tile t + 1 is already in flight): online softmax with a moving reference,
   // rescaled when some row of the wave outgrows it by more than 2^RESCALE_THR (wave-uniform, deferred: P is then bounded by
@@ -573,7 +564,7 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_lazy_ker
     for (int r = 0; r < 16; ++r) zero[r] = 0.f;
     bool staged = true;
     for (; t < nt; ++t) {
-      const char* sk = smem + cur * STAGE + (t % KT) * 2 * C::TILE;
+      const char* sk = smem + cur * 2 * C::TILE;
       if (!staged) stage_next(t);
       staged = false;
       f32x16 s[2];
@@ -600,17 +591,12 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_fwd_lazy_ker
           psum += p;
         }
       l_run = l_run * alpha + psum;
-      drop_pv_sync(t, sk + C::TILE, s);
+      pv_sync(sk + C::TILE, s);
     }
   }
-#ifdef O2_STAMP
-  if (blockIdx.x < 64 && wave == 0 && lane == 0) {
-    unsigned* dd_ = o2_dbg_attn + blockIdx.x * 8;
-    dd_[0] = tS; dd_[1] = tQK; dd_[2] = tSM; dd_[3] = tPV; dd_[4] = tW; dd_[5] = tB; dd_[6] = O2_T() - tstart_; dd_[7] = (unsigned)nt;
-  }
-#endif
+  O2_STAMP_DUMP(nt)
   const float l_tot = l_run + __shfl_xor(l_run, 32);
-  const float inv = (DROP ? dscale : 1.0f) / l_tot;   // dropout scale folded out of the inner loop
+  const float inv = 1.0f / l_tot;
   if (!q_ok) return;
   if (hq == 0) lse[((size_t)(b * H + head)) * L + qrow] = (m_run + log2f(l_tot)) * 0.6931471805599453f;
   bf16_t* orow = out + ((size_t)b * L + qrow) * (size_t)ldo + (size_t)head * D;   // ldo: token-row pitch of out (>= H * D)
@@ -898,7 +884,7 @@ __global__ __launch_bounds__(NW * 64, (D == 256 ? 1 : 2)) void attn_bwd_dq_kerne
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         float p = __builtin_amdgcn_exp2f(s[r]);
-        if (tail && t * 64 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hq >= L) p = 0.f;   // key past the end
+        if (tail && attn_key_past_end(t * 64 + kb * 32, r, hq, L)) p = 0.f;
         s[r] = DLT_INIT ? p * dp[r] : p * (dp[r] - dlt);  // dS^T
       }
       if constexpr (D == 256) {
@@ -1860,7 +1846,6 @@ struct AttnLaunch {              // one pass
 };
 struct AttnPlan {
   bool fwd_w4, dq_w4;            // the generated one-wave-per-SIMD kernels (256-row workgroups) take the forward / the dQ pass
-  bool fwd_lazy;                 // compiler-scheduled forward: the lazy-rescaling kernel (every call without dropout)
   AttnDkv dkv;
   int nw_fwd, nw;                // compiler-scheduled kernels: waves per workgroup (32 rows each), forward and backward
   bool ragged_fwd, ragged;       //   and whether L leaves a partial workgroup
@@ -1891,7 +1876,6 @@ static AttnPlan attn_plan(int d, int L, int B, int H, int flags, int ldq, int ld
   const bool pre = (flags & ORBIT2_ATTN_Q_PRESCALED) != 0, split = (flags & ORBIT2_ATTN_SPLIT_DKV) != 0;
   p.thr = (unsigned)(drop_p * 256.0f + 0.5f);
   p.drop = p.thr != 0;
-  p.fwd_lazy = !p.drop;
   p.dscale = 256.0f / (256.0f - (float)p.thr);
   p.scale = 1.0f / sqrtf((float)d);
   p.opmul = pre ? 1.0f : p.scale * 1.4426950408889634f;      // (q stored pre-scaled: the kernels' multiplier is 1)
@@ -1931,13 +1915,17 @@ static AttnPlan attn_plan(int d, int L, int B, int H, int flags, int ldq, int ld
 }
 
 // the (d, waves) pairs the compiler-scheduled kernels are instantiated for, times dropout and ragged: f(D, NW, DROP, RAGGED)
-template <class F> static void attn_with_variant(int d, int nw, bool drop, bool ragged, F&& f) {
+// FWD: the forward, which runs d = 64 at 4 waves only (attn_plan: nw_fwd) and has no (64, 8) pair
+template <bool FWD = false, class F> static void attn_with_variant(int d, int nw, bool drop, bool ragged, F&& f) {
   o2_with_flags([&](auto DR, auto RG) {
     if (d == 256) f(o2_int<256>{}, o2_int<4>{}, DR, RG);
     else if (d == 128 && nw == 8) f(o2_int<128>{}, o2_int<8>{}, DR, RG);
     else if (d == 128) f(o2_int<128>{}, o2_int<4>{}, DR, RG);
-    else if (nw == 8) f(o2_int<64>{}, o2_int<8>{}, DR, RG);
-    else f(o2_int<64>{}, o2_int<4>{}, DR, RG);
+    else {
+      if constexpr (!FWD)
+        if (nw == 8) return f(o2_int<64>{}, o2_int<8>{}, DR, RG);
+      f(o2_int<64>{}, o2_int<4>{}, DR, RG);
+    }
   }, drop, ragged);
 }
 
@@ -1971,11 +1959,9 @@ static int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int L,
     O2_W4_PASS(p.fwd, attn_fwd_w4_kernel, attn_fwd_w4_gated_kernel, attn_fwd_w4_tq_kernel, q_, o_, lse, L, H, p.thr, p.dscale, seed,
                ldo, ldq);
   else
-    attn_with_variant(d, p.nw_fwd, p.drop, p.ragged_fwd, [&](auto DV, auto NW, auto DR, auto RG) {
-      if constexpr (!DR) {                  // (the lazy-rescaling kernel has no dropout form)
-        if (p.fwd_lazy) { O2_FWD((attn_fwd_lazy_kernel<DV, RG, NW>), p.opmul, p.thr, p.dscale); return; }
-      }
-      O2_FWD((attn_fwd_kernel<DV, DR, RG, NW>), p.opmul, p.thr, p.dscale);
+    attn_with_variant<true>(d, p.nw_fwd, p.drop, p.ragged_fwd, [&](auto DV, auto NW, auto DR, auto RG) {
+      if constexpr (DR) O2_FWD((attn_fwd_kernel<DV, RG, NW>), p.opmul, p.thr, p.dscale);
+      else O2_FWD((attn_fwd_lazy_kernel<DV, RG, NW>), p.opmul, p.thr, p.dscale);      // (no dropout: the lazy-rescaling forward)
     });
 #undef O2_FWD
   O2_CHECK_LAUNCH();
