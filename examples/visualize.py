@@ -11,7 +11,11 @@ stitched field (the reference's validation metrics, loaders.py:247-255).  Forwar
 An optional `mc_dropout: {members: N, seed: S}` block (configs/inference_mc.yaml) adds, after the deterministic run, an
 MC-dropout ensemble of N stitched predictions (climate_learn.utils.mc_dropout_statistics: streamed mean and spread, same
 tiling), prints gaussian_crps / gaussian_spread / gaussian_spread_skill_ratio and the 1-sigma coverage of the denormalised
-field, and saves the mean and the spread as <rank>_mc_mean.npy / <rank>_mc_spread.npy."""
+field, and saves the mean and the spread as <rank>_mc_mean.npy / <rank>_mc_spread.npy.  With `scores: members` in that block
+(configs/inference_mc_members.yaml) the same ensemble is then built as a member stack (climate_learn.utils.mc_dropout_members:
+N fields held) and scored without the Gaussian fit: ensemble_crps, ensemble_crps_fair, ensemble_spread_skill_ratio and one
+rank_histogram line per output channel are printed, <rank>_mc_rank_hist.npy and the 5 % / 50 % / 95 % quantile fields
+<rank>_mc_p05.npy / _p50.npy / _p95.npy saved."""
 import os
 import sys
 
@@ -79,13 +83,17 @@ def main():
         print(loss.name, [round(float(v), 6) for v in loss(pred, gt).reshape(-1)], flush=True)
     mcd = conf.get("mc_dropout")
     if mcd:
+        scores = mcd.get("scores")
+        if scores not in (None, "members"):
+            raise RuntimeError("mc_dropout.scores: 'members' or absent, got %r" % (scores,))
         return mc_dropout_report(model, (x, y, iv, ov), gt, denorm, int(mcd["members"]), int(mcd.get("seed", 0)), div, overlap,
-                                 local_rank)
+                                 local_rank, member_scores=scores == "members")
 
 
-def mc_dropout_report(model, batch, gt, denorm, members, seed, div, overlap, rank):
+def mc_dropout_report(model, batch, gt, denorm, members, seed, div, overlap, rank, *, member_scores=False):
     """MC-dropout ensemble of the stitched field: denormalised mean and spread (the spread takes the denormalisation's
-    scale only, not its shift), the Gaussian scores against the denormalised ground truth, and the 1-sigma coverage"""
+    scale only, not its shift), the Gaussian scores against the denormalised ground truth, and the 1-sigma coverage;
+    member_scores: then the all-member scores of the same ensemble (member_scores_report)"""
     from climate_learn.metrics import functional as fn
     cl.manual_seed(seed)
     stats = cl.utils.mc_dropout_statistics(batch, model, members, div=div, overlap=overlap)
@@ -103,6 +111,32 @@ def mc_dropout_report(model, batch, gt, denorm, members, seed, div, overlap, ran
     np.save("%d_mc_mean.npy" % rank, res["mean"])
     np.save("%d_mc_spread.npy" % rank, res["spread"])
     print("mc_dropout saved", {k: v.shape for k, v in res.items()}, flush=True)
+    if member_scores:
+        res.update(member_scores_report(model, batch, gt, denorm, members, seed, div, overlap, rank))
+    return res
+
+
+def member_scores_report(model, batch, gt, denorm, members, seed, div, overlap, rank):
+    """the same ensemble (same seed) as a member stack, every member denormalised in its slice: all-member CRPS (empirical and
+    fair), spread / skill, the rank histogram per output channel, and the 5 % / 50 % / 95 % quantile fields"""
+    import numpy as np
+    from climate_learn.metrics import functional as fn
+    cl.manual_seed(seed)
+    ens = cl.utils.mc_dropout_members(batch, model, members, div=div, overlap=overlap)
+    model.eval()                                                            # leave MC-dropout mode
+    for k in range(ens.n):
+        ens.members[k].copy_(denorm(ens.members[k]))
+    for name, val in (("ensemble_crps", fn.ensemble_crps(ens, gt)), ("ensemble_crps_fair", fn.ensemble_crps(ens, gt, fair=True)),
+                      ("ensemble_spread_skill_ratio", fn.ensemble_spread_skill_ratio(ens, gt))):
+        print(name, [round(float(v), 6) for v in val.reshape(-1)], flush=True)
+    hist = fn.ensemble_rank_histogram(ens, gt, seed=seed).cpu().numpy()
+    out_vars = batch[3]
+    for c in range(hist.shape[0] - 1):
+        print("rank_histogram", out_vars[c] if c < len(out_vars) else c, [int(v) for v in hist[c]], flush=True)
+    q = fn.ensemble_quantiles(ens, [0.05, 0.5, 0.95]).cpu().numpy()
+    res = {"rank_hist": hist, "p05": q[0], "p50": q[1], "p95": q[2]}
+    for k, v in res.items():
+        np.save("%d_mc_%s.npy" % (rank, k), v)
     return res
 
 

@@ -31,7 +31,7 @@ extern "C" {
  * four names with shorter argument lists, so the number had to change: a binding of one version refuses a build of the other.
  * Everything else is as at version 7, the entries that were added during it included (the fp32 forward entries orbit2_gemm_f32,
  * orbit2_attn_fwd_f32, orbit2_layernorm_fwd_f32, orbit2_varagg_fwd_f32, orbit2_unpatchify_fwd_f32; orbit2_ensemble_update and
- * orbit2_gaussian_scores). */
+ * orbit2_gaussian_scores).  Added during version 8, changing nothing that exists: orbit2_ensemble_scores. */
 int orbit2_abi_version(void);
 
 /* ---- bf16 MFMA GEMM with fused epilogue ------------------------------------------------
@@ -337,6 +337,36 @@ int orbit2_ensemble_update(const float* member, float* mean, float* m2, int64_t 
  * non-positive size, a target smaller than the prediction or B * C > 65535 return O2_ERR_ARG before any launch. */
 int orbit2_gaussian_scores(const float* mean, const float* std_, const float* target, int Ht, int Wt, const float* lat_w,
                            double* out, int B, int C, int H, int W, void* stream);
+/* orbit2_ensemble_scores: the all-member (non-Gaussian) scores of an ensemble, from the N members of every pixel held in
+ * registers, in one pass that reads each member once.
+ * members fp32: member i is the contiguous [B,C,H,W] field at members + i * member_stride (member_stride >= B*C*H*W, in
+ * elements); 2 <= N <= ORBIT2_ENSEMBLE_MAX_MEMBERS.  target fp32 [B,C,Ht,Wt] (top-left crop; Ht >= H, Wt >= W); lat_w fp32 [H]
+ * or NULL (w = 1).  All inputs are finite; non-finite members give unspecified scores but never a fault.
+ * With y the target, d_i = x_i - y and d_(1) <= ... <= d_(N) sorted -- everything summed is centred on the target first (a
+ * field in kelvin is 280 +- 1: the pair term on raw values cancels its low bits away) -- each output is optional (NULL = not
+ * computed), at least one must be given:
+ *   sums       double [B][C][4], zeroed by the entry, accumulated across workgroups as orbit2_gaussian_scores does:
+ *                0 sum_pix w (1/N) sum_i |d_i|        1 sum_pix w sum_{i<j} |x_i - x_j|  ( = sum_k (2k - N - 1) d_(k), k 1-based)
+ *                2 sum_pix w (mean_i d_i)^2           3 sum_pix w (unbiased variance of the members; two passes over the d_i)
+ *              host forms: empirical CRPS = [0] - [1] / N^2, fair CRPS = [0] - [1] / (N (N - 1)), spread / skill from [3], [2].
+ *   crps_field fp32 [B,C,H,W], the per-pixel CRPS, unweighted: empirical (fair == 0) or fair (fair != 0).
+ *   hist       int64 [B][C][N + 1], zeroed by the entry: counts of the rank of the target among the members,
+ *                rank = lt + ((uint64) h * (eq + 1) >> 32),  lt = #{x_i < y}, eq = #{x_i == y},
+ *                h = hash(seed, flat index of the pixel in the [B,C,H,W] prediction)   (the RNG of every seeded entry).
+ *              Ties are broken by the hash because constant output channels are copied from the target into every member: a
+ *              lowest-rank rule would pile those pixels into bin 0 and read as a bias.  UNLIKE EVERY OTHER SEEDED ENTRY THE SEED
+ *              SALT (orbit2_seed_salt) IS NOT MIXED IN: a score is a pure function of its arguments, and the salt advances
+ *              under graph replay.  Integer counts, added by integer atomics: bit-repeatable.
+ *   quant      fp32 [Q][B][C][H][W], the quantiles at levels[Q] (device fp32, 1 <= Q <= 16, each in [0, 1]) as numpy / torch
+ *              "linear" define them: pos = q (N - 1), lo = floor(pos), value = x_(lo) + (pos - lo) (x_(lo+1) - x_(lo)) on the
+ *              raw members; q = 0 and q = 1 are the minimum and the maximum bit for bit.
+ * NULL members or target, all four outputs NULL, N < 2 or > ORBIT2_ENSEMBLE_MAX_MEMBERS, member_stride < B*C*H*W, a
+ * non-positive size, a target smaller than the prediction, B * C > 65535, quant without levels or Q outside 1..16 return
+ * O2_ERR_ARG before any launch, with nothing written. */
+#define ORBIT2_ENSEMBLE_MAX_MEMBERS 64
+int orbit2_ensemble_scores(const float* members, int64_t member_stride, int N, const float* target, int Ht, int Wt,
+                           const float* lat_w, double* sums, float* crps_field, int fair, int64_t* hist, uint64_t seed,
+                           float* quant, const float* levels, int Q, int B, int C, int H, int W, void* stream);
 
 /* ---- perceptual loss = L1 + 0.5 * mean_b LPIPS-VGG16 (metrics/functional.py:17-33, metrics.py:119-187) ------
  * Feature maps are NHWC bf16, so each 3x3 VGG convolution is im2col + orbit2_gemm_bf16 (bias, act = 2) forward and

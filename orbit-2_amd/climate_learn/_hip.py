@@ -104,6 +104,7 @@ PROTOTYPES = {
     "orbit2_eval_moments": (_I, (_P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P)),
     "orbit2_ensemble_update": (_I, (_P, _P, _P, _I64, _I, _P)),
     "orbit2_gaussian_scores": (_I, (_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P)),
+    "orbit2_ensemble_scores": (_I, (_P, _I64, _I, _P, _I, _I, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _I, _I, _I, _I, _P)),
     "orbit2_im2col3x3": (_I, (_P, _P, _I, _I, _I, _I, _P)),
     "orbit2_col2im3x3": (_I, (_P, _P, _P, _P, _I, _I, _I, _I, _P)),
     "orbit2_maxpool2_fwd": (_I, (_P, _P, _I, _I, _I, _I, _P)),
@@ -924,6 +925,70 @@ def gaussian_scores(mean, std, target, lat_w=None):
     out = torch.empty(B, Cc, 4, dtype=torch.float64, device=mean.device)
     _chk(lib().orbit2_gaussian_scores(_p(mean), _p(std), _p(target), target.shape[2], target.shape[3], _p(lat_w), _p(out),
                                       B, Cc, H, W, _stream()), "orbit2_gaussian_scores")
+    return out
+
+
+ENSEMBLE_MAX_MEMBERS = 64       # ORBIT2_ENSEMBLE_MAX_MEMBERS
+ENSEMBLE_MAX_QUANTILES = 16
+
+
+def ensemble_scores(members, target, lat_w=None, *, sums=True, hist=False, seed=0, crps_field=None, quantiles=None):
+    """All-member scores of an [N,B,C,H,W] fp32 ensemble against `target` in one pass (include/orbit2_hip.h:
+    orbit2_ensemble_scores).  `members` is a contiguous stack or a view of one whose member stride is larger than a field.
+    Returns a dict with the outputs that were asked for: "sums" float64 [B,C,4] (sums=True), "hist" int64 [B,C,N+1] (hist=True;
+    `seed` breaks the ties), "crps_field" fp32 [B,C,H,W] (crps_field="empirical" or "fair"), "quantiles" fp32 [Q,B,C,H,W]
+    (quantiles = levels in [0, 1], a sequence or a tensor)."""
+    if not torch.is_tensor(members) or members.dim() != 5:
+        raise HipBackendError("ensemble_scores takes an [N,B,C,H,W] stack of members")
+    if not members.is_cuda:
+        raise HipBackendError("members must be a GPU tensor (HIP backend has no CPU path)")
+    if members.dtype != F32:
+        raise HipBackendError("members must be %s, got %s" % (F32, members.dtype))
+    N, B, Cc, H, W = members.shape
+    if not 2 <= N <= ENSEMBLE_MAX_MEMBERS:
+        raise HipBackendError("ensemble_scores: %d members, 2 to %d are served" % (N, ENSEMBLE_MAX_MEMBERS))
+    field = B * Cc * H * W
+    if not members[0].is_contiguous() or members.stride(0) < field:
+        raise HipBackendError("ensemble_scores: every member must be a contiguous [B,C,H,W] field, members at least one field "
+                              "apart (strides %s)" % (tuple(members.stride()),))
+    _dev(target, F32, "target")
+    if target.dim() != 4 or tuple(target.shape[:2]) != (B, Cc):
+        raise HipBackendError("ensemble_scores: target %s does not match the prediction's [B,C] %s"
+                              % (tuple(target.shape), (B, Cc)))
+    if target.shape[2] < H or target.shape[3] < W:
+        raise HipBackendError("ensemble_scores: target %s is smaller than the prediction %s"
+                              % (tuple(target.shape), (B, Cc, H, W)))
+    if lat_w is not None:
+        _dev(lat_w, F32, "lat_w")
+        if lat_w.numel() < H:
+            raise HipBackendError("lat_w has %d entries, the prediction %d rows" % (lat_w.numel(), H))
+    if crps_field not in (None, "empirical", "fair"):
+        raise HipBackendError("ensemble_scores: crps_field is None, 'empirical' or 'fair', got %r" % (crps_field,))
+    levels = None
+    if quantiles is not None:
+        levels = torch.as_tensor(quantiles, dtype=F32).reshape(-1)
+        if not 1 <= levels.numel() <= ENSEMBLE_MAX_QUANTILES:
+            raise HipBackendError("ensemble_scores: %d quantile levels, 1 to %d are served"
+                                  % (levels.numel(), ENSEMBLE_MAX_QUANTILES))
+        if not bool(((levels >= 0) & (levels <= 1)).all()):
+            raise HipBackendError("ensemble_scores: quantile levels must lie in [0, 1]")
+        levels = levels.to(members.device).contiguous()
+    if not (sums or hist or crps_field or levels is not None):
+        raise HipBackendError("ensemble_scores: no output was asked for")
+    dev, out = members.device, {}
+    if sums:
+        out["sums"] = torch.empty(B, Cc, 4, dtype=torch.float64, device=dev)
+    if hist:
+        out["hist"] = torch.empty(B, Cc, N + 1, dtype=torch.int64, device=dev)
+    if crps_field:
+        out["crps_field"] = torch.empty(B, Cc, H, W, dtype=F32, device=dev)
+    if levels is not None:
+        out["quantiles"] = torch.empty(levels.numel(), B, Cc, H, W, dtype=F32, device=dev)
+    _chk(lib().orbit2_ensemble_scores(_p(members), members.stride(0), N, _p(target), target.shape[2], target.shape[3], _p(lat_w),
+                                      _p(out.get("sums")), _p(out.get("crps_field")), int(crps_field == "fair"),
+                                      _p(out.get("hist")), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(out.get("quantiles")), _p(levels),
+                                      0 if levels is None else levels.numel(), B, Cc, H, W, _stream()),
+         "orbit2_ensemble_scores")
     return out
 
 

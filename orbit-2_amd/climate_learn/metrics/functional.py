@@ -179,3 +179,74 @@ def gaussian_coverage(pred, target):
     not in the reference: the fourth sum of the score kernel, reported by examples/visualize.py"""
     s, n = _gaussian_sums(pred, target)
     return _with_aggregate((s[..., 3].sum(0) / (n * s.shape[0])).float(), False)
+
+
+# ---- all-member (non-Gaussian) scores of an ensemble; `pred` is a utils.mc_dropout.EnsembleMembers (e.g. from
+# utils.mc_dropout_members) or an [N, B, C, H, W] fp32 device tensor.  One kernel (orbit2_ensemble_scores) reads every member
+# once and sorts the N values of a pixel in registers; the reductions are those of the Gaussian scores above: per channel the
+# mean over (b, h, w), then the aggregate.  No reference counterpart: the reference scores its ensembles through a Gaussian fit
+# only. ------------------------------------------------------------------------------------------------------------------------
+def _ensemble(pred):
+    from ..utils.mc_dropout import EnsembleMembers
+    if isinstance(pred, EnsembleMembers):
+        pred = pred.members
+    if not torch.is_tensor(pred) or pred.dim() != 5:
+        raise TypeError("the all-member scores take an EnsembleMembers or an [N, B, C, H, W] fp32 device tensor, got %s"
+                        % (type(pred).__name__ if not torch.is_tensor(pred) else "a tensor of shape %s" % (tuple(pred.shape),)))
+    return pred.detach()
+
+
+def _ensemble_sums(pred, target, lat_weights=None):
+    from .. import _hip
+    m = _ensemble(pred)
+    s = _hip.ensemble_scores(m, target.detach().float().contiguous(), _lat(lat_weights, m[0]), sums=True)["sums"]
+    return s, m.shape[0], m.shape[3] * m.shape[4]
+
+
+def ensemble_crps(pred, target, aggregate_only: bool = False, lat_weights=None, fair: bool = False):
+    """Continuous ranked probability score of the empirical distribution of the N members against `target`,
+    mean_i |x_i - y| - sum_{i<j} |x_i - x_j| / N^2 (the integral of (F_ens(x) - 1{x >= y})^2), or with fair=True the fair form
+    that divides the pair term by N (N - 1) (unbiased for an ensemble of finite size): per channel the mean over (b, h, w)
+    (x latitude weight), and the mean over everything."""
+    s, N, n = _ensemble_sums(pred, target, lat_weights)
+    pairs = float(N * (N - 1)) if fair else float(N * N)
+    return _with_aggregate(((s[..., 0] - s[..., 1] / pairs).sum(0) / (n * s.shape[0])).float(), aggregate_only)
+
+
+def ensemble_spread_skill_ratio(pred, target, aggregate_only: bool = False, lat_weights=None):
+    """sqrt(mean w var) / sqrt(mean w err^2) per channel, means over (b, h, w): var the unbiased variance of the members, err
+    the error of the ensemble mean; the aggregate is formed the same way from the totals over all channels.  Both are a
+    standard deviation over an rmse.  This has no reference counterpart, so it does NOT copy the variance-over-rmse aggregate
+    of gaussian_spread_skill_ratio, which mirrors a reference function.  A channel every member of which equals the target (a
+    constant output channel) has neither spread nor error: its entry is 0 / 0 = NaN, and it adds nothing to the totals."""
+    s, N, n = _ensemble_sums(pred, target, lat_weights)
+    var, err = s[..., 3].sum(0), s[..., 2].sum(0)
+    per_channel = (var / err).sqrt().float()
+    agg = (var.sum() / err.sum()).sqrt().float()
+    return agg if aggregate_only else torch.cat((per_channel, agg.unsqueeze(0)))
+
+
+def ensemble_crps_field(pred, target, fair: bool = False):
+    """the per-pixel CRPS (empirical, or fair), fp32 [B, C, H, W], unweighted"""
+    from .. import _hip
+    return _hip.ensemble_scores(_ensemble(pred), target.detach().float().contiguous(), sums=False,
+                                crps_field="fair" if fair else "empirical")["crps_field"]
+
+
+def ensemble_rank_histogram(pred, target, seed: int = 0):
+    """int64 [C + 1, N + 1]: per channel the counts of the rank of the target among the N members over (b, h, w), the last row
+    their sum over the channels.  A calibrated ensemble gives a flat histogram.  Ties (constant output channels equal the
+    target in every member) are broken uniformly by a hash of (`seed`, pixel): the same seed gives the same counts, bit for
+    bit."""
+    from .. import _hip
+    h = _hip.ensemble_scores(_ensemble(pred), target.detach().float().contiguous(), sums=False, hist=True, seed=seed)["hist"]
+    h = h.sum(0)
+    return torch.cat((h, h.sum(0, keepdim=True)))
+
+
+def ensemble_quantiles(pred, q):
+    """fp32 [Q, B, C, H, W]: the quantiles of the members at the levels `q` (a number, a sequence or a tensor, in [0, 1]) as
+    torch.quantile / numpy define them ("linear"); q = 0 and q = 1 are the minimum and the maximum bit for bit"""
+    from .. import _hip
+    m = _ensemble(pred)
+    return _hip.ensemble_scores(m, m[0], sums=False, quantiles=q)["quantiles"]

@@ -10,3 +10,4 @@ for _n in dir(_loaders):                      # every load_* factory, as the ref
 
 from . import mc_dropout                       # noqa: E402  (after the loaders: it needs the model components)
 from .mc_dropout import enable_dropout, get_monte_carlo_predictions, mc_dropout_statistics      # noqa: E402
+from .mc_dropout import EnsembleMembers, mc_dropout_members                                     # noqa: E402

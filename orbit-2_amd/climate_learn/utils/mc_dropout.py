@@ -10,6 +10,10 @@ one seed reproduces a whole ensemble bit for bit while its members differ from e
 `mc_dropout_statistics` is the form built for the card: the reference stacks N full-resolution predictions and reduces them
 afterwards (N x 100 MB at [16, 3, 512, 1024]); here each member updates a running mean and sum of squared deviations in
 place (`orbit2_ensemble_update`, one Welford step per member), so peak memory does not grow with N.
+
+`mc_dropout_members` is the form for what only the members themselves can give -- order statistics: the all-member CRPS, the
+rank histogram and quantile fields of metrics.functional (`ensemble_*`, one pass of `orbit2_ensemble_scores`).  It holds N
+fields, in one stack allocated once.
 """
 from __future__ import annotations
 
@@ -97,3 +101,43 @@ def mc_dropout_statistics(batch, model_module, n_ensemble_members, *, div=1, ove
             _hip.ensemble_update(member, mean, m2, k)
             del member
     return EnsembleStatistics(mean, m2, n)
+
+
+class EnsembleMembers:
+    """the members of an ensemble themselves: `members` fp32 [N, B, C, H, W] on the device, `n` = N; what the all-member scores
+    of metrics.functional (`ensemble_crps`, `ensemble_rank_histogram`, `ensemble_quantiles`, ...) take.  `statistics()` folds
+    the stack into the running moments of `mc_dropout_statistics` (one `orbit2_ensemble_update` per member)."""
+
+    def __init__(self, members):
+        if not torch.is_tensor(members) or members.dim() != 5:
+            raise TypeError("EnsembleMembers takes an [N, B, C, H, W] tensor")
+        self.members, self.n = members, int(members.shape[0])
+
+    def statistics(self):
+        mean, m2 = torch.empty_like(self.members[0]), torch.empty_like(self.members[0])
+        for k in range(self.n):
+            _hip.ensemble_update(self.members[k], mean, m2, k + 1)
+        return EnsembleStatistics(mean, m2, self.n)
+
+
+def mc_dropout_members(batch, model_module, n_ensemble_members, *, div=1, overlap=0):
+    """The `n_ensemble_members` MC-dropout predictions of `batch` themselves, as an `EnsembleMembers`.  THIS FORM HOLDS N
+    FIELDS: order statistics (all-member CRPS, ranks, quantiles) need every member of a pixel at once, so that is inherent;
+    `mc_dropout_statistics` remains the form whose memory does not grow with N.  The stack is allocated once and each member
+    written into its slice (a torch.stack of a list would hold 2 N fields at its peak).  Mode handling, seeding order and
+    clipping are those of `mc_dropout_statistics`: under one `climate_learn.manual_seed` the stack equals
+    `get_monte_carlo_predictions` bit for bit (div = 1), or the stitched fields of `tiled_predict` (div > 1)."""
+    n = int(n_ensemble_members)
+    if not 2 <= n <= _hip.ENSEMBLE_MAX_MEMBERS:
+        raise ValueError("mc_dropout_members serves 2 to %d ensemble members, got %d" % (_hip.ENSEMBLE_MAX_MEMBERS, n))
+    model_module.eval()
+    enable_dropout(model_module)
+    stack = None
+    with torch.no_grad():
+        for k in range(n):
+            member = _member(batch, model_module, int(div), int(overlap))
+            if stack is None:
+                stack = torch.empty((n,) + tuple(member.shape), dtype=torch.float32, device=member.device)
+            stack[k].copy_(member)
+            del member
+    return EnsembleMembers(stack)
