@@ -218,7 +218,12 @@ def main():
         if hg is True and (tp > 1 or not capturable):
             raise ValueError("trainer.hipgraph: true is not available here (tensor parallelism or a gloo rehearsal): use 'auto' or "
                              "false")     # never a silent fallback
-        use_graph = (hg is True or (hg == "auto" and tokens <= 16384 and capturable and not sharded)) and tp == 1
+        if hg is True and mc["patch_size"] != 2:
+            raise ValueError("trainer.hipgraph: true is built for model.patch_size 2 only (GraphedTrainStep refuses %d): use 'auto' "
+                             "or false" % mc["patch_size"])
+        # `auto` keeps the other patch sizes eager: graph capture of their step is not built (climate_learn/graphs.py refuses it)
+        use_graph = (hg is True or (hg == "auto" and tokens <= 16384 and capturable and not sharded
+                                    and mc["patch_size"] == 2)) and tp == 1
         gstep, gshape = None, None
         for epoch in range(epoch_start, max_epochs):
             eng.train()

@@ -31,7 +31,8 @@ extern "C" {
  * four names with shorter argument lists, so the number had to change: a binding of one version refuses a build of the other.
  * Everything else is as at version 7, the entries that were added during it included (the fp32 forward entries orbit2_gemm_f32,
  * orbit2_attn_fwd_f32, orbit2_layernorm_fwd_f32, orbit2_varagg_fwd_f32, orbit2_unpatchify_fwd_f32; orbit2_ensemble_update and
- * orbit2_gaussian_scores).  Added during version 8, changing nothing that exists: orbit2_ensemble_scores. */
+ * orbit2_gaussian_scores).  Added during version 8, changing nothing that exists: orbit2_ensemble_scores; the folded patch-embed
+ * entries that carry the patch size (orbit2_varagg_fwd_p, orbit2_varagg_fwd_f32_p, orbit2_varagg_bwd_p and its two queries). */
 int orbit2_abi_version(void);
 
 /* ---- bf16 MFMA GEMM with fused epilogue ------------------------------------------------
@@ -216,7 +217,7 @@ int orbit2_attn_fwd_f32(const void* qkv, void* out, float* lse, int B, int L, in
  *      patch_embed.py:44-52; attention.py:132-176) ---------------------------------------------
  * x: fp32 [B, V, h, w]; stab: fp32 [H][V][5] score table; gtab: fp32 [V][5][D] value table
  * (both functions of the weights only);  z: bf16 [B*L, D] (input of var_agg.proj);
- * attw: fp32 [B*L, H, V] softmax weights saved for backward.  patch must be 2. */
+ * attw: fp32 [B*L, H, V] softmax weights saved for backward.  The patch size is 2 (other sizes: the _p entries below). */
 int orbit2_varagg_fwd(const float* x, const float* stab, const float* gtab, void* z, float* attw, int B, int V,
                       int h, int w, int H, int D, void* stream);
 /* the same forward with z written as fp32 [B*L, D] (the fp32 forward path; same reference lines); attw may be NULL */
@@ -241,6 +242,28 @@ int orbit2_tables_scatter(const float* dcmat, float* dw_base, int64_t w_stride, 
  * scalar fallback that accumulates them with fp32 atomics (head dim not 64 / 128 / 256, 5 V > 128, ORBIT2_VARAGG_SCALAR set):
  * callers that keep replicas of the tables in lock-step without exchanging gradients need to know (dist/tp.py ReplicaGuard) */
 int orbit2_varagg_bwd_is_fixed_order(int B, int V, int h, int w, int H, int D);
+/* The same five calls with the patch size as an argument (components/patch_embed.py:22-53: PatchEmbed is generic in it).
+ * patch in {1, 2, 4}, anything else is O2_ERR_ARG, as is a grid with h % patch or w % patch != 0.  With C = patch * patch + 1:
+ * stab: fp32 [H][V][C], gtab: fp32 [V][C][D]; coefficient c < patch * patch multiplies patch element (c / patch, c % patch)
+ * (row-major inside the patch: the order of Conv2d(1, D, patch, patch).weight.view(D, patch * patch)), c = patch * patch is the
+ * constant term.  z: [B * (h / patch) * (w / patch), D] bf16 (_fwd_p) or fp32 (_fwd_f32_p, attw may be NULL); attw: fp32
+ * [tokens, H, V]; dstab [H][V][C] and dgtab [V][C][D] are ACCUMULATED into.
+ * patch == 2 IS the call above: same kernels, same launch, same workspace, same answer of _is_fixed_order.
+ * patch 1 and 4: the forward kernels are the same template; the backward is a two-stage form of its own with NO float atomics
+ * (ds per 16 tokens -> ws; then one workgroup per (variable, token range) holds its dgtab / dstab partial in registers and
+ * stores it into the range's slab; the ranges are added in a fixed order).  orbit2_varagg_bwd_p_ws_floats = tokens * H * V +
+ * ranges * (H V C + V C D) floats, 0 for a shape the backward does not serve; orbit2_varagg_bwd_p_is_fixed_order = 1 for every
+ * shape it serves (bitwise reproducible), 0 otherwise.  A shape whose dynamic LDS need exceeds the 160 KiB of a CU is refused
+ * with O2_ERR_UNSUPPORTED before anything is launched (backward: 16 * (V C + 2 H V + 512) floats, e.g. V = H = 32 at patch 4;
+ * forward: 16 * (V C + H V) floats, within the limit for every V, H <= 32). */
+int orbit2_varagg_fwd_p(const float* x, const float* stab, const float* gtab, void* z, float* attw, int B, int V, int h,
+                        int w, int patch, int H, int D, void* stream);
+int orbit2_varagg_fwd_f32_p(const float* x, const float* stab, const float* gtab, float* z, float* attw, int B, int V,
+                            int h, int w, int patch, int H, int D, void* stream);
+int64_t orbit2_varagg_bwd_p_ws_floats(int B, int V, int h, int w, int patch, int H, int D);
+int orbit2_varagg_bwd_p(const float* x, const float* gtab, const float* attw, const void* dz, float* dstab, float* dgtab,
+                        int B, int V, int h, int w, int patch, int H, int D, float* ws, void* stream);
+int orbit2_varagg_bwd_p_is_fixed_order(int B, int V, int h, int w, int patch, int H, int D);
 
 /* ---- elementwise / reductions ------------------------------------------------------------- */
 /* dym = dy * dropmask * rowscale (backward of the dropout/DropPath epilogue); dym may alias dy */

@@ -82,7 +82,7 @@ def forward(model, x, in_variables, out_variables):
     # front-end: folded patch-embed + variable aggregation (fp32 tables as in the bf16 path), tokens fp32
     stab, gtab = model._tables(model.get_var_ids(tuple(in_variables)))
     D = model.embed_dim
-    L = (h // 2) * (w // 2)
+    L = (h // model.patch_size) * (w // model.patch_size)
     z = _hip.varagg_fwd_f32(x, stab.contiguous(), gtab.contiguous(), model.num_heads, D)
     posres = model._posres().contiguous()                                    # [L, D] fp32, added as it is
     t = linear(z, model.var_agg.proj.weight, model.var_agg.proj.bias, residual=posres, ldr=D, res_mod=L, res_first=True)

@@ -78,6 +78,11 @@ PROTOTYPES = {
     "orbit2_tables_gather": (_I, (_P, _I64, _P, _I64, _P, _P, _P, _I, _I, _P)),
     "orbit2_tables_scatter": (_I, (_P, _P, _I64, _P, _I64, _P, _P, _I, _I, _P)),
     "orbit2_varagg_bwd_is_fixed_order": (_I, (_I, _I, _I, _I, _I, _I)),
+    "orbit2_varagg_fwd_p": (_I, (_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P)),
+    "orbit2_varagg_fwd_f32_p": (_I, (_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P)),
+    "orbit2_varagg_bwd_p_ws_floats": (_I64, (_I, _I, _I, _I, _I, _I, _I)),
+    "orbit2_varagg_bwd_p": (_I, (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P)),
+    "orbit2_varagg_bwd_p_is_fixed_order": (_I, (_I, _I, _I, _I, _I, _I, _I)),
     "orbit2_dropout_bwd": (_I, (_P, _P, _I, _I, _F, _U64, _P, _I, _P)),
     "orbit2_dropout_bwd_colsum": (_I, (_P, _P, _I, _I, _F, _U64, _P, _I, _P, _I, _F, _P, _I, _P)),
     "orbit2_post_reduce": (_I, (_P, _P, _I, _P, _P, _I, _I, _F, _U64, _P, _I, _P)),
@@ -534,26 +539,59 @@ def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0, gate=
     return dqkv
 
 
-def varagg_fwd(x, stab, gtab, H, D):
-    _dev(x, F32, "x"); _dev(stab, F32, "stab"); _dev(gtab, F32, "gtab")
+PATCH_SIZES = (1, 2, 4)         # the patch sizes csrc/varagg.hip instantiates (C = p * p + 1 table coefficients per variable)
+
+
+def _patch_of(C_, what):
+    """the patch size p a table with C = p * p + 1 coefficients per variable was built for; any other C is refused"""
+    for p in PATCH_SIZES:
+        if C_ == p * p + 1:
+            return p
+    raise HipBackendError("%s has %d coefficients per variable: the folded patch-embed kernels take p * p + 1 for a patch size p "
+                          "in %s" % (what, C_, PATCH_SIZES))
+
+
+def _varagg_shapes(x, gtab, stab=None):
+    """(B, V, h, w, p, tokens) of a folded patch-embed call: p from the tables' coefficient count, the grid a multiple of it"""
     B, V, h, w = x.shape
-    ntok = B * (h // 2) * (w // 2)
+    if gtab.dim() != 3 or gtab.shape[0] != V:
+        raise HipBackendError("gtab must be [V = %d, p * p + 1, D], got %s" % (V, tuple(gtab.shape)))
+    p = _patch_of(gtab.shape[1], "gtab")
+    if stab is not None and (stab.dim() != 3 or stab.shape[1] != V or stab.shape[2] != gtab.shape[1]):
+        raise HipBackendError("stab must be [H, V = %d, %d] as gtab is %s, got %s" % (V, gtab.shape[1], tuple(gtab.shape),
+                                                                                  tuple(stab.shape)))
+    if h % p or w % p:
+        raise HipBackendError("the grid %d x %d is not a multiple of the patch size %d" % (h, w, p))
+    return B, V, h, w, p, B * (h // p) * (w // p)
+
+
+def varagg_fwd(x, stab, gtab, H, D):
+    """z bf16 [tokens, D], attw fp32 [tokens, H, V]; the patch size is the tables': stab [H, V, p*p+1], gtab [V, p*p+1, D]"""
+    _dev(x, F32, "x"); _dev(stab, F32, "stab"); _dev(gtab, F32, "gtab")
+    B, V, h, w, p, ntok = _varagg_shapes(x, gtab, stab)
     z = torch.empty(ntok, D, dtype=BF, device=x.device)
     attw = torch.empty(ntok, H, V, dtype=F32, device=x.device)
-    _chk(lib().orbit2_varagg_fwd(_p(x), _p(stab), _p(gtab), _p(z), _p(attw), B, V, h, w, H, D, _stream()),
-         "orbit2_varagg_fwd")
+    if p == 2:
+        _chk(lib().orbit2_varagg_fwd(_p(x), _p(stab), _p(gtab), _p(z), _p(attw), B, V, h, w, H, D, _stream()),
+             "orbit2_varagg_fwd")
+    else:
+        _chk(lib().orbit2_varagg_fwd_p(_p(x), _p(stab), _p(gtab), _p(z), _p(attw), B, V, h, w, p, H, D, _stream()),
+             "orbit2_varagg_fwd_p")
     return z, attw
 
 
 def varagg_fwd_f32(x, stab, gtab, H, D, want_attw=False):
     """the folded variable aggregation with fp32 tokens (orbit2_varagg_fwd_f32); returns z, or (z, attw) with want_attw"""
     _dev(x, F32, "x"); _dev(stab, F32, "stab"); _dev(gtab, F32, "gtab")
-    B, V, h, w = x.shape
-    ntok = B * (h // 2) * (w // 2)
+    B, V, h, w, p, ntok = _varagg_shapes(x, gtab, stab)
     z = torch.empty(ntok, D, dtype=F32, device=x.device)
     attw = torch.empty(ntok, H, V, dtype=F32, device=x.device) if want_attw else None
-    _chk(lib().orbit2_varagg_fwd_f32(_p(x), _p(stab), _p(gtab), _p(z), _p(attw), B, V, h, w, H, D, _stream()),
-         "orbit2_varagg_fwd_f32")
+    if p == 2:
+        _chk(lib().orbit2_varagg_fwd_f32(_p(x), _p(stab), _p(gtab), _p(z), _p(attw), B, V, h, w, H, D, _stream()),
+             "orbit2_varagg_fwd_f32")
+    else:
+        _chk(lib().orbit2_varagg_fwd_f32_p(_p(x), _p(stab), _p(gtab), _p(z), _p(attw), B, V, h, w, p, H, D, _stream()),
+             "orbit2_varagg_fwd_f32_p")
     return (z, attw) if want_attw else z
 
 
@@ -573,11 +611,21 @@ atomics_in_grad_path = False
 def varagg_bwd(x, gtab, attw, dz, H, D):
     global atomics_in_grad_path
     _dev(x, F32, "x"); _dev(gtab, F32, "gtab"); _dev(attw, F32, "attw"); _dev(dz, BF, "dz")
-    B, V, h, w = x.shape
+    B, V, h, w, p, ntok = _varagg_shapes(x, gtab)
+    C_ = p * p + 1
+    dstab = torch.zeros(H, V, C_, dtype=F32, device=x.device)
+    dgtab = torch.zeros(V, C_, D, dtype=F32, device=x.device)
+    if p != 2:
+        # the two-stage fixed-order backward (no float atomics anywhere): `atomics_in_grad_path` is not touched
+        if not lib().orbit2_varagg_bwd_p_is_fixed_order(B, V, h, w, p, H, D):
+            raise HipBackendError("orbit2_varagg_bwd_p does not serve B=%d V=%d grid %dx%d patch %d H=%d D=%d (its LDS need "
+                                  "exceeds a CU's 160 KiB, or the shape is invalid)" % (B, V, h, w, p, H, D))
+        ws = _ws(lib().orbit2_varagg_bwd_p_ws_floats, (B, V, h, w, p, H, D), x.device)
+        _chk(lib().orbit2_varagg_bwd_p(_p(x), _p(gtab), _p(attw), _p(dz), _p(dstab), _p(dgtab), B, V, h, w, p, H, D, _p(ws),
+                                       _stream()), "orbit2_varagg_bwd_p")
+        return dstab, dgtab
     if not atomics_in_grad_path and not lib().orbit2_varagg_bwd_is_fixed_order(B, V, h, w, H, D):
         atomics_in_grad_path = True
-    dstab = torch.zeros(H, V, 5, dtype=F32, device=x.device)
-    dgtab = torch.zeros(V, 5, D, dtype=F32, device=x.device)
     ws = _ws(lib().orbit2_varagg_bwd_ws_floats, (B, V, h, w, H, D), x.device)
     _chk(lib().orbit2_varagg_bwd(_p(x), _p(gtab), _p(attw), _p(dz), _p(dstab), _p(dgtab), B, V, h, w, H, D, _p(ws), _stream()),
          "orbit2_varagg_bwd")

@@ -857,7 +857,10 @@ class EmbedFn(torch.autograd.Function):
         summed over `grp` before the position / resolution embedding and the dropout are applied."""
         B, V, h, w = xgrid.shape
         D, Dl = wp.shape
-        L = (h // 2) * (w // 2)
+        P = _hip._patch_of(gtab.shape[1], "gtab")          # the tables carry the patch size: C = P * P + 1 coefficients
+        if h % P or w % P:
+            raise ValueError("input grid %s is not a multiple of patch_size=%d" % ((h, w), P))
+        L = (h // P) * (w // P)
         M = B * L
         xg = xgrid.contiguous()
         if xg.dtype != F32:

@@ -75,6 +75,9 @@ class GraphedTrainStep:
         if getattr(engine.module, "tensor_par_size", 1) > 1:
             raise NotImplementedError("GraphedTrainStep covers the data-parallel step; tensor-parallel steps (large "
                                       "models, not launch-bound) run eagerly")
+        if getattr(engine.module, "patch_size", 2) != 2:
+            raise NotImplementedError("GraphedTrainStep with patch_size=%d: graph capture of the step is built and tested for "
+                                      "patch_size=2 only; run the step eagerly" % engine.module.patch_size)
         if getattr(engine, "shard_params", False):
             # The parameter-sharding engine is captured in its SINGLE-STREAM form (fsdp_engine.single_stream): per-unit all-gathers,
             # reduce-scatters and pooled-buffer hand-overs in program order on the capturing stream.  Its two-stream form records

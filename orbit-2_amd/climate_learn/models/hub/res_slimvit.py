@@ -23,7 +23,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ... import _fp32, _ops
+from ... import _fp32, _hip, _ops
 from ...dist import tp as _tp
 from ...utils.fused_attn import FusedAttn
 from .components.attention import VariableMapping_Attention
@@ -55,14 +55,19 @@ class Res_Slim_ViT(McDropoutMode, nn.Module):
                  decoder_depth=8, num_heads=16, mlp_ratio=4.0, tensor_par_size=1, tensor_par_group=None,
                  FusedAttn_option=FusedAttn.HIP):
         super().__init__()
+        if patch_size not in _hip.PATCH_SIZES:
+            raise NotImplementedError(
+                "patch_size=%r: the folded patch-embed kernels serve patch_size in %s (at 8 the 65 float4 table rows a thread "
+                "holds and the patch tile in LDS no longer fit the kernel's shape)" % (patch_size, _hip.PATCH_SIZES))
+        if patch_size != 2 and tensor_par_size > 1:
+            raise NotImplementedError("tensor_par_size=%d with patch_size=%d: tensor parallelism is built and tested for "
+                                      "patch_size=2 only" % (tensor_par_size, patch_size))
         if tensor_par_size > 1:
             if tensor_par_group is None or _tp.group_size(tensor_par_group) != tensor_par_size:
                 raise ValueError("tensor_par_size=%d needs a tensor_par_group of that many ranks" % tensor_par_size)
             assert num_heads % tensor_par_size == 0, "model heads % tensor parallel size must be 0"
         else:
             tensor_par_group = None
-        if patch_size != 2:
-            raise NotImplementedError("the folded patch-embed kernel implements patch_size=2 (all interm_* configs)")
         self.default_vars = list(default_vars)
         self.img_size = tuple(img_size)
         self.cnn_ratio, self.superres_mag = cnn_ratio, superres_mag
@@ -175,14 +180,18 @@ class Res_Slim_ViT(McDropoutMode, nn.Module):
             eye = self._idx_cache[ekey] = torch.eye(H, dtype=torch.float32, device=wq.device).unsqueeze(-1)
         qblk = (eye * qv.view(1, H, dh)).view(H, Dl)                             # [H, Dl], head-block structure (one launch)
         u = _ops.sgemm(qblk, wkv[:Dl]) * (dh ** -0.5)                            # [H, D] = scale * q_h^T Wk_h
-        # rows (v, c): the 4 patch weights of variable v and its bias + variable embedding -- built for all variables at once
+        # rows (v, c): the p*p patch weights of variable v (row-major inside the patch, the order of Conv2d(1, D, p, p).weight
+        # .view(D, p*p)) and its bias + variable embedding -- built for all variables at once
         # (five launches forward; the per-variable form was ~12 tiny launches per variable and step, 10 % of an interm_117m step)
         tes = [self.token_embeds[v].proj for v in ids]
         key = (tuple(ids), str(wq.device))
         ids_t = self._idx_cache.get(key)
         if ids_t is None:
             ids_t = self._idx_cache[key] = torch.tensor(list(ids), dtype=torch.long, device=wq.device)
-        lay = self._token_tables_layout() if torch.is_grad_enabled() else None
+        PP = self.patch_size ** 2
+        # the fused gather / scatter (orbit2_tables_gather / _scatter) is 4-wide, tied to the engines' flat buffers at
+        # patch_size=2: every other patch size takes the ATen path below, whose gradients accumulate through autograd
+        lay = self._token_tables_layout() if torch.is_grad_enabled() and self.patch_size == 2 else None
         # the fused path's backward adds into the gradient rows WITHOUT atomics, one workgroup per id, and announces the parameters
         # to the engine itself: it needs distinct variable ids (a duplicated id would make two workgroups race on one row -- the
         # ATen path accumulates duplicates correctly) and at most ONE instance per backward (two forwards feeding one backward: the
@@ -212,13 +221,13 @@ class Res_Slim_ViT(McDropoutMode, nn.Module):
             lay = dict(lay, pending=pending)
             cmat = _ops.TokenTablesFn.apply(lay, ids32, len(ids), D, self.var_embed, *flat)
         else:
-            w4 = torch.stack([te.weight.view(D, 4) for te in tes]).transpose(1, 2)    # [V, 4, D]
+            w4 = torch.stack([te.weight.view(D, PP) for te in tes]).transpose(1, 2)   # [V, p*p, D]
             b1 = torch.stack([te.bias for te in tes]) + self.var_embed[0].index_select(0, ids_t)        # [V, D]
-            cmat = torch.cat([w4, b1.unsqueeze(1)], 1).reshape(len(ids) * 5, D)      # [(v,c), D]
+            cmat = torch.cat([w4, b1.unsqueeze(1)], 1).reshape(len(ids) * (PP + 1), D)   # [(v,c), D]
         if grp is not None:
             cmat = _tp.IdentityFwdAllReduceBwd.apply(cmat, grp)
-        stab = _ops.sgemm(u, cmat, tb=True).view(H, len(ids), 5)
-        gtab = _ops.sgemm(cmat, wkv[Dl:], tb=True).view(len(ids), 5, Dl)
+        stab = _ops.sgemm(u, cmat, tb=True).view(H, len(ids), PP + 1)
+        gtab = _ops.sgemm(cmat, wkv[Dl:], tb=True).view(len(ids), PP + 1, Dl)
         return stab, gtab
 
     def _token_tables_layout(self):
@@ -258,12 +267,18 @@ class Res_Slim_ViT(McDropoutMode, nn.Module):
     def forward(self, x, in_variables, out_variables):
         if x.dim() == 5:
             x = x.flatten(1, 2)
+        if self.patch_size != 2 and any(getattr(p, "_o2_sharded", False) for p in self.parameters()):
+            raise NotImplementedError("Res_Slim_ViT with patch_size=%d under the parameter-sharding engine "
+                                      "(HipFullyShardedDataParallel): that engine is built and tested for patch_size=2 only; "
+                                      "HipDataParallel serves 1, 2 and 4" % self.patch_size)
         if not x.is_cuda:
             raise RuntimeError("Res_Slim_ViT (HIP build) needs its input on a gfx950 device; there is no CPU path")
         x = x.float().contiguous()
         B, V, h, w = x.shape
         if (h, w) != tuple(self.img_size):
             raise ValueError("input grid %s differs from data_config'd img_size %s" % ((h, w), self.img_size))
+        if h % self.patch_size or w % self.patch_size:
+            raise ValueError("input grid %s is not a multiple of patch_size=%d" % ((h, w), self.patch_size))
         if self._compute_dtype == torch.float32:
             _fp32.refuse(self)
             return _fp32.forward(self, x, in_variables, out_variables)

@@ -91,6 +91,10 @@ def tiled_predict(mm, x, y, in_variables, out_variables, div: int, overlap: int,
             (yo1, yo2), (xo1, xo2) = t["out"]
             xdiv = x[:, :, yi1:yi2, xi1:xi2].contiguous()
             ydiv = y[:, :, yo1:yo2, xo1:xo2]
+            ps = int(getattr(mm, "patch_size", 1))
+            if xdiv.shape[2] % ps or xdiv.shape[3] % ps:
+                raise ValueError("tiled_predict: the tile %d x %d (div=%d, overlap=%d, halo included) is not a multiple of "
+                                 "patch_size=%d" % (xdiv.shape[2], xdiv.shape[3], div, overlap, ps))
             if hasattr(mm, "data_config") and tuple(getattr(mm, "img_size", xdiv.shape[2:])) != tuple(xdiv.shape[2:]):
                 if saved is None:
                     saved = (mm.spatial_resolution, mm.img_size, mm.in_channels, mm.out_channels)

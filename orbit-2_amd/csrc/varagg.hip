@@ -10,6 +10,11 @@
 // The two tables depend on the weights only (built per step by small fp32 GEMMs with autograd); this kernel
 // does the per-token work and never materialises the [B,V,L,D] tensor (1.16 GB/sample at interm_1b) nor runs
 // the M = B*L*V "kv" GEMM.  Exact algebra; only the rounding order differs from the reference.
+//
+// Patch sizes P in {1, 2, 4} (the kernels are templates on P): a token's patch of variable v has P*P values, taken row-major
+// inside the patch (c = r*P + col, the order of Conv2d(1, D, P, P).weight.view(D, P*P)), pt_v = (p_v, 1) in R^C with
+// C = P*P + 1, and the tables are stab [H][V][C], gtab [V][C][D].  Everything written with 5 above is C.  P = 2 is the form
+// all interm_* configurations use; its instantiations, entries and summation order are those the file had before P existed.
 #include <stdlib.h>
 #include "tiles32.h"
 #include "../../include/orbit2_hip.h"
@@ -20,35 +25,48 @@ constexpr int VA_T = 16;      // tokens per workgroup
 constexpr int VA_MAXV = 32;   // max variables
 constexpr int VA_MAXH = 32;   // max heads
 
-// LDS: pt[T][V][5], aw[T][H][V]
+// one channel of the value row of (token, variable): sum_c gtab[v][c][i] * pt[c], the patch terms in the order c = 0 .. P*P-1,
+// the constant term last (for P = 2: g0 p0 + g1 p1 + g2 p2 + g3 p3 + g4, the order the kernel has always used)
+template <int P>
+__device__ __forceinline__ float va_row(const f32x4* g, const float* p, int j) {
+  float val = g[0][j] * p[0];
+#pragma unroll
+  for (int c = 1; c < P * P; ++c) val += g[c][j] * p[c];
+  return val + g[P * P][j];
+}
+
+constexpr int VA_LDS_LIMIT = 160 * 1024;   // LDS of a gfx950 CU: a launch that needs more is refused on the host
+
+// LDS: pt[T][V][C], aw[T][H][V]  (+ da[T][H][V] in the backward)
 // ZF32 (forward only): z is written as fp32 and attw may be NULL (the fp32 forward path saves nothing for a backward)
-template <bool BWD, bool ZF32 = false>
+template <bool BWD, bool ZF32 = false, int P = 2>
 __global__ __launch_bounds__(256) void varagg_kernel(const float* __restrict__ x, const float* __restrict__ stab,
                                                      const float* __restrict__ gtab, bf16_t* __restrict__ z,
                                                      float* __restrict__ attw, const bf16_t* __restrict__ dz,
                                                      float* __restrict__ dstab, float* __restrict__ dgtab, int B,
                                                      int V, int h, int w, int H, int D) {
+  constexpr int PP = P * P, C = PP + 1;
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* pt = sm;                       // [T][V][5]
-  float* aw = pt + VA_T * V * 5;        // [T][H][V]
+  float* pt = sm;                       // [T][V][C]
+  float* aw = pt + VA_T * V * C;        // [T][H][V]
   float* da = aw + VA_T * H * V;        // [T][H][V] (backward only)
   const int tid = threadIdx.x;
-  const int Lw = w / 2, L = (h / 2) * Lw;
+  const int Lw = w / P, L = (h / P) * Lw;
   const int64_t tok0 = (int64_t)blockIdx.x * VA_T;
   const int64_t ntok = (int64_t)B * L;
   const int dh = D / H;
 
   // ---- patches ---------------------------------------------------------------------------------
-  for (int e = tid; e < VA_T * V * 5; e += 256) {
-    const int c = e % 5, v = (e / 5) % V, t = e / (5 * V);
+  for (int e = tid; e < VA_T * V * C; e += 256) {
+    const int c = e % C, v = (e / C) % V, t = e / (C * V);
     const int64_t tok = tok0 + t;
     float val = 0.f;
     if (tok < ntok) {
-      if (c == 4) val = 1.f;
+      if (c == PP) val = 1.f;
       else {
         const int b = (int)(tok / L), l = (int)(tok - (int64_t)b * L);
         const int pr = l / Lw, pc = l - pr * Lw;
-        val = x[(((size_t)b * V + v) * h + (2 * pr + (c >> 1))) * w + 2 * pc + (c & 1)];
+        val = x[(((size_t)b * V + v) * h + (P * pr + c / P)) * w + P * pc + c % P];
       }
     }
     pt[e] = val;
@@ -58,20 +76,20 @@ __global__ __launch_bounds__(256) void varagg_kernel(const float* __restrict__ x
   if (!BWD) {
     for (int e = tid; e < VA_T * H; e += 256) {
       const int hh = e % H, t = e / H;
-      const float* st = stab + (size_t)hh * V * 5;
-      const float* pp = pt + (size_t)t * V * 5;
+      const float* st = stab + (size_t)hh * V * C;
+      const float* pp = pt + (size_t)t * V * C;
       float mx = -1e30f;
       for (int v = 0; v < V; ++v) {
         float s = 0.f;
 #pragma unroll
-        for (int c = 0; c < 5; ++c) s += st[v * 5 + c] * pp[v * 5 + c];
+        for (int c = 0; c < C; ++c) s += st[v * C + c] * pp[v * C + c];
         mx = fmaxf(mx, s);
       }
       float sum = 0.f;
       for (int v = 0; v < V; ++v) {
         float s = 0.f;
 #pragma unroll
-        for (int c = 0; c < 5; ++c) s += st[v * 5 + c] * pp[v * 5 + c];
+        for (int c = 0; c < C; ++c) s += st[v * C + c] * pp[v * C + c];
         sum += __expf(s - mx);
       }
       const float inv = 1.f / sum;
@@ -79,7 +97,7 @@ __global__ __launch_bounds__(256) void varagg_kernel(const float* __restrict__ x
       for (int v = 0; v < V; ++v) {
         float s = 0.f;
 #pragma unroll
-        for (int c = 0; c < 5; ++c) s += st[v * 5 + c] * pp[v * 5 + c];
+        for (int c = 0; c < C; ++c) s += st[v * C + c] * pp[v * C + c];
         const float a = __expf(s - mx) * inv;
         aw[(t * H + hh) * V + v] = a;
         if (tok < ntok && (!ZF32 || attw)) attw[((size_t)tok * H + hh) * V + v] = a;
@@ -103,18 +121,15 @@ __global__ __launch_bounds__(256) void varagg_kernel(const float* __restrict__ x
 #pragma unroll
       for (int t = 0; t < VA_T; ++t) { acc[t][0] = acc[t][1] = acc[t][2] = acc[t][3] = 0.f; }
       for (int v = 0; v < V; ++v) {
-        f32x4 g[5];
+        f32x4 g[C];
 #pragma unroll
-        for (int c = 0; c < 5; ++c) g[c] = *reinterpret_cast<const f32x4*>(gtab + ((size_t)(v * 5 + c)) * D + i0);
+        for (int c = 0; c < C; ++c) g[c] = *reinterpret_cast<const f32x4*>(gtab + ((size_t)(v * C + c)) * D + i0);
 #pragma unroll
         for (int t = 0; t < VA_T; ++t) {
-          const float* p = pt + (t * V + v) * 5;
+          const float* p = pt + (t * V + v) * C;
           const float a = aw[(t * H + hh) * V + v];
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float val = g[0][j] * p[0] + g[1][j] * p[1] + g[2][j] * p[2] + g[3][j] * p[3] + g[4][j];
-            acc[t][j] += a * val;
-          }
+          for (int j = 0; j < 4; ++j) acc[t][j] += a * va_row<P>(g, p, j);
         }
       }
 #pragma unroll
@@ -142,32 +157,32 @@ __global__ __launch_bounds__(256) void varagg_kernel(const float* __restrict__ x
         } else { dzv[t][0] = dzv[t][1] = dzv[t][2] = dzv[t][3] = 0.f; }
       }
       for (int v = 0; v < V; ++v) {
-        f32x4 g[5];
-        float dg[5][4];
+        f32x4 g[C];
+        float dg[C][4];
 #pragma unroll
-        for (int c = 0; c < 5; ++c) {
-          g[c] = *reinterpret_cast<const f32x4*>(gtab + ((size_t)(v * 5 + c)) * D + i0);
+        for (int c = 0; c < C; ++c) {
+          g[c] = *reinterpret_cast<const f32x4*>(gtab + ((size_t)(v * C + c)) * D + i0);
           dg[c][0] = dg[c][1] = dg[c][2] = dg[c][3] = 0.f;
         }
 #pragma unroll
         for (int t = 0; t < VA_T; ++t) {
-          const float* p = pt + (t * V + v) * 5;
+          const float* p = pt + (t * V + v) * C;
           const float a = aw[(t * H + hh) * V + v];
           float dav = 0.f;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const float val = g[0][j] * p[0] + g[1][j] * p[1] + g[2][j] * p[2] + g[3][j] * p[3] + g[4][j];
+            const float val = va_row<P>(g, p, j);
             dav += dzv[t][j] * val;
             const float ad = a * dzv[t][j];
 #pragma unroll
-            for (int c = 0; c < 5; ++c) dg[c][j] += ad * p[c];
+            for (int c = 0; c < C; ++c) dg[c][j] += ad * p[c];
           }
           atomicAdd(&da[(t * H + hh) * V + v], dav);   // LDS atomic: reduce over the head's channels
         }
 #pragma unroll
-        for (int c = 0; c < 5; ++c)
+        for (int c = 0; c < C; ++c)
 #pragma unroll
-          for (int j = 0; j < 4; ++j) atomicAdd(dgtab + ((size_t)(v * 5 + c)) * D + i0 + j, dg[c][j]);
+          for (int j = 0; j < 4; ++j) atomicAdd(dgtab + ((size_t)(v * C + c)) * D + i0 + j, dg[c][j]);
       }
     }
   }
@@ -181,11 +196,11 @@ __global__ __launch_bounds__(256) void varagg_kernel(const float* __restrict__ x
     }
     __syncthreads();
     // dstab[h][v][c] += sum_t ds[t][h][v] * pt[t][v][c]
-    for (int e = tid; e < H * V * 5; e += 256) {
-      const int c = e % 5, v = (e / 5) % V, hh = e / (5 * V);
+    for (int e = tid; e < H * V * C; e += 256) {
+      const int c = e % C, v = (e / C) % V, hh = e / (C * V);
       float s = 0.f;
 #pragma unroll
-      for (int t = 0; t < VA_T; ++t) s += da[(t * H + hh) * V + v] * pt[(t * V + v) * 5 + c];
+      for (int t = 0; t < VA_T; ++t) s += da[(t * H + hh) * V + v] * pt[(t * V + v) * C + c];
       atomicAdd(dstab + e, s);
     }
   }
@@ -451,11 +466,284 @@ static void varagg_bwd_mfma_launch(const float* x, const float* gtab, const floa
   o2_sum_parts(ws_g, splits, (int64_t)V * 5 * D, dgtab, (int64_t)V * 5 * D, 1.0f, 1, s);
 }
 
+
+// ---------------------------------------------------------------------------------------------------------
+// Backward for P != 2 (C = 2 or 17): two stages, no float atomics anywhere, every sum in an order fixed by the shape.
+// The scalar kernel above adds its [V*C, D] table partial to HBM once per 16 tokens, and the MFMA form needs C*V <= 128 rows;
+// neither fits C = 17.  Here
+//   (1) varagg_ds_kernel    per 16 tokens:  da[t,h,v] = sum_{i in h} dz[t,i] * sum_c gtab[v,c,i] pt[t,v,c]  (the scalar kernel's
+//       channel loop without the table part; the per-thread partials of a head's channels meet in LDS and ONE thread adds them
+//       in a fixed order), then the softmax backward ds = a * (da - sum_u a_u da_u) per (token, head) -> ds [tokens, H, V] in HBM
+//   (2) varagg_tabgrad_kernel  one workgroup per (variable v, token range):
+//         dgtab[v][c][i] = sum_t a[t,h(i),v] * pt[t,v,c] * dz[t,i]      (does not depend on the softmax backward)
+//         dstab[h][v][c] = sum_t ds[t,h,v] * pt[t,v,c]
+//       a thread owns its 4-channel chunks; dg[C][4] stays in registers over the whole token range and is stored once into the
+//       range's slab, as is the [H][C] piece of dstab; o2_sum_parts then adds the ranges in order (+= into dstab / dgtab).
+// ---------------------------------------------------------------------------------------------------------
+constexpr int VT_T = 32;      // tokens staged per round of the table-gradient kernel
+
+template <int P>
+__global__ __launch_bounds__(256) void varagg_ds_kernel(const float* __restrict__ x, const float* __restrict__ gtab,
+                                                        const float* __restrict__ attw, const bf16_t* __restrict__ dz,
+                                                        float* __restrict__ ds, int B, int V, int h, int w, int H, int D) {
+  constexpr int PP = P * P, C = PP + 1;
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* pt = sm;                       // [T][V][C]
+  float* aw = pt + VA_T * V * C;        // [T][H][V]
+  float* da = aw + VA_T * H * V;        // [T][H][V]
+  float* part = da + VA_T * H * V;      // [2][T][256]: per-thread partials of da, double-buffered over v
+  const int tid = threadIdx.x;
+  const int Lw = w / P, L = (h / P) * Lw;
+  const int64_t tok0 = (int64_t)blockIdx.x * VA_T;
+  const int64_t ntok = (int64_t)B * L;
+  const int dh = D / H;
+  const int gs = dh / 4;                // threads (4-channel chunks) per head
+
+  for (int e = tid; e < VA_T * V * C; e += 256) {
+    const int c = e % C, v = (e / C) % V, t = e / (C * V);
+    const int64_t tok = tok0 + t;
+    float val = 0.f;
+    if (tok < ntok) {
+      if (c == PP) val = 1.f;
+      else {
+        const int b = (int)(tok / L), l = (int)(tok - (int64_t)b * L);
+        const int pr = l / Lw, pc = l - pr * Lw;
+        val = x[(((size_t)b * V + v) * h + (P * pr + c / P)) * w + P * pc + c % P];
+      }
+    }
+    pt[e] = val;
+  }
+  for (int e = tid; e < VA_T * H * V; e += 256) {
+    const int64_t tok = tok0 + e / (H * V);
+    aw[e] = tok < ntok ? attw[(size_t)tok0 * H * V + e] : 0.f;
+    da[e] = 0.f;
+  }
+  __syncthreads();
+  const int nchunk = D / 4;
+  for (int cb = 0; cb < nchunk; cb += 256) {          // (one round for D <= 1024)
+    const int ch = cb + tid;
+    const bool on = ch < nchunk;
+    const int i0 = on ? ch * 4 : 0;
+    float dzv[VA_T][4];
+#pragma unroll
+    for (int t = 0; t < VA_T; ++t) {
+      const int64_t tok = tok0 + t;
+      if (on && tok < ntok) {
+        const u32x2 r = *reinterpret_cast<const u32x2*>(dz + (size_t)tok * D + i0);
+        dzv[t][0] = bf2f((bf16_t)(r[0] & 0xffff)); dzv[t][1] = bf2f((bf16_t)(r[0] >> 16));
+        dzv[t][2] = bf2f((bf16_t)(r[1] & 0xffff)); dzv[t][3] = bf2f((bf16_t)(r[1] >> 16));
+      } else { dzv[t][0] = dzv[t][1] = dzv[t][2] = dzv[t][3] = 0.f; }
+    }
+    // the heads whose chunks lie in [cb, cb + 256): head hh owns chunks [hh * gs, (hh + 1) * gs)
+    const int h_lo = cb / gs, h_hi = min(H, (min(nchunk, cb + 256) + gs - 1) / gs);
+    for (int v = 0; v < V; ++v) {
+      f32x4 g[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) g[c] = *reinterpret_cast<const f32x4*>(gtab + ((size_t)(v * C + c)) * D + i0);
+      float* pb = part + (v & 1) * (VA_T * 256);
+#pragma unroll
+      for (int t = 0; t < VA_T; ++t) {
+        const float* p = pt + (t * V + v) * C;
+        float dav = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dav += dzv[t][j] * va_row<P>(g, p, j);
+        pb[t * 256 + tid] = dav;                       // (0 for a thread without a chunk: its dz is 0)
+      }
+      __syncthreads();     // one barrier per v: round v + 2 reuses this buffer only after every thread has passed round v + 1's
+      // the owner of (token, head) adds the head's partials in a fixed order (the start is rotated by the head so that the
+      // threads of a wave read different banks); da is touched by its owner only
+      for (int e = tid; e < VA_T * (h_hi - h_lo); e += 256) {
+        const int t = e / (h_hi - h_lo), hh = h_lo + e % (h_hi - h_lo);
+        const int lo = max(hh * gs, cb) - cb, n = min((hh + 1) * gs, cb + 256) - cb - lo;
+        const float* src = pb + t * 256 + lo;
+        float sum = 0.f;
+        int k = hh % n;
+        for (int i = 0; i < n; ++i) {
+          sum += src[k];
+          k = k + 1 == n ? 0 : k + 1;
+        }
+        da[(t * H + hh) * V + v] += sum;
+      }
+    }
+    __syncthreads();
+  }
+  // softmax backward per (token, head): ds_v = a_v (da_v - sum_u a_u da_u)
+  for (int e = tid; e < VA_T * H; e += 256) {
+    const int64_t tok = tok0 + e / H;
+    if (tok >= ntok) continue;
+    float dot = 0.f;
+    for (int v = 0; v < V; ++v) dot += aw[e * V + v] * da[e * V + v];
+    float* o = ds + (size_t)tok0 * H * V + (size_t)e * V;
+    for (int v = 0; v < V; ++v) o[v] = aw[e * V + v] * (da[e * V + v] - dot);
+  }
+}
+
+template <int P>
+__global__ __launch_bounds__(256) void varagg_tabgrad_kernel(const float* __restrict__ x, const float* __restrict__ attw,
+                                                             const float* __restrict__ ds, const bf16_t* __restrict__ dz,
+                                                             float* __restrict__ ws_s, float* __restrict__ ws_g, int B, int V,
+                                                             int h, int w, int H, int D, int rounds_per_wg) {
+  constexpr int PP = P * P, C = PP + 1;
+  constexpr int NS = (VA_MAXH * C + 255) / 256;       // dstab entries of this variable a thread owns: [H][C] over 256 threads
+  __shared__ float pt[VT_T][C];
+  __shared__ float aw[VT_T][VA_MAXH];
+  __shared__ float dsv[VT_T][VA_MAXH];
+  const int tid = threadIdx.x;
+  const int v = blockIdx.x;
+  const int Lw = w / P, L = (h / P) * Lw;
+  const int ntok = B * L;
+  const int nround = (ntok + VT_T - 1) / VT_T;
+  const int r0 = blockIdx.y * rounds_per_wg, r1 = min(nround, r0 + rounds_per_wg);
+  const int dh = D / H, nchunk = D / 4;
+  // this token range's slabs: [range][H][V][C] and [range][V][C][D]
+  ws_s += (size_t)blockIdx.y * H * V * C;
+  ws_g += ((size_t)blockIdx.y * V + v) * C * D;
+  float sacc[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) sacc[k] = 0.f;
+
+  for (int cb = 0; cb < nchunk; cb += 256) {          // (one pass over the range for D <= 1024)
+    const int ch = cb + tid;
+    const bool on = ch < nchunk;
+    const int i0 = on ? ch * 4 : 0;
+    const int hh = i0 / dh;
+    float dg[C][4];
+#pragma unroll
+    for (int c = 0; c < C; ++c) dg[c][0] = dg[c][1] = dg[c][2] = dg[c][3] = 0.f;
+    for (int r = r0; r < r1; ++r) {
+      const int tok0 = r * VT_T;
+      const int nt = min(VT_T, ntok - tok0);
+      for (int e = tid; e < VT_T * C; e += 256) {
+        const int t = e / C, c = e - t * C;
+        float val = 0.f;
+        if (t < nt) {
+          if (c == PP) val = 1.f;
+          else {
+            const int tok = tok0 + t;
+            const int b = tok / L, l = tok - b * L;
+            const int pr = l / Lw, pc = l - pr * Lw;
+            val = x[(((size_t)b * V + v) * h + (P * pr + c / P)) * w + P * pc + c % P];
+          }
+        }
+        pt[t][c] = val;
+      }
+      for (int e = tid; e < VT_T * H; e += 256) {
+        const int t = e / H, h2 = e - t * H;
+        const size_t src = ((size_t)(tok0 + t) * H + h2) * V + v;
+        aw[t][h2] = t < nt ? attw[src] : 0.f;
+        dsv[t][h2] = t < nt ? ds[src] : 0.f;
+      }
+      __syncthreads();
+      if (on) {
+#pragma unroll 4
+        for (int t = 0; t < nt; ++t) {
+          const u32x2 q = *reinterpret_cast<const u32x2*>(dz + (size_t)(tok0 + t) * D + i0);
+          const float a = aw[t][hh];
+          const float ad[4] = {a * bf2f((bf16_t)(q[0] & 0xffff)), a * bf2f((bf16_t)(q[0] >> 16)),
+                               a * bf2f((bf16_t)(q[1] & 0xffff)), a * bf2f((bf16_t)(q[1] >> 16))};
+#pragma unroll
+          for (int c = 0; c < C; ++c) {
+            const float pc_ = pt[t][c];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dg[c][j] += ad[j] * pc_;
+          }
+        }
+      }
+      if (cb == 0) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+          const int e = tid + 256 * k;
+          if (e < H * C) {
+            const int h2 = e / C, c = e - h2 * C;
+            float sum = sacc[k];
+            for (int t = 0; t < VT_T; ++t) sum += dsv[t][h2] * pt[t][c];     // (rows >= nt are zero)
+            sacc[k] = sum;
+          }
+        }
+      }
+      __syncthreads();
+    }
+    if (on) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const f32x4 o = {dg[c][0], dg[c][1], dg[c][2], dg[c][3]};
+        *reinterpret_cast<f32x4*>(ws_g + (size_t)c * D + i0) = o;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    const int e = tid + 256 * k;
+    if (e < H * C) {
+      const int h2 = e / C, c = e - h2 * C;
+      ws_s[((size_t)h2 * V + v) * C + c] = sacc[k];
+    }
+  }
+}
+
+// token ranges of the table-gradient kernel: ~2 workgroups per CU over (variables x ranges)
+static int varagg_tabgrad_splits(int ntok, int V, int* rpw_out) {
+  const int nround = (ntok + VT_T - 1) / VT_T;
+  int splits = (512 + V - 1) / V;
+  if (splits > nround) splits = nround;
+  const int rpw = (nround + splits - 1) / splits;
+  if (rpw_out) *rpw_out = rpw;
+  return (nround + rpw - 1) / rpw;
+}
+
+// dynamic LDS of the kernels above, bytes
+static size_t va_fwd_lds(int P, int V, int H) {          // the forward of P != 2: pt + aw
+  return sizeof(float) * ((size_t)VA_T * V * (P * P + 1) + (size_t)VA_T * H * V);
+}
+static size_t va_ds_lds(int P, int V, int H) {           // varagg_ds_kernel: pt + aw + da + part
+  return sizeof(float) * ((size_t)VA_T * V * (P * P + 1) + 2 * (size_t)VA_T * H * V + 2 * (size_t)VA_T * 256);
+}
+
+template <int P, bool ZF32>
+static int varagg_fwd_launch_p(const float* x, const float* stab, const float* gtab, void* z, float* attw, int B, int V, int h,
+                               int w, int H, int D, hipStream_t s) {
+  const int64_t ntok = (int64_t)B * (h / P) * (w / P);
+  const size_t shm = va_fwd_lds(P, V, H);
+  if (shm > (size_t)VA_LDS_LIMIT) return O2_ERR_UNSUPPORTED;
+  static bool attr_set = false;   // one flag per instantiation
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)varagg_kernel<false, ZF32, P>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              VA_LDS_LIMIT);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((varagg_kernel<false, ZF32, P>), dim3((unsigned)((ntok + VA_T - 1) / VA_T)), dim3(256), shm, s, x, stab,
+                     gtab, (bf16_t*)z, attw, (const bf16_t*)nullptr, (float*)nullptr, (float*)nullptr, B, V, h, w, H, D);
+  return O2_OK;
+}
+
+template <int P>
+static void varagg_bwd_launch_p(const float* x, const float* gtab, const float* attw, const void* dz, float* dstab,
+                                float* dgtab, int B, int V, int h, int w, int H, int D, int ntok, float* ws, hipStream_t s) {
+  constexpr int C = P * P + 1;
+  int rpw;
+  const int splits = varagg_tabgrad_splits(ntok, V, &rpw);
+  float* ws_ds = ws;                                           // [tokens][H][V]
+  float* ws_s = ws_ds + (size_t)ntok * H * V;                  // [range][H][V][C]
+  float* ws_g = ws_s + (size_t)splits * H * V * C;             // [range][V][C][D]
+  static bool attr_set = false;   // one flag per instantiation
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)varagg_ds_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, VA_LDS_LIMIT);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(varagg_ds_kernel<P>, dim3((unsigned)((ntok + VA_T - 1) / VA_T)), dim3(256), va_ds_lds(P, V, H), s, x, gtab,
+                     attw, (const bf16_t*)dz, ws_ds, B, V, h, w, H, D);
+  hipLaunchKernelGGL(varagg_tabgrad_kernel<P>, dim3((unsigned)V, (unsigned)splits), dim3(256), 0, s, x, attw, ws_ds,
+                     (const bf16_t*)dz, ws_s, ws_g, B, V, h, w, H, D, rpw);
+  o2_sum_parts(ws_s, splits, (int64_t)H * V * C, dstab, (int64_t)H * V * C, 1.0f, 1, s);     // += into the caller's tables
+  o2_sum_parts(ws_g, splits, (int64_t)V * C * D, dgtab, (int64_t)V * C * D, 1.0f, 1, s);
+}
+
 }  // namespace
 
-static int va_check(int B, int V, int h, int w, int H, int D) {
-  if (B <= 0 || V <= 0 || V > VA_MAXV || H <= 0 || H > VA_MAXH || D <= 0) return O2_ERR_ARG;
-  if ((h & 1) || (w & 1) || (D % 4) || (D % H) || ((D / H) % 4)) return O2_ERR_ARG;
+static int va_check(int B, int V, int h, int w, int H, int D, int P = 2) {
+  if (P != 1 && P != 2 && P != 4) return O2_ERR_ARG;
+  if (B <= 0 || V <= 0 || V > VA_MAXV || H <= 0 || H > VA_MAXH || D <= 0 || h <= 0 || w <= 0) return O2_ERR_ARG;
+  if ((h % P) || (w % P) || (D % 4) || (D % H) || ((D / H) % 4)) return O2_ERR_ARG;
   return O2_OK;
 }
 
@@ -525,6 +813,67 @@ extern "C" int orbit2_varagg_bwd(const float* x, const float* gtab, const float*
   hipLaunchKernelGGL(varagg_kernel<true>, dim3((unsigned)((ntok + VA_T - 1) / VA_T)), dim3(256), shm,
                      (hipStream_t)stream, x, (const float*)nullptr, gtab, (bf16_t*)nullptr, (float*)attw,
                      (const bf16_t*)dz, dstab, dgtab, B, V, h, w, H, D);
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+// ---- the entries that carry the patch size (1, 2 or 4).  patch = 2 is the call above: same kernels, same launch --------------
+extern "C" int orbit2_varagg_fwd_p(const float* x, const float* stab, const float* gtab, void* z, float* attw, int B, int V,
+                                   int h, int w, int patch, int H, int D, void* stream) {
+  if (!x || !stab || !gtab || !z || !attw) return O2_ERR_ARG;
+  int rc = va_check(B, V, h, w, H, D, patch);
+  if (rc) return rc;
+  if (patch == 2) return orbit2_varagg_fwd(x, stab, gtab, z, attw, B, V, h, w, H, D, stream);
+  rc = patch == 1 ? varagg_fwd_launch_p<1, false>(x, stab, gtab, z, attw, B, V, h, w, H, D, (hipStream_t)stream)
+                  : varagg_fwd_launch_p<4, false>(x, stab, gtab, z, attw, B, V, h, w, H, D, (hipStream_t)stream);
+  if (rc) return rc;
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+extern "C" int orbit2_varagg_fwd_f32_p(const float* x, const float* stab, const float* gtab, float* z, float* attw, int B,
+                                       int V, int h, int w, int patch, int H, int D, void* stream) {
+  if (!x || !stab || !gtab || !z) return O2_ERR_ARG;              // attw may be NULL
+  int rc = va_check(B, V, h, w, H, D, patch);
+  if (rc) return rc;
+  if (patch == 2) return orbit2_varagg_fwd_f32(x, stab, gtab, z, attw, B, V, h, w, H, D, stream);
+  rc = patch == 1 ? varagg_fwd_launch_p<1, true>(x, stab, gtab, z, attw, B, V, h, w, H, D, (hipStream_t)stream)
+                  : varagg_fwd_launch_p<4, true>(x, stab, gtab, z, attw, B, V, h, w, H, D, (hipStream_t)stream);
+  if (rc) return rc;
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+// whether orbit2_varagg_bwd_p serves the shape at patch != 2: valid arguments, token count in int range, LDS within a CU's
+static bool varagg_bwd_p_served(int B, int V, int h, int w, int patch, int H, int D) {
+  if (va_check(B, V, h, w, H, D, patch)) return false;
+  if ((int64_t)B * (h / patch) * (w / patch) >= (1ll << 31) - 64) return false;
+  return va_ds_lds(patch, V, H) <= (size_t)VA_LDS_LIMIT;
+}
+
+extern "C" int64_t orbit2_varagg_bwd_p_ws_floats(int B, int V, int h, int w, int patch, int H, int D) {
+  if (patch == 2) return orbit2_varagg_bwd_ws_floats(B, V, h, w, H, D);
+  if (!varagg_bwd_p_served(B, V, h, w, patch, H, D)) return 0;
+  const int64_t ntok = (int64_t)B * (h / patch) * (w / patch);
+  const int64_t C = patch * patch + 1;
+  return ntok * H * V + (int64_t)varagg_tabgrad_splits((int)ntok, V, nullptr) * ((int64_t)H * V * C + (int64_t)V * C * D);
+}
+
+extern "C" int orbit2_varagg_bwd_p_is_fixed_order(int B, int V, int h, int w, int patch, int H, int D) {
+  if (patch == 2) return orbit2_varagg_bwd_is_fixed_order(B, V, h, w, H, D);
+  return varagg_bwd_p_served(B, V, h, w, patch, H, D) ? 1 : 0;     // the only path at patch 1 / 4 is the fixed-order one
+}
+
+extern "C" int orbit2_varagg_bwd_p(const float* x, const float* gtab, const float* attw, const void* dz, float* dstab,
+                                   float* dgtab, int B, int V, int h, int w, int patch, int H, int D, float* ws, void* stream) {
+  if (!x || !gtab || !attw || !dz || !dstab || !dgtab || !ws) return O2_ERR_ARG;
+  int rc = va_check(B, V, h, w, H, D, patch);
+  if (rc) return rc;
+  if (patch == 2) return orbit2_varagg_bwd(x, gtab, attw, dz, dstab, dgtab, B, V, h, w, H, D, ws, stream);
+  if (!varagg_bwd_p_served(B, V, h, w, patch, H, D)) return O2_ERR_UNSUPPORTED;
+  const int ntok = B * (h / patch) * (w / patch);
+  if (patch == 1) varagg_bwd_launch_p<1>(x, gtab, attw, dz, dstab, dgtab, B, V, h, w, H, D, ntok, ws, (hipStream_t)stream);
+  else varagg_bwd_launch_p<4>(x, gtab, attw, dz, dstab, dgtab, B, V, h, w, H, D, ntok, ws, (hipStream_t)stream);
   O2_CHECK_LAUNCH();
   return O2_OK;
 }
