@@ -27,7 +27,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "orbit-2_amd")]
 
 import climate_learn as cl                                                        # noqa: E402
 from climate_learn.utils.fused_attn import FusedAttn                              # noqa: E402
-from climate_learn.utils.visualize import tiled_predict, visualize_at_index      # noqa: E402
+from climate_learn.utils.visualize import stitched_scores, tiled_predict, visualize_at_index      # noqa: E402
 
 
 def main():
@@ -81,6 +81,17 @@ def main():
     gt = denorm(y[:, :, : pred.shape[2], : pred.shape[3]].float())
     for loss in test_losses:
         print(loss.name, [round(float(v), 6) for v in loss(pred, gt).reshape(-1)], flush=True)
+    if conf.get("stitched_scores", False):
+        # PSNR / SSIM of every output variable of the whole batch on the device (visualize_at_index scores one variable of one
+        # sample on the host); latitude weights as the lat_* metrics build them
+        lat = dm_vis.get_lat_lon()[0]
+        w = None
+        if lat is not None:
+            import numpy as np
+            w = np.cos(np.deg2rad(np.asarray(lat, dtype=np.float64)))
+            w = torch.from_numpy(w / w.mean()).float()
+        for var, sc in stitched_scores(pred, gt, ov, w).items():
+            print("stitched_scores", var, {k: round(v, 6) for k, v in sc.items()}, flush=True)
     mcd = conf.get("mc_dropout")
     if mcd:
         scores = mcd.get("scores")

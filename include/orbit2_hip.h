@@ -32,7 +32,8 @@ extern "C" {
  * Everything else is as at version 7, the entries that were added during it included (the fp32 forward entries orbit2_gemm_f32,
  * orbit2_attn_fwd_f32, orbit2_layernorm_fwd_f32, orbit2_varagg_fwd_f32, orbit2_unpatchify_fwd_f32; orbit2_ensemble_update and
  * orbit2_gaussian_scores).  Added during version 8, changing nothing that exists: orbit2_ensemble_scores; the folded patch-embed
- * entries that carry the patch size (orbit2_varagg_fwd_p, orbit2_varagg_fwd_f32_p, orbit2_varagg_bwd_p and its two queries). */
+ * entries that carry the patch size (orbit2_varagg_fwd_p, orbit2_varagg_fwd_f32_p, orbit2_varagg_bwd_p and its two queries);
+ * orbit2_ssim. */
 int orbit2_abi_version(void);
 
 /* ---- bf16 MFMA GEMM with fused epilogue ------------------------------------------------
@@ -390,6 +391,40 @@ int orbit2_gaussian_scores(const float* mean, const float* std_, const float* ta
 int orbit2_ensemble_scores(const float* members, int64_t member_stride, int N, const float* target, int Ht, int Wt,
                            const float* lat_w, double* sums, float* crps_field, int fair, int64_t* hist, uint64_t seed,
                            float* quant, const float* levels, int Q, int B, int C, int H, int W, void* stream);
+
+/* orbit2_ssim: structural similarity (and the squared-error sum that PSNR needs) of every (b, c) image of a prediction against
+ * a target, as scikit-image's structural_similarity defines it by default: a 7 x 7 uniform window (ORBIT2_SSIM_WIN, the only
+ * size built), K1 = 0.01, K2 = 0.03, sample covariance (factor 49 / 48), and the score of an image the mean of S over the
+ * centres whose window lies wholly inside it, rows 3 .. H - 4 and columns 3 .. W - 4 ("valid centres").  With the window means
+ * ux, uy, the variances vx, vy, the covariance vxy, C1 = (K1 R)^2 and C2 = (K2 R)^2 for the data range R:
+ *   S = (2 ux uy + C1) (2 vxy + C2) / ((ux^2 + uy^2 + C1) (vx + vy + C2)).
+ * pred fp32 [B,C,H,W]; target fp32 [B,C,Ht,Wt] (top-left crop; Ht >= H, Wt >= W); lat_w fp32 [H] or NULL (w = 1).
+ * data_range device fp32 [B][C] or NULL: NULL = every image uses max - min of its own target crop, found on the device by a
+ * first launch of the entry and handed to the SSIM pass through sums[3..4] (no host synchronisation); given = that value is
+ * used, min and max are reported all the same.
+ *   sums     double [B][C][6], initialised by the entry, accumulated across workgroups as orbit2_gaussian_scores does (fp32
+ *            per-thread partials, wave and workgroup reduction, one double atomic per workgroup and sum):
+ *              0 sum of S over the valid centres      1 sum of lat_w[y] S (y the centre's row)
+ *              2 sum of (pred - target)^2 over ALL H x W pixels
+ *              3 target min    4 target max    5 the data range actually used (R; max - min in double when not given)
+ *            host forms: SSIM = [0] / ((H - 6) (W - 6)), weighted = [1] / ((W - 6) sum_{y = 3}^{H - 4} lat_w[y]),
+ *            PSNR = 10 log10([5]^2 H W / [2]).
+ *   ssim_map fp32 [B][C][H - 6][W - 6] or NULL: S at every valid centre (scikit-image's full=True map without its border).
+ * CENTRING IS PART OF THE CONTRACT: both fields are centred on one shared pivot, a target value inside the workgroup's tile
+ * (ORBIT2_SSIM_TILE_H x ORBIT2_SSIM_TILE_W centres; in fact one under the 14 x 7 pixels a lane's windows cover), before
+ * anything is squared or summed; variances and covariance come from the centred sums, the means get the pivot added back for
+ * the luminance term.  Why: on a 39 x 71 field at offset 280 (kelvin) with range 5 the raw fp32 form is off by up to 4.8e-1
+ * per pixel, the centred one by 2e-6.
+ * R == 0 (a wholly constant target image) is not special-cased: C1 = C2 = 0, a flat window is 0 / 0, and sums[0..1] of that
+ * image are NaN, as scikit-image's would be; the other images of the call are not affected.  Non-finite inputs give unspecified
+ * scores and never a fault: no address depends on a value.
+ * NULL pred, target or sums, a non-positive size, H < 7 or W < 7, a target smaller than the prediction or B * C > 65535 return
+ * O2_ERR_ARG before any launch, with nothing written. */
+#define ORBIT2_SSIM_WIN 7
+#define ORBIT2_SSIM_TILE_H 32
+#define ORBIT2_SSIM_TILE_W 64
+int orbit2_ssim(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* data_range,
+                double* sums, float* ssim_map, int B, int C, int H, int W, void* stream);
 
 /* ---- perceptual loss = L1 + 0.5 * mean_b LPIPS-VGG16 (metrics/functional.py:17-33, metrics.py:119-187) ------
  * Feature maps are NHWC bf16, so each 3x3 VGG convolution is im2col + orbit2_gemm_bf16 (bias, act = 2) forward and

@@ -110,6 +110,7 @@ PROTOTYPES = {
     "orbit2_ensemble_update": (_I, (_P, _P, _P, _I64, _I, _P)),
     "orbit2_gaussian_scores": (_I, (_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P)),
     "orbit2_ensemble_scores": (_I, (_P, _I64, _I, _P, _I, _I, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _I, _I, _I, _I, _P)),
+    "orbit2_ssim": (_I, (_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P)),
     "orbit2_im2col3x3": (_I, (_P, _P, _I, _I, _I, _I, _P)),
     "orbit2_col2im3x3": (_I, (_P, _P, _P, _P, _I, _I, _I, _I, _P)),
     "orbit2_maxpool2_fwd": (_I, (_P, _P, _I, _I, _I, _I, _P)),
@@ -1038,6 +1039,46 @@ def ensemble_scores(members, target, lat_w=None, *, sums=True, hist=False, seed=
                                       0 if levels is None else levels.numel(), B, Cc, H, W, _stream()),
          "orbit2_ensemble_scores")
     return out
+
+
+SSIM_WIN = 7                    # ORBIT2_SSIM_WIN: the only window size built
+SSIM_TILE = (32, 64)            # (ORBIT2_SSIM_TILE_H, ORBIT2_SSIM_TILE_W): window centres per workgroup
+
+
+def ssim_sums(pred, target, lat_w=None, data_range=None, ssim_map=False):
+    """[B,C,6] float64 sums {S, lat_w S, (pred - target)^2 over all pixels, target min, target max, data range used} of the
+    7 x 7 structural similarity of every (b, c) image (include/orbit2_hip.h:orbit2_ssim); the target may be larger than the
+    prediction (top-left crop).  `data_range`: None = max - min of every image's own target crop (found on the device), a
+    number, or a tensor that broadcasts to [B,C].  With ssim_map=True returns (sums, map), map fp32 [B,C,H-6,W-6]: S at the
+    centres whose window lies inside the image."""
+    if pred.dim() != 4 or target.dim() != 4:
+        raise HipBackendError("ssim_sums takes [B,C,H,W] fields")
+    B, Cc, H, W = pred.shape
+    if H < SSIM_WIN or W < SSIM_WIN:
+        raise HipBackendError("ssim_sums: the prediction is %d x %d, the window needs at least %d x %d"
+                              % (H, W, SSIM_WIN, SSIM_WIN))
+    _dev(pred, F32, "pred"); _dev(target, F32, "target")
+    if tuple(target.shape[:2]) != tuple(pred.shape[:2]):
+        raise HipBackendError("ssim_sums: target %s does not match the prediction's [B,C] %s"
+                              % (tuple(target.shape), tuple(pred.shape[:2])))
+    if target.shape[2] < H or target.shape[3] < W:
+        raise HipBackendError("ssim_sums: target %s is smaller than the prediction %s"
+                              % (tuple(target.shape), (B, Cc, H, W)))
+    if lat_w is not None:
+        _dev(lat_w, F32, "lat_w")
+        if lat_w.numel() < H:
+            raise HipBackendError("lat_w has %d entries, the prediction %d rows" % (lat_w.numel(), H))
+    rng = None
+    if data_range is not None:
+        if torch.is_tensor(data_range):
+            rng = data_range.detach().to(device=pred.device, dtype=F32).expand(B, Cc).contiguous()
+        else:
+            rng = torch.full((B, Cc), float(data_range), dtype=F32, device=pred.device)
+    sums = torch.empty(B, Cc, 6, dtype=torch.float64, device=pred.device)
+    smap = torch.empty(B, Cc, H - SSIM_WIN + 1, W - SSIM_WIN + 1, dtype=F32, device=pred.device) if ssim_map else None
+    _chk(lib().orbit2_ssim(_p(pred), _p(target), target.shape[2], target.shape[3], _p(lat_w), _p(rng), _p(sums), _p(smap),
+                           B, Cc, H, W, _stream()), "orbit2_ssim")
+    return (sums, smap) if ssim_map else sums
 
 
 def seed_salt(value: int, add: bool = False):

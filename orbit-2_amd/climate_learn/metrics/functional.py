@@ -250,3 +250,47 @@ def ensemble_quantiles(pred, q):
     from .. import _hip
     m = _ensemble(pred)
     return _hip.ensemble_scores(m, m[0], sums=False, quantiles=q)["quantiles"]
+
+
+# ---- image-quality scores of a downscaled field (reference utils/visualize.py:366-372, through scikit-image there): SSIM and
+# PSNR per (b, c) image from one windowed kernel (orbit2_ssim: [B,C,6] double sums of S, w S, the squared error, the target's
+# min and max and the data range used), the means on the host.  `data_range`: None = max - min of every image's own target, as
+# the reference passes it; a number or a tensor that broadcasts to [B,C] otherwise. ------------------------------------------------
+def _ssim_sums(pred, target, lat_weights=None, data_range=None):
+    from .. import _hip
+    if isinstance(pred, torch.distributions.Normal):
+        pred = pred.loc
+    pred = pred.detach().float().contiguous()
+    return _hip.ssim_sums(pred, target.detach().float().contiguous(), _lat(lat_weights, pred), data_range), pred
+
+
+def _ssim_per_image(s, pred, lat_weights=None):
+    """[B,C] SSIM from the sums: the mean of S over the valid centres, weighted by the centre row's latitude weight if given"""
+    hv, wv = pred.shape[2] - 6, pred.shape[3] - 6
+    if lat_weights is None:
+        return s[..., 0] / (hv * wv)
+    return s[..., 1] / (wv * _lat(lat_weights, pred)[3:3 + hv].double().sum())
+
+
+def _psnr_per_image(s, pred):
+    """[B,C] PSNR in dB from the sums, in double on the host"""
+    s = s.cpu()
+    mse = s[..., 2] / (pred.shape[2] * pred.shape[3])
+    return torch.where(mse == 0, torch.full_like(mse, float("inf")),
+                       10.0 * torch.log10(s[..., 5] ** 2 / mse.clamp_min(torch.finfo(torch.float64).tiny)))
+
+
+def ssim(pred, target, aggregate_only: bool = False, lat_weights=None, data_range=None):
+    """Structural similarity with scikit-image's defaults (7 x 7 uniform window, K1 = 0.01, K2 = 0.03, sample covariance): per
+    (b, c) image the mean of S over the centres whose window lies inside it -- with latitude weights the mean weighted by the
+    centre row's weight, normalised over those rows -- then the mean over b, then over c.  A wholly constant target image with
+    data_range=None has range 0 and scores NaN, as scikit-image's would."""
+    s, pred = _ssim_sums(pred, target, lat_weights, data_range)
+    return _with_aggregate(_ssim_per_image(s, pred, lat_weights).mean(0).float(), aggregate_only)
+
+
+def psnr(pred, target, aggregate_only: bool = False, data_range=None):
+    """Peak signal-to-noise ratio in dB, 10 log10(range^2 / mse) per (b, c) image (inf at mse == 0), in double on the host from
+    the kernel's sums; the mean over b, then over c."""
+    s, pred = _ssim_sums(pred, target, None, data_range)
+    return _with_aggregate(_psnr_per_image(s, pred).mean(0).float().to(pred.device), aggregate_only)

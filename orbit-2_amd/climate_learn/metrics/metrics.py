@@ -7,7 +7,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from .functional import acc, bayesian_tv, image_gradient, mae, mean_bias, mse, pearson, rmse
+from .functional import acc, bayesian_tv, image_gradient, mae, mean_bias, mse, pearson, psnr, rmse, ssim
 from .utils import MetricsMetaInfo, register
 
 
@@ -149,6 +149,27 @@ class LatWeightedRMSE(LatitudeWeightedMetric):
 class MAE(Metric):
     def __call__(self, pred, target):
         return mae(pred, target, self.aggregate_only)
+
+
+@register("ssim")
+class SSIM(Metric):
+    """structural similarity of every (b, c) image, scikit-image's defaults, data range = max - min of the image's target (the
+    score the reference prints for a stitched field, utils/visualize.py:366-372)"""
+    def __call__(self, pred, target):
+        return ssim(pred, target, self.aggregate_only)
+
+
+@register("lat_ssim")
+class LatWeightedSSIM(LatitudeWeightedMetric):
+    def __call__(self, pred, target):
+        self.cast_to_device(pred)
+        return ssim(pred, target, self.aggregate_only, self.lat_weights)
+
+
+@register("psnr")
+class PSNR(Metric):
+    def __call__(self, pred, target):
+        return psnr(pred, target, self.aggregate_only)
 
 
 class ClimatologyBasedMetric(Metric):

@@ -140,6 +140,22 @@ def psnr_ssim(groundtruth, pred, win: int = 7):
     return psnr, float(smap[pad:-pad, pad:-pad].mean())
 
 
+def stitched_scores(preds, y, out_variables, lat_weights=None):
+    """PSNR and SSIM of a stitched prediction per output variable, on the device: `preds` [B,C,yout,xout] from tiled_predict,
+    `y` the normalised target [B,C,>=yout,>=xout] (its top-left crop is scored), data range = max - min of every image's own
+    target as the reference passes it to scikit-image (utils/visualize.py:366-372).  One pass of orbit2_ssim over the whole
+    batch; only its [B,C,6] sums leave the device.  Returns {variable: {"psnr", "ssim"[, "lat_ssim"]}}, each the mean over the
+    batch -- the per-channel entries of metrics.functional.psnr / ssim on the same tensors."""
+    from .. import _hip
+    from ..metrics import functional as fn
+    preds = preds.detach().float().contiguous()
+    s = _hip.ssim_sums(preds, y.detach().float().contiguous(), fn._lat(lat_weights, preds))
+    cols = {"psnr": fn._psnr_per_image(s, preds).mean(0).float(), "ssim": fn._ssim_per_image(s, preds).mean(0).float().cpu()}
+    if lat_weights is not None:
+        cols["lat_ssim"] = fn._ssim_per_image(s, preds, lat_weights).mean(0).float().cpu()
+    return {v: {k: float(col[c]) for k, col in cols.items()} for c, v in enumerate(out_variables)}
+
+
 def visualize_at_index(mm, dm, dm_vis, out_list, in_transform, out_transform, variable, src, device, div, overlap, index=0,
                        tensor_par_size=1, tensor_par_group=None, save_png: bool = True, prefix: str = ""):
     """Stitched input / prediction / ground truth of test sample `index` for `variable` (reference :38-490; the PNG
