@@ -15,7 +15,11 @@ field, and saves the mean and the spread as <rank>_mc_mean.npy / <rank>_mc_sprea
 (configs/inference_mc_members.yaml) the same ensemble is then built as a member stack (climate_learn.utils.mc_dropout_members:
 N fields held) and scored without the Gaussian fit: ensemble_crps, ensemble_crps_fair, ensemble_spread_skill_ratio and one
 rank_histogram line per output channel are printed, <rank>_mc_rank_hist.npy and the 5 % / 50 % / 95 % quantile fields
-<rank>_mc_p05.npy / _p50.npy / _p95.npy saved."""
+<rank>_mc_p05.npy / _p50.npy / _p95.npy saved.
+
+An optional `baseline: {mode: bilinear}` block (configs/inference_baseline.yaml; nearest, bilinear or bicubic) prints one
+`baseline_scores` line per output variable: the rmse of the stitched field, the rmse of plain interpolation of the model's own
+input, and the mean-squared-error skill of the first against the second (climate_learn.utils.visualize.baseline_scores)."""
 import os
 import sys
 
@@ -27,7 +31,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "orbit-2_amd")]
 
 import climate_learn as cl                                                        # noqa: E402
 from climate_learn.utils.fused_attn import FusedAttn                              # noqa: E402
-from climate_learn.utils.visualize import stitched_scores, tiled_predict, visualize_at_index      # noqa: E402
+from climate_learn.utils.visualize import baseline_scores, stitched_scores, tiled_predict, visualize_at_index      # noqa: E402
 
 
 def main():
@@ -77,21 +81,25 @@ def main():
     print("stitched", {k: (v.shape if hasattr(v, "shape") else v) for k, v in res.items()}, flush=True)
     x, y, iv, ov = next(iter(dm_vis.test_dataloader()))[:4]
     x, y = x.to(device), y.to(device)
-    pred = denorm(tiled_predict(model, x, y, iv, ov, div, overlap))
+    pred_norm = tiled_predict(model, x, y, iv, ov, div, overlap)
+    pred = denorm(pred_norm)
     gt = denorm(y[:, :, : pred.shape[2], : pred.shape[3]].float())
     for loss in test_losses:
         print(loss.name, [round(float(v), 6) for v in loss(pred, gt).reshape(-1)], flush=True)
     if conf.get("stitched_scores", False):
         # PSNR / SSIM of every output variable of the whole batch on the device (visualize_at_index scores one variable of one
         # sample on the host); latitude weights as the lat_* metrics build them
-        lat = dm_vis.get_lat_lon()[0]
-        w = None
-        if lat is not None:
-            import numpy as np
-            w = np.cos(np.deg2rad(np.asarray(lat, dtype=np.float64)))
-            w = torch.from_numpy(w / w.mean()).float()
-        for var, sc in stitched_scores(pred, gt, ov, w).items():
+        for var, sc in stitched_scores(pred, gt, ov, _lat_weights(dm_vis)).items():
             print("stitched_scores", var, {k: round(v, 6) for k, v in sc.items()}, flush=True)
+    baseline = conf.get("baseline")
+    if baseline:
+        # the same field read against plain interpolation of its own input, in physical units; the baseline is scored without
+        # being stored (climate_learn.utils.visualize.baseline_scores)
+        from climate_learn.utils.loaders import _interpolation_rescale
+        for var, sc in baseline_scores(x, y, iv, ov, pred_norm, mode=baseline.get("mode", "bilinear"),
+                                       lat_weights=_lat_weights(dm_vis), denorm=denorm,
+                                       rescale=_interpolation_rescale(dm_vis, ov)).items():
+            print("baseline_scores", var, {k: round(v, 6) for k, v in sc.items()}, flush=True)
     mcd = conf.get("mc_dropout")
     if mcd:
         scores = mcd.get("scores")
@@ -99,6 +107,16 @@ def main():
             raise RuntimeError("mc_dropout.scores: 'members' or absent, got %r" % (scores,))
         return mc_dropout_report(model, (x, y, iv, ov), gt, denorm, int(mcd["members"]), int(mcd.get("seed", 0)), div, overlap,
                                  local_rank, member_scores=scores == "members")
+
+
+def _lat_weights(dm):
+    """cos(latitude) / its mean, as the lat_* metrics build them; None without latitudes"""
+    lat = dm.get_lat_lon()[0]
+    if lat is None:
+        return None
+    import numpy as np
+    w = np.cos(np.deg2rad(np.asarray(lat, dtype=np.float64)))
+    return torch.from_numpy(w / w.mean()).float()
 
 
 def mc_dropout_report(model, batch, gt, denorm, members, seed, div, overlap, rank, *, member_scores=False):

@@ -33,7 +33,7 @@ extern "C" {
  * orbit2_attn_fwd_f32, orbit2_layernorm_fwd_f32, orbit2_varagg_fwd_f32, orbit2_unpatchify_fwd_f32; orbit2_ensemble_update and
  * orbit2_gaussian_scores).  Added during version 8, changing nothing that exists: orbit2_ensemble_scores; the folded patch-embed
  * entries that carry the patch size (orbit2_varagg_fwd_p, orbit2_varagg_fwd_f32_p, orbit2_varagg_bwd_p and its two queries);
- * orbit2_ssim. */
+ * orbit2_ssim; orbit2_resample_fwd and orbit2_resample_moments. */
 int orbit2_abi_version(void);
 
 /* ---- bf16 MFMA GEMM with fused epilogue ------------------------------------------------
@@ -425,6 +425,43 @@ int orbit2_ensemble_scores(const float* members, int64_t member_stride, int N, c
 #define ORBIT2_SSIM_TILE_W 64
 int orbit2_ssim(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* data_range,
                 double* sums, float* ssim_map, int B, int C, int H, int W, void* stream);
+
+/* ---- interpolation baselines (models/hub/interpolation.py) ------------------------------------------------
+ * orbit2_resample_fwd: out[b][c] = scale[c] * resample(x[b][chan_idx[c]]) + shift[c], the resampling being
+ * F.interpolate(size = (H, W), align_corners = False) without antialiasing, for any h, w, H, W >= 1 (integer and non-integer
+ * upsampling, identity, downsampling).  mode: 0 nearest, 1 bilinear, 2 bicubic.
+ *   x        fp32 [B][in_ctotal][h][w]
+ *   chan_idx device int[C] or NULL (identity; then C == in_ctotal), as in orbit2_conv3x3_fwd.  It lives on the device, so the
+ *            entry trusts it: the caller checks 0 <= idx < in_ctotal.
+ *   scale, shift  device fp32 [C], both or neither: the pixel is fmaf(scale[c], r, shift[c]), or r.
+ *   out      fp32 [B][C][H][W]
+ * THE COORDINATES ARE PART OF THE CONTRACT: fp32, every product and difference rounded on its own (no fused multiply-add).
+ *   ratio = (float)in / (float)out
+ *   nearest   i = min((int)floorf(o * ratio), in - 1)
+ *   bilinear  s = max(ratio * (o + 0.5f) - 0.5f, 0), i0 = (int)s, i1 = min(i0 + 1, in - 1), l1 = s - i0, l0 = 1 - l1
+ *   bicubic   s = ratio * (o + 0.5f) - 0.5f, b = floorf(s), t = s - b, taps b - 1 .. b + 2 with clamped indices,
+ *             cubic-convolution weights with A = -0.75: ((A x - 5A) x + 8A) x - 4A at x = t + 1 and 2 - t,
+ *             ((A + 2) x - (A + 3)) x x + 1 at x = t and 1 - t, every product rounded on its own here too
+ * A row interpolant is its taps left to right (a product, then fused multiply-adds), a pixel its row interpolants top to bottom.
+ * Nearest picks ATen's source pixel; identity is exact in all three modes.
+ * A workgroup owns an ORBIT2_RESAMPLE_TILE_H x ORBIT2_RESAMPLE_TILE_W tile of one image and stages the source pixels under it in
+ * LDS when (ceil(TILE_H h / H) + 4) (ceil(TILE_W w / W) + 4) <= ORBIT2_RESAMPLE_LDS_FLOATS, which holds for every upsampling
+ * ratio and the identity; otherwise it reads the taps from global memory.  Same values either way.
+ * orbit2_resample_moments: out[b][c][12] (double) = the twelve sums of orbit2_eval_moments, in its order, of that same field
+ * WITHOUT storing it: a = value - clim, b = target - clim (clim fp32 [C][H][W] or NULL; target fp32 [B][C][Ht][Wt] through its
+ * top-left crop; w = lat_w[y] or 1).  The entry zeroes out and accumulates as orbit2_eval_moments does (fp32 per-lane
+ * partials, here over at most TILE_H / 4 x 4 pixels, a wave and workgroup reduction, one double atomic per workgroup and sum).
+ * No address depends on a value: non-finite inputs give unspecified values, never a fault.
+ * NULL x, out or target, exactly one of scale and shift, chan_idx NULL with C != in_ctotal, a mode outside 0..2, a non-positive
+ * size, a target smaller than H x W or B * C > 65535 return O2_ERR_ARG before any launch, with nothing written. */
+#define ORBIT2_RESAMPLE_TILE_H 32
+#define ORBIT2_RESAMPLE_TILE_W 256
+#define ORBIT2_RESAMPLE_LDS_FLOATS 10240
+int orbit2_resample_fwd(const float* x, const int* chan_idx, int in_ctotal, const float* scale, const float* shift,
+                        float* out, int B, int C, int h, int w, int H, int W, int mode, void* stream);
+int orbit2_resample_moments(const float* x, const int* chan_idx, int in_ctotal, const float* scale, const float* shift,
+                            const float* target, int Ht, int Wt, const float* lat_w, const float* clim, double* out,
+                            int B, int C, int h, int w, int H, int W, int mode, void* stream);
 
 /* ---- perceptual loss = L1 + 0.5 * mean_b LPIPS-VGG16 (metrics/functional.py:17-33, metrics.py:119-187) ------
  * Feature maps are NHWC bf16, so each 3x3 VGG convolution is im2col + orbit2_gemm_bf16 (bias, act = 2) forward and

@@ -111,6 +111,8 @@ PROTOTYPES = {
     "orbit2_gaussian_scores": (_I, (_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P)),
     "orbit2_ensemble_scores": (_I, (_P, _I64, _I, _P, _I, _I, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _I, _I, _I, _I, _P)),
     "orbit2_ssim": (_I, (_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P)),
+    "orbit2_resample_fwd": (_I, (_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P)),
+    "orbit2_resample_moments": (_I, (_P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P)),
     "orbit2_im2col3x3": (_I, (_P, _P, _I, _I, _I, _I, _P)),
     "orbit2_col2im3x3": (_I, (_P, _P, _P, _P, _I, _I, _I, _I, _P)),
     "orbit2_maxpool2_fwd": (_I, (_P, _P, _I, _I, _I, _I, _P)),
@@ -1079,6 +1081,109 @@ def ssim_sums(pred, target, lat_w=None, data_range=None, ssim_map=False):
     _chk(lib().orbit2_ssim(_p(pred), _p(target), target.shape[2], target.shape[3], _p(lat_w), _p(rng), _p(sums), _p(smap),
                            B, Cc, H, W, _stream()), "orbit2_ssim")
     return (sums, smap) if ssim_map else sums
+
+
+RESAMPLE_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}
+RESAMPLE_TILE = (32, 256)       # (ORBIT2_RESAMPLE_TILE_H, ORBIT2_RESAMPLE_TILE_W): output pixels per workgroup
+RESAMPLE_LDS_FLOATS = 10240     # ORBIT2_RESAMPLE_LDS_FLOATS: the staged source window of a tile
+
+
+_RESAMPLE_IDX = {}              # (channels, device) -> the validated device int32 copy
+
+
+def resample_staged(h: int, w: int, H: int, W: int) -> bool:
+    """whether orbit2_resample_* stages a tile's source window in LDS at this pair of sizes (the header's rule: the full-tile
+    footprint of the ratio fits the budget) or reads the taps from global memory"""
+    th, tw = RESAMPLE_TILE
+    return (-(-th * h // H) + 4) * (-(-tw * w // W) + 4) <= RESAMPLE_LDS_FLOATS
+
+
+def _resample_args(x, size, mode, channels, scale, shift, what):
+    """the checked operands both resample entries share: (B, Cin, h, w, C, H, W, mode code, chan_idx, scale, shift)"""
+    if not torch.is_tensor(x) or x.dim() != 4:
+        raise HipBackendError("%s takes an [B,C,h,w] field" % what)
+    if mode not in RESAMPLE_MODES:
+        raise HipBackendError("%s: mode is one of %s, got %r" % (what, ", ".join(RESAMPLE_MODES), mode))
+    try:
+        H, W = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise HipBackendError("%s: size is (H, W), got %r" % (what, size)) from None
+    B, Cin, h, w = x.shape
+    if min(B, Cin, h, w) < 1 or H < 1 or W < 1:
+        raise HipBackendError("%s: every size must be positive (x %s, size %s)" % (what, tuple(x.shape), (H, W)))
+    idx = None
+    Cc = Cin
+    if channels is not None:
+        chans = [int(c) for c in (channels.tolist() if torch.is_tensor(channels) else channels)]
+        if not chans:
+            raise HipBackendError("%s: channels is empty" % what)
+        bad = [c for c in chans if not 0 <= c < Cin]
+        if bad:                                 # the C entry trusts the device copy: this is the only check
+            raise HipBackendError("%s: channels %s outside 0..%d" % (what, bad, Cin - 1))
+        Cc = len(chans)
+    _dev(x, F32, "x")
+    if x.requires_grad:
+        raise HipBackendError("%s has no backward: x requires grad" % what)
+    if channels is not None:
+        key = (tuple(chans), str(x.device))     # cached: no host-to-device copy per call (a captured hipGraph forbids one)
+        idx = _RESAMPLE_IDX.get(key)
+        if idx is None:
+            idx = _RESAMPLE_IDX[key] = torch.tensor(chans, dtype=torch.int32, device=x.device)
+    if B * Cc > 65535:
+        raise HipBackendError("%s: B * C = %d images, at most 65535 are served in one call" % (what, B * Cc))
+    if (scale is None) != (shift is None):
+        raise HipBackendError("%s: scale and shift are given together or not at all" % what)
+    if scale is not None:
+        scale = torch.as_tensor(scale, dtype=F32).detach().to(x.device).reshape(-1).contiguous()
+        shift = torch.as_tensor(shift, dtype=F32).detach().to(x.device).reshape(-1).contiguous()
+        if scale.numel() != Cc or shift.numel() != Cc:
+            raise HipBackendError("%s: scale (%d) and shift (%d) need one entry per output channel (%d)"
+                                  % (what, scale.numel(), shift.numel(), Cc))
+    return B, Cin, h, w, Cc, H, W, RESAMPLE_MODES[mode], idx, scale, shift
+
+
+def resample(x, size, mode="bilinear", channels=None, scale=None, shift=None, out=None):
+    """fp32 [B,C,H,W]: F.interpolate(x[:, channels], size, mode, align_corners=False) * scale[c] + shift[c] in one kernel
+    (include/orbit2_hip.h:orbit2_resample_fwd).  mode: nearest, bilinear or bicubic; channels: input channel of every output
+    channel (None = all, in order); scale / shift: [C], both or neither; out: a contiguous fp32 [B,C,H,W] to write into."""
+    B, Cin, h, w, Cc, H, W, m, idx, scale, shift = _resample_args(x, size, mode, channels, scale, shift, "resample")
+    if out is None:
+        out = torch.empty(B, Cc, H, W, dtype=F32, device=x.device)
+    else:
+        _dev(out, F32, "out")
+        if tuple(out.shape) != (B, Cc, H, W):
+            raise HipBackendError("resample: out is %s, the result %s" % (tuple(out.shape), (B, Cc, H, W)))
+    _chk(lib().orbit2_resample_fwd(_p(x), _p(idx), Cin, _p(scale), _p(shift), _p(out), B, Cc, h, w, H, W, m, _stream()),
+         "orbit2_resample_fwd")
+    return out
+
+
+def resample_moments(x, size, mode, target, channels=None, scale=None, shift=None, lat_w=None, clim=None):
+    """[B,C,12] float64: eval_moments(resample(x, ...), target, lat_w, clim) without the resampled field ever being stored
+    (include/orbit2_hip.h:orbit2_resample_moments); the target may be larger than (H, W) (top-left crop)"""
+    B, Cin, h, w, Cc, H, W, m, idx, scale, shift = _resample_args(x, size, mode, channels, scale, shift, "resample_moments")
+    if not torch.is_tensor(target) or target.dim() != 4:
+        raise HipBackendError("resample_moments takes an [B,C,Ht,Wt] target")
+    _dev(target, F32, "target")
+    if tuple(target.shape[:2]) != (B, Cc):
+        raise HipBackendError("resample_moments: target %s does not match the prediction's [B,C] %s"
+                              % (tuple(target.shape), (B, Cc)))
+    if target.shape[2] < H or target.shape[3] < W:
+        raise HipBackendError("resample_moments: target %s is smaller than the prediction %s"
+                              % (tuple(target.shape), (B, Cc, H, W)))
+    if lat_w is not None:
+        _dev(lat_w, F32, "lat_w")
+        if lat_w.numel() < H:
+            raise HipBackendError("lat_w has %d entries, the prediction %d rows" % (lat_w.numel(), H))
+    if clim is not None:
+        _dev(clim, F32, "clim")
+        if tuple(clim.shape[-3:]) != (Cc, H, W) or clim.numel() != Cc * H * W:
+            raise HipBackendError("climatology must be [C,H,W] of the prediction's size")
+    out = torch.empty(B, Cc, 12, dtype=torch.float64, device=x.device)
+    _chk(lib().orbit2_resample_moments(_p(x), _p(idx), Cin, _p(scale), _p(shift), _p(target), target.shape[2], target.shape[3],
+                                       _p(lat_w), _p(clim), _p(out), B, Cc, h, w, H, W, m, _stream()),
+         "orbit2_resample_moments")
+    return out
 
 
 def seed_salt(value: int, add: bool = False):

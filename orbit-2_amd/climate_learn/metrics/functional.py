@@ -59,12 +59,16 @@ def image_gradient(pred, target, var_names: Optional[List[str]] = None, var_weig
 # ---- evaluation metrics (reference :236-324); one reduction kernel, the [B,C,6] -> [C+1] algebra on the host ----------
 def _moments(pred, target, lat_weights=None, climatology=None):
     from .. import _hip
+    from ..models.hub.interpolation import Resampled
     if isinstance(pred, torch.distributions.Normal):
         pred = pred.loc
     clim = None
     if climatology is not None:
         clim = climatology.detach().to(device=pred.device, dtype=torch.float32)
         clim = clim.reshape(-1, *clim.shape[-2:])[:, : pred.shape[2], : pred.shape[3]].contiguous()
+    if isinstance(pred, Resampled):             # an interpolation baseline: scored in the pass that resamples it, never stored
+        return pred.moments(target.detach().float().contiguous(), _lat(lat_weights, pred), clim), \
+            pred.shape[2] * pred.shape[3]
     return _hip.eval_moments(pred.detach().float().contiguous(), target.detach().float().contiguous(),
                              _lat(lat_weights, pred), clim), pred.shape[2] * pred.shape[3]
 
@@ -124,6 +128,24 @@ def acc(pred, target, climatology, aggregate_only: bool = False, lat_weights=Non
     va = s[:, 10] - 2 * ma * s[:, 7] + ma * ma * sw
     vb = s[:, 11] - 2 * mb * s[:, 8] + mb * mb * sw
     return _with_aggregate((cov / (va * vb).sqrt()).float(), aggregate_only)
+
+
+def mse_skill(pred, target, baseline, aggregate_only: bool = False, lat_weights=None):
+    """Mean-squared-error skill score of `pred` against a baseline prediction of the same target: per channel
+    1 - MSE_c(pred) / MSE_c(baseline), and as the aggregate 1 - MSE(pred) / MSE(baseline) over all channels; 1 is a perfect
+    prediction, 0 no better than the baseline, negative worse.  The mean squared errors are means over (b, h, w), latitude
+    weighted if `lat_weights` is given.  This is the reference's msess (metrics/functional.py:205-215) with a baseline field in
+    place of the climatology; the reference's body hands its arguments to mse in the wrong positions (the climatology lands
+    in var_names), so its evident meaning is built, not its text.  `baseline` is a tensor or a Resampled (an interpolation
+    baseline that is scored without being stored: models.hub.Interpolation.lazy); so is `pred`.
+    Not in METRICS_REGISTRY: evaluate_func calls a registry metric as (pred, target), and this one has a third operand.
+    A channel the baseline predicts exactly is 1 - x / 0: -inf, or NaN where the prediction is exact too."""
+    num = _moments(pred, target, lat_weights)[0][..., 5].sum(0)         # [C] sums of w (pred - target)^2 over the batch
+    # the same object is scored once: its skill is 0 exactly, not to the last bit of two atomic accumulations
+    den = num if baseline is pred else _moments(baseline, target, lat_weights)[0][..., 5].sum(0)
+    per_channel = (1.0 - num / den).float()
+    agg = (1.0 - num.sum() / den.sum()).float()
+    return agg if aggregate_only else torch.cat((per_channel, agg.unsqueeze(0)))
 
 
 # ---- probabilistic scores of a Gaussian prediction (reference :340-386); `pred` is a torch.distributions.Normal, e.g.

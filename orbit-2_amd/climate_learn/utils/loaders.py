@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 from ..metrics import METRICS_REGISTRY, MetricsMetaInfo
-from ..models.hub import MODEL_REGISTRY, Res_Slim_ViT
+from ..models.hub import MODEL_REGISTRY, Interpolation, Res_Slim_ViT
 from ..models.lr_scheduler import LinearWarmupCosineAnnealingLR
 from ..transforms import TRANSFORMS_REGISTRY
 from .fused_attn import FusedAttn
@@ -18,11 +18,47 @@ def _issue(what, name):
     return ("%s is not an implemented %s. If you think it should be, please raise an issue" % (name, what))
 
 
+# the reference's two names (utils/loaders.py:321-332) and bicubic, which it does not have
+INTERPOLATION_ARCHITECTURES = ("nearest-interpolation", "bilinear-interpolation", "bicubic-interpolation")
+
+
+def _interpolation_rescale(data_module, out_vars):
+    """(scale, shift) per output variable that take a field in the INPUTS' normalisation to the OUTPUTS':
+    scale = std_in / std_out, shift = (mean_in - mean_out) / std_out; 1 and 0 for precipitation variables (log-transformed, not
+    normalised) and wherever the data module carries no separate normalisers (shared statistics, the synthetic module)."""
+    from ..data.processing.era5_constants import PRECIP_VARIABLES
+    tin, tout = getattr(data_module, "transforms", None), getattr(data_module, "output_transforms", None)
+    scale, shift = [], []
+    for v in out_vars:
+        a, b = (tin or {}).get(v), (tout or {}).get(v)
+        if v in PRECIP_VARIABLES or not all(hasattr(t, "mean") and hasattr(t, "std") for t in (a, b)):
+            scale.append(1.0)
+            shift.append(0.0)
+        else:
+            scale.append(float(a.std) / float(b.std))
+            shift.append((float(a.mean) - float(b.mean)) / float(b.std))
+    return scale, shift
+
+
+def _load_interpolation(data_module, architecture, in_vars, out_vars, out_shape):
+    """the interpolation baseline of the downscaling task: the reference asks for equal sets of input and output variables;
+    here every output variable must be among the inputs, and the channels are picked by name"""
+    if not set(out_vars) <= set(in_vars):
+        raise RuntimeError("Interpolation requires the output variables to match the input variables.")
+    scale, shift = _interpolation_rescale(data_module, out_vars)
+    if all(s == 1.0 for s in scale) and all(s == 0.0 for s in shift):
+        scale = shift = None                     # the reference's plain op
+    return Interpolation(tuple(int(v) for v in out_shape[2:]), architecture.split("-")[0],
+                         channels=[list(in_vars).index(v) for v in out_vars], scale=scale, shift=shift)
+
+
 def load_architecture(task, data_module, architecture, default_vars, superres_mag=4, cnn_ratio=4, patch_size=2,
                       embed_dim=256, depth=6, decoder_depth=1, num_heads=4, mlp_ratio=4, drop_path=0.1, drop_rate=0.1,
                       tensor_par_size=1, tensor_par_group=None, FusedAttn_option=FusedAttn.HIP):
     in_vars, out_vars = data_module.get_data_variables()
     in_shape, out_shape = data_module.get_data_dims()
+    if task == "downscaling" and architecture.lower() in INTERPOLATION_ARCHITECTURES:
+        return _load_interpolation(data_module, architecture.lower(), in_vars, out_vars, out_shape)
     if task != "downscaling" or architecture != "res_slimvit":
         raise NotImplementedError(
             f"{architecture} is not an implemented architecture for the {task} task in the MI355X hot-path build "

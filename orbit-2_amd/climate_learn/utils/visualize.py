@@ -156,6 +156,43 @@ def stitched_scores(preds, y, out_variables, lat_weights=None):
     return {v: {k: float(col[c]) for k, col in cols.items()} for c, v in enumerate(out_variables)}
 
 
+def baseline_scores(x, y, in_variables, out_variables, pred, mode="bilinear", lat_weights=None, denorm=None, rescale=None):
+    """A prediction read against the interpolation baseline of its own input: {variable: {"rmse", "rmse_baseline", "mse_skill"}}
+    (plus "lat_rmse", "lat_rmse_baseline", "lat_mse_skill" when `lat_weights` is given), rmse as metrics.functional.rmse forms
+    it per channel and mse_skill = 1 - MSE(pred) / MSE(baseline) (metrics.functional.mse_skill).
+    x [B,V,h,w] the normalised input, y [B,C,>=H,>=W] the normalised target (its top-left crop is scored), pred [B,C,H,W] the
+    normalised prediction (e.g. from tiled_predict); the baseline is x's channels named by `out_variables`, resampled to
+    (H, W) in `mode`.  It is never stored: a models.hub.Resampled is scored in the pass that resamples it.  `rescale` =
+    (scale, shift) per output variable takes the baseline from the inputs' normalisation to the outputs' (utils.loaders builds
+    it from the data module); `denorm`, a transforms.Denormalize, moves all three fields to physical units, for the baseline
+    folded into the same pass (Resampled.affine).
+    Constant output channels (CONSTANTS) are the target's own in the prediction and in the baseline, as clip_replace_constant
+    leaves them: both errors are 0 and the skill, 0 / 0, is reported as NaN."""
+    from ..data.processing.era5_constants import CONSTANTS
+    from ..metrics import functional as fn
+    from ..models.hub.interpolation import Interpolation
+    scale, shift = rescale if rescale is not None else (None, None)
+    pred = pred.detach().float().contiguous()
+    H, W = pred.shape[2:]
+    base = Interpolation(size=(H, W), mode=mode, scale=scale, shift=shift).lazy(x, in_variables, out_variables)
+    y = y.detach().float()
+    if denorm is not None:
+        pred, y, base = denorm(pred), denorm(y[:, :, :H, :W]), base.affine(denorm.std, denorm.mean)
+    const = torch.tensor([v in CONSTANTS for v in out_variables])
+
+    def columns(w, prefix):
+        sp, sb = fn._moments(pred, y, w)[0][..., 5].cpu(), fn._moments(base, y, w)[0][..., 5].cpu()    # [B,C] sums of w err^2
+        sp, sb = sp.masked_fill(const, 0.0), sb.masked_fill(const, 0.0)
+        skill = (1.0 - sp.sum(0) / sb.sum(0)).masked_fill(const, float("nan"))
+        return {prefix + "rmse": (sp / (H * W)).sqrt().mean(0), prefix + "rmse_baseline": (sb / (H * W)).sqrt().mean(0),
+                prefix + "mse_skill": skill}
+
+    cols = columns(None, "")
+    if lat_weights is not None:
+        cols.update(columns(lat_weights, "lat_"))
+    return {v: {k: float(col[c]) for k, col in cols.items()} for c, v in enumerate(out_variables)}
+
+
 def visualize_at_index(mm, dm, dm_vis, out_list, in_transform, out_transform, variable, src, device, div, overlap, index=0,
                        tensor_par_size=1, tensor_par_group=None, save_png: bool = True, prefix: str = ""):
     """Stitched input / prediction / ground truth of test sample `index` for `variable` (reference :38-490; the PNG
