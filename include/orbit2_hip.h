@@ -348,6 +348,33 @@ int orbit2_loss_bwd(const float* pred, const float* target, int Ht, int Wt, cons
 int orbit2_eval_moments(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* clim,
                         double* out, int B, int C, int H, int W, void* stream);
 
+/* ---- missing-data masks (csrc/masked.hip; metrics/functional.py masked_mse / masked_bayesian_tv / rmse(mask=) ...) ------
+ * A pixel is VALID where the target is finite and the mask (if any) is non-zero:
+ *   v[b][c][i][j] = isfinite(target[b][c][i][j]) && (mask == NULL || mask[b * mask_sb + c * mask_sc + i * mask_pitch + j] != 0)
+ * mask: bytes, read through its top-left H x W crop; mask_pitch >= W elements between rows; mask_sb / mask_sc the batch and
+ * channel strides, 0 = the same plane for every batch entry / channel (a broadcast mask is never expanded).  At an invalid pixel
+ * neither pred nor target enters any arithmetic (they may be NaN / Inf there).  pred, target, lat_w, chan_w as orbit2_loss_fwd.
+ * When pred and target are 16-byte aligned with W % 4 == Wt % 4 == 0 and the mask, its pitch and its strides are multiples of 4,
+ * the kernels read float4 / dword groups; any other layout is read by scalar lanes (same results to rounding of the sums' order).
+ *
+ * orbit2_masked_loss_fwd: kind 0 = mse, 1 = bayesian_tv (a difference term of the prior counts only if both of its pixels are
+ * valid); any other kind is O2_ERR_ARG.  With num_c = sum_{b,i,j} v w_i cw_c err and n_c = sum_{b,i,j} v:
+ *   out[c] = num_c / n_c (0 if n_c == 0), out[C] = sum_c num_c / sum_c n_c (0 if nothing is valid); cnt[c] = n_c, cnt[C] = sum_c n_c.
+ * out fp32 [C+1], cnt int64 [C+1] (counted as integers: exact), ws >= 2*B*C*64 four-byte words.  Fixed-order sums, no atomics:
+ * two calls give the same bits.
+ * orbit2_masked_loss_bwd: dpred = gscale[0] * d(out[C])/dpred with the divisor cnt[C] read on the device; exactly 0.0 at every
+ * invalid pixel, and everywhere when cnt[C] == 0.
+ * orbit2_masked_moments: out[b][c][13] (double) = the twelve sums of orbit2_eval_moments over the valid pixels, then their number. */
+int orbit2_masked_loss_fwd(const float* pred, const float* target, int Ht, int Wt, const uint8_t* mask, int mask_pitch,
+                           int64_t mask_sb, int64_t mask_sc, const float* lat_w, const float* chan_w, float* out, int64_t* cnt,
+                           float* ws, int B, int C, int H, int W, int kind, void* stream);
+int orbit2_masked_loss_bwd(const float* pred, const float* target, int Ht, int Wt, const uint8_t* mask, int mask_pitch,
+                           int64_t mask_sb, int64_t mask_sc, const float* lat_w, const float* chan_w, const float* gscale,
+                           const int64_t* cnt, float* dpred, int B, int C, int H, int W, int kind, void* stream);
+int orbit2_masked_moments(const float* pred, const float* target, int Ht, int Wt, const uint8_t* mask, int mask_pitch,
+                          int64_t mask_sb, int64_t mask_sc, const float* lat_w, const float* clim, double* out, int B, int C,
+                          int H, int W, void* stream);
+
 /* ---- MC-dropout ensembles (utils/mc_dropout.py) and the Gaussian scores (metrics/functional.py:340-386) ------
  * orbit2_ensemble_update: the k-th (1-based) Welford step over n fp32 elements, in place:
  *   d = member - mean; mean += d / k; m2 += d * (member - mean).   k = 1 initialises (mean = member, m2 = 0; neither is read).

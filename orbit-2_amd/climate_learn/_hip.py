@@ -107,6 +107,9 @@ PROTOTYPES = {
     "orbit2_loss_fwd": (_I, (_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P)),
     "orbit2_loss_bwd": (_I, (_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P)),
     "orbit2_eval_moments": (_I, (_P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P)),
+    "orbit2_masked_loss_fwd": (_I, (_P, _P, _I, _I, _P, _I, _I64, _I64, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P)),
+    "orbit2_masked_loss_bwd": (_I, (_P, _P, _I, _I, _P, _I, _I64, _I64, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P)),
+    "orbit2_masked_moments": (_I, (_P, _P, _I, _I, _P, _I, _I64, _I64, _P, _P, _P, _I, _I, _I, _I, _P)),
     "orbit2_ensemble_update": (_I, (_P, _P, _P, _I64, _I, _P)),
     "orbit2_gaussian_scores": (_I, (_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P)),
     "orbit2_ensemble_scores": (_I, (_P, _I64, _I, _P, _I, _I, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _I, _I, _I, _I, _P)),
@@ -943,6 +946,78 @@ def eval_moments(pred, target, lat_w=None, clim=None):
     out = torch.empty(B, Cc, 12, dtype=torch.float64, device=pred.device)
     _chk(lib().orbit2_eval_moments(_p(pred), _p(target), target.shape[2], target.shape[3], _p(lat_w), _p(clim), _p(out),
                                    B, Cc, H, W, _stream()), "orbit2_eval_moments")
+    return out
+
+
+# ---- missing-data masks (csrc/masked.hip) --------------------------------------------------------------------------------------
+def _mask_args(mask, strides, pred, target):
+    """(pointer, row pitch, batch stride, channel stride) of the mask operand: uint8 device bytes whose `strides` =
+    (pitch, batch stride, channel stride) address an H x W crop of at least the prediction's size; (None, 0, 0, 0) without one"""
+    if mask is None:
+        return None, 0, 0, 0
+    _dev(mask, torch.uint8, "mask")
+    pitch, sb, sc = (int(v) for v in strides)
+    B, Cc, H, W = pred.shape
+    if pitch < W or sb < 0 or sc < 0 or mask.numel() < (B - 1) * sb + (Cc - 1) * sc + (H - 1) * pitch + W:
+        raise HipBackendError("mask of %d bytes does not hold [%d,%d,%d,%d] at pitch %d and strides (%d, %d)"
+                              % (mask.numel(), B, Cc, H, W, pitch, sb, sc))
+    return mask.data_ptr(), pitch, sb, sc
+
+
+def _masked_operands(pred, target, lat_w, name):
+    _dev(pred, F32, "pred"); _dev(target, F32, "target")
+    if pred.dim() != 4 or target.dim() != 4 or target.shape[:2] != pred.shape[:2] or target.shape[2] < pred.shape[2] \
+            or target.shape[3] < pred.shape[3]:
+        raise HipBackendError("%s: pred %s needs a target [B,C,>=H,>=W], got %s" % (name, tuple(pred.shape), tuple(target.shape)))
+    if lat_w is not None and _dev(lat_w, F32, "lat_w").numel() < pred.shape[2]:
+        raise HipBackendError("%s: lat_w has %d entries for %d rows" % (name, lat_w.numel(), pred.shape[2]))
+
+
+def masked_loss_fwd(pred, target, lat_w, chan_w, kind, mask=None, mask_strides=(0, 0, 0)):
+    """(out fp32 [C+1], cnt int64 [C+1]) over the valid pixels (include/orbit2_hip.h:orbit2_masked_loss_fwd); kind 0 = mse,
+    1 = bayesian_tv.  mask: uint8 bytes, mask_strides = (row pitch, batch stride, channel stride), a stride of 0 broadcasts."""
+    _masked_operands(pred, target, lat_w, "masked_loss_fwd")
+    B, Cc, H, W = pred.shape
+    if chan_w is not None and _dev(chan_w, F32, "chan_w").numel() != Cc:
+        raise HipBackendError("masked_loss_fwd: chan_w has %d entries for %d channels" % (chan_w.numel(), Cc))
+    mp = _mask_args(mask, mask_strides, pred, target)
+    out = torch.empty(Cc + 1, dtype=F32, device=pred.device)
+    cnt = torch.empty(Cc + 1, dtype=torch.int64, device=pred.device)
+    ws = torch.empty(2 * Cc * B * 64, dtype=F32, device=pred.device)
+    _chk(lib().orbit2_masked_loss_fwd(_p(pred), _p(target), target.shape[2], target.shape[3], *mp, _p(lat_w), _p(chan_w),
+                                      _p(out), _p(cnt), _p(ws), B, Cc, H, W, kind, _stream()), "orbit2_masked_loss_fwd")
+    return out, cnt
+
+
+def masked_loss_bwd(pred, target, lat_w, chan_w, gscale, cnt, kind, mask=None, mask_strides=(0, 0, 0)):
+    """dpred = gscale[0] * d(out[C])/dpred; the divisor cnt[C] (masked_loss_fwd's count) is read on the device"""
+    _masked_operands(pred, target, lat_w, "masked_loss_bwd")
+    B, Cc, H, W = pred.shape
+    if chan_w is not None and _dev(chan_w, F32, "chan_w").numel() != Cc:
+        raise HipBackendError("masked_loss_bwd: chan_w has %d entries for %d channels" % (chan_w.numel(), Cc))
+    if _dev(cnt, torch.int64, "cnt").numel() != Cc + 1:
+        raise HipBackendError("masked_loss_bwd: cnt must be the [C+1] counts of masked_loss_fwd")
+    mp = _mask_args(mask, mask_strides, pred, target)
+    dpred = torch.empty_like(pred)
+    _chk(lib().orbit2_masked_loss_bwd(_p(pred), _p(target), target.shape[2], target.shape[3], *mp, _p(lat_w), _p(chan_w),
+                                      _p(_dev(gscale, F32, "gscale")), _p(cnt), _p(dpred), B, Cc, H, W, kind, _stream()),
+         "orbit2_masked_loss_bwd")
+    return dpred
+
+
+def masked_moments(pred, target, lat_w=None, clim=None, mask=None, mask_strides=(0, 0, 0)):
+    """[B,C,13] float64: the twelve sums of eval_moments over the valid pixels, then their number
+    (include/orbit2_hip.h:orbit2_masked_moments)"""
+    _masked_operands(pred, target, lat_w, "masked_moments")
+    B, Cc, H, W = pred.shape
+    if clim is not None:
+        _dev(clim, F32, "clim")
+        if tuple(clim.shape[-3:]) != (Cc, H, W):
+            raise HipBackendError("climatology must be [C,H,W] of the prediction's size")
+    mp = _mask_args(mask, mask_strides, pred, target)
+    out = torch.empty(B, Cc, 13, dtype=torch.float64, device=pred.device)
+    _chk(lib().orbit2_masked_moments(_p(pred), _p(target), target.shape[2], target.shape[3], *mp, _p(lat_w), _p(clim), _p(out),
+                                     B, Cc, H, W, _stream()), "orbit2_masked_moments")
     return out
 
 

@@ -989,3 +989,31 @@ class LossFn(torch.autograd.Function):
         dp = _hip.loss_bwd(pred, target, lat_w if lat_w.numel() else None, chan_w if chan_w.numel() else None, gs,
                            ctx.kind)
         return dp, None, None, None, None
+
+
+class MaskedLossFn(torch.autograd.Function):
+    """fused mse / bayesian_tv over the valid pixels (finite target, non-zero mask).  Returns [C+1] (per-channel means over the
+    valid pixels, aggregate).  mask: uint8 bytes or None, addressed by (pitch, sb, sc) (metrics/functional.py:_mask_operand).
+    Nothing here reads the device or copies to it: the valid count stays a device tensor that the backward kernel divides by,
+    so forward + backward can be captured in a hipGraph and replayed on targets whose missing pixels have moved."""
+
+    @staticmethod
+    def forward(ctx, pred, target, lat_w, chan_w, kind, mask, pitch, sb, sc):
+        pred = pred.contiguous()
+        if pred.dtype != F32:
+            pred = pred.float()
+        target = target.contiguous()
+        out, cnt = _hip.masked_loss_fwd(pred, target, lat_w, chan_w, kind, mask, (pitch, sb, sc))
+        ctx.kind, ctx.mask_strides = kind, (pitch, sb, sc)
+        ctx.save_for_backward(pred, target, mask if mask is not None else pred.new_empty(0, dtype=torch.uint8), cnt,
+                              lat_w if lat_w is not None else pred.new_empty(0),
+                              chan_w if chan_w is not None else pred.new_empty(0))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, target, mask, cnt, lat_w, chan_w = ctx.saved_tensors
+        gs = g[-1:].contiguous().float()          # gradient flows through the aggregate entry only
+        dp = _hip.masked_loss_bwd(pred, target, lat_w if lat_w.numel() else None, chan_w if chan_w.numel() else None, gs, cnt,
+                                  ctx.kind, mask if mask.numel() else None, ctx.mask_strides)
+        return dp, None, None, None, None, None, None, None, None

@@ -56,6 +56,114 @@ def image_gradient(pred, target, var_names: Optional[List[str]] = None, var_weig
     return _fused(pred, target, var_names, var_weights, True, None, 2)
 
 
+# ---- missing data: losses and metrics over the VALID pixels only (csrc/masked.hip) ------------------------------
+# valid = the target is finite there, and the mask (if one is given) is non-zero.  The reference has no such loss
+# (examples/era5_daymet_downscaling.py names `masked_mse` but its metrics package has none) and a `mask` argument on rmse /
+# lat_rmse / acc only.
+def _mask_operand(mask, pred, target):
+    """`mask` -> (uint8 bytes, row pitch, batch stride, channel stride) as the masked kernels address it, or (None, 0, 0, 0).
+    mask: bool, integer or float (non-zero = keep) of shape [H,W], [1,1,H,W], [B,1,H,W] or [B,C,H,W], its spatial size the
+    prediction's or the target's (then read through its top-left crop, as the target is).  A stride of 0 broadcasts: the mask is
+    never expanded to [B,C,H,W].  A bool or uint8 mask is used in place; any other dtype costs one `!= 0` of the mask's own size
+    (once, for a static mask: metrics.Masked*.set_mask)."""
+    from ..models.hub.interpolation import Resampled
+    if isinstance(pred, Resampled):
+        raise TypeError("a Resampled prediction cannot be scored over a mask or a target with missing values: its fused scoring "
+                        "pass has no mask -- materialize() it first")
+    if mask is None:
+        return None, 0, 0, 0
+    B, C, H, W = pred.shape
+    ok_hw = ((H, W), tuple(target.shape[-2:]))
+    shape = tuple(mask.shape)
+    if len(shape) == 2 and shape in ok_hw:
+        sb = sc = 0
+    elif len(shape) == 4 and shape[2:] in ok_hw and shape[:2] in ((1, 1), (B, 1), (B, C)):
+        plane = shape[2] * shape[3]
+        sb = 0 if shape[0] == 1 else shape[1] * plane
+        sc = 0 if shape[1] == 1 else plane
+    else:
+        raise ValueError("mask of shape %s: a mask is [H,W], [1,1,H,W], [B,1,H,W] or [B,C,H,W] with B, C = %d, %d and H, W = %s "
+                         "(the prediction's) or %s (the target's)" % (shape, B, C, ok_hw[0], ok_hw[1]))
+    m = mask.detach()
+    if m.device != pred.device:
+        m = m.to(pred.device)
+    if m.dtype == torch.bool:
+        m = m.contiguous().view(torch.uint8)
+    elif m.dtype != torch.uint8:
+        m = (m != 0).view(torch.uint8)
+    return m.contiguous(), shape[-1], sb, sc
+
+
+def _fused_masked(pred, target, var_names, var_weights, aggregate_only, lat_weights, mask, kind):
+    if isinstance(pred, torch.distributions.Normal):
+        pred = pred.loc
+    m, pitch, sb, sc = _mask_operand(mask, pred, target)
+    out = _ops.MaskedLossFn.apply(pred, target.float(), _lat(lat_weights, pred), _chan_weights(pred, var_names, var_weights),
+                                  kind, m, pitch, sb, sc)
+    return out[-1] if aggregate_only else out
+
+
+def masked_mse(pred, target, var_names: Optional[List[str]] = None, var_weights: Optional[Dict[str, float]] = None,
+               aggregate_only: bool = False, lat_weights=None, mask=None):
+    """mse over the valid pixels: per channel sum(v w_lat w_var (pred - target)^2) / sum(v), 0 for a channel without data; the
+    aggregate is the sum of the numerators over the sum of the counts (0 if nothing is valid).  Latitude weights are not
+    renormalised over the valid set.  With everything valid this is mse.  The gradient is exactly 0 at an invalid pixel, where
+    pred and target may hold NaN or Inf."""
+    return _fused_masked(pred, target, var_names, var_weights, aggregate_only, lat_weights, mask, 0)
+
+
+def masked_bayesian_tv(pred, target, var_names: Optional[List[str]] = None, var_weights: Optional[Dict[str, float]] = None,
+                       aggregate_only: bool = False, lat_weights=None, mask=None):
+    """bayesian_tv over the valid pixels: masked_mse plus the total-variation prior stored at every valid pixel, a difference
+    term of which counts only if its neighbour is valid too.  With the valid region one top-left rectangle this is bayesian_tv
+    of the cropped fields."""
+    return _fused_masked(pred, target, var_names, var_weights, aggregate_only, lat_weights, mask, 1)
+
+
+def _masked_sums(pred, target, lat_weights=None, mask=None):
+    """[B,C,13] float64: the twelve sums of _moments over the valid pixels, then their number"""
+    from .. import _hip
+    if isinstance(pred, torch.distributions.Normal):
+        pred = pred.loc
+    m, pitch, sb, sc = _mask_operand(mask, pred, target)
+    return _hip.masked_moments(pred.detach().float().contiguous(), target.detach().float().contiguous(),
+                               _lat(lat_weights, pred), None, m, (pitch, sb, sc))
+
+
+def _with_nan_aggregate(per_channel, aggregate_only):
+    """a channel without data is NaN; the aggregate is the mean over the channels that have data"""
+    agg = per_channel.nanmean()
+    return agg if aggregate_only else torch.cat((per_channel, agg.unsqueeze(0)))
+
+
+def _masked_rmse(pred, target, aggregate_only=False, lat_weights=None, mask=None):
+    """the reference's masked rmse (:243-255) with the validity as its mask: per (b, c)
+    sqrt((sum_ij v w d^2 / (H W)) / (mean_{c,i,j} v[b] + 1e-9)), mean over b, then over c"""
+    m = _masked_sums(pred, target, lat_weights, mask)
+    n = pred.shape[2] * pred.shape[3]
+    frac = m[..., 12].sum(1, keepdim=True) / (m.shape[1] * n) + 1e-9             # [B,1]
+    return _with_aggregate((m[..., 5] / n / frac).sqrt().mean(0).float(), aggregate_only)
+
+
+def _masked_pearson(pred, target, aggregate_only=False, mask=None):
+    s = _masked_sums(pred, target, None, mask).sum(0)                            # [C,13] over the batch
+    N = s[:, 12]
+    cov = s[:, 4] - s[:, 0] * s[:, 1] / N
+    vp = (s[:, 2] - s[:, 0] ** 2 / N).clamp_min(0).sqrt().clamp_min(1e-8)
+    vt = (s[:, 3] - s[:, 1] ** 2 / N).clamp_min(0).sqrt().clamp_min(1e-8)
+    return _with_nan_aggregate((cov / (vp * vt)).float(), aggregate_only)
+
+
+def _masked_mean_bias(pred, target, aggregate_only=False, mask=None):
+    s = _masked_sums(pred, target, None, mask).sum(0)
+    return _with_nan_aggregate(((s[:, 1] - s[:, 0]) / s[:, 12]).float(), aggregate_only)
+
+
+def _masked_mae(pred, target, aggregate_only=False, lat_weights=None, mask=None):
+    s = _masked_sums(pred, target, lat_weights, mask).sum(0)
+    return _with_nan_aggregate((s[:, 6] / s[:, 12]).float(), aggregate_only)
+
+
 # ---- evaluation metrics (reference :236-324); one reduction kernel, the [B,C,6] -> [C+1] algebra on the host ----------
 def _moments(pred, target, lat_weights=None, climatology=None):
     from .. import _hip
@@ -79,15 +187,20 @@ def _with_aggregate(per_channel, aggregate_only):
 
 
 def rmse(pred, target, aggregate_only: bool = False, lat_weights=None, mask=None):
-    """sqrt(mean_hw((pred-target)^2 * w_lat)) per (b, c), mean over b, then over c (reference :236-255)."""
+    """sqrt(mean_hw((pred-target)^2 * w_lat)) per (b, c), mean over b, then over c (reference :236-255).  With a `mask`
+    (_mask_operand) the reference's masked form over the valid pixels -- mask non-zero and target finite: the squared error of
+    an image is divided by the valid fraction of its batch entry + 1e-9 before the root."""
     if mask is not None:
-        raise NotImplementedError("masked rmse is not on the downscaling path")
+        return _masked_rmse(pred, target, aggregate_only, lat_weights, mask)
     m, n = _moments(pred, target, lat_weights)
     return _with_aggregate((m[..., 5] / n).sqrt().mean(0).float(), aggregate_only)
 
 
-def pearson(pred, target, aggregate_only: bool = False):
-    """cosine similarity of the mean-removed, channel-wise flattened [C, B*H*W] fields (reference :294-308)."""
+def pearson(pred, target, aggregate_only: bool = False, mask=None):
+    """cosine similarity of the mean-removed, channel-wise flattened [C, B*H*W] fields (reference :294-308).  With a `mask`:
+    over the valid pixels of each channel (NaN for a channel without any; the aggregate is the mean of the others)."""
+    if mask is not None:
+        return _masked_pearson(pred, target, aggregate_only, mask)
     m, n = _moments(pred, target)
     s = m.sum(0)                                                   # [C,6] over the batch
     N = n * pred.shape[0]
@@ -97,16 +210,22 @@ def pearson(pred, target, aggregate_only: bool = False):
     return _with_aggregate((cov / (vp * vt)).float(), aggregate_only)
 
 
-def mean_bias(pred, target, aggregate_only: bool = False):
-    """mean(target) - mean(pred) per channel (reference :311-324)."""
+def mean_bias(pred, target, aggregate_only: bool = False, mask=None):
+    """mean(target) - mean(pred) per channel (reference :311-324).  With a `mask`: means over the valid pixels of each channel
+    (NaN for a channel without any; the aggregate is the mean of the others)."""
+    if mask is not None:
+        return _masked_mean_bias(pred, target, aggregate_only, mask)
     m, n = _moments(pred, target)
     s = m.sum(0)
     return _with_aggregate(((s[:, 1] - s[:, 0]) / (n * pred.shape[0])).float(), aggregate_only)
 
 
-def mae(pred, target, aggregate_only: bool = False, lat_weights=None):
+def mae(pred, target, aggregate_only: bool = False, lat_weights=None, mask=None):
     """mean |pred - target| (x latitude weight) per channel and over everything (reference :219-232; with equal
-    channel sizes the overall mean is the mean of the channel means)."""
+    channel sizes the overall mean is the mean of the channel means).  With a `mask`: the mean over the valid pixels of each
+    channel (NaN for a channel without any; the aggregate is the mean of the others)."""
+    if mask is not None:
+        return _masked_mae(pred, target, aggregate_only, lat_weights, mask)
     m, n = _moments(pred, target, lat_weights)
     return _with_aggregate((m[..., 6].sum(0) / (n * pred.shape[0])).float(), aggregate_only)
 

@@ -7,6 +7,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from . import functional as _F
 from .functional import acc, bayesian_tv, image_gradient, mae, mean_bias, mse, pearson, psnr, rmse, ssim
 from .utils import MetricsMetaInfo, register
 
@@ -170,6 +171,89 @@ class LatWeightedSSIM(LatitudeWeightedMetric):
 class PSNR(Metric):
     def __call__(self, pred, target):
         return psnr(pred, target, self.aggregate_only)
+
+
+# ---- missing data (functional.masked_*): the same call signatures as their unmasked namesakes, so that
+# training_step and evaluate_func run unchanged on targets that are NaN where there is no data (land-only Daymet / PRISM).
+# A pixel counts where the target is finite AND the mask (if any) is non-zero; without any mask the finite test alone decides.
+class _Masked:
+    """set_mask(mask): a static mask (e.g. the high-resolution land_sea_mask) for every later call, converted and uploaded
+    once; `mask=` on a call overrides it.  Shapes: [H,W], [1,1,H,W], [B,1,H,W], [B,C,H,W] (functional._mask_operand)."""
+
+    graph_capturable = True       # the valid count stays on the device: forward and backward read it there
+
+    _static_mask = None
+
+    def set_mask(self, mask):
+        if mask is not None:
+            mask = torch.as_tensor(mask)
+            mask = mask if mask.dtype in (torch.bool, torch.uint8) else mask != 0
+        self._static_mask = mask
+        return self
+
+    def _mask(self, mask, pred):
+        if mask is not None:
+            return mask
+        m = self._static_mask
+        device = pred.loc.device if isinstance(pred, torch.distributions.Normal) else pred.device
+        if m is not None and m.device != device:
+            m = self._static_mask = m.to(device)               # once: later calls find it there
+        return m
+
+
+@register("masked_mse")
+class MaskedMSE(_Masked, Metric):
+    def __call__(self, pred, target, var_names: Optional[List[str]] = None,
+                 var_weights: Optional[Dict[str, float]] = None, mask=None):
+        return _F.masked_mse(pred, target, var_names, var_weights, self.aggregate_only, None, self._mask(mask, pred))
+
+
+@register("masked_lat_mse")
+class MaskedLatWeightedMSE(_Masked, LatitudeWeightedMetric):
+    def __call__(self, pred, target, var_names: Optional[List[str]] = None,
+                 var_weights: Optional[Dict[str, float]] = None, mask=None):
+        self.cast_to_device(pred)
+        return _F.masked_mse(pred, target, var_names, var_weights, self.aggregate_only, self.lat_weights,
+                             self._mask(mask, pred))
+
+
+@register("masked_bayesian_tv")
+class MaskedBayesian_TV(_Masked, Metric):
+    def __call__(self, pred, target, var_names: Optional[List[str]] = None,
+                 var_weights: Optional[Dict[str, float]] = None, mask=None):
+        return _F.masked_bayesian_tv(pred, target, var_names, var_weights, self.aggregate_only, None, self._mask(mask, pred))
+
+
+@register("masked_rmse")
+class MaskedRMSE(_Masked, Metric):
+    def __call__(self, pred, target, mask=None):
+        return _F._masked_rmse(pred, target, self.aggregate_only, None, self._mask(mask, pred))
+
+
+@register("masked_lat_rmse")
+class MaskedLatWeightedRMSE(_Masked, LatitudeWeightedMetric):
+    """the reference's RMSE object passes its mask into the lat_weights slot (metrics.py:319-372); the evident meaning is built"""
+    def __call__(self, pred, target, mask=None):
+        self.cast_to_device(pred)
+        return _F._masked_rmse(pred, target, self.aggregate_only, self.lat_weights, self._mask(mask, pred))
+
+
+@register("masked_mae")
+class MaskedMAE(_Masked, Metric):
+    def __call__(self, pred, target, mask=None):
+        return _F._masked_mae(pred, target, self.aggregate_only, None, self._mask(mask, pred))
+
+
+@register("masked_pearson")
+class MaskedPearson(_Masked, Metric):
+    def __call__(self, pred, target, mask=None):
+        return _F._masked_pearson(pred, target, self.aggregate_only, self._mask(mask, pred))
+
+
+@register("masked_mean_bias")
+class MaskedMeanBias(_Masked, Metric):
+    def __call__(self, pred, target, mask=None):
+        return _F._masked_mean_bias(pred, target, self.aggregate_only, self._mask(mask, pred))
 
 
 class ClimatologyBasedMetric(Metric):

@@ -1,0 +1,370 @@
+// Missing-data masks: the training losses (mse, bayesian_tv) and the evaluation sums over the VALID pixels only (gfx950).
+// include/orbit2_hip.h: orbit2_masked_*; metrics/functional.py: masked_mse / masked_bayesian_tv / rmse(mask=) ...; DESIGN 4.10d.
+//
+//   valid(b,c,i,j) = isfinite(target[b,c,i,j]) and (mask == NULL or mask[b,c,i,j] != 0)
+//
+// At an invalid pixel neither pred nor target enters any arithmetic: every use is a SELECT (v ? x : 0), never a product with
+// the validity -- 0 * NaN is NaN, and clip_replace_constant copies NaN targets of constant channels into pred.
+//
+// One work item is 4 consecutive pixels of one row.  When every row of pred, target and mask starts on a 16-byte (mask:
+// 4-byte) boundary the item's centre is one float4 / one dword per operand (VEC); otherwise the same item is read by four
+// guarded scalar lanes.  The total-variation stencil needs the pixels left and right of the group and the rows above (backward)
+// and below: those edge pixels are scalar loads, and a pixel outside the plane is invalid.
+#include "common.h"
+
+namespace {
+
+constexpr int ML_NBLK = 64;          // workgroups per (b, c) plane of the forward; the partials are added in this order
+constexpr int MM_NM = 13;            // the twelve sums of orbit2_eval_moments + the valid count
+
+struct MaskArg {
+  const uint8_t* m;                  // NULL: no mask
+  int pitch;                         // bytes (= elements) between two rows
+  int64_t sb, sc;                    // batch and channel strides; 0 = broadcast
+};
+
+__device__ __forceinline__ bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
+// One row of one (b, c) plane around the item's columns j0 .. j0+3:
+//   pv[k], vv[k]  k = 0..5  <->  column j0 - 1 + k   (pv = 0 and vv = false outside the plane or where invalid is irrelevant:
+//                                                    pv is only ever used under vv)
+//   tc[k]         k = 0..3  <->  target at column j0 + k (only meaningful where vv[k + 1])
+// EDGES = false: columns j0-1 and j0+4 are not read (vv false).
+template <bool VEC, bool EDGES>
+__device__ __forceinline__ void load_row(const float* __restrict__ p, const float* __restrict__ t, const uint8_t* __restrict__ m,
+                                         int i, int j0, int H, int W, int Wt, int mp, float (&pv)[6], bool (&vv)[6],
+                                         float (&tc)[4]) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { pv[k] = 0.f; vv[k] = false; }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) tc[k] = 0.f;
+  if (i < 0 || i >= H) return;
+  const float* pr = p + (size_t)i * W;
+  const float* tr = t + (size_t)i * Wt;
+  const uint8_t* mr = m ? m + (size_t)i * mp : nullptr;
+  if (VEC) {                                           // W % 4 == 0: the whole group is inside the row
+    const f32x4 p4 = *reinterpret_cast<const f32x4*>(pr + j0);
+    const f32x4 t4 = *reinterpret_cast<const f32x4*>(tr + j0);
+    const uint32_t m4 = mr ? *reinterpret_cast<const uint32_t*>(mr + j0) : 0x01010101u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      pv[k + 1] = p4[k];
+      tc[k] = t4[k];
+      vv[k + 1] = finite_f(t4[k]) && ((m4 >> (8 * k)) & 0xffu) != 0;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int j = j0 + k;
+      if (j < W) {
+        pv[k + 1] = pr[j];
+        tc[k] = tr[j];
+        vv[k + 1] = finite_f(tc[k]) && (!mr || mr[j] != 0);
+      }
+    }
+  }
+  if (EDGES) {
+    if (j0 > 0) {
+      pv[0] = pr[j0 - 1];
+      vv[0] = finite_f(tr[j0 - 1]) && (!mr || mr[j0 - 1] != 0);
+    }
+    if (j0 + 4 < W) {
+      pv[5] = pr[j0 + 4];
+      vv[5] = finite_f(tr[j0 + 4]) && (!mr || mr[j0 + 4] != 0);
+    }
+  }
+}
+
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (int64_t)__shfl_xor((long long)v, o);
+  return v;
+}
+
+__device__ __forceinline__ float sgnf(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }
+// |a - b| if both pixels are valid, else 0 (select: a and b may be NaN where invalid)
+__device__ __forceinline__ float absdiff_if(bool v, float a, float b) { return v ? fabsf(a - b) : 0.f; }
+__device__ __forceinline__ float sgndiff_if(bool v, float a, float b) { return v ? sgnf(a - b) : 0.f; }
+
+// ---- forward: per-workgroup partials of num = sum v w cw err and of the valid count per (b, c) plane ----------------------
+//   err(i,j) = (p - t)^2 + [TV] 0.02 (|p[i+1][j]-p| + |p[i][j+1]-p| + 0.7 |p[i+1][j+1]-p| + 0.7 |p[i+1][j-1]-p|), each
+//   difference only if its neighbour is valid too
+template <bool VEC, bool TV>
+__global__ __launch_bounds__(256) void masked_loss_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                              int Ht, int Wt, MaskArg mk, const float* __restrict__ latw,
+                                                              const float* __restrict__ chanw, float* __restrict__ part,
+                                                              int* __restrict__ partn, int C, int H, int W) {
+  const int plane = blockIdx.y, c = plane % C, b = plane / C;
+  const float* p = pred + (size_t)plane * H * W;
+  const float* t = tgt + (size_t)plane * Ht * Wt;
+  const uint8_t* m = mk.m ? mk.m + b * mk.sb + c * mk.sc : nullptr;
+  const int W4 = (W + 3) >> 2;
+  float s = 0.f;
+  int n = 0;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < H * W4; e += gridDim.x * 256) {
+    const int i = e / W4, j0 = (e - i * W4) << 2;
+    float p0[6], p1[6], t0[4], t1[4];
+    bool v0[6], v1[6];
+    load_row<VEC, TV>(p, t, m, i, j0, H, W, Wt, mk.pitch, p0, v0, t0);
+    if (TV) load_row<VEC, true>(p, t, m, i + 1, j0, H, W, Wt, mk.pitch, p1, v1, t1);
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 1; k <= 4; ++k) {
+      const bool v = v0[k];
+      const float d = v ? p0[k] - t0[k - 1] : 0.f;
+      float err = d * d;
+      if (TV) {
+        const float tv = absdiff_if(v && v1[k], p1[k], p0[k]) + absdiff_if(v && v0[k + 1], p0[k + 1], p0[k]) +
+                         0.7f * absdiff_if(v && v1[k + 1], p1[k + 1], p0[k]) +
+                         0.7f * absdiff_if(v && v1[k - 1], p1[k - 1], p0[k]);
+        err += 0.02f * tv;
+      }
+      acc += err;
+      n += v ? 1 : 0;
+    }
+    s += acc * (latw ? latw[i] : 1.f);
+  }
+  s = wave_sum(s * (chanw ? chanw[c] : 1.f));
+  n = wave_sum_i(n);
+  __shared__ float sw[4];
+  __shared__ int sn[4];
+  if ((threadIdx.x & 63) == 0) { sw[threadIdx.x >> 6] = s; sn[threadIdx.x >> 6] = n; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part[(size_t)plane * gridDim.x + blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
+    partn[(size_t)plane * gridDim.x + blockIdx.x] = sn[0] + sn[1] + sn[2] + sn[3];
+  }
+}
+
+// one wave: out[c] = num_c / n_c (0 if n_c == 0), out[C] = sum num / sum n (0 if nothing is valid); cnt[c] = n_c, cnt[C] = sum n
+__global__ void masked_loss_final_kernel(const float* __restrict__ part, const int* __restrict__ partn, int nblk, int B, int C,
+                                         float* __restrict__ out, int64_t* __restrict__ cnt) {
+  float tot = 0.f;
+  int64_t ntot = 0;
+  for (int c = 0; c < C; ++c) {
+    float s = 0.f;
+    int64_t n = 0;
+    for (int e = threadIdx.x; e < B * nblk; e += 64) {
+      const int b = e / nblk, k = e - b * nblk;
+      s += part[(size_t)(b * C + c) * nblk + k];
+      n += partn[(size_t)(b * C + c) * nblk + k];
+    }
+    s = wave_sum(s);
+    n = wave_sum_i64(n);            // a plane holds fewer than 2^31 pixels, a channel may hold more
+    if (threadIdx.x == 0) { out[c] = n ? s / (float)n : 0.f; cnt[c] = n; }
+    tot += s;
+    ntot += n;
+  }
+  if (threadIdx.x == 0) { out[C] = ntot ? tot / (float)ntot : 0.f; cnt[C] = ntot; }
+}
+
+// ---- backward: dpred = gscale[0] / cnt[C] * d(sum_c num_c)/dpred; exactly 0 at an invalid pixel and when nothing is valid --
+template <bool VEC, bool TV>
+__global__ __launch_bounds__(256) void masked_loss_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                              int Ht, int Wt, MaskArg mk, const float* __restrict__ latw,
+                                                              const float* __restrict__ chanw,
+                                                              const float* __restrict__ gscale,
+                                                              const int64_t* __restrict__ cnt, float* __restrict__ dpred,
+                                                              int B, int C, int H, int W) {
+  const int W4 = (W + 3) >> 2;
+  const int64_t items = (int64_t)B * C * H * W4;
+  const int64_t ntot = cnt[C];
+  const float g0 = ntot ? gscale[0] / (float)ntot : 0.f;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;           // one item per thread: the grid covers them all
+  if (e < items) {
+    int64_t q = e;
+    const int j0 = (int)(q % W4) << 2; q /= W4;
+    const int i = (int)(q % H); q /= H;
+    const int c = (int)(q % C), b = (int)(q / C);
+    const size_t plane = (size_t)b * C + c;
+    const float* p = pred + plane * H * W;
+    const float* t = tgt + plane * Ht * Wt;
+    const uint8_t* m = mk.m ? mk.m + b * mk.sb + c * mk.sc : nullptr;
+    float p0[6], pa[6], pb[6], t0[4], tx[4];
+    bool v0[6], va[6], vb[6];
+    load_row<VEC, TV>(p, t, m, i, j0, H, W, Wt, mk.pitch, p0, v0, t0);
+    if (TV) {
+      load_row<VEC, true>(p, t, m, i - 1, j0, H, W, Wt, mk.pitch, pa, va, tx);      // the row above
+      load_row<VEC, true>(p, t, m, i + 1, j0, H, W, Wt, mk.pitch, pb, vb, tx);      // the row below
+    }
+    const float wi = latw ? latw[i] : 1.f;
+    const float wim = (TV && latw && i > 0) ? latw[i - 1] : 1.f;
+    const float sc = (chanw ? chanw[c] : 1.f) * g0;
+    float g[4];
+#pragma unroll
+    for (int k = 1; k <= 4; ++k) {
+      const bool v = v0[k];
+      const float x = p0[k];
+      float gk = v ? 2.f * (x - t0[k - 1]) * wi : 0.f;
+      if (TV) {
+        // terms stored at (i, j) (weight wi), in which p[i][j] is the subtrahend
+        float tv = -(sgndiff_if(v && vb[k], pb[k], x) + sgndiff_if(v && v0[k + 1], p0[k + 1], x) +
+                     0.7f * sgndiff_if(v && vb[k + 1], pb[k + 1], x) + 0.7f * sgndiff_if(v && vb[k - 1], pb[k - 1], x)) * wi;
+        // terms in which p[i][j] is the minuend: dh stored at (i, j-1); dv at (i-1, j), d1 at (i-1, j-1), d2 at (i-1, j+1)
+        tv += sgndiff_if(v && v0[k - 1], x, p0[k - 1]) * wi;
+        tv += (sgndiff_if(v && va[k], x, pa[k]) + 0.7f * sgndiff_if(v && va[k - 1], x, pa[k - 1]) +
+               0.7f * sgndiff_if(v && va[k + 1], x, pa[k + 1])) * wim;
+        gk += 0.02f * tv;
+      }
+      g[k - 1] = v ? gk * sc : 0.f;
+    }
+    float* dp = dpred + plane * H * W + (size_t)i * W + j0;
+    if (VEC) {
+      f32x4 o = {g[0], g[1], g[2], g[3]};
+      *reinterpret_cast<f32x4*>(dp) = o;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (j0 + k < W) dp[k] = g[k];
+    }
+  }
+}
+
+// ---- the twelve sums of orbit2_eval_moments over the valid pixels, and their number ------------------------------------------
+template <bool VEC>
+__global__ __launch_bounds__(256) void masked_moments_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                             int Ht, int Wt, MaskArg mk, const float* __restrict__ latw,
+                                                             const float* __restrict__ clim, double* __restrict__ out,
+                                                             int C, int H, int W) {
+  __shared__ float red[4][MM_NM - 1];
+  __shared__ int redn[4];
+  const int plane = blockIdx.y, c = plane % C, b = plane / C;
+  const float* p = pred + (size_t)plane * H * W;
+  const float* t = tgt + (size_t)plane * Ht * Wt;
+  const uint8_t* m = mk.m ? mk.m + b * mk.sb + c * mk.sc : nullptr;
+  const float* cl = clim ? clim + (size_t)c * H * W : nullptr;
+  const int W4 = (W + 3) >> 2;
+  float s[MM_NM - 1];
+#pragma unroll
+  for (int k = 0; k < MM_NM - 1; ++k) s[k] = 0.f;
+  int n = 0;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < H * W4; e += gridDim.x * 256) {
+    const int i = e / W4, j0 = (e - i * W4) << 2;
+    float p0[6], t0[4], c0[4] = {0.f, 0.f, 0.f, 0.f};
+    bool v0[6];
+    load_row<VEC, false>(p, t, m, i, j0, H, W, Wt, mk.pitch, p0, v0, t0);
+    if (cl) {
+      if (VEC) {
+        const f32x4 c4 = *reinterpret_cast<const f32x4*>(cl + (size_t)i * W + j0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c0[k] = c4[k];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (j0 + k < W) c0[k] = cl[(size_t)i * W + j0 + k];
+      }
+    }
+    const float w = latw ? latw[i] : 1.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const bool v = v0[k + 1];
+      const float a = v ? p0[k + 1] - c0[k] : 0.f, bb = v ? t0[k] - c0[k] : 0.f;      // zeros add nothing to any sum
+      const float d = a - bb;
+      s[0] += a; s[1] += bb; s[2] += a * a; s[3] += bb * bb; s[4] += a * bb;
+      s[5] += w * d * d; s[6] += w * fabsf(d);
+      s[7] += w * a; s[8] += w * bb; s[9] += w * a * bb; s[10] += w * a * a; s[11] += w * bb * bb;
+      n += v ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < MM_NM - 1; ++k) {
+    const float v = wave_sum(s[k]);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
+  }
+  n = wave_sum_i(n);
+  if ((threadIdx.x & 63) == 0) redn[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x < MM_NM - 1) {
+    const int k = threadIdx.x;
+    atomicAdd(out + (size_t)plane * MM_NM + k,
+              (double)red[0][k] + (double)red[1][k] + (double)red[2][k] + (double)red[3][k]);
+  } else if (threadIdx.x == MM_NM - 1) {
+    atomicAdd(out + (size_t)plane * MM_NM + MM_NM - 1, (double)(redn[0] + redn[1] + redn[2] + redn[3]));   // exact below 2^53
+  }
+}
+
+inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+// the mask argument as given; false if it cannot be what it says
+inline bool mask_arg(MaskArg& mk, const uint8_t* mask, int pitch, int64_t sb, int64_t sc, int Ht, int Wt, int W) {
+  mk.m = mask; mk.pitch = pitch; mk.sb = sb; mk.sc = sc;
+  if ((int64_t)Ht * Wt > 0x7fffffff) return false;                   // a plane is indexed with 32 bits
+  return !mask || (pitch >= W && sb >= 0 && sc >= 0);
+}
+// float4 / dword centres: every row of every operand starts aligned (and W % 4 == 0: no partial group)
+inline bool vec_ok(const float* pred, const float* target, const MaskArg& mk, int W, int Wt) {
+  if (W % 4 || Wt % 4 || !aligned(pred, 16) || !aligned(target, 16)) return false;
+  return !mk.m || (aligned(mk.m, 4) && mk.pitch % 4 == 0 && mk.sb % 4 == 0 && mk.sc % 4 == 0);
+}
+
+}  // namespace
+
+extern "C" int orbit2_masked_loss_fwd(const float* pred, const float* target, int Ht, int Wt, const uint8_t* mask,
+                                      int mask_pitch, int64_t mask_sb, int64_t mask_sc, const float* lat_w,
+                                      const float* chan_w, float* out, int64_t* cnt, float* ws, int B, int C, int H, int W,
+                                      int kind, void* stream) {
+  if (!pred || !target || !out || !cnt || !ws || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Ht < H || Wt < W) return O2_ERR_ARG;
+  if (kind != 0 && kind != 1) return O2_ERR_ARG;
+  MaskArg mk;
+  if (!mask_arg(mk, mask, mask_pitch, mask_sb, mask_sc, Ht, Wt, W)) return O2_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  int* wsn = reinterpret_cast<int*>(ws + (size_t)B * C * ML_NBLK);
+  o2_with_flags(
+      [&](auto vec, auto tv) {
+        hipLaunchKernelGGL((masked_loss_fwd_kernel<decltype(vec)::value, decltype(tv)::value>), dim3(ML_NBLK, B * C), dim3(256),
+                           0, s, pred, target, Ht, Wt, mk, lat_w, chan_w, ws, wsn, C, H, W);
+      },
+      vec_ok(pred, target, mk, W, Wt), kind == 1);
+  O2_CHECK_LAUNCH();
+  hipLaunchKernelGGL(masked_loss_final_kernel, dim3(1), dim3(64), 0, s, ws, wsn, ML_NBLK, B, C, out, cnt);
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+extern "C" int orbit2_masked_loss_bwd(const float* pred, const float* target, int Ht, int Wt, const uint8_t* mask,
+                                      int mask_pitch, int64_t mask_sb, int64_t mask_sc, const float* lat_w,
+                                      const float* chan_w, const float* gscale, const int64_t* cnt, float* dpred, int B,
+                                      int C, int H, int W, int kind, void* stream) {
+  if (!pred || !target || !gscale || !cnt || !dpred || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Ht < H || Wt < W)
+    return O2_ERR_ARG;
+  if (kind != 0 && kind != 1) return O2_ERR_ARG;
+  MaskArg mk;
+  if (!mask_arg(mk, mask, mask_pitch, mask_sb, mask_sc, Ht, Wt, W)) return O2_ERR_ARG;
+  const int64_t items = (int64_t)B * C * H * ((W + 3) / 4);
+  const int64_t nblk = (items + 255) / 256;
+  if (nblk > 0x7fffffff) return O2_ERR_ARG;
+  o2_with_flags(
+      [&](auto vec, auto tv) {
+        hipLaunchKernelGGL((masked_loss_bwd_kernel<decltype(vec)::value, decltype(tv)::value>), dim3((unsigned)nblk), dim3(256),
+                           0, (hipStream_t)stream, pred, target, Ht, Wt, mk, lat_w, chan_w, gscale, cnt, dpred, B, C, H, W);
+      },
+      vec_ok(pred, target, mk, W, Wt) && aligned(dpred, 16), kind == 1);
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+extern "C" int orbit2_masked_moments(const float* pred, const float* target, int Ht, int Wt, const uint8_t* mask,
+                                     int mask_pitch, int64_t mask_sb, int64_t mask_sc, const float* lat_w, const float* clim,
+                                     double* out, int B, int C, int H, int W, void* stream) {
+  if (!pred || !target || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Ht < H || Wt < W) return O2_ERR_ARG;
+  MaskArg mk;
+  if (!mask_arg(mk, mask, mask_pitch, mask_sb, mask_sc, Ht, Wt, W)) return O2_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(out, 0, sizeof(double) * (size_t)B * C * MM_NM, s) != hipSuccess) return O2_ERR_LAUNCH;
+  int nblk = (H * ((W + 3) / 4) + 256 * 2 - 1) / (256 * 2);
+  if (nblk > 64) nblk = 64;
+  o2_with_flags(
+      [&](auto vec) {
+        hipLaunchKernelGGL((masked_moments_kernel<decltype(vec)::value>), dim3(nblk, B * C), dim3(256), 0, s, pred, target, Ht,
+                           Wt, mk, lat_w, clim, out, C, H, W);
+      },
+      vec_ok(pred, target, mk, W, Wt) && (!clim || aligned(clim, 16)));
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
