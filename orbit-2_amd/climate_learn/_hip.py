@@ -935,14 +935,33 @@ def l1_mean(a, b, out):
     _chk(lib().orbit2_l1_mean(_p(a), _p(b), _p(out), a.numel(), _p(ws), _stream()), "orbit2_l1_mean")
 
 
+def _scored_pair(name, pred, target, lat_w=None, clim=None):
+    """(B, C, H, W) of a prediction scored against `target`, after the checks every such entry shares: both [B,C,H,W] fp32
+    contiguous device tensors, the target of the same [B,C] and spatially not smaller (it is read through its top-left crop),
+    lat_w fp32 with at least H entries, clim [C,H,W] of the prediction's size.  `pred` may be the shape alone, for a prediction
+    that is never stored (resample_moments)."""
+    shape = tuple(pred.shape) if torch.is_tensor(pred) else tuple(pred)
+    if len(shape) != 4 or not torch.is_tensor(target) or target.dim() != 4:
+        raise HipBackendError("%s takes [B,C,H,W] fields" % name)
+    if torch.is_tensor(pred):
+        _dev(pred, F32, "pred")
+    _dev(target, F32, "target")
+    B, Cc, H, W = shape
+    if tuple(target.shape[:2]) != (B, Cc):
+        raise HipBackendError("%s: target %s does not match the prediction's [B,C] %s" % (name, tuple(target.shape), (B, Cc)))
+    if target.shape[2] < H or target.shape[3] < W:             # (the wording serves every wrapper's tests: one of them pins the code)
+        raise HipBackendError("%s: target %s is smaller than the prediction %s; the entry would return code -1 (bad argument)"
+                              % (name, tuple(target.shape), shape))
+    if lat_w is not None and _dev(lat_w, F32, "lat_w").numel() < H:
+        raise HipBackendError("%s: lat_w has %d entries, the prediction %d rows" % (name, lat_w.numel(), H))
+    if clim is not None and (tuple(_dev(clim, F32, "clim").shape[-3:]) != (Cc, H, W) or clim.numel() != Cc * H * W):
+        raise HipBackendError("%s: climatology must be [C,H,W] of the prediction's size" % name)
+    return B, Cc, H, W
+
+
 def eval_moments(pred, target, lat_w=None, clim=None):
     """[B,C,12] float64 sums over a = pred - clim, b = target - clim (see include/orbit2_hip.h:orbit2_eval_moments)"""
-    _dev(pred, F32, "pred"); _dev(target, F32, "target")
-    B, Cc, H, W = pred.shape
-    if clim is not None:
-        _dev(clim, F32, "clim")
-        if tuple(clim.shape[-3:]) != (Cc, H, W):
-            raise HipBackendError("climatology must be [C,H,W] of the prediction's size")
+    B, Cc, H, W = _scored_pair("eval_moments", pred, target, lat_w, clim)
     out = torch.empty(B, Cc, 12, dtype=torch.float64, device=pred.device)
     _chk(lib().orbit2_eval_moments(_p(pred), _p(target), target.shape[2], target.shape[3], _p(lat_w), _p(clim), _p(out),
                                    B, Cc, H, W, _stream()), "orbit2_eval_moments")
@@ -964,20 +983,10 @@ def _mask_args(mask, strides, pred, target):
     return mask.data_ptr(), pitch, sb, sc
 
 
-def _masked_operands(pred, target, lat_w, name):
-    _dev(pred, F32, "pred"); _dev(target, F32, "target")
-    if pred.dim() != 4 or target.dim() != 4 or target.shape[:2] != pred.shape[:2] or target.shape[2] < pred.shape[2] \
-            or target.shape[3] < pred.shape[3]:
-        raise HipBackendError("%s: pred %s needs a target [B,C,>=H,>=W], got %s" % (name, tuple(pred.shape), tuple(target.shape)))
-    if lat_w is not None and _dev(lat_w, F32, "lat_w").numel() < pred.shape[2]:
-        raise HipBackendError("%s: lat_w has %d entries for %d rows" % (name, lat_w.numel(), pred.shape[2]))
-
-
 def masked_loss_fwd(pred, target, lat_w, chan_w, kind, mask=None, mask_strides=(0, 0, 0)):
     """(out fp32 [C+1], cnt int64 [C+1]) over the valid pixels (include/orbit2_hip.h:orbit2_masked_loss_fwd); kind 0 = mse,
     1 = bayesian_tv.  mask: uint8 bytes, mask_strides = (row pitch, batch stride, channel stride), a stride of 0 broadcasts."""
-    _masked_operands(pred, target, lat_w, "masked_loss_fwd")
-    B, Cc, H, W = pred.shape
+    B, Cc, H, W = _scored_pair("masked_loss_fwd", pred, target, lat_w)
     if chan_w is not None and _dev(chan_w, F32, "chan_w").numel() != Cc:
         raise HipBackendError("masked_loss_fwd: chan_w has %d entries for %d channels" % (chan_w.numel(), Cc))
     mp = _mask_args(mask, mask_strides, pred, target)
@@ -991,8 +1000,7 @@ def masked_loss_fwd(pred, target, lat_w, chan_w, kind, mask=None, mask_strides=(
 
 def masked_loss_bwd(pred, target, lat_w, chan_w, gscale, cnt, kind, mask=None, mask_strides=(0, 0, 0)):
     """dpred = gscale[0] * d(out[C])/dpred; the divisor cnt[C] (masked_loss_fwd's count) is read on the device"""
-    _masked_operands(pred, target, lat_w, "masked_loss_bwd")
-    B, Cc, H, W = pred.shape
+    B, Cc, H, W = _scored_pair("masked_loss_bwd", pred, target, lat_w)
     if chan_w is not None and _dev(chan_w, F32, "chan_w").numel() != Cc:
         raise HipBackendError("masked_loss_bwd: chan_w has %d entries for %d channels" % (chan_w.numel(), Cc))
     if _dev(cnt, torch.int64, "cnt").numel() != Cc + 1:
@@ -1008,12 +1016,7 @@ def masked_loss_bwd(pred, target, lat_w, chan_w, gscale, cnt, kind, mask=None, m
 def masked_moments(pred, target, lat_w=None, clim=None, mask=None, mask_strides=(0, 0, 0)):
     """[B,C,13] float64: the twelve sums of eval_moments over the valid pixels, then their number
     (include/orbit2_hip.h:orbit2_masked_moments)"""
-    _masked_operands(pred, target, lat_w, "masked_moments")
-    B, Cc, H, W = pred.shape
-    if clim is not None:
-        _dev(clim, F32, "clim")
-        if tuple(clim.shape[-3:]) != (Cc, H, W):
-            raise HipBackendError("climatology must be [C,H,W] of the prediction's size")
+    B, Cc, H, W = _scored_pair("masked_moments", pred, target, lat_w, clim)
     mp = _mask_args(mask, mask_strides, pred, target)
     out = torch.empty(B, Cc, 13, dtype=torch.float64, device=pred.device)
     _chk(lib().orbit2_masked_moments(_p(pred), _p(target), target.shape[2], target.shape[3], *mp, _p(lat_w), _p(clim), _p(out),
@@ -1035,19 +1038,9 @@ def ensemble_update(member, mean, m2, k: int):
 def gaussian_scores(mean, std, target, lat_w=None):
     """[B,C,4] float64 sums {w crps, w std^2, w (mean - target)^2, 1{|target - mean| <= std}} of a Gaussian prediction
     (include/orbit2_hip.h:orbit2_gaussian_scores); the target may be larger than the prediction (top-left crop)"""
-    _dev(mean, F32, "mean"); _dev(std, F32, "std"); _dev(target, F32, "target")
-    if mean.dim() != 4 or target.dim() != 4:
-        raise HipBackendError("gaussian_scores takes [B,C,H,W] fields")
-    if std.shape != mean.shape:
+    if _dev(std, F32, "std").shape != mean.shape:
         raise HipBackendError("gaussian_scores: mean %s and std %s differ in shape" % (tuple(mean.shape), tuple(std.shape)))
-    if tuple(target.shape[:2]) != tuple(mean.shape[:2]):
-        raise HipBackendError("gaussian_scores: target %s does not match the prediction's [B,C] %s"
-                              % (tuple(target.shape), tuple(mean.shape[:2])))
-    B, Cc, H, W = mean.shape
-    if lat_w is not None:
-        _dev(lat_w, F32, "lat_w")
-        if lat_w.numel() < H:
-            raise HipBackendError("lat_w has %d entries, the prediction %d rows" % (lat_w.numel(), H))
+    B, Cc, H, W = _scored_pair("gaussian_scores", mean, target, lat_w)
     out = torch.empty(B, Cc, 4, dtype=torch.float64, device=mean.device)
     _chk(lib().orbit2_gaussian_scores(_p(mean), _p(std), _p(target), target.shape[2], target.shape[3], _p(lat_w), _p(out),
                                       B, Cc, H, W, _stream()), "orbit2_gaussian_scores")
@@ -1077,17 +1070,7 @@ def ensemble_scores(members, target, lat_w=None, *, sums=True, hist=False, seed=
     if not members[0].is_contiguous() or members.stride(0) < field:
         raise HipBackendError("ensemble_scores: every member must be a contiguous [B,C,H,W] field, members at least one field "
                               "apart (strides %s)" % (tuple(members.stride()),))
-    _dev(target, F32, "target")
-    if target.dim() != 4 or tuple(target.shape[:2]) != (B, Cc):
-        raise HipBackendError("ensemble_scores: target %s does not match the prediction's [B,C] %s"
-                              % (tuple(target.shape), (B, Cc)))
-    if target.shape[2] < H or target.shape[3] < W:
-        raise HipBackendError("ensemble_scores: target %s is smaller than the prediction %s"
-                              % (tuple(target.shape), (B, Cc, H, W)))
-    if lat_w is not None:
-        _dev(lat_w, F32, "lat_w")
-        if lat_w.numel() < H:
-            raise HipBackendError("lat_w has %d entries, the prediction %d rows" % (lat_w.numel(), H))
+    _scored_pair("ensemble_scores", members[0], target, lat_w)
     if crps_field not in (None, "empirical", "fair"):
         raise HipBackendError("ensemble_scores: crps_field is None, 'empirical' or 'fair', got %r" % (crps_field,))
     levels = None
@@ -1128,23 +1111,10 @@ def ssim_sums(pred, target, lat_w=None, data_range=None, ssim_map=False):
     prediction (top-left crop).  `data_range`: None = max - min of every image's own target crop (found on the device), a
     number, or a tensor that broadcasts to [B,C].  With ssim_map=True returns (sums, map), map fp32 [B,C,H-6,W-6]: S at the
     centres whose window lies inside the image."""
-    if pred.dim() != 4 or target.dim() != 4:
-        raise HipBackendError("ssim_sums takes [B,C,H,W] fields")
-    B, Cc, H, W = pred.shape
-    if H < SSIM_WIN or W < SSIM_WIN:
+    if pred.dim() == 4 and min(pred.shape[2:]) < SSIM_WIN:           # before the device check: a property of the call
         raise HipBackendError("ssim_sums: the prediction is %d x %d, the window needs at least %d x %d"
-                              % (H, W, SSIM_WIN, SSIM_WIN))
-    _dev(pred, F32, "pred"); _dev(target, F32, "target")
-    if tuple(target.shape[:2]) != tuple(pred.shape[:2]):
-        raise HipBackendError("ssim_sums: target %s does not match the prediction's [B,C] %s"
-                              % (tuple(target.shape), tuple(pred.shape[:2])))
-    if target.shape[2] < H or target.shape[3] < W:
-        raise HipBackendError("ssim_sums: target %s is smaller than the prediction %s"
-                              % (tuple(target.shape), (B, Cc, H, W)))
-    if lat_w is not None:
-        _dev(lat_w, F32, "lat_w")
-        if lat_w.numel() < H:
-            raise HipBackendError("lat_w has %d entries, the prediction %d rows" % (lat_w.numel(), H))
+                              % (pred.shape[2], pred.shape[3], SSIM_WIN, SSIM_WIN))
+    B, Cc, H, W = _scored_pair("ssim_sums", pred, target, lat_w)
     rng = None
     if data_range is not None:
         if torch.is_tensor(data_range):
@@ -1237,23 +1207,7 @@ def resample_moments(x, size, mode, target, channels=None, scale=None, shift=Non
     """[B,C,12] float64: eval_moments(resample(x, ...), target, lat_w, clim) without the resampled field ever being stored
     (include/orbit2_hip.h:orbit2_resample_moments); the target may be larger than (H, W) (top-left crop)"""
     B, Cin, h, w, Cc, H, W, m, idx, scale, shift = _resample_args(x, size, mode, channels, scale, shift, "resample_moments")
-    if not torch.is_tensor(target) or target.dim() != 4:
-        raise HipBackendError("resample_moments takes an [B,C,Ht,Wt] target")
-    _dev(target, F32, "target")
-    if tuple(target.shape[:2]) != (B, Cc):
-        raise HipBackendError("resample_moments: target %s does not match the prediction's [B,C] %s"
-                              % (tuple(target.shape), (B, Cc)))
-    if target.shape[2] < H or target.shape[3] < W:
-        raise HipBackendError("resample_moments: target %s is smaller than the prediction %s"
-                              % (tuple(target.shape), (B, Cc, H, W)))
-    if lat_w is not None:
-        _dev(lat_w, F32, "lat_w")
-        if lat_w.numel() < H:
-            raise HipBackendError("lat_w has %d entries, the prediction %d rows" % (lat_w.numel(), H))
-    if clim is not None:
-        _dev(clim, F32, "clim")
-        if tuple(clim.shape[-3:]) != (Cc, H, W) or clim.numel() != Cc * H * W:
-            raise HipBackendError("climatology must be [C,H,W] of the prediction's size")
+    _scored_pair("resample_moments", (B, Cc, H, W), target, lat_w, clim)
     out = torch.empty(B, Cc, 12, dtype=torch.float64, device=x.device)
     _chk(lib().orbit2_resample_moments(_p(x), _p(idx), Cin, _p(scale), _p(shift), _p(target), target.shape[2], target.shape[3],
                                        _p(lat_w), _p(clim), _p(out), B, Cc, h, w, H, W, m, _stream()),

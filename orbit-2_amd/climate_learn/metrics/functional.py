@@ -60,6 +60,9 @@ def image_gradient(pred, target, var_names: Optional[List[str]] = None, var_weig
 # valid = the target is finite there, and the mask (if one is given) is non-zero.  The reference has no such loss
 # (examples/era5_daymet_downscaling.py names `masked_mse` but its metrics package has none) and a `mask` argument on rmse /
 # lat_rmse / acc only.
+TARGET_FINITE = "target_finite"       # as a `mask`: the masked form of a metric with no mask operand (metrics.Masked*)
+
+
 def _mask_operand(mask, pred, target):
     """`mask` -> (uint8 bytes, row pitch, batch stride, channel stride) as the masked kernels address it, or (None, 0, 0, 0).
     mask: bool, integer or float (non-zero = keep) of shape [H,W], [1,1,H,W], [B,1,H,W] or [B,C,H,W], its spatial size the
@@ -70,7 +73,7 @@ def _mask_operand(mask, pred, target):
     if isinstance(pred, Resampled):
         raise TypeError("a Resampled prediction cannot be scored over a mask or a target with missing values: its fused scoring "
                         "pass has no mask -- materialize() it first")
-    if mask is None:
+    if mask is None or mask is TARGET_FINITE:
         return None, 0, 0, 0
     B, C, H, W = pred.shape
     ok_hw = ((H, W), tuple(target.shape[-2:]))
@@ -145,25 +148,6 @@ def _masked_rmse(pred, target, aggregate_only=False, lat_weights=None, mask=None
     return _with_aggregate((m[..., 5] / n / frac).sqrt().mean(0).float(), aggregate_only)
 
 
-def _masked_pearson(pred, target, aggregate_only=False, mask=None):
-    s = _masked_sums(pred, target, None, mask).sum(0)                            # [C,13] over the batch
-    N = s[:, 12]
-    cov = s[:, 4] - s[:, 0] * s[:, 1] / N
-    vp = (s[:, 2] - s[:, 0] ** 2 / N).clamp_min(0).sqrt().clamp_min(1e-8)
-    vt = (s[:, 3] - s[:, 1] ** 2 / N).clamp_min(0).sqrt().clamp_min(1e-8)
-    return _with_nan_aggregate((cov / (vp * vt)).float(), aggregate_only)
-
-
-def _masked_mean_bias(pred, target, aggregate_only=False, mask=None):
-    s = _masked_sums(pred, target, None, mask).sum(0)
-    return _with_nan_aggregate(((s[:, 1] - s[:, 0]) / s[:, 12]).float(), aggregate_only)
-
-
-def _masked_mae(pred, target, aggregate_only=False, lat_weights=None, mask=None):
-    s = _masked_sums(pred, target, lat_weights, mask).sum(0)
-    return _with_nan_aggregate((s[:, 6] / s[:, 12]).float(), aggregate_only)
-
-
 # ---- evaluation metrics (reference :236-324); one reduction kernel, the [B,C,6] -> [C+1] algebra on the host ----------
 def _moments(pred, target, lat_weights=None, climatology=None):
     from .. import _hip
@@ -186,6 +170,17 @@ def _with_aggregate(per_channel, aggregate_only):
     return agg if aggregate_only else torch.cat((per_channel, agg.unsqueeze(0)))
 
 
+def _channel_sums(pred, target, lat_weights=None, mask=None):
+    """(s, N, aggregate): s [C,>=12] float64, the sums over the batch; N the pixels of a channel they run over -- B H W, or with a
+    `mask` the [C] counts of the valid ones; aggregate the rule that goes with it: without a mask a NaN channel makes the
+    aggregate NaN, with one a channel without data is NaN and the aggregate is the mean of the others"""
+    if mask is not None:
+        s = _masked_sums(pred, target, lat_weights, mask).sum(0)
+        return s, s[:, 12], _with_nan_aggregate
+    m, n = _moments(pred, target, lat_weights)
+    return m.sum(0), n * pred.shape[0], _with_aggregate
+
+
 def rmse(pred, target, aggregate_only: bool = False, lat_weights=None, mask=None):
     """sqrt(mean_hw((pred-target)^2 * w_lat)) per (b, c), mean over b, then over c (reference :236-255).  With a `mask`
     (_mask_operand) the reference's masked form over the valid pixels -- mask non-zero and target finite: the squared error of
@@ -199,35 +194,26 @@ def rmse(pred, target, aggregate_only: bool = False, lat_weights=None, mask=None
 def pearson(pred, target, aggregate_only: bool = False, mask=None):
     """cosine similarity of the mean-removed, channel-wise flattened [C, B*H*W] fields (reference :294-308).  With a `mask`:
     over the valid pixels of each channel (NaN for a channel without any; the aggregate is the mean of the others)."""
-    if mask is not None:
-        return _masked_pearson(pred, target, aggregate_only, mask)
-    m, n = _moments(pred, target)
-    s = m.sum(0)                                                   # [C,6] over the batch
-    N = n * pred.shape[0]
+    s, N, aggregate = _channel_sums(pred, target, None, mask)
     cov = s[:, 4] - s[:, 0] * s[:, 1] / N
     vp = (s[:, 2] - s[:, 0] ** 2 / N).clamp_min(0).sqrt().clamp_min(1e-8)      # F.cosine_similarity's eps
     vt = (s[:, 3] - s[:, 1] ** 2 / N).clamp_min(0).sqrt().clamp_min(1e-8)
-    return _with_aggregate((cov / (vp * vt)).float(), aggregate_only)
+    return aggregate((cov / (vp * vt)).float(), aggregate_only)
 
 
 def mean_bias(pred, target, aggregate_only: bool = False, mask=None):
     """mean(target) - mean(pred) per channel (reference :311-324).  With a `mask`: means over the valid pixels of each channel
     (NaN for a channel without any; the aggregate is the mean of the others)."""
-    if mask is not None:
-        return _masked_mean_bias(pred, target, aggregate_only, mask)
-    m, n = _moments(pred, target)
-    s = m.sum(0)
-    return _with_aggregate(((s[:, 1] - s[:, 0]) / (n * pred.shape[0])).float(), aggregate_only)
+    s, N, aggregate = _channel_sums(pred, target, None, mask)
+    return aggregate(((s[:, 1] - s[:, 0]) / N).float(), aggregate_only)
 
 
 def mae(pred, target, aggregate_only: bool = False, lat_weights=None, mask=None):
     """mean |pred - target| (x latitude weight) per channel and over everything (reference :219-232; with equal
     channel sizes the overall mean is the mean of the channel means).  With a `mask`: the mean over the valid pixels of each
     channel (NaN for a channel without any; the aggregate is the mean of the others)."""
-    if mask is not None:
-        return _masked_mae(pred, target, aggregate_only, lat_weights, mask)
-    m, n = _moments(pred, target, lat_weights)
-    return _with_aggregate((m[..., 6].sum(0) / (n * pred.shape[0])).float(), aggregate_only)
+    s, N, aggregate = _channel_sums(pred, target, lat_weights, mask)
+    return aggregate((s[:, 6] / N).float(), aggregate_only)
 
 
 def acc(pred, target, climatology, aggregate_only: bool = False, lat_weights=None, mask=None):

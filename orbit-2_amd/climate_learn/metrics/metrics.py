@@ -198,7 +198,7 @@ class _Masked:
         device = pred.loc.device if isinstance(pred, torch.distributions.Normal) else pred.device
         if m is not None and m.device != device:
             m = self._static_mask = m.to(device)               # once: later calls find it there
-        return m
+        return _F.TARGET_FINITE if m is None else m            # no mask at all: still the masked form, over the finite targets
 
 
 @register("masked_mse")
@@ -241,19 +241,19 @@ class MaskedLatWeightedRMSE(_Masked, LatitudeWeightedMetric):
 @register("masked_mae")
 class MaskedMAE(_Masked, Metric):
     def __call__(self, pred, target, mask=None):
-        return _F._masked_mae(pred, target, self.aggregate_only, None, self._mask(mask, pred))
+        return _F.mae(pred, target, self.aggregate_only, None, self._mask(mask, pred))
 
 
 @register("masked_pearson")
 class MaskedPearson(_Masked, Metric):
     def __call__(self, pred, target, mask=None):
-        return _F._masked_pearson(pred, target, self.aggregate_only, self._mask(mask, pred))
+        return _F.pearson(pred, target, self.aggregate_only, self._mask(mask, pred))
 
 
 @register("masked_mean_bias")
 class MaskedMeanBias(_Masked, Metric):
     def __call__(self, pred, target, mask=None):
-        return _F._masked_mean_bias(pred, target, self.aggregate_only, self._mask(mask, pred))
+        return _F.mean_bias(pred, target, self.aggregate_only, self._mask(mask, pred))
 
 
 class ClimatologyBasedMetric(Metric):

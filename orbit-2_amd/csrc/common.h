@@ -198,6 +198,21 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
   return v;
 }
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (int64_t)__shfl_xor((long long)v, o);
+  return v;
+}
 
 // ---- two-stage sums (instead of float atomics): every producer workgroup stores its partial result in its own slab of a
 // caller-provided workspace, and this kernel adds the slabs in a FIXED order -- bitwise reproducible from launch to launch and

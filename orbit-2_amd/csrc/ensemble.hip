@@ -8,7 +8,7 @@
 // values centred on the target, d_(k) = x_(k) - y, are sorted too: the quantiles come from the raw values (q = 0 and q = 1 are
 // the minimum and the maximum bit for bit), every sum from the centred ones -- a field in kelvin is 280 +- 1, and the pair term
 // sum_k (2k - N - 1) x_(k) on raw values loses its low bits to cancellation.
-#include "common.h"
+#include "score_sums.h"
 #include "../../include/orbit2_hip.h"
 
 namespace {
@@ -44,7 +44,6 @@ __global__ __launch_bounds__(256) void ensemble_scores_kernel(const float* __res
                                                               unsigned long long* __restrict__ hist, uint64_t seed,
                                                               float* __restrict__ quant, const float* __restrict__ levels, int Q,
                                                               int64_t field, int H, int W) {
-  __shared__ float red[4][ES_NM];
   __shared__ unsigned int bins[ORBIT2_ENSEMBLE_MAX_MEMBERS + 1];
   __shared__ int q_lo[ES_MAX_Q];
   __shared__ float q_fr[ES_MAX_Q];
@@ -135,18 +134,8 @@ __global__ __launch_bounds__(256) void ensemble_scores_kernel(const float* __res
       }
     }
   }
-  if (sums) {
-#pragma unroll
-    for (int k = 0; k < ES_NM; ++k) {
-      const float r = wave_sum(s[k]);
-      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = r;
-    }
-  }
-  __syncthreads();
-  if (sums && threadIdx.x < ES_NM) {
-    const int k = threadIdx.x;
-    atomicAdd(sums + (size_t)bc * ES_NM + k, (double)red[0][k] + (double)red[1][k] + (double)red[2][k] + (double)red[3][k]);
-  }
+  if (sums) o2_block_sums_add(s, sums + (size_t)bc * ES_NM);          // grid-uniform; holds the workgroup's barrier
+  else __syncthreads();                                                 // bins[] is complete
   if (hist) {
     for (int k = threadIdx.x; k <= N; k += 256) {
       const unsigned int c = bins[k];
@@ -168,8 +157,8 @@ extern "C" int orbit2_ensemble_scores(const float* members, int64_t member_strid
                                       const float* lat_w, double* sums, float* crps_field, int fair, int64_t* hist,
                                       uint64_t seed, float* quant, const float* levels, int Q, int B, int C, int H, int W,
                                       void* stream) {
-  if (!members || !target || (!sums && !crps_field && !hist && !quant)) return O2_ERR_ARG;
-  if (N < 2 || N > ORBIT2_ENSEMBLE_MAX_MEMBERS || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Ht < H || Wt < W) return O2_ERR_ARG;
+  if (!sums && !crps_field && !hist && !quant) return O2_ERR_ARG;
+  if (N < 2 || N > ORBIT2_ENSEMBLE_MAX_MEMBERS || !o2_pair_ok(members, target, B, C, H, W, Ht, Wt)) return O2_ERR_ARG;
   if ((int64_t)B * C > 65535 || (int64_t)H * W > (int64_t)INT32_MAX - 1024 * 256) return O2_ERR_ARG;
   const int64_t field = (int64_t)B * C * H * W;
   if (member_stride < field) return O2_ERR_ARG;
@@ -177,11 +166,8 @@ extern "C" int orbit2_ensemble_scores(const float* members, int64_t member_strid
   hipStream_t s = (hipStream_t)stream;
   if (sums && hipMemsetAsync(sums, 0, sizeof(double) * (size_t)B * C * ES_NM, s) != hipSuccess) return O2_ERR_LAUNCH;
   if (hist && hipMemsetAsync(hist, 0, sizeof(int64_t) * (size_t)B * C * (N + 1), s) != hipSuccess) return O2_ERR_LAUNCH;
-  // one pixel per lane and trip; at most 64 workgroups per image, more only where B * C images alone would not fill the card
-  const int cap = B * C >= 16 ? 64 : 1024 / (B * C);
-  int nblk = (H * W + 255) / 256;
-  if (nblk > cap) nblk = cap;
-  const dim3 grid(nblk, B * C);
+  const int cap = o2_image_block_cap(B * C), nblk = (H * W + 255) / 256;       // one pixel per lane and trip
+  const dim3 grid(nblk < cap ? nblk : cap, B * C);
 #define ES_LAUNCH(P) \
   launch<P>(grid, s, members, member_stride, N, target, Ht, Wt, lat_w, sums, crps_field, fair, hist, seed, quant, levels, Q, field, H, W)
   if (N <= 2) ES_LAUNCH(2);

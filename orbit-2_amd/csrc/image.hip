@@ -1,6 +1,6 @@
 // Hi-res tail of Res_Slim_ViT (fp32, HBM-bound, tiny): unpatchify, 3x3 convs (+GELU+PixelShuffle),
 // precipitation clamp, and the fused losses (mse / bayesian_tv with latitude and variable weights).
-#include "common.h"
+#include "score_sums.h"
 #include "../../include/orbit2_hip.h"
 
 namespace {
@@ -213,7 +213,6 @@ __global__ __launch_bounds__(256) void clamp_channel_kernel(float* __restrict__ 
 // err(b,c,i,j) = [(p-t)^2 + 0.02*(dv + dh + 0.7*d1 + 0.7*d2)] * latw[i] * chanw[c]     (kind 1; kind 0: no TV)
 //   dv = |p[i+1][j]-p[i][j]| (i<H-1)        dh = |p[i][j+1]-p[i][j]| (j<W-1)
 //   d1 = |p[i+1][j+1]-p[i][j]| (i<H-1,j<W-1)   d2 = |p[i+1][j-1]-p[i][j]| (i<H-1, j>=1)
-__device__ __forceinline__ float sgn(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }
 
 __global__ __launch_bounds__(256) void loss_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                        int Ht, int Wt, const float* __restrict__ latw,
@@ -432,7 +431,7 @@ static const int LOSS_NBLK = 64;
 extern "C" int orbit2_loss_fwd(const float* pred, const float* target, int Ht, int Wt, const float* lat_w,
                                const float* chan_w, float* out, float* ws, int B, int C, int H, int W, int kind,
                                void* stream) {
-  if (!pred || !target || !out || !ws || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Ht < H || Wt < W) return O2_ERR_ARG;
+  if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !out || !ws) return O2_ERR_ARG;
   if (kind < 0 || kind > 2) return O2_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   float* ws2 = ws + (size_t)B * C * LOSS_NBLK;
@@ -447,8 +446,7 @@ extern "C" int orbit2_loss_fwd(const float* pred, const float* target, int Ht, i
 extern "C" int orbit2_loss_bwd(const float* pred, const float* target, int Ht, int Wt, const float* lat_w,
                                const float* chan_w, const float* gscale, float* dpred, int B, int C, int H, int W,
                                int kind, void* stream) {
-  if (!pred || !target || !gscale || !dpred || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Ht < H || Wt < W)
-    return O2_ERR_ARG;
+  if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !gscale || !dpred) return O2_ERR_ARG;
   if (kind < 0 || kind > 2) return O2_ERR_ARG;
   hipLaunchKernelGGL(loss_bwd_kernel, dim3(grid_for((int64_t)B * C * H * W, 256)), dim3(256), 0, (hipStream_t)stream,
                      pred, target, Ht, Wt, lat_w, chan_w, gscale, dpred, B, C, H, W, kind);
@@ -457,17 +455,15 @@ extern "C" int orbit2_loss_bwd(const float* pred, const float* target, int Ht, i
 }
 
 // ---- evaluation metrics (metrics/functional.py:219-324: mae, rmse, acc, pearson, mean_bias) ------------------------------
-// twelve sums per (b, c) image over a = pred - clim, b = target - clim (clim optional, [C][H][W]), w = lat_w[y] or 1:
-//   0 sum a, 1 sum b, 2 sum a^2, 3 sum b^2, 4 sum a*b, 5 sum w (a-b)^2, 6 sum w |a-b|,
-//   7 sum w a, 8 sum w b, 9 sum w a*b, 10 sum w a^2, 11 sum w b^2
-// per-thread fp32 partials, double accumulation across the grid.
+// the twelve sums of score_sums.h (o2_moments_add) per (b, c) image, clim optional [C][H][W]; one pixel per lane and trip.
+// orbit2_masked_moments with no mask is NOT this kernel with a count: on rows that are not 16-byte aligned its four-pixel items
+// of guarded scalar loads take 1.36 x the time of this sweep (profiles/score_sums.md), so both stay.
 namespace {
-constexpr int EVAL_NM = 12;
+constexpr int EVAL_NM = O2_NMOMENTS;
 __global__ __launch_bounds__(256) void eval_moments_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                            int Ht, int Wt, const float* __restrict__ lat_w,
                                                            const float* __restrict__ clim, double* __restrict__ out,
                                                            int C, int H, int W) {
-  __shared__ float red[4][EVAL_NM];
   const int bc = blockIdx.y;
   const float* p = pred + (size_t)bc * H * W;
   const float* t = target + (size_t)bc * Ht * Wt;
@@ -478,36 +474,19 @@ __global__ __launch_bounds__(256) void eval_moments_kernel(const float* __restri
   for (int i = blockIdx.x * 256 + threadIdx.x; i < H * W; i += gridDim.x * 256) {
     const int y = i / W, x = i - y * W;
     const float c0 = cl ? cl[i] : 0.f;
-    const float a = p[i] - c0, b = t[(size_t)y * Wt + x] - c0;
-    const float w = lat_w ? lat_w[y] : 1.f;
-    const float d = a - b;
-    s[0] += a; s[1] += b; s[2] += a * a; s[3] += b * b; s[4] += a * b;
-    s[5] += w * d * d; s[6] += w * fabsf(d);
-    s[7] += w * a; s[8] += w * b; s[9] += w * a * b; s[10] += w * a * a; s[11] += w * b * b;
+    o2_moments_add(s, p[i] - c0, t[(size_t)y * Wt + x] - c0, lat_w ? lat_w[y] : 1.f);
   }
-#pragma unroll
-  for (int k = 0; k < EVAL_NM; ++k) {
-    const float v = wave_sum(s[k]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < EVAL_NM) {
-    const int k = threadIdx.x;
-    atomicAdd(out + (size_t)bc * EVAL_NM + k,
-              (double)red[0][k] + (double)red[1][k] + (double)red[2][k] + (double)red[3][k]);
-  }
+  o2_block_sums_add(s, out + (size_t)bc * EVAL_NM);
 }
 }  // namespace
 
 extern "C" int orbit2_eval_moments(const float* pred, const float* target, int Ht, int Wt, const float* lat_w,
                                    const float* clim, double* out, int B, int C, int H, int W, void* stream) {
-  if (!pred || !target || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Ht < H || Wt < W) return O2_ERR_ARG;
+  if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !out) return O2_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(out, 0, sizeof(double) * (size_t)B * C * EVAL_NM, s) != hipSuccess) return O2_ERR_LAUNCH;
-  int nblk = (H * W + 256 * 8 - 1) / (256 * 8);
-  if (nblk > 64) nblk = 64;
-  hipLaunchKernelGGL(eval_moments_kernel, dim3(nblk, B * C), dim3(256), 0, s, pred, target, Ht, Wt, lat_w, clim, out, C,
-                     H, W);
+  hipLaunchKernelGGL(eval_moments_kernel, dim3(o2_image_blocks((int64_t)H * W), B * C), dim3(256), 0, s, pred, target, Ht, Wt,
+                     lat_w, clim, out, C, H, W);
   O2_CHECK_LAUNCH();
   return O2_OK;
 }
@@ -580,7 +559,7 @@ extern "C" int orbit2_ensemble_update(const float* member, float* mean, float* m
 }
 
 // Scores of a Gaussian prediction N(mean, std^2) against a target, four sums per (b, c) image (target: top-left crop,
-// w = lat_w[y] or 1), double accumulation across the grid as in orbit2_eval_moments:
+// w = lat_w[y] or 1), added up by o2_block_sums_add as in orbit2_eval_moments:
 //   0 sum w crps, 1 sum w std^2, 2 sum w (mean - target)^2, 3 sum 1{|target - mean| <= std}
 // crps is the closed form of the Gaussian CRPS, std (z (2 Phi(z) - 1) + 2 phi(z) - 1 / sqrt(pi)) with z = (target - mean) / std
 // (functional.py:353 there has 1 / pi, and cannot be called: see metrics/functional.py:gaussian_crps here).  It is evaluated as
@@ -594,7 +573,6 @@ __global__ __launch_bounds__(256) void gaussian_scores_kernel(const float* __res
                                                               const float* __restrict__ target, int Ht, int Wt,
                                                               const float* __restrict__ lat_w, double* __restrict__ out, int H,
                                                               int W) {
-  __shared__ float red[4][GS_NM];
   const int bc = blockIdx.y;
   const float* m = mean + (size_t)bc * H * W;
   const float* sd = std_ + (size_t)bc * H * W;
@@ -617,28 +595,18 @@ __global__ __launch_bounds__(256) void gaussian_scores_kernel(const float* __res
     s[2] += w * d * d;
     s[3] += ad <= sg ? 1.f : 0.f;
   }
-#pragma unroll
-  for (int k = 0; k < GS_NM; ++k) {
-    const float v = wave_sum(s[k]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < GS_NM) {
-    const int k = threadIdx.x;
-    atomicAdd(out + (size_t)bc * GS_NM + k, (double)red[0][k] + (double)red[1][k] + (double)red[2][k] + (double)red[3][k]);
-  }
+  o2_block_sums_add(s, out + (size_t)bc * GS_NM);
 }
 }  // namespace
 
 extern "C" int orbit2_gaussian_scores(const float* mean, const float* std_, const float* target, int Ht, int Wt,
                                       const float* lat_w, double* out, int B, int C, int H, int W, void* stream) {
-  if (!mean || !std_ || !target || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Ht < H || Wt < W) return O2_ERR_ARG;
+  if (!o2_pair_ok(mean, target, B, C, H, W, Ht, Wt) || !std_ || !out) return O2_ERR_ARG;
   if ((int64_t)B * C > 65535 || (int64_t)H * W > (int64_t)INT32_MAX - 64 * 256) return O2_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(out, 0, sizeof(double) * (size_t)B * C * GS_NM, s) != hipSuccess) return O2_ERR_LAUNCH;
-  int nblk = (H * W + 256 * 8 - 1) / (256 * 8);
-  if (nblk > 64) nblk = 64;
-  hipLaunchKernelGGL(gaussian_scores_kernel, dim3(nblk, B * C), dim3(256), 0, s, mean, std_, target, Ht, Wt, lat_w, out, H, W);
+  hipLaunchKernelGGL(gaussian_scores_kernel, dim3(o2_image_blocks((int64_t)H * W), B * C), dim3(256), 0, s, mean, std_, target, Ht,
+                     Wt, lat_w, out, H, W);
   O2_CHECK_LAUNCH();
   return O2_OK;
 }

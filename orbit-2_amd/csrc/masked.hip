@@ -10,20 +10,18 @@
 // 4-byte) boundary the item's centre is one float4 / one dword per operand (VEC); otherwise the same item is read by four
 // guarded scalar lanes.  The total-variation stencil needs the pixels left and right of the group and the rows above (backward)
 // and below: those edge pixels are scalar loads, and a pixel outside the plane is invalid.
-#include "common.h"
+#include "score_sums.h"
 
 namespace {
 
 constexpr int ML_NBLK = 64;          // workgroups per (b, c) plane of the forward; the partials are added in this order
-constexpr int MM_NM = 13;            // the twelve sums of orbit2_eval_moments + the valid count
+constexpr int MM_NM = O2_NMOMENTS + 1;   // the twelve sums of orbit2_eval_moments + the valid count
 
 struct MaskArg {
   const uint8_t* m;                  // NULL: no mask
   int pitch;                         // bytes (= elements) between two rows
   int64_t sb, sc;                    // batch and channel strides; 0 = broadcast
 };
-
-__device__ __forceinline__ bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
 // One row of one (b, c) plane around the item's columns j0 .. j0+3:
 //   pv[k], vv[k]  k = 0..5  <->  column j0 - 1 + k   (pv = 0 and vv = false outside the plane or where invalid is irrelevant:
@@ -75,22 +73,9 @@ __device__ __forceinline__ void load_row(const float* __restrict__ p, const floa
   }
 }
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (int64_t)__shfl_xor((long long)v, o);
-  return v;
-}
-
-__device__ __forceinline__ float sgnf(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : 0.f); }
 // |a - b| if both pixels are valid, else 0 (select: a and b may be NaN where invalid)
 __device__ __forceinline__ float absdiff_if(bool v, float a, float b) { return v ? fabsf(a - b) : 0.f; }
-__device__ __forceinline__ float sgndiff_if(bool v, float a, float b) { return v ? sgnf(a - b) : 0.f; }
+__device__ __forceinline__ float sgndiff_if(bool v, float a, float b) { return v ? sgn(a - b) : 0.f; }
 
 // ---- forward: per-workgroup partials of num = sum v w cw err and of the valid count per (b, c) plane ----------------------
 //   err(i,j) = (p - t)^2 + [TV] 0.02 (|p[i+1][j]-p| + |p[i][j+1]-p| + 0.7 |p[i+1][j+1]-p| + 0.7 |p[i+1][j-1]-p|), each
@@ -226,13 +211,13 @@ __global__ __launch_bounds__(256) void masked_loss_bwd_kernel(const float* __res
   }
 }
 
-// ---- the twelve sums of orbit2_eval_moments over the valid pixels, and their number ------------------------------------------
+// ---- the twelve sums of orbit2_eval_moments (score_sums.h: o2_moments_add) over the valid pixels, and their number, which must
+// stay exact: an integer beside the epilogue's floats, not a thirteenth of them ------------------------------------------------
 template <bool VEC>
 __global__ __launch_bounds__(256) void masked_moments_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                              int Ht, int Wt, MaskArg mk, const float* __restrict__ latw,
                                                              const float* __restrict__ clim, double* __restrict__ out,
                                                              int C, int H, int W) {
-  __shared__ float red[4][MM_NM - 1];
   __shared__ int redn[4];
   const int plane = blockIdx.y, c = plane % C, b = plane / C;
   const float* p = pred + (size_t)plane * H * W;
@@ -240,9 +225,9 @@ __global__ __launch_bounds__(256) void masked_moments_kernel(const float* __rest
   const uint8_t* m = mk.m ? mk.m + b * mk.sb + c * mk.sc : nullptr;
   const float* cl = clim ? clim + (size_t)c * H * W : nullptr;
   const int W4 = (W + 3) >> 2;
-  float s[MM_NM - 1];
+  float s[O2_NMOMENTS];
 #pragma unroll
-  for (int k = 0; k < MM_NM - 1; ++k) s[k] = 0.f;
+  for (int k = 0; k < O2_NMOMENTS; ++k) s[k] = 0.f;
   int n = 0;
   for (int e = blockIdx.x * 256 + threadIdx.x; e < H * W4; e += gridDim.x * 256) {
     const int i = e / W4, j0 = (e - i * W4) << 2;
@@ -265,28 +250,15 @@ __global__ __launch_bounds__(256) void masked_moments_kernel(const float* __rest
     for (int k = 0; k < 4; ++k) {
       const bool v = v0[k + 1];
       const float a = v ? p0[k + 1] - c0[k] : 0.f, bb = v ? t0[k] - c0[k] : 0.f;      // zeros add nothing to any sum
-      const float d = a - bb;
-      s[0] += a; s[1] += bb; s[2] += a * a; s[3] += bb * bb; s[4] += a * bb;
-      s[5] += w * d * d; s[6] += w * fabsf(d);
-      s[7] += w * a; s[8] += w * bb; s[9] += w * a * bb; s[10] += w * a * a; s[11] += w * bb * bb;
+      o2_moments_add(s, a, bb, w);
       n += v ? 1 : 0;
     }
   }
-#pragma unroll
-  for (int k = 0; k < MM_NM - 1; ++k) {
-    const float v = wave_sum(s[k]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
-  }
   n = wave_sum_i(n);
   if ((threadIdx.x & 63) == 0) redn[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x < MM_NM - 1) {
-    const int k = threadIdx.x;
-    atomicAdd(out + (size_t)plane * MM_NM + k,
-              (double)red[0][k] + (double)red[1][k] + (double)red[2][k] + (double)red[3][k]);
-  } else if (threadIdx.x == MM_NM - 1) {
+  o2_block_sums_add(s, out + (size_t)plane * MM_NM);                 // its barrier orders redn as well
+  if (threadIdx.x == MM_NM - 1)
     atomicAdd(out + (size_t)plane * MM_NM + MM_NM - 1, (double)(redn[0] + redn[1] + redn[2] + redn[3]));   // exact below 2^53
-  }
 }
 
 inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
@@ -309,7 +281,7 @@ extern "C" int orbit2_masked_loss_fwd(const float* pred, const float* target, in
                                       int mask_pitch, int64_t mask_sb, int64_t mask_sc, const float* lat_w,
                                       const float* chan_w, float* out, int64_t* cnt, float* ws, int B, int C, int H, int W,
                                       int kind, void* stream) {
-  if (!pred || !target || !out || !cnt || !ws || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Ht < H || Wt < W) return O2_ERR_ARG;
+  if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !out || !cnt || !ws) return O2_ERR_ARG;
   if (kind != 0 && kind != 1) return O2_ERR_ARG;
   MaskArg mk;
   if (!mask_arg(mk, mask, mask_pitch, mask_sb, mask_sc, Ht, Wt, W)) return O2_ERR_ARG;
@@ -331,8 +303,7 @@ extern "C" int orbit2_masked_loss_bwd(const float* pred, const float* target, in
                                       int mask_pitch, int64_t mask_sb, int64_t mask_sc, const float* lat_w,
                                       const float* chan_w, const float* gscale, const int64_t* cnt, float* dpred, int B,
                                       int C, int H, int W, int kind, void* stream) {
-  if (!pred || !target || !gscale || !cnt || !dpred || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Ht < H || Wt < W)
-    return O2_ERR_ARG;
+  if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !gscale || !cnt || !dpred) return O2_ERR_ARG;
   if (kind != 0 && kind != 1) return O2_ERR_ARG;
   MaskArg mk;
   if (!mask_arg(mk, mask, mask_pitch, mask_sb, mask_sc, Ht, Wt, W)) return O2_ERR_ARG;
@@ -352,13 +323,12 @@ extern "C" int orbit2_masked_loss_bwd(const float* pred, const float* target, in
 extern "C" int orbit2_masked_moments(const float* pred, const float* target, int Ht, int Wt, const uint8_t* mask,
                                      int mask_pitch, int64_t mask_sb, int64_t mask_sc, const float* lat_w, const float* clim,
                                      double* out, int B, int C, int H, int W, void* stream) {
-  if (!pred || !target || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0 || Ht < H || Wt < W) return O2_ERR_ARG;
+  if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !out) return O2_ERR_ARG;
   MaskArg mk;
   if (!mask_arg(mk, mask, mask_pitch, mask_sb, mask_sc, Ht, Wt, W)) return O2_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(out, 0, sizeof(double) * (size_t)B * C * MM_NM, s) != hipSuccess) return O2_ERR_LAUNCH;
-  int nblk = (H * ((W + 3) / 4) + 256 * 2 - 1) / (256 * 2);
-  if (nblk > 64) nblk = 64;
+  const int nblk = o2_image_blocks((int64_t)H * ((W + 3) / 4) * 4);   // an item is four pixels
   o2_with_flags(
       [&](auto vec) {
         hipLaunchKernelGGL((masked_moments_kernel<decltype(vec)::value>), dim3(nblk, B * C), dim3(256), 0, s, pred, target, Ht,

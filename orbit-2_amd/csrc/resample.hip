@@ -20,12 +20,12 @@
 // Summation order: a row interpolant is its taps left to right (first product, then fmaf), a pixel its row interpolants top to
 // bottom in the same way, then fmaf(scale[c], r, shift[c]).  Every source index is clamped into the grid and no address depends
 // on a data value: non-finite inputs give unspecified values, never a fault.
-#include "common.h"
+#include "score_sums.h"
 #include "../../include/orbit2_hip.h"
 
 namespace {
 constexpr int RS_TH = ORBIT2_RESAMPLE_TILE_H, RS_TW = ORBIT2_RESAMPLE_TILE_W, RS_LDS = ORBIT2_RESAMPLE_LDS_FLOATS;
-constexpr int RS_NM = 12;
+constexpr int RS_NM = O2_NMOMENTS;
 static_assert(RS_TW == 256 && RS_TH % 4 == 0, "a wave's 64 lanes x 4 columns span the tile, four waves share its rows");
 
 template <int MODE> struct rs_ntaps { static constexpr int value = MODE == 0 ? 1 : (MODE == 1 ? 2 : 4); };
@@ -77,7 +77,7 @@ template <int MODE, bool MOMENTS, bool STAGED>
 __device__ __forceinline__ void rs_rows(const float* __restrict__ src, int pitch, int yoff, int xoff, int h, int w, int H,
                                         int W, float ry, float rx, int y0, int x0, bool affine, float sc, float sh,
                                         float* __restrict__ orow0, const float* __restrict__ trow0, int Wt,
-                                        const float* __restrict__ lat_w, const float* __restrict__ crow0, float* s) {
+                                        const float* __restrict__ lat_w, const float* __restrict__ crow0, float (&s)[RS_NM]) {
   constexpr int NT = rs_ntaps<MODE>::value;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -153,12 +153,7 @@ __device__ __forceinline__ void rs_rows(const float* __restrict__ src, int pitch
       const float lw = lat_w ? lat_w[y] : 1.f;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if (xl + j >= W) continue;
-        const float a = v[j] - cv[j], b = tv[j] - cv[j];
-        const float d = a - b;
-        s[0] += a; s[1] += b; s[2] += a * a; s[3] += b * b; s[4] += a * b;
-        s[5] += lw * d * d; s[6] += lw * fabsf(d);
-        s[7] += lw * a; s[8] += lw * b; s[9] += lw * a * b; s[10] += lw * a * a; s[11] += lw * b * b;
+        if (xl + j < W) o2_moments_add(s, v[j] - cv[j], tv[j] - cv[j], lw);
       }
     }
   }
@@ -174,7 +169,6 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
                                                        int stage, float ry, float rx) {
   constexpr int NT = rs_ntaps<MODE>::value;
   __shared__ float win[RS_LDS];
-  __shared__ float red[4][RS_NM];
   const int bc = blockIdx.y, b = bc / C, c = bc - b * C;
   const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
   const int y0 = ty * RS_TH, x0 = tx * RS_TW;
@@ -210,18 +204,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
   } else {
     rs_rows<MODE, MOMENTS, false>(src, w, 0, 0, h, w, H, W, ry, rx, y0, x0, affine, sc, sh, orow0, trow0, Wt, lat_w, crow0, s);
   }
-  if (MOMENTS) {
-#pragma unroll
-    for (int k = 0; k < RS_NM; ++k) {
-      const float v = wave_sum(s[k]);
-      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < RS_NM) {
-      const int k = threadIdx.x;
-      atomicAdd(sums + (size_t)bc * RS_NM + k, (double)red[0][k] + (double)red[1][k] + (double)red[2][k] + (double)red[3][k]);
-    }
-  }
+  if (MOMENTS) o2_block_sums_add(s, sums + (size_t)bc * RS_NM);
 }
 
 // ceil(tile * in / out) + 4: no window of a tile at this ratio is larger (a bicubic footprint is the span of the floors + 4)

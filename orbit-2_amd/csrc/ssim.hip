@@ -20,7 +20,7 @@
 // The data range (max - min of the image's target crop, unless given) is found by a launch of its own in front and handed over
 // in sums[3..4]: stream order, no host synchronisation.  A range of 0 is NOT special-cased: C1 = C2 = 0 and a flat window is
 // 0 / 0 = NaN, as in scikit-image; no address depends on a value, so non-finite inputs give unspecified scores, never a fault.
-#include "common.h"
+#include "score_sums.h"
 #include "../../include/orbit2_hip.h"
 
 namespace {
@@ -30,12 +30,6 @@ constexpr int SS_IH = SS_TH + SS_HALO, SS_IW = SS_TW + SS_HALO;      // the stag
 constexpr int SS_STRIP = SS_TH / 4;                                  // centre rows per wave
 constexpr int SS_NS = 6;
 static_assert(SS_WIN == 7 && SS_TW == 64 && SS_TH % 4 == 0, "one column per lane, four waves, a 7-deep register ring");
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
-}
 
 // sums[bc] = {0, 0, 0, +inf, -inf, 0}: the zeroing of the entry, with the neutral elements of min and max
 __global__ void ssim_init_kernel(double* __restrict__ sums, int n) {
@@ -80,7 +74,6 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ pre
                                                    const float* __restrict__ data_range, double* sums,
                                                    float* __restrict__ ssim_map, int H, int W, int ntx) {
   __shared__ float sa[SS_IH * SS_IW], sb[SS_IH * SS_IW];
-  __shared__ float red[4][3];
   const int bc = blockIdx.y;
   const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
   const int y0 = ty * SS_TH, x0 = tx * SS_TW;         // first centre of the tile in valid coordinates = its first pixel
@@ -163,31 +156,21 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ pre
       if (ssim_map) ssim_map[((size_t)bc * Hv + cy) * Wv + x0 + lx] = ssim;
     }
   }
-  const float r0 = wave_sum(s0), r1 = wave_sum(s1), r2 = wave_sum(se);
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6][0] = r0;
-    red[threadIdx.x >> 6][1] = r1;
-    red[threadIdx.x >> 6][2] = r2;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int k = threadIdx.x;
-    atomicAdd(S + k, (double)red[0][k] + (double)red[1][k] + (double)red[2][k] + (double)red[3][k]);
-  }
+  const float s[3] = {s0, s1, se};
+  o2_block_sums_add(s, S);
 }
 }  // namespace
 
 extern "C" int orbit2_ssim(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* data_range,
                            double* sums, float* ssim_map, int B, int C, int H, int W, void* stream) {
-  if (!pred || !target || !sums || B <= 0 || C <= 0 || H < SS_WIN || W < SS_WIN || Ht < H || Wt < W) return O2_ERR_ARG;
+  if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !sums || H < SS_WIN || W < SS_WIN) return O2_ERR_ARG;
   if ((int64_t)B * C > 65535) return O2_ERR_ARG;
   const int ntx = (W - SS_HALO + SS_TW - 1) / SS_TW, nty = (H - SS_HALO + SS_TH - 1) / SS_TH;
   if ((int64_t)ntx * nty > INT32_MAX) return O2_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const int BC = B * C;
   hipLaunchKernelGGL(ssim_init_kernel, dim3((BC + 255) / 256), dim3(256), 0, s, sums, BC);
-  // at most 64 workgroups per image, more only where B * C images alone would not fill the card
-  const int cap = BC >= 16 ? 64 : 1024 / BC;
+  const int cap = o2_image_block_cap(BC);
   hipLaunchKernelGGL(ssim_range_kernel, dim3(H < cap ? H : cap, BC), dim3(256), 0, s, target, Ht, Wt, sums, H, W);
   hipLaunchKernelGGL(ssim_kernel, dim3(ntx * nty, BC), dim3(256), 0, s, pred, target, Ht, Wt, lat_w, data_range, sums, ssim_map,
                      H, W, ntx);
