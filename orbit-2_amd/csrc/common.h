@@ -32,6 +32,18 @@ __device__ __forceinline__ unsigned pack_bf2(float lo, float hi) {
   const o2_f32x2 v = {lo, hi};
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, o2_bf16x2));
 }
+// eight consecutive bf16 (one 16-byte access) <-> eight floats.  (The vector goes in BY VALUE: by reference the row-shared LayerNorm
+// backward compiles to other code, profiles/row_kernels_equivalence.txt.)
+__device__ __forceinline__ void unpack8(const u32x4 r, float* f) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { f[2 * k] = bf2f((bf16_t)(r[k] & 0xffff)); f[2 * k + 1] = bf2f((bf16_t)(r[k] >> 16)); }
+}
+__device__ __forceinline__ u32x4 pack8(const float* v) {
+  u32x4 o;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) o[k] = pack_bf2(v[2 * k], v[2 * k + 1]);
+  return o;
+}
 
 // 16-byte LDS-DMA: every lane supplies its own global source; the LDS destination is
 // (wave-uniform base) + lane*16.
@@ -107,6 +119,17 @@ __device__ __host__ __forceinline__ uint32_t o2_hash(uint32_t seed_lo, uint32_t 
 }
 __device__ __forceinline__ uint32_t o2_hash64(uint64_t seed, uint64_t idx) {
   return o2_hash((uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)idx, (uint32_t)(idx >> 32));
+}
+// the rule above on the eight consecutive elements f[0..8) from flat index idx (a multiple of 8: two hash groups) under the
+// seed with the salt already in it: kept values times dscale, dropped ones 0.  The element-wise kernels outside the GEMM
+// (post_reduce, the dropout backward) mask through this one function; gemm.hip's epilogues apply the same keep bit to two values at once.
+__device__ __forceinline__ void o2_drop8(float* f, uint64_t salted_seed, int64_t idx, unsigned thr, float dscale) {
+  const uint32_t h0 = o2_hash64(salted_seed, (uint64_t)idx >> 2), h1 = o2_hash64(salted_seed, ((uint64_t)idx >> 2) + 1);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    f[j] = (((h0 >> (8 * j)) & 0xffu) >= thr) ? f[j] * dscale : 0.f;
+    f[4 + j] = (((h1 >> (8 * j)) & 0xffu) >= thr) ? f[4 + j] * dscale : 0.f;
+  }
 }
 
 // ---- attention-probability dropout: a factored hash ------------------------------------------------------------
@@ -252,6 +275,14 @@ template <class F> static inline void o2_with_flags(F&& f) { f(); }
 template <class F, class... Rest> static inline void o2_with_flags(F&& f, bool flag, Rest... rest) {
   if (flag) o2_with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
   else o2_with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+// blocks of a grid-stride launch: one per per_block work items, at least 1, at most max_blocks
+static inline int grid_for(int64_t work_items, int per_block, int max_blocks = 4096) {
+  int64_t g = (work_items + per_block - 1) / per_block;
+  if (g < 1) g = 1;
+  if (g > max_blocks) g = max_blocks;
+  return (int)g;
 }
 
 #define O2_CHECK_LAUNCH()                                   \

@@ -201,16 +201,6 @@ __device__ __forceinline__ void epilogue4(const Epi& e, int m, int n, f32x4 v) {
 // and j+1 regroups them so that a lane holds 8 consecutive n (16 bytes of bf16): every epilogue load and store is a
 // dwordx4 instead of two dwordx2 (the store tail is issue-bound), and loads are issued in batches ahead of the
 // stores so no load queues behind a store (vmcnt retires in order).
-__device__ __forceinline__ void unpack8(const u32x4& r, float* f) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { f[2 * k] = bf2f((bf16_t)(r[k] & 0xffff)); f[2 * k + 1] = bf2f((bf16_t)(r[k] >> 16)); }
-}
-__device__ __forceinline__ u32x4 pack8(const float* v) {
-  u32x4 o;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) o[k] = pack_bf2(v[2 * k], v[2 * k + 1]);
-  return o;
-}
 struct Pre8 { u32x4 res, pre, old; };
 
 __device__ __forceinline__ void epi8_load(const Epi& e, int m, int n, Pre8& q) {

@@ -5,12 +5,7 @@
 
 namespace {
 
-inline int grid_for(int64_t n, int per_block) {
-  int64_t g = (n + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  if (g > 8192) g = 8192;
-  return (int)g;
-}
+inline int img_grid(int64_t n) { return grid_for(n, 256, 8192); }   // this file's grid-stride launches: up to 8192 blocks of 256
 
 // ---- unpatchify (res_slimvit.py:167-179): pure index permutation -------------------------------
 // img[b][c][hh*p+pp][ww*p+qq] = t[b][ (((hh*wf + ww)*p + pp)*p + qq)*C + c ],  hf = h*s/p, wf = w*s/p
@@ -343,7 +338,7 @@ extern "C" int orbit2_unpatchify_fwd(const void* t, float* img, int B, int C, in
                                      void* stream) {
   if (!t || !img || B <= 0 || C <= 0 || p <= 0 || s <= 0 || (h * s) % p || (w * s) % p) return O2_ERR_ARG;
   const int64_t n = (int64_t)B * C * h * s * w * s;
-  hipLaunchKernelGGL(unpatchify_kernel<false>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)t,
+  hipLaunchKernelGGL(unpatchify_kernel<false>, dim3(img_grid(n)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)t,
                      img, B, C, h * s, w * s, p);
   O2_CHECK_LAUNCH();
   return O2_OK;
@@ -352,7 +347,7 @@ extern "C" int orbit2_unpatchify_fwd_f32(const float* t, float* img, int B, int 
                                          void* stream) {
   if (!t || !img || B <= 0 || C <= 0 || p <= 0 || s <= 0 || (h * s) % p || (w * s) % p) return O2_ERR_ARG;
   const int64_t n = (int64_t)B * C * h * s * w * s;
-  hipLaunchKernelGGL((unpatchify_kernel<false, true>), dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL((unpatchify_kernel<false, true>), dim3(img_grid(n)), dim3(256), 0, (hipStream_t)stream,
                      (bf16_t*)t, img, B, C, h * s, w * s, p);
   O2_CHECK_LAUNCH();
   return O2_OK;
@@ -361,7 +356,7 @@ extern "C" int orbit2_unpatchify_bwd(const float* dimg, void* dt, int B, int C, 
                                      void* stream) {
   if (!dimg || !dt || B <= 0 || C <= 0 || p <= 0 || s <= 0 || (h * s) % p || (w * s) % p) return O2_ERR_ARG;
   const int64_t n = (int64_t)B * C * h * s * w * s;
-  hipLaunchKernelGGL(unpatchify_kernel<true>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)dt,
+  hipLaunchKernelGGL(unpatchify_kernel<true>, dim3(img_grid(n)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)dt,
                      (float*)dimg, B, C, h * s, w * s, p);
   O2_CHECK_LAUNCH();
   return O2_OK;
@@ -375,7 +370,7 @@ extern "C" int orbit2_conv3x3_fwd(const float* in, const int* chan_idx, int in_c
   if (mode == 1 && (!pre || r <= 0 || Cout % (r * r))) return O2_ERR_ARG;
   if (mode != 0 && mode != 1) return O2_ERR_ARG;
   if (addend && (mode != 0 || Ha < H || Wa < W)) return O2_ERR_ARG;
-  dim3 grid(grid_for((int64_t)B * H * W, 256), (Cout + COB - 1) / COB);
+  dim3 grid(img_grid((int64_t)B * H * W), (Cout + COB - 1) / COB);
   hipLaunchKernelGGL(conv3x3_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, in, chan_idx, in_ctotal, weight,
                      bias, out, pre, addend, Ha, Wa, B, Cin, Cout, H, W, mode, r);
   O2_CHECK_LAUNCH();
@@ -396,7 +391,7 @@ extern "C" int orbit2_conv3x3_bwd(const float* dout, const float* in, const int*
   if (mode != 0 && mode != 1) return O2_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (din) {
-    hipLaunchKernelGGL(conv3x3_bwd_data_kernel, dim3(grid_for((int64_t)B * Cin * H * W, 256)), dim3(256), 0, s, dout,
+    hipLaunchKernelGGL(conv3x3_bwd_data_kernel, dim3(img_grid((int64_t)B * Cin * H * W)), dim3(256), 0, s, dout,
                        pre, weight, din, B, Cin, Cout, H, W, mode, r);
     O2_CHECK_LAUNCH();
   }
@@ -413,7 +408,7 @@ extern "C" int orbit2_conv3x3_bwd(const float* dout, const float* in, const int*
 
 extern "C" int orbit2_clamp_channel(float* img, int B, int C, int HW, int chan, void* stream) {
   if (!img || B <= 0 || C <= 0 || HW <= 0 || chan < 0 || chan >= C) return O2_ERR_ARG;
-  hipLaunchKernelGGL(clamp_channel_kernel, dim3(grid_for((int64_t)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(clamp_channel_kernel, dim3(img_grid((int64_t)B * HW)), dim3(256), 0, (hipStream_t)stream,
                      img, (const float*)nullptr, (float*)nullptr, B, C, HW, chan);
   O2_CHECK_LAUNCH();
   return O2_OK;
@@ -421,7 +416,7 @@ extern "C" int orbit2_clamp_channel(float* img, int B, int C, int HW, int chan, 
 extern "C" int orbit2_clamp_channel_bwd(const float* img_clamped, float* dimg, int B, int C, int HW, int chan,
                                         void* stream) {
   if (!img_clamped || !dimg || B <= 0 || C <= 0 || HW <= 0 || chan < 0 || chan >= C) return O2_ERR_ARG;
-  hipLaunchKernelGGL(clamp_channel_kernel, dim3(grid_for((int64_t)B * HW, 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(clamp_channel_kernel, dim3(img_grid((int64_t)B * HW)), dim3(256), 0, (hipStream_t)stream,
                      (float*)nullptr, img_clamped, dimg, B, C, HW, chan);
   O2_CHECK_LAUNCH();
   return O2_OK;
@@ -448,7 +443,7 @@ extern "C" int orbit2_loss_bwd(const float* pred, const float* target, int Ht, i
                                int kind, void* stream) {
   if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !gscale || !dpred) return O2_ERR_ARG;
   if (kind < 0 || kind > 2) return O2_ERR_ARG;
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3(grid_for((int64_t)B * C * H * W, 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(loss_bwd_kernel, dim3(img_grid((int64_t)B * C * H * W)), dim3(256), 0, (hipStream_t)stream,
                      pred, target, Ht, Wt, lat_w, chan_w, gscale, dpred, B, C, H, W, kind);
   O2_CHECK_LAUNCH();
   return O2_OK;

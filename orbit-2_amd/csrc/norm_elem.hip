@@ -6,11 +6,6 @@ namespace {
 
 constexpr int LN_MAXD = 8192;  // up to 16 16-byte chunks per lane
 
-__device__ __forceinline__ void unpack8(const u32x4 r, float* f) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { f[2 * j] = bf2f((bf16_t)(r[j] & 0xffff)); f[2 * j + 1] = bf2f((bf16_t)(r[j] >> 16)); }
-}
-
 // one wave per row; 4 rows per 256-thread block; NC = 16-byte chunks per lane (compile time)
 template <int NC>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ gamma,
@@ -198,10 +193,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
 #pragma unroll
           for (int j = 0; j < 8; ++j) o[j] += rv[j];
         }
-        u32x4 ov;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ov[j] = pack_bf2(o[2 * j], o[2 * j + 1]);
-        *reinterpret_cast<u32x4*>(dxr + ch * 8) = ov;
+        *reinterpret_cast<u32x4*>(dxr + ch * 8) = pack8(o);
       }
     }
   }
@@ -318,10 +310,7 @@ __global__ __launch_bounds__(TPB) void ln_bwd_wide_kernel(const bf16_t* __restri
 #pragma unroll
           for (int j = 0; j < 8; ++j) o[j] += rv[j];
         }
-        u32x4 ov;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ov[j] = pack_bf2(o[2 * j], o[2 * j + 1]);
-        *reinterpret_cast<u32x4*>(dx + (size_t)row * D + ch * 8) = ov;
+        *reinterpret_cast<u32x4*>(dx + (size_t)row * D + ch * 8) = pack8(o);
       }
     }
 #pragma unroll
@@ -340,6 +329,33 @@ __global__ __launch_bounds__(TPB) void ln_bwd_wide_kernel(const bf16_t* __restri
   }
 }
 
+// ---- what the two-stage sums of this file share (LayerNorm dgamma / dbeta, the column sums, batch_sum) -----------------
+// stage 2, one of the eight row-lanes ty of a block: the sum of src[p * step] over p = ty, ty + 8, .. < n.
+// eight partial rows in flight per thread (one dependent add chain per row kept the launch at 0.5 TB/s: 100 us for
+// 50 MB at the interm_1b shape); fixed order: the eight chains, then their tree
+template <class S>
+__device__ __forceinline__ float sum_parts8(const float* src, S step, int n, int ty) {
+  float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int p = ty;
+  for (; p + 56 < n; p += 64) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] += src[(size_t)(p + 8 * k) * step];
+  }
+  for (int k = 0; p < n; p += 8, ++k) a[k] += src[(size_t)p * step];
+  return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+}
+// dst[i] = t + beta * dst[i] into an fp32 or a bf16 sink (beta = 0: dst is not read)
+template <class I>
+__device__ __forceinline__ void store_beta(void* dst, int fp32, I i, float t, float beta) {
+  if (fp32) {
+    float* o = (float*)dst + i;
+    *o = t + (beta != 0.f ? beta * *o : 0.f);
+  } else {
+    bf16_t* o = (bf16_t*)dst + i;
+    *o = f2bf(t + (beta != 0.f ? beta * bf2f(*o) : 0.f));
+  }
+}
+
 // out[which][col] = beta*out + sum_p part[p][which][col]; 32 columns x 8 partial-groups per block
 __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* __restrict__ part, int nblk, int D,
                                                             void* dgamma, void* dbeta, int fp32, float beta) {
@@ -349,18 +365,7 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* __restr
   float s = 0.f;
   if (e < 2 * D) {
     const int which = e / D, col = e - which * D;
-    // eight partial rows in flight per thread (one dependent add chain per row kept the launch at 0.5 TB/s: 100 us for
-    // 50 MB at the interm_1b shape); fixed order: the eight chains, then their tree
-    const float* src = part + (size_t)which * D + col;
-    const size_t step = (size_t)2 * D;
-    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int p = ty;
-    for (; p + 56 < nblk; p += 64) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) a[k] += src[(size_t)(p + 8 * k) * step];
-    }
-    for (int k = 0; p < nblk; p += 8, ++k) a[k] += src[(size_t)p * step];
-    s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+    s = sum_parts8(part + (size_t)which * D + col, (size_t)2 * D, nblk, ty);
   }
   red[ty][tx] = s;
   __syncthreads();
@@ -369,14 +374,7 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* __restr
 #pragma unroll
     for (int k = 0; k < 8; ++k) t += red[k][tx];
     const int which = e / D, col = e - which * D;
-    void* dst = which ? dbeta : dgamma;
-    if (fp32) {
-      float* o = (float*)dst + col;
-      *o = t + (beta != 0.f ? beta * *o : 0.f);
-    } else {
-      bf16_t* o = (bf16_t*)dst + col;
-      *o = f2bf(t + (beta != 0.f ? beta * bf2f(*o) : 0.f));
-    }
+    store_beta(which ? dbeta : dgamma, fp32, col, t, beta);
   }
 }
 
@@ -393,72 +391,54 @@ __global__ __launch_bounds__(256) void post_reduce_kernel(const bf16_t* __restri
     const int64_t idx = ch * 8;
     const int m = (int)(idx / N);
     const int n = (int)(idx - (int64_t)m * N);
-    const u32x4 v = *reinterpret_cast<const u32x4*>(x + idx);
-    float f[8];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { f[2 * j] = bf2f((bf16_t)(v[j] & 0xffff)); f[2 * j + 1] = bf2f((bf16_t)(v[j] >> 16)); }
+    float f[8], t[8];
+    unpack8(*reinterpret_cast<const u32x4*>(x + idx), f);
     if (addend) {
       const int rm = res_mod > 0 ? (m % res_mod) : m;
-      const u32x4 a = *reinterpret_cast<const u32x4*>(addend + (size_t)rm * N + n);
+      unpack8(*reinterpret_cast<const u32x4*>(addend + (size_t)rm * N + n), t);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { f[2 * j] += bf2f((bf16_t)(a[j] & 0xffff)); f[2 * j + 1] += bf2f((bf16_t)(a[j] >> 16)); }
+      for (int j = 0; j < 8; ++j) f[j] += t[j];
     }
-    if (thr) {
-      const uint64_t sd = seed ^ o2_seed_salt;
-      const uint32_t h0 = o2_hash64(sd, (uint64_t)idx >> 2), h1 = o2_hash64(sd, ((uint64_t)idx >> 2) + 1);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        f[j] = (((h0 >> (8 * j)) & 0xffu) >= thr) ? f[j] * dscale : 0.f;
-        f[4 + j] = (((h1 >> (8 * j)) & 0xffu) >= thr) ? f[4 + j] * dscale : 0.f;
-      }
-    }
+    if (thr) o2_drop8(f, seed ^ o2_seed_salt, idx, thr, dscale);
     if (rowscale) {
       const float s = rowscale[m / rows_per_scale];
 #pragma unroll
       for (int j = 0; j < 8; ++j) f[j] *= s;
     }
     if (residual) {
-      const u32x4 r = *reinterpret_cast<const u32x4*>(residual + idx);
+      unpack8(*reinterpret_cast<const u32x4*>(residual + idx), t);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { f[2 * j] += bf2f((bf16_t)(r[j] & 0xffff)); f[2 * j + 1] += bf2f((bf16_t)(r[j] >> 16)); }
+      for (int j = 0; j < 8; ++j) f[j] += t[j];
     }
-    u32x4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = pack_bf2(f[2 * j], f[2 * j + 1]);
-    *reinterpret_cast<u32x4*>(y + idx) = o;
+    *reinterpret_cast<u32x4*>(y + idx) = pack8(f);
   }
 }
 
 // ---- dropout backward ---------------------------------------------------------------------
+// dym = rowscale[m / rows_per_scale] * dropout(dy) on the eight values of row m from flat index idx (both optional), stored and
+// returned as packed: the one row transform of dropout_bwd_kernel and of its twin with the fused column sums
+__device__ __forceinline__ u32x4 dropout_bwd8(const bf16_t* __restrict__ dy, bf16_t* __restrict__ dym, int64_t idx, int m,
+                                              unsigned thr, float dscale, uint64_t seed,
+                                              const float* __restrict__ rowscale, int rows_per_scale) {
+  float f[8];
+  unpack8(*reinterpret_cast<const u32x4*>(dy + idx), f);
+  if (thr) o2_drop8(f, seed ^ o2_seed_salt, idx, thr, dscale);
+  if (rowscale) {
+    const float s = rowscale[m / rows_per_scale];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] *= s;
+  }
+  const u32x4 o = pack8(f);
+  *reinterpret_cast<u32x4*>(dym + idx) = o;
+  return o;
+}
 __global__ __launch_bounds__(256) void dropout_bwd_kernel(const bf16_t* __restrict__ dy, bf16_t* __restrict__ dym,
                                                           int M, int N, unsigned thr, float dscale, uint64_t seed,
                                                           const float* __restrict__ rowscale, int rows_per_scale) {
   const int64_t nch = (int64_t)M * N / 8;
   for (int64_t ch = (int64_t)blockIdx.x * 256 + threadIdx.x; ch < nch; ch += (int64_t)gridDim.x * 256) {
     const int64_t idx = ch * 8;
-    const int m = (int)(idx / N);
-    const u32x4 v = *reinterpret_cast<const u32x4*>(dy + idx);
-    float f[8];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { f[2 * j] = bf2f((bf16_t)(v[j] & 0xffff)); f[2 * j + 1] = bf2f((bf16_t)(v[j] >> 16)); }
-    if (thr) {
-      const uint64_t sd = seed ^ o2_seed_salt;
-      const uint32_t h0 = o2_hash64(sd, (uint64_t)idx >> 2), h1 = o2_hash64(sd, ((uint64_t)idx >> 2) + 1);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        f[j] = (((h0 >> (8 * j)) & 0xffu) >= thr) ? f[j] * dscale : 0.f;
-        f[4 + j] = (((h1 >> (8 * j)) & 0xffu) >= thr) ? f[4 + j] * dscale : 0.f;
-      }
-    }
-    if (rowscale) {
-      const float s = rowscale[m / rows_per_scale];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] *= s;
-    }
-    u32x4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = pack_bf2(f[2 * j], f[2 * j + 1]);
-    *reinterpret_cast<u32x4*>(dym + idx) = o;
+    dropout_bwd8(dy, dym, idx, (int)(idx / N), thr, dscale, seed, rowscale, rows_per_scale);
   }
 }
 
@@ -467,10 +447,26 @@ __global__ __launch_bounds__(256) void dropout_bwd_kernel(const bf16_t* __restri
 // were 128 workgroups walking 16 rows each one after the other -- half the CUs, latency-bound; 512 workgroups of 4 rows now).
 // One function decides for the workspace query and both launchers.
 static inline int cs_rows(int M) { return M >= 32768 ? 128 : 32; }
+// stage 1, the block's tail: the eight row-lanes' sums acc[8] of the columns c0 .. c0 + 7 go through LDS, row-lane 0 adds them in
+// order 0 .. 7 and stores the block's partial sums.  Every thread of the block calls it (a barrier inside).
+__device__ __forceinline__ void colsum_store_part(const float* acc, float* __restrict__ part, int N, int c0, int tx, int ty) {
+  __shared__ float red[8][32][9];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) red[ty][tx][j] = acc[j];
+  __syncthreads();
+  if (ty == 0 && c0 < N) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float t = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) t += red[k][tx][j];
+      part[(size_t)blockIdx.y * N + c0 + j] = t;
+    }
+  }
+}
 template <bool FP32>
 __global__ __launch_bounds__(256) void colsum_part_kernel(const void* __restrict__ xv, int M, int N, int ldx,
                                                           float* __restrict__ part, int rpp) {
-  __shared__ float red[8][32][9];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int c0 = (blockIdx.x * 32 + tx) * 8;
   const int r0 = blockIdx.y * rpp;
@@ -495,72 +491,31 @@ __global__ __launch_bounds__(256) void colsum_part_kernel(const void* __restrict
       }
     }
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) red[ty][tx][j] = acc[j];
-  __syncthreads();
-  if (ty == 0 && c0 < N) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float t = 0.f;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) t += red[k][tx][j];
-      part[(size_t)blockIdx.y * N + c0 + j] = t;
-    }
-  }
+  colsum_store_part(acc, part, N, c0, tx, ty);
 }
 // dropout / DropPath backward FUSED with the column sums of its result (the bias gradient of the Linear whose output
 // gradient this is): the same [128 rows x 256 columns] blocks, thread mapping and summation order as colsum_part_kernel, so
-// the partials -- and the bias gradient -- are bit-identical to dropout_bwd + colsum, without re-reading dym from HBM.
+// the partials -- and the bias gradient -- are bit-identical to dropout_bwd + colsum, without re-reading dym from HBM.  The row
+// transform (dropout_bwd8) and the block's tail (colsum_store_part) ARE the two kernels' code.
 __global__ __launch_bounds__(256) void dropout_bwd_colsum_kernel(const bf16_t* __restrict__ dy, bf16_t* __restrict__ dym,
                                                                  int M, int N, unsigned thr, float dscale, uint64_t seed,
                                                                  const float* __restrict__ rowscale, int rows_per_scale,
                                                                  float* __restrict__ part, int rpp) {
-  __shared__ float red[8][32][9];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int c0 = (blockIdx.x * 32 + tx) * 8;
   const int r0 = blockIdx.y * rpp;
   const int r1 = r0 + rpp < M ? r0 + rpp : M;
-  const uint64_t sd = seed ^ o2_seed_salt;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (c0 < N) {
     for (int r = r0 + ty; r < r1; r += 8) {
-      const int64_t idx = (int64_t)r * N + c0;
       float f[8];
-      unpack8(*reinterpret_cast<const u32x4*>(dy + idx), f);
-      if (thr) {
-        const uint32_t h0 = o2_hash64(sd, (uint64_t)idx >> 2), h1 = o2_hash64(sd, ((uint64_t)idx >> 2) + 1);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          f[j] = (((h0 >> (8 * j)) & 0xffu) >= thr) ? f[j] * dscale : 0.f;
-          f[4 + j] = (((h1 >> (8 * j)) & 0xffu) >= thr) ? f[4 + j] * dscale : 0.f;
-        }
-      }
-      if (rowscale) {
-        const float sc = rowscale[r / rows_per_scale];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] *= sc;
-      }
-      u32x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = pack_bf2(f[2 * j], f[2 * j + 1]);
-      *reinterpret_cast<u32x4*>(dym + idx) = o;
-      unpack8(o, f);                                   // the sum is over the ROUNDED values (what colsum would read back)
+      // the sum is over the ROUNDED values (what colsum would read back)
+      unpack8(dropout_bwd8(dy, dym, (int64_t)r * N + c0, r, thr, dscale, seed, rowscale, rows_per_scale), f);
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[j] += f[j];
     }
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) red[ty][tx][j] = acc[j];
-  __syncthreads();
-  if (ty == 0 && c0 < N) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float t = 0.f;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) t += red[k][tx][j];
-      part[(size_t)blockIdx.y * N + c0 + j] = t;
-    }
-  }
+  colsum_store_part(acc, part, N, c0, tx, ty);
 }
 __global__ __launch_bounds__(256) void colsum_reduce_kernel(const float* __restrict__ part, int P, int N, void* out,
                                                             int out_fp32, float beta) {
@@ -568,30 +523,14 @@ __global__ __launch_bounds__(256) void colsum_reduce_kernel(const float* __restr
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int col = blockIdx.x * 32 + tx;
   float s = 0.f;
-  if (col < N) {
-    const float* src = part + col;           // eight partial rows in flight per thread, fixed order (see ln_bwd_reduce_kernel)
-    float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    int p = ty;
-    for (; p + 56 < P; p += 64) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) a[k] += src[(size_t)(p + 8 * k) * N];
-    }
-    for (int k = 0; p < P; p += 8, ++k) a[k] += src[(size_t)p * N];
-    s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-  }
+  if (col < N) s = sum_parts8(part + col, N, P, ty);
   red[ty][tx] = s;
   __syncthreads();
   if (ty == 0 && col < N) {
     float t = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) t += red[k][tx];
-    if (out_fp32) {
-      float* o = (float*)out + col;
-      *o = t + (beta != 0.f ? beta * *o : 0.f);
-    } else {
-      bf16_t* o = (bf16_t*)out + col;
-      *o = f2bf(t + (beta != 0.f ? beta * bf2f(*o) : 0.f));
-    }
+    store_beta(out, out_fp32, col, t, beta);
   }
 }
 
@@ -600,13 +539,7 @@ __global__ __launch_bounds__(256) void batch_sum_kernel(const bf16_t* __restrict
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     float s = 0.f;
     for (int b = 0; b < B; ++b) s += bf2f(x[(size_t)b * n + i]);
-    if (out_fp32) {
-      float* o = (float*)out + i;
-      *o = s + (beta != 0.f ? beta * *o : 0.f);
-    } else {
-      bf16_t* o = (bf16_t*)out + i;
-      *o = f2bf(s + (beta != 0.f ? beta * bf2f(*o) : 0.f));
-    }
+    store_beta(out, out_fp32, i, s, beta);
   }
 }
 
@@ -724,36 +657,33 @@ __global__ void droppath_scales_kernel(float* __restrict__ out, int B, float p, 
   out[b] = (u >= p) ? 1.0f / (1.0f - p) : 0.f;
 }
 
-inline int grid_for(int64_t work_items, int per_block) {
-  int64_t g = (work_items + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  if (g > 4096) g = 4096;
-  return (int)g;
+// the one-wave-per-row kernels (ln_fwd_kernel, ln_bwd_kernel) are compiled for 1, 2, 4, 6, 8 and 16 chunks per lane:
+// ln_chunks(D) is the smallest of them that holds a row of D bf16, ln_with_chunks(nc, f) calls f(o2_int<nc>)
+inline int ln_chunks(int D) {
+  const int nc = (D / 8 + 63) / 64;
+  return nc <= 1 ? 1 : nc <= 2 ? 2 : nc <= 4 ? 4 : nc <= 6 ? 6 : nc <= 8 ? 8 : 16;
+}
+template <class F> inline void ln_with_chunks(int nc, F&& f) {
+  switch (nc) {
+    case 1: f(o2_int<1>{}); break;
+    case 2: f(o2_int<2>{}); break;
+    case 4: f(o2_int<4>{}); break;
+    case 6: f(o2_int<6>{}); break;
+    case 8: f(o2_int<8>{}); break;
+    default: f(o2_int<16>{});
+  }
 }
 
 }  // namespace
-
-#define LN_DISPATCH(NCV, CALL)            \
-  do {                                    \
-    if (NCV <= 1) { CALL(1); }            \
-    else if (NCV <= 2) { CALL(2); }       \
-    else if (NCV <= 4) { CALL(4); }       \
-    else if (NCV <= 6) { CALL(6); }       \
-    else if (NCV <= 8) { CALL(8); }       \
-    else { CALL(16); }                    \
-  } while (0)
 
 extern "C" int orbit2_layernorm_fwd_ld(const void* x, const void* gamma, const void* beta, void* y, float* mean,
                                        float* rstd, int rows, int D, int ldy, float eps, void* stream) {
   if (!x || !gamma || !beta || !y || !mean || !rstd || rows <= 0 || D <= 0 || (D & 7) || D > LN_MAXD || ldy < D || (ldy & 7))
     return O2_ERR_ARG;
-  const int nc = (D / 8 + 63) / 64;
-#define CALL(N)                                                                                              \
-  hipLaunchKernelGGL(ln_fwd_kernel<N>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream,              \
-                     (const bf16_t*)x, (const bf16_t*)gamma, (const bf16_t*)beta, (bf16_t*)y, mean, rstd,  \
-                     rows, D, eps, ldy)
-  LN_DISPATCH(nc, CALL);
-#undef CALL
+  ln_with_chunks(ln_chunks(D), [&](auto NC) {
+    hipLaunchKernelGGL(ln_fwd_kernel<NC>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                       (const bf16_t*)gamma, (const bf16_t*)beta, (bf16_t*)y, mean, rstd, rows, D, eps, ldy);
+  });
   O2_CHECK_LAUNCH();
   return O2_OK;
 }
@@ -762,24 +692,54 @@ extern "C" int orbit2_layernorm_fwd_f32(const void* x, const void* gamma, const 
                                         float* rstd, int rows, int D, int ldy, float eps, void* stream) {
   if (!x || !gamma || !beta || !y || rows <= 0 || D <= 0 || (D & 3) || D > LN_MAXD || ldy < D || (ldy & 3)) return O2_ERR_ARG;
   const int nc = (D / 4 + 63) / 64;                                  // float4 chunks per lane: up to 32 at D = 8192
-#define CALL(N)                                                                                              \
-  hipLaunchKernelGGL(ln_fwd_f32_kernel<N>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream,          \
-                     (const float*)x, (const float*)gamma, (const float*)beta, (float*)y, mean, rstd, rows,  \
-                     D, eps, ldy)
-  if (nc <= 2) { CALL(2); } else if (nc <= 4) { CALL(4); } else if (nc <= 8) { CALL(8); } else if (nc <= 16) { CALL(16); } else { CALL(32); }
-#undef CALL
+  auto call = [&](auto NC) {
+    hipLaunchKernelGGL(ln_fwd_f32_kernel<NC>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+                       (const float*)gamma, (const float*)beta, (float*)y, mean, rstd, rows, D, eps, ldy);
+  };
+  if (nc <= 2) call(o2_int<2>{}); else if (nc <= 4) call(o2_int<4>{}); else if (nc <= 8) call(o2_int<8>{}); else if (nc <= 16) call(o2_int<16>{}); else call(o2_int<32>{});
   O2_CHECK_LAUNCH();
   return O2_OK;
 }
 
-static inline int ln_bwd_nparts(int rows) { return ((rows + 4 * LN_RPW - 1) / (4 * LN_RPW)) * 4; }
+// ---- LayerNorm backward: which kernel on which partition.  ln_bwd_plan decides everything and launches nothing ------------
 // few rows (the 32 x 64-grid presets): LN_FEW_RPB rows per workgroup of the row-shared form -- 4096 rows at 16 per workgroup were
 // 256 workgroups of two waves walking their rows one global-load latency after the other (18 us at D = 1024, a quarter of it
 // bandwidth); 4 per workgroup put four workgroups on every CU
 constexpr int LN_FEW_RPB = 4;
-static inline int ln_bwd_nparts_few(int rows) { return (rows + LN_FEW_RPB - 1) / LN_FEW_RPB; }
+constexpr int LN_WAVE_RPB = 4 * LN_RPW;      // the per-wave form: four waves of LN_RPW rows each
+static inline int ln_shared_rpb(int rows) { return rows < 32768 ? LN_FEW_RPB : 64; }
+static inline int ln_blocks(int rows, int rpb) { return (rows + rpb - 1) / rpb; }
+struct LnBwdPlan {
+  bool shared;       // ln_bwd_wide_kernel<nc, tpb, rpb, exact>; else ln_bwd_kernel<nc> (tpb = 256, rpb = LN_WAVE_RPB)
+  int nc, tpb, rpb;  // 16-byte chunks per thread, threads and rows per block
+  bool exact;        // D == 8 nc tpb: no chunk of the row-shared form is ever out of range
+  int grid;          // blocks = partial dgamma / dbeta rows in the workspace (one per block)
+  size_t lds;        // dynamic LDS (the per-wave form's [2][D] exchange)
+};
+static LnBwdPlan ln_bwd_plan(int rows, int D) {
+  LnBwdPlan p = {};
+  // row-shared form for the model widths (8m / 117m / 1b / 10b); 64 rows per block, LN_FEW_RPB when there are few rows (the
+  // small grids: 4096 rows would otherwise occupy 64 CUs)
+  if (D == 3072) { p.shared = true; p.nc = 3; p.tpb = 128; }          // 363 vs 414 us (per-wave form) at 65536 rows
+  else if (D == 1024) { p.shared = true; p.nc = 1; p.tpb = 128; }
+  else if (D == 256) { p.shared = true; p.nc = 1; p.tpb = 64; }
+  else if (D > 4096) { p.shared = true; p.nc = 4; p.tpb = 256; }      // the per-wave form spills (1127 -> 115 us at D = 8192)
+  if (p.shared) {
+    p.rpb = ln_shared_rpb(rows);
+    p.exact = D == 8 * p.nc * p.tpb;
+  } else {                                                            // other widths: per-wave form, its partition
+    p.nc = ln_chunks(D);
+    p.tpb = 256;
+    p.rpb = LN_WAVE_RPB;
+    p.lds = 2 * D * sizeof(float);
+  }
+  p.grid = ln_blocks(rows, p.rpb);
+  return p;
+}
+// The workspace holds 4 partial rows per 64 input rows, or the row-shared form's one per LN_FEW_RPB when that is more: enough
+// for every form at these rows, whatever the width.
 extern "C" int orbit2_layernorm_bwd_ws_floats(int rows, int D) {
-  const int a = ln_bwd_nparts(rows), b = rows < 32768 ? ln_bwd_nparts_few(rows) : 0;
+  const int a = 4 * ln_blocks(rows, LN_WAVE_RPB), b = ln_blocks(rows, ln_shared_rpb(rows));
   return (a > b ? a : b) * 2 * D;
 }
 
@@ -789,53 +749,26 @@ extern "C" int orbit2_layernorm_bwd(const void* dy, const void* x, const void* g
                                     void* stream) {
   if (!dy || !x || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || !ws) return O2_ERR_ARG;
   if (rows <= 0 || (D & 7) || D > LN_MAXD) return O2_ERR_ARG;
-  const int nparts = ln_bwd_nparts(rows);
   if (ws_floats < orbit2_layernorm_bwd_ws_floats(rows, D)) return O2_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int nc = (D / 8 + 63) / 64;
-  // row-shared form for the model widths (8m / 117m / 1b / 10b); 64 rows per block, LN_FEW_RPB when there are few rows (the
-  // small grids: 4096 rows would otherwise occupy 64 CUs).  The workspace holds 4 partial rows per 64 input rows.
-  const bool few = rows < 32768;
-  const int npart_used = few ? ln_bwd_nparts_few(rows) : nparts / 4;
-#define WIDE_(NCW, TPB, EX)                                                                                         \
-  do {                                                                                                              \
-    if (few)                                                                                                        \
-      hipLaunchKernelGGL((ln_bwd_wide_kernel<NCW, TPB, LN_FEW_RPB, EX>), dim3(npart_used), dim3(TPB), 0, s, (const bf16_t*)dy, \
-                         (const bf16_t*)x, (const bf16_t*)gamma, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx, ws,  \
-                         rows, D);                                                                                  \
-    else                                                                                                            \
-      hipLaunchKernelGGL((ln_bwd_wide_kernel<NCW, TPB, 64, EX>), dim3(npart_used), dim3(TPB), 0, s, (const bf16_t*)dy,  \
-                         (const bf16_t*)x, (const bf16_t*)gamma, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx, ws,  \
-                         rows, D);                                                                                  \
-  } while (0)
-#define WIDE(NCW, TPB)                                                                                              \
-  do {                                                                                                              \
-    if (D == 8 * (NCW) * (TPB)) WIDE_(NCW, TPB, true);                                                              \
-    else WIDE_(NCW, TPB, false);                                                                                    \
-  } while (0)
-  if (D == 3072) WIDE(3, 128);          // 363 vs 414 us (per-wave form) at 65536 rows
-  else if (D == 1024) WIDE(1, 128);
-  else if (D == 256) WIDE(1, 64);
-  else if (nc > 8) WIDE(4, 256);        // D in (4096, 8192]: the per-wave form spills (1127 -> 115 us at D = 8192)
-  else if (few) {
-    // other widths with few rows: per-wave form, its partition (64 rows per block)
-#define CALL(N)                                                                                                  \
-  hipLaunchKernelGGL(ln_bwd_kernel<N>, dim3(nparts / 4), dim3(256), 2 * D * sizeof(float), s, (const bf16_t*)dy, (const bf16_t*)x, \
-                     (const bf16_t*)gamma, mean, rstd, (const bf16_t*)dres, (bf16_t*)dx, ws, rows, D)
-    LN_DISPATCH(nc, CALL);
-    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((2 * D + 31) / 32), dim3(256), 0, s, ws, nparts / 4, D, dgamma, dbeta,
-                       grads_fp32, beta_acc);
-    O2_CHECK_LAUNCH();
-    return O2_OK;
-  } else {
-    LN_DISPATCH(nc, CALL);
-#undef CALL
-  }
-#undef WIDE
-#undef WIDE_
+  const LnBwdPlan p = ln_bwd_plan(rows, D);
+#define O2_LN_BWD_LAUNCH(KERN)                                                                                              \
+  hipLaunchKernelGGL(KERN, dim3(p.grid), dim3(p.tpb), p.lds, s, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)gamma, mean, \
+                     rstd, (const bf16_t*)dres, (bf16_t*)dx, ws, rows, D)
+  auto shared = [&](auto NCW_, auto TPB_) {
+    constexpr int NCW = NCW_, TPB = TPB_;
+    o2_with_flags([&](auto FEW, auto EX) { O2_LN_BWD_LAUNCH((ln_bwd_wide_kernel<NCW, TPB, FEW ? LN_FEW_RPB : 64, EX>)); },
+                  p.rpb == LN_FEW_RPB, p.exact);
+  };
+  if (!p.shared) ln_with_chunks(p.nc, [&](auto NC) { O2_LN_BWD_LAUNCH(ln_bwd_kernel<NC>); });
+  else if (p.nc == 3) shared(o2_int<3>{}, o2_int<128>{});
+  else if (p.nc == 4) shared(o2_int<4>{}, o2_int<256>{});
+  else if (p.tpb == 128) shared(o2_int<1>{}, o2_int<128>{});
+  else shared(o2_int<1>{}, o2_int<64>{});
+#undef O2_LN_BWD_LAUNCH
   O2_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((2 * D + 31) / 32), dim3(256), 0, s, ws, npart_used, D, dgamma, dbeta,
-                     grads_fp32, beta_acc);
+  hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((2 * D + 31) / 32), dim3(256), 0, s, ws, p.grid, D, dgamma, dbeta, grads_fp32,
+                     beta_acc);
   O2_CHECK_LAUNCH();
   return O2_OK;
 }
@@ -875,8 +808,8 @@ extern "C" int orbit2_colsum(const void* x, int x_fp32, int M, int N, int ldx, v
   hipStream_t s = (hipStream_t)stream;
   if ((N & 7) || (ldx & 7)) return O2_ERR_ARG;
   dim3 g1((N + 255) / 256, P);
-  if (x_fp32) hipLaunchKernelGGL(colsum_part_kernel<true>, g1, dim3(256), 0, s, x, M, N, ldx, ws, rpp);
-  else hipLaunchKernelGGL(colsum_part_kernel<false>, g1, dim3(256), 0, s, x, M, N, ldx, ws, rpp);
+  o2_with_flags([&](auto FP32) { hipLaunchKernelGGL(colsum_part_kernel<FP32>, g1, dim3(256), 0, s, x, M, N, ldx, ws, rpp); },
+                x_fp32 != 0);
   O2_CHECK_LAUNCH();
   hipLaunchKernelGGL(colsum_reduce_kernel, dim3((N + 31) / 32), dim3(256), 0, s, ws, P, N, out, out_fp32, beta);
   O2_CHECK_LAUNCH();
@@ -941,12 +874,10 @@ extern "C" int orbit2_adamw(float* p, float* m, float* v, const void* g, int g_f
   const float rsbc2 = 1.0f / sqrtf(bc2);
   dim3 grid(grid_for((n + 3) / 4, 256)), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (g_fp32)
-    hipLaunchKernelGGL(adamw_kernel<true>, grid, block, 0, s, p, m, v, g, (bf16_t*)p16, n, lr, beta1, beta2, eps, wd,
-                       bc1, rsbc2, grad_scale, found_inf);
-  else
-    hipLaunchKernelGGL(adamw_kernel<false>, grid, block, 0, s, p, m, v, g, (bf16_t*)p16, n, lr, beta1, beta2, eps, wd,
-                       bc1, rsbc2, grad_scale, found_inf);
+  o2_with_flags([&](auto GFP32) {
+    hipLaunchKernelGGL(adamw_kernel<GFP32>, grid, block, 0, s, p, m, v, g, (bf16_t*)p16, n, lr, beta1, beta2, eps, wd, bc1,
+                       rsbc2, grad_scale, found_inf);
+  }, g_fp32 != 0);
   O2_CHECK_LAUNCH();
   return O2_OK;
 }
@@ -954,8 +885,8 @@ extern "C" int orbit2_adamw(float* p, float* m, float* v, const void* g, int g_f
 extern "C" int orbit2_check_finite(const void* g, int g_fp32, int64_t n, float* found_inf, void* stream) {
   if (!g || !found_inf || n <= 0) return O2_ERR_ARG;
   dim3 grid(grid_for(n, 256 * 8)), block(256);
-  if (g_fp32) hipLaunchKernelGGL(check_finite_kernel<true>, grid, block, 0, (hipStream_t)stream, g, n, found_inf);
-  else hipLaunchKernelGGL(check_finite_kernel<false>, grid, block, 0, (hipStream_t)stream, g, n, found_inf);
+  o2_with_flags([&](auto GFP32) { hipLaunchKernelGGL(check_finite_kernel<GFP32>, grid, block, 0, (hipStream_t)stream, g, n, found_inf); },
+                g_fp32 != 0);
   O2_CHECK_LAUNCH();
   return O2_OK;
 }

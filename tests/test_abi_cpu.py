@@ -172,3 +172,15 @@ def test_gemm_colsum_dispatch_is_host_logic():
         assert lib.orbit2_gemm_bf16_colsum_rows(ctypes.byref(bad)) == 0
         bad.colsum_ws = 0x60000
         assert lib.orbit2_gemm_bf16(ctypes.byref(bad), None, 0, None, -1, None) == -3
+
+
+def test_row_kernel_workspace_queries():
+    """orbit2_layernorm_bwd_ws_floats and orbit2_colsum_ws_floats are host arithmetic over the kernels' partitions: the values of
+    max(4 ceil(rows / 64), rows < 32768 ? ceil(rows / 4) : 0) * 2 D   and   ceil(M / (M >= 32768 ? 128 : 32)) * N"""
+    from climate_learn import _hip
+    lib = _hip.lib()
+    for (rows, D), want in (((200, 64), 6400), ((4096, 1024), 2097152), ((33000, 3072), 12681216), ((131072, 3072), 50331648),
+                            ((16384, 8192), 67108864)):
+        assert lib.orbit2_layernorm_bwd_ws_floats(rows, D) == want, (rows, D)
+    for (M, N), want in (((4096, 1024), 131072), ((131072, 12288), 12582912)):
+        assert lib.orbit2_colsum_ws_floats(M, N) == want, (M, N)
