@@ -335,7 +335,9 @@ int orbit2_clamp_channel_bwd(const float* img_clamped, float* dimg, int B, int C
 
 /* ---- losses (metrics/functional.py:59-202): kind 0 = mse, 1 = bayesian_tv, 2 = image_gradient ------
  * pred fp32 [B,C,H,W]; target fp32 [B,C,Ht,Wt] (top-left crop used); lat_w fp32 [H] or NULL;
- * chan_w fp32 [C] or NULL.  out: fp32 [C+1] (per-channel means, aggregate mean). ws fp32 >= 2*B*C*64 */
+ * chan_w fp32 [C] or NULL.  out: fp32 [C+1] (per-channel means, aggregate mean). ws fp32 >= 2*B*C*ORBIT2_LOSS_BLOCKS */
+/* workgroups per (b, c) plane of orbit2_loss_fwd and orbit2_masked_loss_fwd; their partial sums are added in this order */
+#define ORBIT2_LOSS_BLOCKS 64
 int orbit2_loss_fwd(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* chan_w,
                     float* out, float* ws, int B, int C, int H, int W, int kind, void* stream);
 /* dpred = gscale[0] * d(aggregate)/dpred */
@@ -360,8 +362,8 @@ int orbit2_eval_moments(const float* pred, const float* target, int Ht, int Wt, 
  * orbit2_masked_loss_fwd: kind 0 = mse, 1 = bayesian_tv (a difference term of the prior counts only if both of its pixels are
  * valid); any other kind is O2_ERR_ARG.  With num_c = sum_{b,i,j} v w_i cw_c err and n_c = sum_{b,i,j} v:
  *   out[c] = num_c / n_c (0 if n_c == 0), out[C] = sum_c num_c / sum_c n_c (0 if nothing is valid); cnt[c] = n_c, cnt[C] = sum_c n_c.
- * out fp32 [C+1], cnt int64 [C+1] (counted as integers: exact), ws >= 2*B*C*64 four-byte words.  Fixed-order sums, no atomics:
- * two calls give the same bits.
+ * out fp32 [C+1], cnt int64 [C+1] (counted as integers: exact), ws >= 2*B*C*ORBIT2_LOSS_BLOCKS four-byte words.
+ * Fixed-order sums, no atomics: two calls give the same bits.
  * orbit2_masked_loss_bwd: dpred = gscale[0] * d(out[C])/dpred with the divisor cnt[C] read on the device; exactly 0.0 at every
  * invalid pixel, and everywhere when cnt[C] == 0.
  * orbit2_masked_moments: out[b][c][13] (double) = the twelve sums of orbit2_eval_moments over the valid pixels, then their number. */

@@ -1,9 +1,26 @@
 """ctypes binding of liborbit2_hip.so (C ABI in include/orbit2_hip.h).
 
-This is the ONLY compute backend of the package: there is no CPU or eager fallback.  Every wrapper
-checks that its operands are contiguous device tensors of the expected dtype and passes raw device
-pointers plus torch's current HIP stream across the ABI.  A missing library or a non-zero return
-code raises immediately."""
+This is the ONLY compute backend of the package: there is no CPU or eager fallback.  A missing library
+or a non-zero return code raises immediately.
+
+Every launch goes through ONE call path, `_call(name, *args)`.  It looks the entry up by the one name
+it is given, turns every tensor argument into its address through `_p`, appends torch's current HIP
+stream, and raises HipBackendError naming that entry on a non-zero code.  What it guarantees:
+  * `_p` is the only place an address is produced, and it refuses a tensor that is not on the device
+    (`_on_device`, the one predicate `_dev` and `_dev_rows` ask too): no host pointer crosses the ABI,
+    whatever a wrapper forgot;
+  * the stream is always the last argument and always the current one;
+  * the name in an error message is the entry that was called.
+ctypes adds, from PROTOTYPES, that the argument count and kinds are the header's.
+
+What a wrapper must do, since `_call` cannot: pass EVERY tensor its caller supplied through `_dev`
+(contiguous), `_dev_rows` (rows contiguous, any row pitch) or their `_opt` forms (None passes) with the
+dtype -- or tuple of dtypes -- the entry reads it as, and check the sizes the kernel relies on, BEFORE
+the call.  Tensors the wrapper allocated itself need no check.  It hands `_call` tensors, never
+addresses, and no stream.  The queries that launch nothing (`*_ws_floats`, `*_is_fixed_order`,
+`*_colsum_rows`, `orbit2_abi_version`) are plain `lib().entry(...)` calls.  Two wrappers that differ
+in a dtype share one body that takes it as a parameter; a constant of the header is mirrored once
+here and pinned by tests/test_abi_cpu.py."""
 from __future__ import annotations
 
 import contextlib
@@ -167,8 +184,18 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _on_device(t) -> bool:
+    """whether `t` lives in device memory: the one such test of the module (_p, _dev and _dev_rows ask it)"""
+    return t.is_cuda
+
+
 def _p(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
+    """the address of a device tensor (None: NULL) -- the one place a pointer that crosses the ABI is produced"""
+    if t is None:
+        return None
+    if not _on_device(t):
+        raise HipBackendError("a pointer operand must be a GPU tensor (HIP backend has no CPU path)")
+    return t.data_ptr()
 
 
 def _chk(rc: int, name: str):
@@ -176,17 +203,45 @@ def _chk(rc: int, name: str):
         raise HipBackendError("%s failed with code %d (-1 bad argument, -2 launch error, -3 unsupported)" % (name, rc))
 
 
+def _call(name: str, *args):
+    """the one call path of every launching entry (module docstring): tensors become addresses, the current stream goes last"""
+    _chk(getattr(lib(), name)(*[_p(a) if torch.is_tensor(a) else a for a in args], _stream()), name)
+
+
+def _reads(dtype, t) -> bool:
+    """whether an entry that reads `dtype` -- one dtype, or a tuple of those it takes -- reads t's"""
+    return t.dtype in dtype if isinstance(dtype, tuple) else t.dtype == dtype
+
+
 def _dev(t: torch.Tensor, dtype, name: str):
-    if not t.is_cuda:
+    """a contiguous device tensor of `dtype` (as in _reads)"""
+    if not _on_device(t):
         raise HipBackendError("%s must be a GPU tensor (HIP backend has no CPU path)" % name)
-    if t.dtype != dtype:
+    if not _reads(dtype, t):
         raise HipBackendError("%s must be %s, got %s" % (name, dtype, t.dtype))
     if not t.is_contiguous():
         raise HipBackendError("%s must be contiguous" % name)
     return t
 
 
+def _dev_rows(t: torch.Tensor, dtype, name: str):
+    """an operand handed over with an explicit leading dimension: rows contiguous, any row pitch"""
+    if t.dim() == 2 and t.stride(1) == 1 and _on_device(t) and _reads(dtype, t):
+        return t
+    return _dev(t, dtype, name)
+
+
+def _dev_opt(t, dtype, name):
+    return None if t is None else _dev(t, dtype, name)
+
+
+def _dev_rows_opt(t, dtype, name):
+    return None if t is None else _dev_rows(t, dtype, name)
+
+
 BF, F32 = torch.bfloat16, torch.float32
+I32 = torch.int32
+BF_F32 = (BF, F32)              # a gradient sink or a reduction's output: the entry takes a flag that says which
 
 
 # ---- tail queue (include/orbit2_hip.h: orbit2_gemm_bf16) ----------------------------------------------------------------------
@@ -222,7 +277,7 @@ def _sched_word(device) -> int:
         if slot >= _SCHED_SLOTS:
             raise HipBackendError("tail queue: more than %d streams asked for a counter word" % _SCHED_SLOTS)
         _sched_slots[key] = slot
-    return buf.data_ptr() + 4 * _SCHED_STRIDE * slot
+    return _p(buf) + 4 * _SCHED_STRIDE * slot
 
 
 def _tail_arg(tail_queue):
@@ -235,13 +290,6 @@ def _tail_arg(tail_queue):
     if int(tail_queue) <= 0:
         raise HipBackendError("tail_queue: True, or a positive number of tiles")
     return int(tail_queue)
-
-
-def _dev_rows(t: torch.Tensor, dtype, name: str):
-    """a GEMM operand / epilogue tensor handed over with an explicit leading dimension: rows contiguous, any row pitch"""
-    if t.dim() == 2 and t.stride(1) == 1 and t.is_cuda and t.dtype == dtype:
-        return t
-    return _dev(t, dtype, name)
 
 
 class KernelTimer:
@@ -282,9 +330,10 @@ def _timed(name, flops, nbytes=0.0):
 
 
 def _queue(tail, device):
-    """the (sched_ws, tail, stream) that end a GEMM or attention entry's arguments: the stream's counter word on `device` when a
-    tail queue is asked for (tail >= 0), NULL for a static call -- which so never allocates the counter buffer or claims a slot"""
-    return (_sched_word(device) if tail >= 0 else None), tail, _stream()
+    """the (sched_ws, tail) that end a GEMM or attention entry's arguments before the stream: the stream's counter word on `device`
+    when a tail queue is asked for (tail >= 0), NULL for a static call -- which so never allocates the counter buffer or claims a
+    slot"""
+    return (_sched_word(device) if tail >= 0 else None), tail
 
 
 # ------------------------------------------------------------------------------------------------
@@ -293,26 +342,26 @@ def _gemm_fill(a, A, B, out, M, N, K, lda, ldb, ldc, a_kc=True, b_kc=True, bias=
                res_first=False, beta=0.0, tile=0, colscale=None, save_dact=None, mul=None):
     for t, nm in ((A, "A"), (B, "B")):
         _dev_rows(t, BF, nm)
-    if out.dtype not in (BF, F32) or not out.is_cuda:
+    if out.dtype not in BF_F32 or not _on_device(out):
         raise HipBackendError("gemm out must be a bf16/fp32 GPU tensor")
-    a.A, a.B, a.C = A.data_ptr(), B.data_ptr(), out.data_ptr()
+    a.A, a.B, a.C = _p(A), _p(B), _p(out)
     a.M, a.N, a.K, a.lda, a.ldb, a.ldc = M, N, K, lda, ldb, ldc
     a.a_kc, a.b_kc = int(a_kc), int(b_kc)
-    a.bias = None if bias is None else _dev(bias, BF, "bias").data_ptr()
+    a.bias = _p(_dev_opt(bias, BF, "bias"))
     a.act = act
-    a.save_pre = None if save_pre is None else _dev_rows(save_pre, BF, "save_pre").data_ptr()      # row pitch = ldc
-    a.dgelu_pre = None if dgelu_pre is None else _dev_rows(dgelu_pre, BF, "dgelu_pre").data_ptr()  # row pitch = ldc
+    a.save_pre = _p(_dev_rows_opt(save_pre, BF, "save_pre"))            # row pitch = ldc
+    a.dgelu_pre = _p(_dev_rows_opt(dgelu_pre, BF, "dgelu_pre"))         # row pitch = ldc
     a.drop_p, a.seed = float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF
-    a.rowscale = None if rowscale is None else _dev(rowscale, F32, "rowscale").data_ptr()
+    a.rowscale = _p(_dev_opt(rowscale, F32, "rowscale"))
     a.rows_per_scale = rows_per_scale
-    a.residual = None if residual is None else _dev(residual, BF, "residual").data_ptr()
+    a.residual = _p(_dev_opt(residual, BF, "residual"))
     a.ldr, a.res_mod, a.res_first = ldr, res_mod, int(res_first)
     a.out_fp32 = int(out.dtype == F32)
     a.beta = float(beta)
     a.tile_hint = int(tile)
     a.colscale_n, a.colscale = (0, 1.0) if colscale is None else (int(colscale[0]), float(colscale[1]))
-    a.save_dact = None if save_dact is None else _dev_rows(save_dact, torch.int16, "save_dact").data_ptr()    # int16 q14, row pitch = ldc
-    a.mul = None if mul is None else _dev_rows(mul, torch.int16, "mul").data_ptr()                   # int16 q14, row pitch = ldc
+    a.save_dact = _p(_dev_rows_opt(save_dact, torch.int16, "save_dact"))    # int16 q14, row pitch = ldc
+    a.mul = _p(_dev_rows_opt(mul, torch.int16, "mul"))                      # int16 q14, row pitch = ldc
     a.colsum_ws = None
     return 2.0 * M * N * K, 2.0 * (M * K + N * K) + M * N * (4.0 if out.dtype == F32 else 2.0)
 
@@ -337,10 +386,9 @@ def gemm(A, B, out, M, N, K, lda, ldb, ldc, want_colsum=False, gate=None, rows_p
         rows = lib().orbit2_gemm_bf16_colsum_rows(C.byref(a))
         if rows > 0:
             parts = torch.empty(rows, N, dtype=F32, device=out.device)
-            a.colsum_ws = parts.data_ptr()
+            a.colsum_ws = _p(parts)
     with _timed("gemm_bf16", flops, nbytes):
-        _chk(lib().orbit2_gemm_bf16(C.byref(a), _p(gate), rows_per_gate if gate is not None else 0, *_queue(tail, out.device)),
-             "orbit2_gemm_bf16")
+        _call("orbit2_gemm_bf16", C.byref(a), gate, rows_per_gate if gate is not None else 0, *_queue(tail, out.device))
     return (out, parts) if want_colsum else out
 
 
@@ -351,19 +399,19 @@ def gemm_f32(A, B, out, M, N, K, lda, ldb, ldc, bias=None, act=0, residual=None,
     for t, nm in ((A, "A"), (B, "B"), (out, "out")):
         _dev_rows(t, F32, nm)
     a = GemmArgs()
-    a.A, a.B, a.C = A.data_ptr(), B.data_ptr(), out.data_ptr()
+    a.A, a.B, a.C = _p(A), _p(B), _p(out)
     a.M, a.N, a.K, a.lda, a.ldb, a.ldc = M, N, K, lda, ldb, ldc
     a.a_kc = a.b_kc = 1
-    a.bias = None if bias is None else _dev(bias, F32, "bias").data_ptr()
+    a.bias = _p(_dev_opt(bias, F32, "bias"))
     a.act = act
-    a.residual = None if residual is None else _dev_rows(residual, F32, "residual").data_ptr()
+    a.residual = _p(_dev_rows_opt(residual, F32, "residual"))
     a.ldr, a.res_mod, a.res_first = ldr, res_mod, int(res_first)
     a.out_fp32 = 1
     a.beta = float(beta)
     a.tile_hint = int(tile)
     a.colscale_n, a.colscale = (0, 1.0) if colscale is None else (int(colscale[0]), float(colscale[1]))
     with _timed("gemm_f32", 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N)):
-        _chk(lib().orbit2_gemm_f32(C.byref(a), _stream()), "orbit2_gemm_f32")
+        _call("orbit2_gemm_f32", C.byref(a))
     return out
 
 
@@ -389,14 +437,14 @@ def gemm_grouped(problems, tail_queue=None):
             vec, per = kg
             if per <= 0 or _dev(vec, F32, "kgate").numel() * per < K:
                 raise HipBackendError("gemm_grouped kgate needs one entry per k_per_gate rows of the contraction")
-            kgates[i], kper[i], gated = vec.data_ptr(), per, True
+            kgates[i], kper[i], gated = _p(vec), per, True
         f, b = _gemm_fill(arr[i], A, B, out, M, N, K, lda, ldb, ldc, **kw)
         flops += f
         nbytes += b
 
     with _timed("gemm_bf16", flops, nbytes):
-        _chk(lib().orbit2_gemm_bf16_grouped(arr, n, kgates if gated else None, kper if gated else None,
-                                            *_queue(tail, problems[0][2].device)), "orbit2_gemm_bf16_grouped")
+        _call("orbit2_gemm_bf16_grouped", arr, n, kgates if gated else None, kper if gated else None,
+              *_queue(tail, problems[0][2].device))
 
 
 def sgemm(A, B, out, M, N, K, lda, ldb, ldc, ta=False, tb=False, alpha=1.0, beta=0.0):
@@ -404,50 +452,47 @@ def sgemm(A, B, out, M, N, K, lda, ldb, ldc, ta=False, tb=False, alpha=1.0, beta
         _dev(t, F32, nm)
     n = lib().orbit2_sgemm_f32_ws_floats(M, N, K)
     ws = torch.empty(n, dtype=F32, device=out.device) if n else None
-    _chk(lib().orbit2_sgemm_f32_ws(_p(A), _p(B), _p(out), M, N, K, lda, ldb, ldc, int(ta), int(tb), alpha, beta, _p(ws), n,
-                                   _stream()), "orbit2_sgemm_f32_ws")
+    _call("orbit2_sgemm_f32_ws", A, B, out, M, N, K, lda, ldb, ldc, int(ta), int(tb), alpha, beta, ws, n)
     return out
+
+
+def _layernorm_fwd(dtype, x, gamma, beta, eps, out, stats):
+    """LayerNorm forward in `dtype` (BF: orbit2_layernorm_fwd_ld, F32: orbit2_layernorm_fwd_f32): (y, mean, rstd), the statistics
+    None unless `stats`"""
+    _dev(x, dtype, "x"); _dev(gamma, dtype, "gamma"); _dev(beta, dtype, "beta")
+    D = x.shape[-1]
+    rows = x.numel() // D
+    y = torch.empty_like(x) if out is None else _dev_rows(out, dtype, "out")
+    ldy = D if out is None else y.stride(0)
+    mean = torch.empty(rows, dtype=F32, device=x.device) if stats else None
+    rstd = torch.empty(rows, dtype=F32, device=x.device) if stats else None
+    _call("orbit2_layernorm_fwd_ld" if dtype == BF else "orbit2_layernorm_fwd_f32", x, gamma, beta, y, mean, rstd, rows, D, ldy, eps)
+    return y, mean, rstd
 
 
 def layernorm_fwd(x, gamma, beta, eps=1e-5, out=None):
     """out: optional [rows, D] bf16 destination with any row pitch (a view of a padded buffer: orbit2_layernorm_fwd_ld)"""
-    _dev(x, BF, "x"); _dev(gamma, BF, "gamma"); _dev(beta, BF, "beta")
-    D = x.shape[-1]
-    rows = x.numel() // D
-    y = torch.empty_like(x) if out is None else _dev_rows(out, BF, "out")
-    ldy = D if out is None else y.stride(0)
-    mean = torch.empty(rows, dtype=F32, device=x.device)
-    rstd = torch.empty(rows, dtype=F32, device=x.device)
-    _chk(lib().orbit2_layernorm_fwd_ld(_p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, D, ldy, eps,
-                                       _stream()), "orbit2_layernorm_fwd_ld")
-    return y, mean, rstd
+    return _layernorm_fwd(BF, x, gamma, beta, eps, out, True)
 
 
 def layernorm_fwd_f32(x, gamma, beta, eps=1e-5, out=None, stats=False):
     """fp32 LayerNorm (orbit2_layernorm_fwd_f32); returns y, or (y, mean, rstd) with stats=True"""
-    _dev(x, F32, "x"); _dev(gamma, F32, "gamma"); _dev(beta, F32, "beta")
-    D = x.shape[-1]
-    rows = x.numel() // D
-    y = torch.empty_like(x) if out is None else _dev_rows(out, F32, "out")
-    ldy = D if out is None else y.stride(0)
-    mean = torch.empty(rows, dtype=F32, device=x.device) if stats else None
-    rstd = torch.empty(rows, dtype=F32, device=x.device) if stats else None
-    _chk(lib().orbit2_layernorm_fwd_f32(_p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), rows, D, ldy, eps,
-                                        _stream()), "orbit2_layernorm_fwd_f32")
-    return (y, mean, rstd) if stats else y
+    res = _layernorm_fwd(F32, x, gamma, beta, eps, out, stats)
+    return res if stats else res[0]
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, beta_acc=0.0):
+    """dgamma / dbeta: the two gradient sinks, both bf16 or both fp32 (the entry takes one flag for the pair); dres: bf16 or None"""
     _dev(dy, BF, "dy"); _dev(x, BF, "x"); _dev(gamma, BF, "gamma")
+    _dev(mean, F32, "mean"); _dev(rstd, F32, "rstd"); _dev_opt(dres, BF, "dres")
+    _dev(dgamma, BF_F32, "dgamma"); _dev(dbeta, dgamma.dtype, "dbeta")
     D = x.shape[-1]
     rows = x.numel() // D
     dx = torch.empty_like(x)
     n = lib().orbit2_layernorm_bwd_ws_floats(rows, D)
     ws = torch.empty(n, dtype=F32, device=x.device)
-    fp32 = int(dgamma.dtype == F32)
-    _chk(lib().orbit2_layernorm_bwd(_p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dres), _p(dx), _p(dgamma),
-                                    _p(dbeta), fp32, beta_acc, _p(ws), n, rows, D, _stream()),
-         "orbit2_layernorm_bwd")
+    _call("orbit2_layernorm_bwd", dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, int(dgamma.dtype == F32), beta_acc, ws, n,
+          rows, D)
     return dx
 
 
@@ -456,8 +501,8 @@ ATTN_4WAVES, ATTN_SPLIT_DKV, ATTN_Q_PRESCALED, ATTN_NO_W4 = 1, 2, 4, 8      # in
 
 def probe_read(buf, blocks, inflight, sink):
     """diagnostic calibration stream (include/orbit2_hip.h: orbit2_probe_read)"""
-    _chk(lib().orbit2_probe_read(_p(buf), buf.numel() * buf.element_size(), int(blocks), int(inflight), _p(sink),
-                                 _stream()), "orbit2_probe_read")
+    _dev(buf, F32, "buf"); _dev(sink, F32, "sink")
+    _call("orbit2_probe_read", buf, buf.numel() * buf.element_size(), int(blocks), int(inflight), sink)
 
 
 def mall_calibration():
@@ -487,42 +532,37 @@ def _attn_gate(gate, B):
     return gate
 
 
+def _attn_fwd(dtype, qkv, B, L, H, d, drop_p, seed, flags, out, gate=None, tail=-1):
+    """the attention forward in `dtype`: BF = orbit2_attn_fwd_ld (seed, gate and tail queue), F32 = orbit2_attn_fwd_f32 (none of
+    them).  qkv [B * L, 3 * H * d] with a token-row pitch, or contiguous; out likewise, default [B, L, H * d]"""
+    _dev_rows(qkv, dtype, "qkv")
+    ldq = qkv.stride(0) if qkv.dim() == 2 else 3 * H * d
+    if out is None:
+        out, ldo = torch.empty(B, L, H * d, dtype=dtype, device=qkv.device), H * d
+    else:
+        out = _dev_rows(out, dtype, "out")
+        ldo = out.stride(0)
+    lse = torch.empty(B, H, L, dtype=F32, device=qkv.device)
+    name, ends = ("attn_fwd", (gate,) + _queue(tail, qkv.device)) if dtype == BF else ("attn_fwd_f32", ())
+    # algorithmic bytes: qkv read once, out + lse written once
+    with _timed(name, 4.0 * B * H * L * L * d, qkv.element_size() * 4.0 * B * L * H * d + 4.0 * B * H * L):
+        _call("orbit2_attn_fwd_ld" if dtype == BF else "orbit2_attn_fwd_f32", qkv, out, lse, B, L, H, d, drop_p, seed, int(flags),
+              int(ldq), int(ldo), *ends)
+    return out, lse
+
+
 def attn_fwd(qkv, B, L, H, d, drop_p=0.0, seed=0, flags=0, out=None, gate=None, tail_queue=None):
     """out: optional [B * L, H * d] bf16 destination with any token-row pitch (orbit2_attn_fwd_ld); default [B, L, H * d].
     gate: fp32 [B] path gate: out and lse of a sample whose entry is 0.0 may be stored as zeros
     tail_queue: as in gemm"""
     tail = _tail_arg(tail_queue)
-    _attn_gate(gate, B)
-    _dev_rows(qkv, BF, "qkv")
-    ldq = qkv.stride(0) if qkv.dim() == 2 else 3 * H * d       # [B * L, 3 * H * d] with a token-row pitch, or contiguous
-    if out is None:
-        out, ldo = torch.empty(B, L, H * d, dtype=BF, device=qkv.device), H * d
-    else:
-        out = _dev_rows(out, BF, "out")
-        ldo = out.stride(0)
-    lse = torch.empty(B, H, L, dtype=F32, device=qkv.device)
-    # algorithmic bytes: qkv read once, out + lse written once
-    with _timed("attn_fwd", 4.0 * B * H * L * L * d, 2.0 * 4 * B * L * H * d + 4.0 * B * H * L):
-        _chk(lib().orbit2_attn_fwd_ld(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo), _p(gate),
-                                      *_queue(tail, qkv.device)), "orbit2_attn_fwd_ld")
-    return out, lse
+    return _attn_fwd(BF, qkv, B, L, H, d, drop_p, seed, flags, out, _attn_gate(gate, B), tail)
 
 
 def attn_fwd_f32(qkv, B, L, H, d, drop_p=0.0, flags=0, out=None):
     """fp32 attention core (orbit2_attn_fwd_f32): qkv fp32 [B * L, 3 * H * d] (any token-row pitch) or contiguous
     [B, L, 3, H, d]; returns (out [B, L, H * d] fp32 or the given `out`, lse [B, H, L])"""
-    _dev_rows(qkv, F32, "qkv")
-    ldq = qkv.stride(0) if qkv.dim() == 2 else 3 * H * d
-    if out is None:
-        out, ldo = torch.empty(B, L, H * d, dtype=F32, device=qkv.device), H * d
-    else:
-        out = _dev_rows(out, F32, "out")
-        ldo = out.stride(0)
-    lse = torch.empty(B, H, L, dtype=F32, device=qkv.device)
-    with _timed("attn_fwd_f32", 4.0 * B * H * L * L * d, 4.0 * 4 * B * L * H * d + 4.0 * B * H * L):
-        _chk(lib().orbit2_attn_fwd_f32(_p(qkv), _p(out), _p(lse), B, L, H, d, drop_p, 0, int(flags), int(ldq), int(ldo),
-                                       _stream()), "orbit2_attn_fwd_f32")
-    return out, lse
+    return _attn_fwd(F32, qkv, B, L, H, d, drop_p, 0, flags, out)
 
 
 def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0, gate=None, tail_queue=None):
@@ -540,8 +580,8 @@ def attn_bwd(qkv, out, dout, lse, B, L, H, d, drop_p=0.0, seed=0, flags=0, gate=
     delta = torch.empty(lib().orbit2_attn_bwd_ws_floats(B, L, H), dtype=F32, device=qkv.device)
     # algorithmic: 2x the forward's FLOPs (recompute not credited); qkv, out, dout read once, dqkv written once
     with _timed("attn_bwd", 8.0 * B * H * L * L * d, 2.0 * 8 * B * L * H * d + 8.0 * B * H * L):
-        _chk(lib().orbit2_attn_bwd_ld(_p(qkv), _p(out), _p(dout), _p(lse), _p(delta), _p(dqkv), B, L, H, d, drop_p, seed, int(flags),
-                                      int(ldq), int(ldo), _p(gate), *_queue(tail, qkv.device)), "orbit2_attn_bwd_ld")
+        _call("orbit2_attn_bwd_ld", qkv, out, dout, lse, delta, dqkv, B, L, H, d, drop_p, seed, int(flags), int(ldq), int(ldo), gate,
+              *_queue(tail, qkv.device))
     return dqkv
 
 
@@ -571,33 +611,25 @@ def _varagg_shapes(x, gtab, stab=None):
     return B, V, h, w, p, B * (h // p) * (w // p)
 
 
-def varagg_fwd(x, stab, gtab, H, D):
-    """z bf16 [tokens, D], attw fp32 [tokens, H, V]; the patch size is the tables': stab [H, V, p*p+1], gtab [V, p*p+1, D]"""
+def _varagg_fwd(zdtype, x, stab, gtab, H, D, want_attw):
+    """the folded variable aggregation with tokens in `zdtype` (BF: orbit2_varagg_fwd_p, F32: orbit2_varagg_fwd_f32_p): (z, attw).
+    Every patch size goes through the _p entries: at patch 2 they are the plain entries' own code (include/orbit2_hip.h)"""
     _dev(x, F32, "x"); _dev(stab, F32, "stab"); _dev(gtab, F32, "gtab")
     B, V, h, w, p, ntok = _varagg_shapes(x, gtab, stab)
-    z = torch.empty(ntok, D, dtype=BF, device=x.device)
-    attw = torch.empty(ntok, H, V, dtype=F32, device=x.device)
-    if p == 2:
-        _chk(lib().orbit2_varagg_fwd(_p(x), _p(stab), _p(gtab), _p(z), _p(attw), B, V, h, w, H, D, _stream()),
-             "orbit2_varagg_fwd")
-    else:
-        _chk(lib().orbit2_varagg_fwd_p(_p(x), _p(stab), _p(gtab), _p(z), _p(attw), B, V, h, w, p, H, D, _stream()),
-             "orbit2_varagg_fwd_p")
+    z = torch.empty(ntok, D, dtype=zdtype, device=x.device)
+    attw = torch.empty(ntok, H, V, dtype=F32, device=x.device) if want_attw else None
+    _call("orbit2_varagg_fwd_p" if zdtype == BF else "orbit2_varagg_fwd_f32_p", x, stab, gtab, z, attw, B, V, h, w, p, H, D)
     return z, attw
 
 
+def varagg_fwd(x, stab, gtab, H, D):
+    """z bf16 [tokens, D], attw fp32 [tokens, H, V]; the patch size is the tables': stab [H, V, p*p+1], gtab [V, p*p+1, D]"""
+    return _varagg_fwd(BF, x, stab, gtab, H, D, True)
+
+
 def varagg_fwd_f32(x, stab, gtab, H, D, want_attw=False):
-    """the folded variable aggregation with fp32 tokens (orbit2_varagg_fwd_f32); returns z, or (z, attw) with want_attw"""
-    _dev(x, F32, "x"); _dev(stab, F32, "stab"); _dev(gtab, F32, "gtab")
-    B, V, h, w, p, ntok = _varagg_shapes(x, gtab, stab)
-    z = torch.empty(ntok, D, dtype=F32, device=x.device)
-    attw = torch.empty(ntok, H, V, dtype=F32, device=x.device) if want_attw else None
-    if p == 2:
-        _chk(lib().orbit2_varagg_fwd_f32(_p(x), _p(stab), _p(gtab), _p(z), _p(attw), B, V, h, w, H, D, _stream()),
-             "orbit2_varagg_fwd_f32")
-    else:
-        _chk(lib().orbit2_varagg_fwd_f32_p(_p(x), _p(stab), _p(gtab), _p(z), _p(attw), B, V, h, w, p, H, D, _stream()),
-             "orbit2_varagg_fwd_f32_p")
+    """the folded variable aggregation with fp32 tokens (orbit2_varagg_fwd_f32_p); returns z, or (z, attw) with want_attw"""
+    z, attw = _varagg_fwd(F32, x, stab, gtab, H, D, want_attw)
     return (z, attw) if want_attw else z
 
 
@@ -615,125 +647,114 @@ atomics_in_grad_path = False
 
 
 def varagg_bwd(x, gtab, attw, dz, H, D):
+    """(dstab, dgtab) through orbit2_varagg_bwd_p at every patch size.  A shape the entry does not serve (workspace query 0) is
+    refused; a served one whose sums are not in a fixed order (the atomics fallback, which exists at patch 2 only) sets
+    `atomics_in_grad_path`"""
     global atomics_in_grad_path
     _dev(x, F32, "x"); _dev(gtab, F32, "gtab"); _dev(attw, F32, "attw"); _dev(dz, BF, "dz")
     B, V, h, w, p, ntok = _varagg_shapes(x, gtab)
     C_ = p * p + 1
     dstab = torch.zeros(H, V, C_, dtype=F32, device=x.device)
     dgtab = torch.zeros(V, C_, D, dtype=F32, device=x.device)
-    if p != 2:
-        # the two-stage fixed-order backward (no float atomics anywhere): `atomics_in_grad_path` is not touched
-        if not lib().orbit2_varagg_bwd_p_is_fixed_order(B, V, h, w, p, H, D):
-            raise HipBackendError("orbit2_varagg_bwd_p does not serve B=%d V=%d grid %dx%d patch %d H=%d D=%d (its LDS need "
-                                  "exceeds a CU's 160 KiB, or the shape is invalid)" % (B, V, h, w, p, H, D))
-        ws = _ws(lib().orbit2_varagg_bwd_p_ws_floats, (B, V, h, w, p, H, D), x.device)
-        _chk(lib().orbit2_varagg_bwd_p(_p(x), _p(gtab), _p(attw), _p(dz), _p(dstab), _p(dgtab), B, V, h, w, p, H, D, _p(ws),
-                                       _stream()), "orbit2_varagg_bwd_p")
-        return dstab, dgtab
-    if not atomics_in_grad_path and not lib().orbit2_varagg_bwd_is_fixed_order(B, V, h, w, H, D):
+    fixed = lib().orbit2_varagg_bwd_p_is_fixed_order(B, V, h, w, p, H, D)
+    n = lib().orbit2_varagg_bwd_p_ws_floats(B, V, h, w, p, H, D)
+    if n <= 0:
+        raise HipBackendError("orbit2_varagg_bwd_p does not serve B=%d V=%d grid %dx%d patch %d H=%d D=%d (its LDS need "
+                              "exceeds a CU's 160 KiB, or the shape is invalid)" % (B, V, h, w, p, H, D))
+    if not fixed:
         atomics_in_grad_path = True
-    ws = _ws(lib().orbit2_varagg_bwd_ws_floats, (B, V, h, w, H, D), x.device)
-    _chk(lib().orbit2_varagg_bwd(_p(x), _p(gtab), _p(attw), _p(dz), _p(dstab), _p(dgtab), B, V, h, w, H, D, _p(ws), _stream()),
-         "orbit2_varagg_bwd")
+    ws = torch.empty(n, dtype=F32, device=x.device)
+    _call("orbit2_varagg_bwd_p", x, gtab, attw, dz, dstab, dgtab, B, V, h, w, p, H, D, ws)
     return dstab, dgtab
 
 
 def tables_gather(w0, w_stride, b0, b_stride, var_embed, ids, V, D):
     """cmat [5 V, D] fp32 from the per-variable patch-embed parameters laid out at a uniform pitch (w0 / b0 = parameter 0)"""
     _dev(w0, F32, "token_embeds.0.proj.weight"); _dev(b0, F32, "token_embeds.0.proj.bias"); _dev(var_embed, F32, "var_embed")
-    _dev(ids, torch.int32, "ids")
+    _dev(ids, I32, "ids")
     cmat = torch.empty(5 * V, D, dtype=F32, device=w0.device)
-    _chk(lib().orbit2_tables_gather(_p(w0), w_stride, _p(b0), b_stride, _p(var_embed), _p(ids), _p(cmat), V, D, _stream()),
-         "orbit2_tables_gather")
+    _call("orbit2_tables_gather", w0, w_stride, b0, b_stride, var_embed, ids, cmat, V, D)
     return cmat
 
 
 def tables_scatter(dcmat, gw0, w_stride, gb0, b_stride, gvar_embed, ids, V, D):
     """accumulates the rows' gradient into the parameters' gradient buffers (same pitches)"""
     _dev(dcmat, F32, "dcmat"); _dev(gw0, F32, "dW"); _dev(gb0, F32, "db"); _dev(gvar_embed, F32, "dvar_embed")
-    _chk(lib().orbit2_tables_scatter(_p(dcmat), _p(gw0), w_stride, _p(gb0), b_stride, _p(gvar_embed), _p(ids), V, D,
-                                     _stream()), "orbit2_tables_scatter")
+    _dev(ids, I32, "ids")
+    _call("orbit2_tables_scatter", dcmat, gw0, w_stride, gb0, b_stride, gvar_embed, ids, V, D)
 
 
 def dropout_bwd(dy, M, N, drop_p, seed, rowscale=None, rows_per_scale=0, out=None):
-    _dev(dy, BF, "dy")
-    out = torch.empty_like(dy) if out is None else out
-    _chk(lib().orbit2_dropout_bwd(_p(dy), _p(out), M, N, drop_p, seed, _p(rowscale), rows_per_scale, _stream()),
-         "orbit2_dropout_bwd")
+    _dev(dy, BF, "dy"); _dev_opt(rowscale, F32, "rowscale")
+    out = torch.empty_like(dy) if out is None else _dev(out, BF, "out")
+    _call("orbit2_dropout_bwd", dy, out, M, N, drop_p, seed, rowscale, rows_per_scale)
     return out
 
 
 def dropout_bwd_colsum(dy, M, N, drop_p, seed, rowscale, rows_per_scale, colsum_out, beta=0.0):
     """dym = dy * dropmask * rowscale and colsum_out[n] (+)= sum_m dym[m][n] in one pass"""
-    _dev(dy, BF, "dy")
+    _dev(dy, BF, "dy"); _dev_opt(rowscale, F32, "rowscale"); _dev(colsum_out, BF_F32, "colsum_out")
     out = torch.empty_like(dy)
     n = lib().orbit2_colsum_ws_floats(M, N)
     ws = torch.empty(n, dtype=F32, device=dy.device)
-    _chk(lib().orbit2_dropout_bwd_colsum(_p(dy), _p(out), M, N, drop_p, seed, _p(rowscale), rows_per_scale, _p(colsum_out),
-                                         int(colsum_out.dtype == F32), beta, _p(ws), n, _stream()), "orbit2_dropout_bwd_colsum")
+    _call("orbit2_dropout_bwd_colsum", dy, out, M, N, drop_p, seed, rowscale, rows_per_scale, colsum_out,
+          int(colsum_out.dtype == F32), beta, ws, n)
     return out
 
 
 def post_reduce(x, M, N, addend=None, res_mod=0, residual=None, drop_p=0.0, seed=0, rowscale=None, rows_per_scale=0,
                 out=None):
     """y = residual + rowscale * dropout(x + addend[m % res_mod]); in place on x unless `out` is given"""
-    _dev(x, BF, "x")
-    for t, nm in ((addend, "addend"), (residual, "residual")):
-        if t is not None:
-            _dev(t, BF, nm)
-    out = x if out is None else out
-    _chk(lib().orbit2_post_reduce(_p(x), _p(addend), res_mod, _p(residual), _p(out), M, N, drop_p, seed, _p(rowscale),
-                                  rows_per_scale, _stream()), "orbit2_post_reduce")
+    _dev(x, BF, "x"); _dev_opt(addend, BF, "addend"); _dev_opt(residual, BF, "residual"); _dev_opt(rowscale, F32, "rowscale")
+    out = x if out is None else _dev(out, BF, "out")
+    _call("orbit2_post_reduce", x, addend, res_mod, residual, out, M, N, drop_p, seed, rowscale, rows_per_scale)
     return out
 
 
 def colsum(x, M, N, ldx, out, beta=0.0):
-    if x.dtype not in (BF, F32):
-        raise HipBackendError("colsum input must be bf16/fp32")
+    """out[n] = beta * out[n] + sum_m x[m][n]; x bf16 or fp32 with rows ldx apart (a padded view, or the padded buffer itself)"""
+    _dev_rows(x, BF_F32, "x"); _dev(out, BF_F32, "out")
     n = lib().orbit2_colsum_ws_floats(M, N)
     ws = torch.empty(n, dtype=F32, device=x.device)
-    _chk(lib().orbit2_colsum(_p(x), int(x.dtype == F32), M, N, ldx, _p(out), int(out.dtype == F32), beta,
-                             _p(ws), n, _stream()), "orbit2_colsum")
+    _call("orbit2_colsum", x, int(x.dtype == F32), M, N, ldx, out, int(out.dtype == F32), beta, ws, n)
     return out
 
 
 def batch_sum(x, B, rows, N, out, beta=0.0):
-    _dev(x, BF, "x")
-    _chk(lib().orbit2_batch_sum(_p(x), _p(out), B, rows, N, int(out.dtype == F32), beta, _stream()),
-         "orbit2_batch_sum")
+    _dev(x, BF, "x"); _dev(out, BF_F32, "out")
+    _call("orbit2_batch_sum", x, out, B, rows, N, int(out.dtype == F32), beta)
     return out
 
 
-def cast_to_bf16(src, dst=None):
-    _dev(src, F32, "src")
-    dst = torch.empty(src.shape, dtype=BF, device=src.device) if dst is None else dst
-    _chk(lib().orbit2_cast_f32_to_bf16(_p(src), _p(dst), src.numel(), _stream()), "orbit2_cast_f32_to_bf16")
+def _cast(name, to, src, dst):
+    """dst (default: a new tensor of src's shape) = src in the dtype `to`; the entry `name` reads the other of bf16 / fp32"""
+    _dev(src, F32 if to == BF else BF, "src")
+    dst = torch.empty(src.shape, dtype=to, device=src.device) if dst is None else _dev(dst, to, "dst")
+    _call(name, src, dst, src.numel())
     return dst
+
+
+def cast_to_bf16(src, dst=None):
+    return _cast("orbit2_cast_f32_to_bf16", BF, src, dst)
 
 
 def cast_to_f32(src, dst=None):
-    _dev(src, BF, "src")
-    dst = torch.empty(src.shape, dtype=F32, device=src.device) if dst is None else dst
-    _chk(lib().orbit2_cast_bf16_to_f32(_p(src), _p(dst), src.numel(), _stream()), "orbit2_cast_bf16_to_f32")
-    return dst
+    return _cast("orbit2_cast_bf16_to_f32", F32, src, dst)
 
 
 def add_rowvec(a, vec, rows, N):
     _dev(a, BF, "a"); _dev(vec, BF, "vec")
     y = torch.empty_like(a)
-    _chk(lib().orbit2_add_rowvec(_p(a), _p(vec), _p(y), rows, N, _stream()), "orbit2_add_rowvec")
+    _call("orbit2_add_rowvec", a, vec, y, rows, N)
     return y
 
 
 def posembed_fwd(pe, sw, sb, res, oh, ow, nh, nw):
     """[nh*nw, D] fp32 = bicubic re-grid of the [oh*ow, D] table (identity when oh == nh) + sw * res + sb"""
-    _dev(pe, F32, "pos_embed")
+    _dev(pe, F32, "pos_embed"); _dev_opt(sw, F32, "spatial_embed.weight"); _dev_opt(sb, F32, "spatial_embed.bias")
     D = pe.shape[-1]
-    if sw is not None:
-        _dev(sw, F32, "spatial_embed.weight"); _dev(sb, F32, "spatial_embed.bias")
     out = torch.empty(nh * nw, D, dtype=F32, device=pe.device)
-    _chk(lib().orbit2_posembed_fwd(_p(pe), _p(sw), _p(sb), res, _p(out), oh, ow, nh, nw, D, _stream()),
-         "orbit2_posembed_fwd")
+    _call("orbit2_posembed_fwd", pe, sw, sb, res, out, oh, ow, nh, nw, D)
     return out
 
 
@@ -741,34 +762,36 @@ def posembed_bwd(dout, oh, ow, nh, nw):
     _dev(dout, F32, "dposres")
     D = dout.shape[-1]
     dpe = torch.empty(oh * ow, D, dtype=F32, device=dout.device)
-    _chk(lib().orbit2_posembed_bwd(_p(dout), _p(dpe), oh, ow, nh, nw, D, _stream()), "orbit2_posembed_bwd")
+    _call("orbit2_posembed_bwd", dout, dpe, oh, ow, nh, nw, D)
     return dpe
 
 
-def unpatchify_fwd(t, B, Cc, h, w, p, s):
-    _dev(t, BF, "t")
+def _unpatchify_fwd(dtype, t, B, Cc, h, w, p, s):
+    """tokens in `dtype` (BF: orbit2_unpatchify_fwd, F32: orbit2_unpatchify_fwd_f32) -> the fp32 image"""
+    _dev(t, dtype, "t")
     img = torch.empty(B, Cc, h * s, w * s, dtype=F32, device=t.device)
-    _chk(lib().orbit2_unpatchify_fwd(_p(t), _p(img), B, Cc, h, w, p, s, _stream()), "orbit2_unpatchify_fwd")
+    _call("orbit2_unpatchify_fwd" if dtype == BF else "orbit2_unpatchify_fwd_f32", t, img, B, Cc, h, w, p, s)
     return img
+
+
+def unpatchify_fwd(t, B, Cc, h, w, p, s):
+    return _unpatchify_fwd(BF, t, B, Cc, h, w, p, s)
 
 
 def unpatchify_fwd_f32(t, B, Cc, h, w, p, s):
-    _dev(t, F32, "t")
-    img = torch.empty(B, Cc, h * s, w * s, dtype=F32, device=t.device)
-    _chk(lib().orbit2_unpatchify_fwd_f32(_p(t), _p(img), B, Cc, h, w, p, s, _stream()), "orbit2_unpatchify_fwd_f32")
-    return img
+    return _unpatchify_fwd(F32, t, B, Cc, h, w, p, s)
 
 
 def unpatchify_bwd(dimg, B, Cc, h, w, p, s):
     _dev(dimg, F32, "dimg")
     L = h * w // (p * p)
     dt = torch.empty(B, L, Cc * (s * p) ** 2, dtype=BF, device=dimg.device)
-    _chk(lib().orbit2_unpatchify_bwd(_p(dimg), _p(dt), B, Cc, h, w, p, s, _stream()), "orbit2_unpatchify_bwd")
+    _call("orbit2_unpatchify_bwd", dimg, dt, B, Cc, h, w, p, s)
     return dt
 
 
 def conv3x3_fwd(x, chan_idx, weight, bias, mode=0, r=1, addend=None):
-    _dev(x, F32, "in"); _dev(weight, F32, "weight"); _dev(bias, F32, "bias")
+    _dev(x, F32, "in"); _dev_opt(chan_idx, I32, "chan_idx"); _dev(weight, F32, "weight"); _dev(bias, F32, "bias")
     B, ctot, H, W = x.shape
     Cout, Cin = weight.shape[0], weight.shape[1]
     pre = None
@@ -781,89 +804,99 @@ def conv3x3_fwd(x, chan_idx, weight, bias, mode=0, r=1, addend=None):
     if addend is not None:
         _dev(addend, F32, "addend")
         Ha, Wa = addend.shape[2], addend.shape[3]
-    _chk(lib().orbit2_conv3x3_fwd(_p(x), _p(chan_idx), ctot, _p(weight), _p(bias), _p(out), _p(pre), _p(addend), Ha, Wa,
-                                  B, Cin, Cout, H, W, mode, r, _stream()), "orbit2_conv3x3_fwd")
+    _call("orbit2_conv3x3_fwd", x, chan_idx, ctot, weight, bias, out, pre, addend, Ha, Wa, B, Cin, Cout, H, W, mode, r)
     return out, pre
 
 
 def conv3x3_bwd(dout, x, chan_idx, weight, pre, need_din, mode=0, r=1):
-    _dev(dout, F32, "dout"); _dev(x, F32, "in"); _dev(weight, F32, "weight")
+    _dev(dout, F32, "dout"); _dev(x, F32, "in"); _dev_opt(chan_idx, I32, "chan_idx"); _dev(weight, F32, "weight")
+    _dev_opt(pre, F32, "pre")
     B, ctot, H, W = x.shape
     Cout, Cin = weight.shape[0], weight.shape[1]
     din = torch.empty(B, Cin, H, W, dtype=F32, device=x.device) if need_din else None
     dw = torch.zeros_like(weight)
     db = torch.zeros(Cout, dtype=F32, device=x.device)
     ws = _ws(lib().orbit2_conv3x3_bwd_ws_floats, (B, Cin, Cout, H, W), x.device)
-    _chk(lib().orbit2_conv3x3_bwd(_p(dout), _p(x), _p(chan_idx), ctot, _p(weight), _p(pre), _p(din), _p(dw), _p(db), B,
-                                  Cin, Cout, H, W, mode, r, _p(ws), _stream()), "orbit2_conv3x3_bwd")
+    _call("orbit2_conv3x3_bwd", dout, x, chan_idx, ctot, weight, pre, din, dw, db, B, Cin, Cout, H, W, mode, r, ws)
     return din, dw, db
 
 
 def clamp_channel_(img, chan):
     _dev(img, F32, "img")
     B, Cc, H, W = img.shape
-    _chk(lib().orbit2_clamp_channel(_p(img), B, Cc, H * W, chan, _stream()), "orbit2_clamp_channel")
+    _call("orbit2_clamp_channel", img, B, Cc, H * W, chan)
     return img
 
 
 def clamp_channel_bwd_(img_clamped, dimg, chan):
     _dev(img_clamped, F32, "img"); _dev(dimg, F32, "dimg")
     B, Cc, H, W = img_clamped.shape
-    _chk(lib().orbit2_clamp_channel_bwd(_p(img_clamped), _p(dimg), B, Cc, H * W, chan, _stream()),
-         "orbit2_clamp_channel_bwd")
+    _call("orbit2_clamp_channel_bwd", img_clamped, dimg, B, Cc, H * W, chan)
     return dimg
 
 
+LOSS_BLOCKS = 64                # ORBIT2_LOSS_BLOCKS: the partial sums per (b, c) plane of the two loss forwards
+
+
+def _loss_ws(B, Cc, device):
+    """the fp32 workspace of orbit2_loss_fwd and orbit2_masked_loss_fwd: two partials per block of every (b, c) plane"""
+    return torch.empty(2 * Cc * B * LOSS_BLOCKS, dtype=F32, device=device)
+
+
+def _loss_pair(name, pred, target, lat_w, chan_w):
+    """(B, C, H, W) of a loss wrapper's operands: the scored pair's checks, and chan_w fp32 with one entry per channel or None"""
+    B, Cc, H, W = _scored_pair(name, pred, target, lat_w)
+    if chan_w is not None and _dev(chan_w, F32, "chan_w").numel() != Cc:
+        raise HipBackendError("%s: chan_w has %d entries for %d channels" % (name, chan_w.numel(), Cc))
+    return B, Cc, H, W
+
+
 def loss_fwd(pred, target, lat_w, chan_w, kind):
-    _dev(pred, F32, "pred"); _dev(target, F32, "target")
-    B, Cc, H, W = pred.shape
-    Ht, Wt = target.shape[2], target.shape[3]
+    B, Cc, H, W = _loss_pair("loss_fwd", pred, target, lat_w, chan_w)
     out = torch.empty(Cc + 1, dtype=F32, device=pred.device)
-    ws = torch.empty(2 * Cc * B * 64, dtype=F32, device=pred.device)
-    _chk(lib().orbit2_loss_fwd(_p(pred), _p(target), Ht, Wt, _p(lat_w), _p(chan_w), _p(out), _p(ws), B, Cc, H, W, kind,
-                               _stream()), "orbit2_loss_fwd")
+    ws = _loss_ws(B, Cc, pred.device)
+    _call("orbit2_loss_fwd", pred, target, target.shape[2], target.shape[3], lat_w, chan_w, out, ws, B, Cc, H, W, kind)
     return out
 
 
 def loss_bwd(pred, target, lat_w, chan_w, gscale, kind):
-    B, Cc, H, W = pred.shape
-    Ht, Wt = target.shape[2], target.shape[3]
+    B, Cc, H, W = _loss_pair("loss_bwd", pred, target, lat_w, chan_w)
+    _dev(gscale, F32, "gscale")
     dpred = torch.empty_like(pred)
-    _chk(lib().orbit2_loss_bwd(_p(pred), _p(target), Ht, Wt, _p(lat_w), _p(chan_w), _p(_dev(gscale, F32, "gscale")),
-                               _p(dpred), B, Cc, H, W, kind, _stream()), "orbit2_loss_bwd")
+    _call("orbit2_loss_bwd", pred, target, target.shape[2], target.shape[3], lat_w, chan_w, gscale, dpred, B, Cc, H, W, kind)
     return dpred
 
 
 def adamw(p, m, v, g, p16, n, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, found_inf=None):
     _dev(p, F32, "p"); _dev(m, F32, "m"); _dev(v, F32, "v")
+    _dev(g, BF_F32, "g"); _dev_opt(p16, BF, "p16"); _dev_opt(found_inf, F32, "found_inf")
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
-    _chk(lib().orbit2_adamw(_p(p), _p(m), _p(v), _p(g), int(g.dtype == F32), _p(p16), n, lr, beta1, beta2, eps, wd, bc1, bc2,
-                            grad_scale, _p(found_inf), _stream()), "orbit2_adamw")
+    _call("orbit2_adamw", p, m, v, g, int(g.dtype == F32), p16, n, lr, beta1, beta2, eps, wd, bc1, bc2, grad_scale, found_inf)
 
 
 def check_finite(g, n, found_inf):
-    _chk(lib().orbit2_check_finite(_p(g), int(g.dtype == F32), n, _p(found_inf), _stream()),
-         "orbit2_check_finite")
+    _dev(g, BF_F32, "g"); _dev(found_inf, F32, "found_inf")
+    _call("orbit2_check_finite", g, int(g.dtype == F32), n, found_inf)
 
 
 def selftest(device="cuda") -> int:
     buf = torch.zeros(512, dtype=torch.int32, device=device)
-    _chk(lib().orbit2_selftest(_p(buf), _stream()), "orbit2_selftest")
+    _call("orbit2_selftest", buf)
     torch.cuda.synchronize()
     return int(buf[0].item())
 
 
 def droppath_scales(B, p, seed, device):
     out = torch.empty(B, dtype=F32, device=device)
-    _chk(lib().orbit2_droppath_scales(_p(out), B, p, seed, _stream()), "orbit2_droppath_scales")
+    _call("orbit2_droppath_scales", out, B, p, seed)
     return out
 
 
 def transpose_bf16(src, dst):
     _dev(src, BF, "src"); _dev(dst, BF, "dst")
     R, Cc = src.shape
-    _chk(lib().orbit2_transpose_bf16(_p(src), _p(dst), R, Cc, _stream()), "orbit2_transpose_bf16")
+    _call("orbit2_transpose_bf16", src, dst, R, Cc)
     return dst
 
 
@@ -871,28 +904,28 @@ def transpose_bf16(src, dst):
 def im2col3x3(x, N, H, W, Cc):
     _dev(x, BF, "x")
     col = torch.empty(N * H * W, 9 * Cc, dtype=BF, device=x.device)
-    _chk(lib().orbit2_im2col3x3(_p(x), _p(col), N, H, W, Cc, _stream()), "orbit2_im2col3x3")
+    _call("orbit2_im2col3x3", x, col, N, H, W, Cc)
     return col
 
 
 def col2im3x3(dcol, N, H, W, Cc, act=None, tapg=None):
-    _dev(dcol, BF, "dcol")
+    _dev(dcol, BF, "dcol"); _dev_opt(act, BF, "act"); _dev_opt(tapg, BF, "tapg")
     out = torch.empty(N * H * W, Cc, dtype=BF, device=dcol.device)
-    _chk(lib().orbit2_col2im3x3(_p(dcol), _p(act), _p(tapg), _p(out), N, H, W, Cc, _stream()), "orbit2_col2im3x3")
+    _call("orbit2_col2im3x3", dcol, act, tapg, out, N, H, W, Cc)
     return out
 
 
 def maxpool2_fwd(x, N, H, W, Cc):
     _dev(x, BF, "x")
     y = torch.empty(N * (H // 2) * (W // 2), Cc, dtype=BF, device=x.device)
-    _chk(lib().orbit2_maxpool2_fwd(_p(x), _p(y), N, H, W, Cc, _stream()), "orbit2_maxpool2_fwd")
+    _call("orbit2_maxpool2_fwd", x, y, N, H, W, Cc)
     return y
 
 
 def maxpool2_bwd(g, x, N, H, W, Cc, tapg=None):
-    _dev(g, BF, "g"); _dev(x, BF, "x")
+    _dev(g, BF, "g"); _dev(x, BF, "x"); _dev_opt(tapg, BF, "tapg")
     dz = torch.empty(N * H * W, Cc, dtype=BF, device=g.device)
-    _chk(lib().orbit2_maxpool2_bwd(_p(g), _p(x), _p(tapg), _p(dz), N, H, W, Cc, _stream()), "orbit2_maxpool2_bwd")
+    _call("orbit2_maxpool2_bwd", g, x, tapg, dz, N, H, W, Cc)
     return dz
 
 
@@ -900,39 +933,35 @@ def lpips_conv1_fwd(img, w1, b1):
     _dev(img, F32, "img"); _dev(w1, F32, "w1"); _dev(b1, F32, "b1")
     N, _, H, W = img.shape
     out = torch.empty(N * H * W, 64, dtype=BF, device=img.device)
-    _chk(lib().orbit2_lpips_conv1_fwd(_p(img), _p(w1), _p(b1), _p(out), N, H, W, _stream()), "orbit2_lpips_conv1_fwd")
+    _call("orbit2_lpips_conv1_fwd", img, w1, b1, out, N, H, W)
     return out
 
 
 def lpips_conv1_bwd(dz, w1, pred, target, l1_coef, gscale=None):
-    _dev(dz, BF, "dz"); _dev(pred, F32, "pred"); _dev(target, F32, "target")
+    _dev(dz, BF, "dz"); _dev(w1, F32, "w1"); _dev(pred, F32, "pred"); _dev(target, F32, "target"); _dev_opt(gscale, F32, "gscale")
     N, _, H, W = pred.shape
     dimg = torch.empty_like(pred)
-    gs = None if gscale is None else _p(_dev(gscale, F32, "gscale"))
-    _chk(lib().orbit2_lpips_conv1_bwd(_p(dz), _p(w1), _p(pred), _p(target), l1_coef, gs, _p(dimg), N, H, W,
-                                      _stream()), "orbit2_lpips_conv1_bwd")
+    _call("orbit2_lpips_conv1_bwd", dz, w1, pred, target, l1_coef, gscale, dimg, N, H, W)
     return dimg
 
 
 def lpips_tap_fwd(feats, lin, val, B, HW, Cc):
     _dev(feats, BF, "feats"); _dev(lin, F32, "lin"); _dev(val, F32, "val")
     ws = _ws(lib().orbit2_lpips_tap_ws_floats, (B, HW, Cc), feats.device)
-    _chk(lib().orbit2_lpips_tap_fwd(_p(feats), _p(lin), _p(val), B, HW, Cc, _p(ws), _stream()), "orbit2_lpips_tap_fwd")
+    _call("orbit2_lpips_tap_fwd", feats, lin, val, B, HW, Cc, ws)
 
 
 def lpips_tap_bwd(feats, lin, coef, B, HW, Cc, gscale=None):
-    _dev(feats, BF, "feats"); _dev(lin, F32, "lin")
+    _dev(feats, BF, "feats"); _dev(lin, F32, "lin"); _dev_opt(gscale, F32, "gscale")
     g = torch.empty(B * HW, Cc, dtype=BF, device=feats.device)
-    gs = None if gscale is None else _p(_dev(gscale, F32, "gscale"))
-    _chk(lib().orbit2_lpips_tap_bwd(_p(feats), _p(lin), _p(g), coef, gs, B, HW, Cc, _stream()),
-         "orbit2_lpips_tap_bwd")
+    _call("orbit2_lpips_tap_bwd", feats, lin, g, coef, gscale, B, HW, Cc)
     return g
 
 
 def l1_mean(a, b, out):
     _dev(a, F32, "a"); _dev(b, F32, "b"); _dev(out, F32, "out")
     ws = _ws(lib().orbit2_l1_mean_ws_floats, (a.numel(),), a.device)
-    _chk(lib().orbit2_l1_mean(_p(a), _p(b), _p(out), a.numel(), _p(ws), _stream()), "orbit2_l1_mean")
+    _call("orbit2_l1_mean", a, b, out, a.numel(), ws)
 
 
 def _scored_pair(name, pred, target, lat_w=None, clim=None):
@@ -963,14 +992,13 @@ def eval_moments(pred, target, lat_w=None, clim=None):
     """[B,C,12] float64 sums over a = pred - clim, b = target - clim (see include/orbit2_hip.h:orbit2_eval_moments)"""
     B, Cc, H, W = _scored_pair("eval_moments", pred, target, lat_w, clim)
     out = torch.empty(B, Cc, 12, dtype=torch.float64, device=pred.device)
-    _chk(lib().orbit2_eval_moments(_p(pred), _p(target), target.shape[2], target.shape[3], _p(lat_w), _p(clim), _p(out),
-                                   B, Cc, H, W, _stream()), "orbit2_eval_moments")
+    _call("orbit2_eval_moments", pred, target, target.shape[2], target.shape[3], lat_w, clim, out, B, Cc, H, W)
     return out
 
 
 # ---- missing-data masks (csrc/masked.hip) --------------------------------------------------------------------------------------
 def _mask_args(mask, strides, pred, target):
-    """(pointer, row pitch, batch stride, channel stride) of the mask operand: uint8 device bytes whose `strides` =
+    """(mask, row pitch, batch stride, channel stride) of the mask operand: uint8 device bytes whose `strides` =
     (pitch, batch stride, channel stride) address an H x W crop of at least the prediction's size; (None, 0, 0, 0) without one"""
     if mask is None:
         return None, 0, 0, 0
@@ -980,36 +1008,32 @@ def _mask_args(mask, strides, pred, target):
     if pitch < W or sb < 0 or sc < 0 or mask.numel() < (B - 1) * sb + (Cc - 1) * sc + (H - 1) * pitch + W:
         raise HipBackendError("mask of %d bytes does not hold [%d,%d,%d,%d] at pitch %d and strides (%d, %d)"
                               % (mask.numel(), B, Cc, H, W, pitch, sb, sc))
-    return mask.data_ptr(), pitch, sb, sc
+    return mask, pitch, sb, sc
 
 
 def masked_loss_fwd(pred, target, lat_w, chan_w, kind, mask=None, mask_strides=(0, 0, 0)):
     """(out fp32 [C+1], cnt int64 [C+1]) over the valid pixels (include/orbit2_hip.h:orbit2_masked_loss_fwd); kind 0 = mse,
     1 = bayesian_tv.  mask: uint8 bytes, mask_strides = (row pitch, batch stride, channel stride), a stride of 0 broadcasts."""
-    B, Cc, H, W = _scored_pair("masked_loss_fwd", pred, target, lat_w)
-    if chan_w is not None and _dev(chan_w, F32, "chan_w").numel() != Cc:
-        raise HipBackendError("masked_loss_fwd: chan_w has %d entries for %d channels" % (chan_w.numel(), Cc))
+    B, Cc, H, W = _loss_pair("masked_loss_fwd", pred, target, lat_w, chan_w)
     mp = _mask_args(mask, mask_strides, pred, target)
     out = torch.empty(Cc + 1, dtype=F32, device=pred.device)
     cnt = torch.empty(Cc + 1, dtype=torch.int64, device=pred.device)
-    ws = torch.empty(2 * Cc * B * 64, dtype=F32, device=pred.device)
-    _chk(lib().orbit2_masked_loss_fwd(_p(pred), _p(target), target.shape[2], target.shape[3], *mp, _p(lat_w), _p(chan_w),
-                                      _p(out), _p(cnt), _p(ws), B, Cc, H, W, kind, _stream()), "orbit2_masked_loss_fwd")
+    ws = _loss_ws(B, Cc, pred.device)
+    _call("orbit2_masked_loss_fwd", pred, target, target.shape[2], target.shape[3], *mp, lat_w, chan_w, out, cnt, ws, B, Cc, H, W,
+          kind)
     return out, cnt
 
 
 def masked_loss_bwd(pred, target, lat_w, chan_w, gscale, cnt, kind, mask=None, mask_strides=(0, 0, 0)):
     """dpred = gscale[0] * d(out[C])/dpred; the divisor cnt[C] (masked_loss_fwd's count) is read on the device"""
-    B, Cc, H, W = _scored_pair("masked_loss_bwd", pred, target, lat_w)
-    if chan_w is not None and _dev(chan_w, F32, "chan_w").numel() != Cc:
-        raise HipBackendError("masked_loss_bwd: chan_w has %d entries for %d channels" % (chan_w.numel(), Cc))
+    B, Cc, H, W = _loss_pair("masked_loss_bwd", pred, target, lat_w, chan_w)
     if _dev(cnt, torch.int64, "cnt").numel() != Cc + 1:
         raise HipBackendError("masked_loss_bwd: cnt must be the [C+1] counts of masked_loss_fwd")
     mp = _mask_args(mask, mask_strides, pred, target)
+    _dev(gscale, F32, "gscale")
     dpred = torch.empty_like(pred)
-    _chk(lib().orbit2_masked_loss_bwd(_p(pred), _p(target), target.shape[2], target.shape[3], *mp, _p(lat_w), _p(chan_w),
-                                      _p(_dev(gscale, F32, "gscale")), _p(cnt), _p(dpred), B, Cc, H, W, kind, _stream()),
-         "orbit2_masked_loss_bwd")
+    _call("orbit2_masked_loss_bwd", pred, target, target.shape[2], target.shape[3], *mp, lat_w, chan_w, gscale, cnt, dpred,
+          B, Cc, H, W, kind)
     return dpred
 
 
@@ -1019,8 +1043,7 @@ def masked_moments(pred, target, lat_w=None, clim=None, mask=None, mask_strides=
     B, Cc, H, W = _scored_pair("masked_moments", pred, target, lat_w, clim)
     mp = _mask_args(mask, mask_strides, pred, target)
     out = torch.empty(B, Cc, 13, dtype=torch.float64, device=pred.device)
-    _chk(lib().orbit2_masked_moments(_p(pred), _p(target), target.shape[2], target.shape[3], *mp, _p(lat_w), _p(clim), _p(out),
-                                     B, Cc, H, W, _stream()), "orbit2_masked_moments")
+    _call("orbit2_masked_moments", pred, target, target.shape[2], target.shape[3], *mp, lat_w, clim, out, B, Cc, H, W)
     return out
 
 
@@ -1031,8 +1054,7 @@ def ensemble_update(member, mean, m2, k: int):
     if mean.shape != member.shape or m2.shape != member.shape:
         raise HipBackendError("ensemble_update: member %s, mean %s and m2 %s must have one shape"
                               % (tuple(member.shape), tuple(mean.shape), tuple(m2.shape)))
-    _chk(lib().orbit2_ensemble_update(_p(member), _p(mean), _p(m2), member.numel(), int(k), _stream()),
-         "orbit2_ensemble_update")
+    _call("orbit2_ensemble_update", member, mean, m2, member.numel(), int(k))
 
 
 def gaussian_scores(mean, std, target, lat_w=None):
@@ -1042,8 +1064,7 @@ def gaussian_scores(mean, std, target, lat_w=None):
         raise HipBackendError("gaussian_scores: mean %s and std %s differ in shape" % (tuple(mean.shape), tuple(std.shape)))
     B, Cc, H, W = _scored_pair("gaussian_scores", mean, target, lat_w)
     out = torch.empty(B, Cc, 4, dtype=torch.float64, device=mean.device)
-    _chk(lib().orbit2_gaussian_scores(_p(mean), _p(std), _p(target), target.shape[2], target.shape[3], _p(lat_w), _p(out),
-                                      B, Cc, H, W, _stream()), "orbit2_gaussian_scores")
+    _call("orbit2_gaussian_scores", mean, std, target, target.shape[2], target.shape[3], lat_w, out, B, Cc, H, W)
     return out
 
 
@@ -1059,7 +1080,7 @@ def ensemble_scores(members, target, lat_w=None, *, sums=True, hist=False, seed=
     (quantiles = levels in [0, 1], a sequence or a tensor)."""
     if not torch.is_tensor(members) or members.dim() != 5:
         raise HipBackendError("ensemble_scores takes an [N,B,C,H,W] stack of members")
-    if not members.is_cuda:
+    if not _on_device(members):
         raise HipBackendError("members must be a GPU tensor (HIP backend has no CPU path)")
     if members.dtype != F32:
         raise HipBackendError("members must be %s, got %s" % (F32, members.dtype))
@@ -1093,11 +1114,9 @@ def ensemble_scores(members, target, lat_w=None, *, sums=True, hist=False, seed=
         out["crps_field"] = torch.empty(B, Cc, H, W, dtype=F32, device=dev)
     if levels is not None:
         out["quantiles"] = torch.empty(levels.numel(), B, Cc, H, W, dtype=F32, device=dev)
-    _chk(lib().orbit2_ensemble_scores(_p(members), members.stride(0), N, _p(target), target.shape[2], target.shape[3], _p(lat_w),
-                                      _p(out.get("sums")), _p(out.get("crps_field")), int(crps_field == "fair"),
-                                      _p(out.get("hist")), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(out.get("quantiles")), _p(levels),
-                                      0 if levels is None else levels.numel(), B, Cc, H, W, _stream()),
-         "orbit2_ensemble_scores")
+    _call("orbit2_ensemble_scores", members, members.stride(0), N, target, target.shape[2], target.shape[3], lat_w,
+          out.get("sums"), out.get("crps_field"), int(crps_field == "fair"), out.get("hist"), int(seed) & 0xFFFFFFFFFFFFFFFF,
+          out.get("quantiles"), levels, 0 if levels is None else levels.numel(), B, Cc, H, W)
     return out
 
 
@@ -1123,8 +1142,7 @@ def ssim_sums(pred, target, lat_w=None, data_range=None, ssim_map=False):
             rng = torch.full((B, Cc), float(data_range), dtype=F32, device=pred.device)
     sums = torch.empty(B, Cc, 6, dtype=torch.float64, device=pred.device)
     smap = torch.empty(B, Cc, H - SSIM_WIN + 1, W - SSIM_WIN + 1, dtype=F32, device=pred.device) if ssim_map else None
-    _chk(lib().orbit2_ssim(_p(pred), _p(target), target.shape[2], target.shape[3], _p(lat_w), _p(rng), _p(sums), _p(smap),
-                           B, Cc, H, W, _stream()), "orbit2_ssim")
+    _call("orbit2_ssim", pred, target, target.shape[2], target.shape[3], lat_w, rng, sums, smap, B, Cc, H, W)
     return (sums, smap) if ssim_map else sums
 
 
@@ -1198,8 +1216,7 @@ def resample(x, size, mode="bilinear", channels=None, scale=None, shift=None, ou
         _dev(out, F32, "out")
         if tuple(out.shape) != (B, Cc, H, W):
             raise HipBackendError("resample: out is %s, the result %s" % (tuple(out.shape), (B, Cc, H, W)))
-    _chk(lib().orbit2_resample_fwd(_p(x), _p(idx), Cin, _p(scale), _p(shift), _p(out), B, Cc, h, w, H, W, m, _stream()),
-         "orbit2_resample_fwd")
+    _call("orbit2_resample_fwd", x, idx, Cin, scale, shift, out, B, Cc, h, w, H, W, m)
     return out
 
 
@@ -1209,12 +1226,11 @@ def resample_moments(x, size, mode, target, channels=None, scale=None, shift=Non
     B, Cin, h, w, Cc, H, W, m, idx, scale, shift = _resample_args(x, size, mode, channels, scale, shift, "resample_moments")
     _scored_pair("resample_moments", (B, Cc, H, W), target, lat_w, clim)
     out = torch.empty(B, Cc, 12, dtype=torch.float64, device=x.device)
-    _chk(lib().orbit2_resample_moments(_p(x), _p(idx), Cin, _p(scale), _p(shift), _p(target), target.shape[2], target.shape[3],
-                                       _p(lat_w), _p(clim), _p(out), B, Cc, h, w, H, W, m, _stream()),
-         "orbit2_resample_moments")
+    _call("orbit2_resample_moments", x, idx, Cin, scale, shift, target, target.shape[2], target.shape[3], lat_w, clim, out,
+          B, Cc, h, w, H, W, m)
     return out
 
 
 def seed_salt(value: int, add: bool = False):
     """device-side salt xored into every kernel seed (see include/orbit2_hip.h:orbit2_seed_salt); stream-ordered"""
-    _chk(lib().orbit2_seed_salt(value, int(add), _stream()), "orbit2_seed_salt")
+    _call("orbit2_seed_salt", value, int(add))

@@ -149,6 +149,18 @@ def _needs(ctx, i):
     return ctx.needs_input_grad[i]
 
 
+def _bf16_rows(t, M, N):
+    """t as a contiguous bf16 [M, N] (an incoming gradient, as the kernels read it): t itself when it already is one"""
+    t = t.reshape(M, N)
+    return t if t.dtype == BF and t.is_contiguous() else t.contiguous().to(BF)
+
+
+def _f32(t):
+    """t contiguous and fp32: t itself when it already is"""
+    t = t.contiguous()
+    return t if t.dtype == F32 else t.float()
+
+
 # GELU layers: True = the forward epilogue stores GELU'(pre) x dropout factor (save_dact) and the backward multiplies by it (mul);
 # False = round 2's form (the forward stores the pre-activation, the backward epilogue evaluates GELU' and the mask again)
 _DACT = True
@@ -517,9 +529,7 @@ class BlockFn(torch.autograd.Function):
             x2d, dp1, dp2, h1, mean1, rstd1, qkv, o2d, lse, x1, h2, mean2, rstd2, gsaved, hm = ctx.saved_tensors
         grp, Dl = ctx.grp, H * d
         g1, g2 = (_gate_kw(dp1, L), _gate_kw(dp2, L)) if grp is None else ({}, {})
-        dx2 = dx2.reshape(M, D)
-        if dx2.dtype != BF or not dx2.is_contiguous():
-            dx2 = dx2.contiguous().to(BF)
+        dx2 = _bf16_rows(dx2, M, D)
         # ---- MLP branch   (the four dW GEMMs are queued and issued as one grouped launch at the end)
         dws = _DwBatch()
         dym2, gb2, done2 = _drop_bwd_bias(dx2, M, D, p_mlp, s2, dp2, L, b2)      # fc2's bias gradient rides along
@@ -610,9 +620,7 @@ class ChainFn(torch.autograd.Function):
             x2d, mean, rstd = sv[:3]
             sv = sv[3:]
         nl = len(layers)
-        dy = dy.reshape(M, dy.shape[-1])
-        if dy.dtype != BF or not dy.is_contiguous():
-            dy = dy.contiguous().to(BF)
+        dy = _bf16_rows(dy, M, dy.shape[-1])
         g = _drop_bwd(dy, M, dy.shape[-1], p_out, sds[-1], None, 0)
         grads = [None] * (2 * nl)
         # the weight gradients of the wide layers go out as ONE grouped launch at the end (alone, a D x D weight gradient is
@@ -670,9 +678,7 @@ class LinearFn(torch.autograd.Function):
         M, N, K, p, s, lead = ctx.meta
         W, b = ctx.prm
         (x2d,) = ctx.saved_tensors
-        dy2 = dy.reshape(M, N)
-        if dy2.dtype != BF or not dy2.is_contiguous():
-            dy2 = dy2.contiguous().to(BF)
+        dy2 = _bf16_rows(dy, M, N)
         g = _drop_bwd(dy2, M, N, p, s, None, 0)
         gw, gb = _dw(g, x2d, W, b, M, N, K)
         dx = _dx(g, W, M, N, K).view(*lead, K) if ctx.needs_input_grad[0] else None
@@ -692,7 +698,7 @@ class LayerNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x2d, mean, rstd = ctx.saved_tensors
-        dy2 = dy.reshape(x2d.shape).contiguous().to(BF)
+        dy2 = _bf16_rows(dy, *x2d.shape)
         dx, gg, gb = _ln_bwd(dy2, x2d, ctx.prm[0], ctx.prm[1], mean, rstd, None)
         return dx.view(dy.shape), gg, gb
 
@@ -784,9 +790,7 @@ class TokenTablesFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dcmat):
         lay = ctx.layout
-        dcmat = dcmat.contiguous()
-        if dcmat.dtype != F32:
-            dcmat = dcmat.float()
+        dcmat = _f32(dcmat)
         var_embed = ctx.params[0]
         _hip.tables_scatter(dcmat, lay["w0"].grad, lay["ws"], lay["b0"].grad, lay["bs"], var_embed.grad.view(-1, ctx.D), ctx.ids_t,
                             ctx.V, ctx.D)
@@ -836,9 +840,7 @@ class PosResFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         res, oh, ow, nh, nw, shape = ctx.meta
-        dout = dout.contiguous()
-        if dout.dtype != F32:
-            dout = dout.float()
+        dout = _f32(dout)
         dpe = dsw = dsb = None
         if ctx.needs_input_grad[0]:
             dpe = _hip.posembed_bwd(dout, oh, ow, nh, nw).view(shape)
@@ -862,9 +864,7 @@ class EmbedFn(torch.autograd.Function):
             raise ValueError("input grid %s is not a multiple of patch_size=%d" % ((h, w), P))
         L = (h // P) * (w // P)
         M = B * L
-        xg = xgrid.contiguous()
-        if xg.dtype != F32:
-            xg = xg.float()
+        xg = _f32(xgrid)
         st, gt = stab.contiguous(), gtab.contiguous()
         z, attw = _hip.varagg_fwd(xg, st, gt, H, Dl)
         pr16 = _hip.cast_to_bf16(posres.contiguous())
@@ -886,9 +886,7 @@ class EmbedFn(torch.autograd.Function):
         B, V, h, w, H, D, Dl, L, M, p, s = ctx.meta
         wp, bp = ctx.prm
         xg, gt, attw, z = ctx.saved_tensors
-        d2 = dtok.reshape(M, D)
-        if d2.dtype != BF or not d2.is_contiguous():
-            d2 = d2.contiguous().to(BF)
+        d2 = _bf16_rows(dtok, M, D)
         g = _drop_bwd(d2, M, D, p, s, None, 0)
         dposres = None
         if ctx.needs_input_grad[3]:
@@ -921,9 +919,7 @@ class Conv3x3Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, chan_idx, mode, r, addend):
-        x = x.contiguous()
-        if x.dtype != F32:
-            x = x.float()
+        x = _f32(x)
         wd, bd = weight.detach().contiguous(), bias.detach().contiguous()
         out, pre = _hip.conv3x3_fwd(x, chan_idx, wd, bd, mode, r, None if addend is None else addend.contiguous())
         ctx.meta = (mode, r, None if addend is None else tuple(addend.shape))
@@ -972,9 +968,7 @@ class LossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, lat_w, chan_w, kind):
-        pred = pred.contiguous()
-        if pred.dtype != F32:
-            pred = pred.float()
+        pred = _f32(pred)
         target = target.contiguous()
         out = _hip.loss_fwd(pred, target, lat_w, chan_w, kind)
         ctx.kind = kind
@@ -999,9 +993,7 @@ class MaskedLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, lat_w, chan_w, kind, mask, pitch, sb, sc):
-        pred = pred.contiguous()
-        if pred.dtype != F32:
-            pred = pred.float()
+        pred = _f32(pred)
         target = target.contiguous()
         out, cnt = _hip.masked_loss_fwd(pred, target, lat_w, chan_w, kind, mask, (pitch, sb, sc))
         ctx.kind, ctx.mask_strides = kind, (pitch, sb, sc)

@@ -422,18 +422,17 @@ extern "C" int orbit2_clamp_channel_bwd(const float* img_clamped, float* dimg, i
   return O2_OK;
 }
 
-static const int LOSS_NBLK = 64;
 extern "C" int orbit2_loss_fwd(const float* pred, const float* target, int Ht, int Wt, const float* lat_w,
                                const float* chan_w, float* out, float* ws, int B, int C, int H, int W, int kind,
                                void* stream) {
   if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !out || !ws) return O2_ERR_ARG;
   if (kind < 0 || kind > 2) return O2_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  float* ws2 = ws + (size_t)B * C * LOSS_NBLK;
-  hipLaunchKernelGGL(loss_fwd_kernel, dim3(LOSS_NBLK, B * C), dim3(256), 0, s, pred, target, Ht, Wt, lat_w, chan_w, ws,
+  float* ws2 = ws + (size_t)B * C * ORBIT2_LOSS_BLOCKS;
+  hipLaunchKernelGGL(loss_fwd_kernel, dim3(ORBIT2_LOSS_BLOCKS, B * C), dim3(256), 0, s, pred, target, Ht, Wt, lat_w, chan_w, ws,
                      ws2, C, H, W, kind);
   O2_CHECK_LAUNCH();
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, s, ws, ws2, LOSS_NBLK, B, C, H * W, chan_w, kind, out);
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, s, ws, ws2, ORBIT2_LOSS_BLOCKS, B, C, H * W, chan_w, kind, out);
   O2_CHECK_LAUNCH();
   return O2_OK;
 }

@@ -11,10 +11,10 @@
 // guarded scalar lanes.  The total-variation stencil needs the pixels left and right of the group and the rows above (backward)
 // and below: those edge pixels are scalar loads, and a pixel outside the plane is invalid.
 #include "score_sums.h"
+#include "../../include/orbit2_hip.h"
 
 namespace {
 
-constexpr int ML_NBLK = 64;          // workgroups per (b, c) plane of the forward; the partials are added in this order
 constexpr int MM_NM = O2_NMOMENTS + 1;   // the twelve sums of orbit2_eval_moments + the valid count
 
 struct MaskArg {
@@ -286,15 +286,15 @@ extern "C" int orbit2_masked_loss_fwd(const float* pred, const float* target, in
   MaskArg mk;
   if (!mask_arg(mk, mask, mask_pitch, mask_sb, mask_sc, Ht, Wt, W)) return O2_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  int* wsn = reinterpret_cast<int*>(ws + (size_t)B * C * ML_NBLK);
+  int* wsn = reinterpret_cast<int*>(ws + (size_t)B * C * ORBIT2_LOSS_BLOCKS);
   o2_with_flags(
       [&](auto vec, auto tv) {
-        hipLaunchKernelGGL((masked_loss_fwd_kernel<decltype(vec)::value, decltype(tv)::value>), dim3(ML_NBLK, B * C), dim3(256),
-                           0, s, pred, target, Ht, Wt, mk, lat_w, chan_w, ws, wsn, C, H, W);
+        hipLaunchKernelGGL((masked_loss_fwd_kernel<decltype(vec)::value, decltype(tv)::value>), dim3(ORBIT2_LOSS_BLOCKS, B * C),
+                           dim3(256), 0, s, pred, target, Ht, Wt, mk, lat_w, chan_w, ws, wsn, C, H, W);
       },
       vec_ok(pred, target, mk, W, Wt), kind == 1);
   O2_CHECK_LAUNCH();
-  hipLaunchKernelGGL(masked_loss_final_kernel, dim3(1), dim3(64), 0, s, ws, wsn, ML_NBLK, B, C, out, cnt);
+  hipLaunchKernelGGL(masked_loss_final_kernel, dim3(1), dim3(64), 0, s, ws, wsn, ORBIT2_LOSS_BLOCKS, B, C, out, cnt);
   O2_CHECK_LAUNCH();
   return O2_OK;
 }

@@ -92,6 +92,7 @@ def test_binding_constants_match_the_header():
     defines = dict(re.findall(r"^#define\s+ORBIT2_(\w+)\s+(\d+)", _header(), flags=re.M))
     assert int(defines["ABI_VERSION"]) == _hip.ABI_VERSION == 8
     assert int(defines["GEMM_MAX_GROUP"]) == _hip.GEMM_MAX_GROUP
+    assert int(defines["LOSS_BLOCKS"]) == _hip.LOSS_BLOCKS
     flags = {k: int(v) for k, v in defines.items() if k.startswith("ATTN_")}
     assert flags and flags == {k: getattr(_hip, k) for k in dir(_hip) if k.startswith("ATTN_")}
     assert _hip.lib().orbit2_abi_version() == 8
