@@ -19,7 +19,11 @@ rank_histogram line per output channel are printed, <rank>_mc_rank_hist.npy and 
 
 An optional `baseline: {mode: bilinear}` block (configs/inference_baseline.yaml; nearest, bilinear or bicubic) prints one
 `baseline_scores` line per output variable: the rmse of the stitched field, the rmse of plain interpolation of the model's own
-input, and the mean-squared-error skill of the first against the second (climate_learn.utils.visualize.baseline_scores)."""
+input, and the mean-squared-error skill of the first against the second (climate_learn.utils.visualize.baseline_scores).
+
+An optional `consistency: {mode: bilinear}` block (configs/inference_consistency.yaml; bilinear or bicubic) prints, before any
+`baseline_scores` line, one `consistency_scores` line per output variable: the stitched field coarsened back to the input grid
+with antialiasing and read against the field the model was given (climate_learn.utils.visualize.consistency_scores)."""
 import os
 import sys
 
@@ -31,7 +35,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "orbit-2_amd")]
 
 import climate_learn as cl                                                        # noqa: E402
 from climate_learn.utils.fused_attn import FusedAttn                              # noqa: E402
-from climate_learn.utils.visualize import baseline_scores, stitched_scores, tiled_predict, visualize_at_index      # noqa: E402
+from climate_learn.utils.visualize import (baseline_scores, consistency_scores, stitched_scores, tiled_predict,    # noqa: E402
+                                           visualize_at_index)
 
 
 def main():
@@ -91,6 +96,15 @@ def main():
         # sample on the host); latitude weights as the lat_* metrics build them
         for var, sc in stitched_scores(pred, gt, ov, _lat_weights(dm_vis)).items():
             print("stitched_scores", var, {k: round(v, 6) for k, v in sc.items()}, flush=True)
+    consistency = conf.get("consistency")
+    if consistency:
+        # the stitched field coarsened back to the input grid and read against the input, both normalised as the outputs are;
+        # the coarsened field is scored without being stored (climate_learn.utils.visualize.consistency_scores)
+        from climate_learn.utils.loaders import _interpolation_rescale
+        for var, sc in consistency_scores(x, pred_norm, iv, ov, mode=consistency.get("mode", "bilinear"),
+                                          lat_weights=_lat_weights(dm_vis, pred_norm.shape[2] // x.shape[2]),
+                                          rescale=_interpolation_rescale(dm_vis, ov)).items():
+            print("consistency_scores", var, {k: round(v, 6) for k, v in sc.items()}, flush=True)
     baseline = conf.get("baseline")
     if baseline:
         # the same field read against plain interpolation of its own input, in physical units; the baseline is scored without
@@ -109,13 +123,17 @@ def main():
                                  local_rank, member_scores=scores == "members")
 
 
-def _lat_weights(dm):
-    """cos(latitude) / its mean, as the lat_* metrics build them; None without latitudes"""
+def _lat_weights(dm, coarsen=1):
+    """cos(latitude) / its mean, as the lat_* metrics build them; None without latitudes.  coarsen = s: those of the rows of a
+    grid s times coarser, a row's latitude being the mean of the s rows it covers"""
     lat = dm.get_lat_lon()[0]
     if lat is None:
         return None
     import numpy as np
-    w = np.cos(np.deg2rad(np.asarray(lat, dtype=np.float64)))
+    lat = np.asarray(lat, dtype=np.float64)
+    if coarsen > 1:
+        lat = lat[: len(lat) // coarsen * coarsen].reshape(-1, coarsen).mean(1)
+    w = np.cos(np.deg2rad(lat))
     return torch.from_numpy(w / w.mean()).float()
 
 

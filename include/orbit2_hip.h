@@ -33,7 +33,8 @@ extern "C" {
  * orbit2_attn_fwd_f32, orbit2_layernorm_fwd_f32, orbit2_varagg_fwd_f32, orbit2_unpatchify_fwd_f32; orbit2_ensemble_update and
  * orbit2_gaussian_scores).  Added during version 8, changing nothing that exists: orbit2_ensemble_scores; the folded patch-embed
  * entries that carry the patch size (orbit2_varagg_fwd_p, orbit2_varagg_fwd_f32_p, orbit2_varagg_bwd_p and its two queries);
- * orbit2_ssim; orbit2_resample_fwd and orbit2_resample_moments. */
+ * orbit2_ssim; orbit2_resample_fwd and orbit2_resample_moments; the mode values 5 and 6 of those two (bilinear and bicubic with
+ * ORBIT2_ANTIALIAS), which earlier builds of version 8 refuse with O2_ERR_ARG. */
 int orbit2_abi_version(void);
 
 /* ---- bf16 MFMA GEMM with fused epilogue ------------------------------------------------
@@ -481,8 +482,49 @@ int orbit2_ssim(const float* pred, const float* target, int Ht, int Wt, const fl
  * top-left crop; w = lat_w[y] or 1).  The entry zeroes out and accumulates as orbit2_eval_moments does (fp32 per-lane
  * partials, here over at most TILE_H / 4 x 4 pixels, a wave and workgroup reduction, one double atomic per workgroup and sum).
  * No address depends on a value: non-finite inputs give unspecified values, never a fault.
- * NULL x, out or target, exactly one of scale and shift, chan_idx NULL with C != in_ctotal, a mode outside 0..2, a non-positive
- * size, a target smaller than H x W or B * C > 65535 return O2_ERR_ARG before any launch, with nothing written. */
+ * NULL x, out or target, exactly one of scale and shift, chan_idx NULL with C != in_ctotal, a mode outside 0..2 (and 5, 6: below), a non-positive
+ * size, a target smaller than H x W or B * C > 65535 return O2_ERR_ARG before any launch, with nothing written.
+ *
+ * ANTIALIASED MODES: mode = base | ORBIT2_ANTIALIAS with base 1 (bilinear: 5) or 2 (bicubic: 6) is
+ * F.interpolate(size = (H, W), align_corners = False, antialias = True).  Nearest has no antialiased form: 3, 4, 7, anything
+ * above and anything negative stay O2_ERR_ARG, and 0, 1, 2 run the kernels above, unchanged.  Everything else in this comment
+ * (chan_idx, scale / shift, the target crop, lat_w, clim, the twelve sums, the zeroing of out by the moments entry, every other
+ * refusal) holds for 5 and 6 as it stands; orbit2_resample_moments scores exactly the values orbit2_resample_fwd stores.
+ * An output coordinate o reads a window of the source axis, clipped to the grid (NOT index-clamped) and renormalised; per axis,
+ * fp32, with interp = 2 (bilinear) or 4 (bicubic):
+ *   ratio   = (float)in / (float)out
+ *   support = ratio >= 1 ? (interp / 2) * ratio : interp / 2;    inv = ratio >= 1 ? 1 / ratio : 1
+ *   center  = ratio * (o + 0.5f)
+ *   lo      = max((int)((center - support) + 0.5f), 0);    n = min((int)((center + support) + 0.5f), in) - lo
+ *   raw_j   = f((((float)(j + lo) - center) + 0.5f) * inv),  j = 0 .. n - 1;    weight_j = raw_j / sum_j raw_j
+ *   f bilinear: |x| < 1 ? 1 - |x| : 0
+ *   f bicubic (A = -0.5, not the plain mode's -0.75): |x| < 1 ? ((1.5 |x| - 2.5) |x|) |x| + 1
+ *                                                    : |x| < 2 ? (((|x| - 5) |x| + 8) |x| - 4) * -0.5 : 0
+ * Rounded on their own, never fused: every product above (ratio * (o + 0.5f), the product by inv, each product of the two
+ * polynomials) and every sum and difference.  sum_j raw_j adds the taps in ascending order, starting from 0; the normalisation
+ * is a DIVISION by that sum (skipped if the sum is 0), correctly rounded.  At most 2 ceil(support) + 1 taps, possibly the whole
+ * axis.  A tap on the edge of the support has weight 0 in both filters, so which side of an integer lo or lo + n falls on moves
+ * a pixel by rounding only.
+ * The pixel is separable, horizontal pass first: a row interpolant is weight_0 * src[lo] (a product), then one fused multiply-add
+ * per tap in ascending order, and is ROUNDED TO fp32; the pixel is its rows' interpolants top to bottom in the same way (a
+ * product, then fused multiply-adds), then fmaf(scale[c], r, shift[c]).  The identity (in == out) is exact for finite input; an
+ * antialiased bilinear upsample is the plain one to rounding (two clipped taps are the clamped index), a bicubic one differs
+ * by A and near the borders.
+ * A workgroup owns an ORBIT2_AA_TILE_H x ORBIT2_AA_TILE_W tile and keeps the windows' normalised weights in LDS when the tile's
+ * longest windows KX (columns) and KY (rows) satisfy TILE_W KX <= ORBIT2_AA_WX_FLOATS and TILE_H KY <= ORBIT2_AA_WY_FLOATS and
+ * one row of the tile's source footprint fits ORBIT2_AA_SRC_FLOATS; it then works through the source rows under the tile in
+ * chunks of min(ORBIT2_AA_CHUNK_ROWS, SRC_FLOATS / footprint width) rows staged in LDS.  Otherwise (bicubic beyond a ratio of
+ * about 11, bilinear beyond 23, a long axis reduced to a few pixels) it forms the weights where it uses them and reads the taps
+ * from global memory, in chunks of CHUNK_ROWS rows.  The choice is per workgroup; the operations and their order are the same,
+ * so are the bits.  LDS use does not depend on the sizes.  Per-lane fp32 partial sums of the moments cover 4 pixels here.
+ * No window index depends on a value: non-finite inputs give unspecified values, never a fault. */
+#define ORBIT2_ANTIALIAS 4
+#define ORBIT2_AA_TILE_H 16
+#define ORBIT2_AA_TILE_W 64
+#define ORBIT2_AA_CHUNK_ROWS 32
+#define ORBIT2_AA_SRC_FLOATS 6144
+#define ORBIT2_AA_WX_FLOATS 3072
+#define ORBIT2_AA_WY_FLOATS 768
 #define ORBIT2_RESAMPLE_TILE_H 32
 #define ORBIT2_RESAMPLE_TILE_W 256
 #define ORBIT2_RESAMPLE_LDS_FLOATS 10240

@@ -1149,6 +1149,7 @@ def ssim_sums(pred, target, lat_w=None, data_range=None, ssim_map=False):
 RESAMPLE_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}
 RESAMPLE_TILE = (32, 256)       # (ORBIT2_RESAMPLE_TILE_H, ORBIT2_RESAMPLE_TILE_W): output pixels per workgroup
 RESAMPLE_LDS_FLOATS = 10240     # ORBIT2_RESAMPLE_LDS_FLOATS: the staged source window of a tile
+ANTIALIAS = 4                   # ORBIT2_ANTIALIAS: or-ed into the mode code of bilinear and bicubic
 
 
 _RESAMPLE_IDX = {}              # (channels, device) -> the validated device int32 copy
@@ -1161,12 +1162,14 @@ def resample_staged(h: int, w: int, H: int, W: int) -> bool:
     return (-(-th * h // H) + 4) * (-(-tw * w // W) + 4) <= RESAMPLE_LDS_FLOATS
 
 
-def _resample_args(x, size, mode, channels, scale, shift, what):
+def _resample_args(x, size, mode, channels, scale, shift, what, antialias=False):
     """the checked operands both resample entries share: (B, Cin, h, w, C, H, W, mode code, chan_idx, scale, shift)"""
     if not torch.is_tensor(x) or x.dim() != 4:
         raise HipBackendError("%s takes an [B,C,h,w] field" % what)
     if mode not in RESAMPLE_MODES:
         raise HipBackendError("%s: mode is one of %s, got %r" % (what, ", ".join(RESAMPLE_MODES), mode))
+    if antialias and mode == "nearest":
+        raise HipBackendError("%s: antialias goes with bilinear or bicubic, nearest has no antialiased form" % what)
     try:
         H, W = (int(v) for v in size)
     except (TypeError, ValueError):
@@ -1202,14 +1205,15 @@ def _resample_args(x, size, mode, channels, scale, shift, what):
         if scale.numel() != Cc or shift.numel() != Cc:
             raise HipBackendError("%s: scale (%d) and shift (%d) need one entry per output channel (%d)"
                                   % (what, scale.numel(), shift.numel(), Cc))
-    return B, Cin, h, w, Cc, H, W, RESAMPLE_MODES[mode], idx, scale, shift
+    return B, Cin, h, w, Cc, H, W, RESAMPLE_MODES[mode] | (ANTIALIAS if antialias else 0), idx, scale, shift
 
 
-def resample(x, size, mode="bilinear", channels=None, scale=None, shift=None, out=None):
+def resample(x, size, mode="bilinear", channels=None, scale=None, shift=None, out=None, antialias=False):
     """fp32 [B,C,H,W]: F.interpolate(x[:, channels], size, mode, align_corners=False) * scale[c] + shift[c] in one kernel
     (include/orbit2_hip.h:orbit2_resample_fwd).  mode: nearest, bilinear or bicubic; channels: input channel of every output
-    channel (None = all, in order); scale / shift: [C], both or neither; out: a contiguous fp32 [B,C,H,W] to write into."""
-    B, Cin, h, w, Cc, H, W, m, idx, scale, shift = _resample_args(x, size, mode, channels, scale, shift, "resample")
+    channel (None = all, in order); scale / shift: [C], both or neither; out: a contiguous fp32 [B,C,H,W] to write into;
+    antialias: F.interpolate's antialias=True (bilinear and bicubic only), the mode code with ORBIT2_ANTIALIAS."""
+    B, Cin, h, w, Cc, H, W, m, idx, scale, shift = _resample_args(x, size, mode, channels, scale, shift, "resample", antialias)
     if out is None:
         out = torch.empty(B, Cc, H, W, dtype=F32, device=x.device)
     else:
@@ -1220,10 +1224,11 @@ def resample(x, size, mode="bilinear", channels=None, scale=None, shift=None, ou
     return out
 
 
-def resample_moments(x, size, mode, target, channels=None, scale=None, shift=None, lat_w=None, clim=None):
+def resample_moments(x, size, mode, target, channels=None, scale=None, shift=None, lat_w=None, clim=None, antialias=False):
     """[B,C,12] float64: eval_moments(resample(x, ...), target, lat_w, clim) without the resampled field ever being stored
     (include/orbit2_hip.h:orbit2_resample_moments); the target may be larger than (H, W) (top-left crop)"""
-    B, Cin, h, w, Cc, H, W, m, idx, scale, shift = _resample_args(x, size, mode, channels, scale, shift, "resample_moments")
+    B, Cin, h, w, Cc, H, W, m, idx, scale, shift = _resample_args(x, size, mode, channels, scale, shift, "resample_moments",
+                                                                  antialias)
     _scored_pair("resample_moments", (B, Cc, H, W), target, lat_w, clim)
     out = torch.empty(B, Cc, 12, dtype=torch.float64, device=x.device)
     _call("orbit2_resample_moments", x, idx, Cin, scale, shift, target, target.shape[2], target.shape[3], lat_w, clim, out,

@@ -38,6 +38,7 @@ class Resampled:
     channels: Optional[Tuple[int, ...]] = None
     scale: Optional[torch.Tensor] = None
     shift: Optional[torch.Tensor] = None
+    antialias: bool = False
 
     @property
     def shape(self):
@@ -49,11 +50,13 @@ class Resampled:
         return self.x.device
 
     def materialize(self, out=None):
-        return _hip.resample(self.x, self.size, self.mode, self.channels, self.scale, self.shift, out=out)
+        return _hip.resample(self.x, self.size, self.mode, self.channels, self.scale, self.shift, out=out,
+                             antialias=self.antialias)
 
     def moments(self, target, lat_w=None, clim=None):
         """[B,C,12] float64 sums of _hip.eval_moments(self.materialize(), target, lat_w, clim), without the field"""
-        return _hip.resample_moments(self.x, self.size, self.mode, target, self.channels, self.scale, self.shift, lat_w, clim)
+        return _hip.resample_moments(self.x, self.size, self.mode, target, self.channels, self.scale, self.shift, lat_w, clim,
+                                     antialias=self.antialias)
 
     def affine(self, std, mean):
         """this field times std[c] plus mean[c] (a Denormalize), folded into scale and shift: still one pass, nothing stored"""
@@ -68,22 +71,26 @@ class Resampled:
 class Interpolation(nn.Module):
     """size: the output (H, W); or superres_mag: the output is the input's size times it (what tiled_predict and
     trainer.evaluate_func expect of a model).  Exactly one of the two.  mode: nearest, bilinear or bicubic, as F.interpolate
-    defines them at align_corners=False without antialiasing.  channels: the input channel of every output channel; scale,
-    shift: per output channel, both or neither.  No parameters, no autograd."""
+    defines them at align_corners=False; antialias: its antialias=True (bilinear and bicubic only: the filter widens with a
+    downsampling ratio).  channels: the input channel of every output channel; scale, shift: per output channel, both or
+    neither.  No parameters, no autograd."""
 
     def __init__(self, size=None, mode: str = "bilinear", superres_mag: Optional[int] = None,
-                 channels: Optional[Sequence[int]] = None, scale=None, shift=None):
+                 channels: Optional[Sequence[int]] = None, scale=None, shift=None, antialias: bool = False):
         super().__init__()
         if (size is None) == (superres_mag is None):
             raise ValueError("Interpolation takes exactly one of size and superres_mag")
         if mode not in MODES:
             raise ValueError("Interpolation mode is one of %s, got %r" % (", ".join(MODES), mode))
+        if antialias and mode == "nearest":
+            raise ValueError("Interpolation: antialias goes with bilinear or bicubic, nearest has no antialiased form")
         if (scale is None) != (shift is None):
             raise ValueError("Interpolation takes scale and shift together or not at all")
         if superres_mag is not None and (int(superres_mag) != superres_mag or superres_mag < 1):
             raise ValueError("superres_mag is a positive integer, got %r" % (superres_mag,))
         self.size = None if size is None else (int(size[0]), int(size[1]))
         self.mode = mode
+        self.antialias = bool(antialias)
         self.superres_mag = None if superres_mag is None else int(superres_mag)
         self.channels = None if channels is None else tuple(int(c) for c in channels)
         self.scale = None if scale is None else torch.as_tensor(scale, dtype=torch.float32).reshape(-1)
@@ -104,11 +111,11 @@ class Interpolation(nn.Module):
         x = x.detach().float().contiguous()
         scale = None if self.scale is None else self.scale.to(x.device)
         shift = None if self.shift is None else self.shift.to(x.device)
-        return Resampled(x, size, self.mode, self._channels(in_variables, out_variables), scale, shift)
+        return Resampled(x, size, self.mode, self._channels(in_variables, out_variables), scale, shift, self.antialias)
 
     def forward(self, x, in_variables=None, out_variables=None):
         return self.lazy(x, in_variables, out_variables).materialize()
 
     def extra_repr(self):
-        return "size=%s, mode=%s, superres_mag=%s, channels=%s, affine=%s" % (self.size, self.mode, self.superres_mag,
-                                                                              self.channels, self.scale is not None)
+        return "size=%s, mode=%s, superres_mag=%s, channels=%s, affine=%s, antialias=%s" % (
+            self.size, self.mode, self.superres_mag, self.channels, self.scale is not None, self.antialias)

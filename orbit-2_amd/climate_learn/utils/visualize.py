@@ -193,6 +193,48 @@ def baseline_scores(x, y, in_variables, out_variables, pred, mode="bilinear", la
     return {v: {k: float(col[c]) for k, col in cols.items()} for c, v in enumerate(out_variables)}
 
 
+def consistency_scores(x, pred, in_variables, out_variables, mode="bilinear", lat_weights=None, rescale=None):
+    """A prediction read against its own input: {variable: {"consistency_rmse", "consistency_bias"}} (plus
+    "lat_consistency_rmse" when `lat_weights`, those of the LOW-resolution rows, is given).  A downscaled field that is sharp
+    but does not average back to the field the model was given is wrong in a way no score against the target shows.
+    x [B,V,h,w] the normalised input, pred [B,C,H,W] the normalised prediction (e.g. from tiled_predict).  With s = H // h the
+    prediction is coarsened to (H // s, W // s) in `mode` (bilinear or bicubic) WITH antialiasing and scored against x's
+    channels named by `out_variables`, through their top-left crop where the prediction covers less than x.  Those channels are
+    gathered here (the tensor is low-resolution); `rescale` = (scale, shift) per output variable moves them from the inputs'
+    normalisation to the outputs', as utils.loaders builds it for the baseline.  The coarsened field is never stored: a
+    models.hub.Resampled is scored in the pass that resamples it (one pass, a second one for the latitude-weighted column).
+    consistency_rmse is the root mean squared difference per image, averaged over the batch (metrics.functional.rmse);
+    consistency_bias is mean(coarsened - input).  Constant output channels (CONSTANTS) are reported as baseline_scores
+    reports them: both 0."""
+    from ..data.processing.era5_constants import CONSTANTS
+    from ..metrics import functional as fn
+    from ..models.hub.interpolation import Resampled
+    pred = pred.detach().float().contiguous()
+    B, C, H, W = pred.shape
+    s = H // x.shape[2]
+    if s < 1 or H // s > x.shape[2] or W // s > x.shape[3]:
+        raise ValueError("consistency_scores: a prediction of %s does not coarsen onto an input of %s"
+                         % (tuple(pred.shape), tuple(x.shape)))
+    in_variables = list(in_variables)
+    if any(v not in in_variables for v in out_variables):
+        raise RuntimeError("consistency_scores requires the output variables to be among the input variables.")
+    given = x.detach().float()[:, [in_variables.index(v) for v in out_variables]]
+    if rescale is not None and rescale[0] is not None:
+        scale, shift = (torch.as_tensor(v, dtype=torch.float32, device=given.device).view(1, -1, 1, 1) for v in rescale)
+        given = given * scale + shift
+    given = given.contiguous()
+    coarse = Resampled(pred, (H // s, W // s), mode, antialias=True)
+    n = coarse.shape[2] * coarse.shape[3]
+    const = torch.tensor([v in CONSTANTS for v in out_variables])
+    m = coarse.moments(given, None).cpu()                                                   # [B,C,12] float64
+    cols = {"consistency_rmse": (m[..., 5] / n).sqrt().mean(0).masked_fill(const, 0.0),
+            "consistency_bias": ((m[..., 0] - m[..., 1]).sum(0) / (B * n)).masked_fill(const, 0.0)}
+    if lat_weights is not None:
+        m = coarse.moments(given, fn._lat(lat_weights, coarse)).cpu()
+        cols["lat_consistency_rmse"] = (m[..., 5] / n).sqrt().mean(0).masked_fill(const, 0.0)
+    return {v: {k: float(col[c]) for k, col in cols.items()} for c, v in enumerate(out_variables)}
+
+
 def visualize_at_index(mm, dm, dm_vis, out_list, in_transform, out_transform, variable, src, device, div, overlap, index=0,
                        tensor_par_size=1, tensor_par_group=None, save_png: bool = True, prefix: str = ""):
     """Stitched input / prediction / ground truth of test sample `index` for `variable` (reference :38-490; the PNG

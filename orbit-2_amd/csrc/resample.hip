@@ -2,6 +2,8 @@
 // of gathered channels of an fp32 [B, in_ctotal, h, w] field, with an optional per-channel affine, either stored
 // (orbit2_resample_fwd) or scored against a target without ever being stored (orbit2_resample_moments: the twelve sums of
 // orbit2_eval_moments).  include/orbit2_hip.h: orbit2_resample_*; models/hub/interpolation.py; DESIGN 4.10c.
+// The antialiased forms of bilinear and bicubic (mode | ORBIT2_ANTIALIAS) have a kernel of their own further down; what follows
+// here is the plain modes'.
 //
 // A workgroup owns one RS_TH x RS_TW tile of one (b, c) output image.  A lane owns FOUR CONSECUTIVE output columns, so a wave
 // covers the tile's 256 columns and stores (or reads the target as) one float4 per lane and row; wave v takes rows v, v + 4, ...
@@ -207,6 +209,222 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
   if (MOMENTS) o2_block_sums_add(s, sums + (size_t)bc * RS_NM);
 }
 
+// ---- antialiased bilinear / bicubic (mode | ORBIT2_ANTIALIAS): F.interpolate(..., antialias=True) -----------------------------
+// An output coordinate o reads a WINDOW of the source axis whose length grows with the downsampling ratio (include/orbit2_hip.h
+// states the rule): lo .. lo + n - 1, clipped to the grid, with weights f(.) / sum f(.).  The pixel is separable, horizontal
+// pass first.  A workgroup owns an AA_TH x AA_TW output tile of one (b, c) image; thread t owns row t / 16 and the four
+// consecutive columns 4 (t % 16) .. + 3 of it (one float4 store or target read, as in the plain kernel).
+//   1. threads 0 .. AA_TW - 1 form the window and the weight sum of one tile column each, the next AA_TH threads those of a
+//      tile row; when the tile's longest windows fit (AA_TW KX <= AA_WX, AA_TH KY <= AA_WY, KX / KY the longest window of a
+//      column / row) the normalised weights go into LDS tables of pitch KX / KY, once per workgroup.
+//   2. the source rows under the tile, ylo .. yhi - 1, are worked through in chunks of at most AA_CR rows, and of as many as
+//      AA_SRC floats hold at the tile's footprint width: staged coalesced (a wave per row), then the horizontal pass writes
+//      mid[chunk row][tile column], then every thread adds the rows of the chunk that its own vertical window covers to its four
+//      accumulators.  Chunks ascend, so a pixel's rows are still added top to bottom.  LDS is bounded whatever the ratio.
+//   3. a tile whose windows or footprint width do not fit (a ratio beyond about 11 for bicubic, 23 for bilinear, or a whole long
+//      axis reduced to a few pixels) runs the same loops with the weights formed where they are used and the taps read from
+//      global memory: the same operations in the same order, hence the same bits.
+// Every window index is formed from the sizes alone and clipped into the grid: no address depends on a data value.
+constexpr int AA_TH = ORBIT2_AA_TILE_H, AA_TW = ORBIT2_AA_TILE_W, AA_CR = ORBIT2_AA_CHUNK_ROWS, AA_SRC = ORBIT2_AA_SRC_FLOATS;
+constexpr int AA_WX = ORBIT2_AA_WX_FLOATS, AA_WY = ORBIT2_AA_WY_FLOATS;
+constexpr int AA_MP = AA_TW + 4;                  // pitch of mid: float4 reads stay aligned, a column's rows spread over banks
+static_assert(AA_TW == 64 && AA_TH == 16, "256 threads: sixteen rows of sixteen float4 columns");
+static_assert(AA_TW + AA_TH <= 256 && AA_CR >= 1 && AA_SRC >= 1, "one thread per tile column and row forms its window");
+
+// the filter at x: bilinear 1 - |x|; bicubic the cubic convolution with A = -0.5, in Horner form, every product on its own
+template <int MODE>
+__device__ __forceinline__ float aa_filter(float x) {
+  x = fabsf(x);
+  if (MODE == 1) return x < 1.f ? 1.f - x : 0.f;
+  if (x < 1.f) return rs_rounded(rs_rounded((rs_rounded(1.5f * x) - 2.5f) * x) * x) + 1.f;
+  if (x < 2.f) return rs_rounded((rs_rounded((rs_rounded((x - 5.f) * x) + 8.f) * x) - 4.f) * -0.5f);
+  return 0.f;
+}
+
+// the weight of tap j of a window that starts at lo, before (raw) and after normalisation by the window's sum
+template <int MODE>
+__device__ __forceinline__ float aa_raw(int j, int lo, float center, float inv) {
+  return aa_filter<MODE>(rs_rounded((((float)(j + lo) - center) + 0.5f) * inv));
+}
+__device__ __forceinline__ float aa_norm(float raw, float total) { return total != 0.f ? raw / total : raw; }
+
+// window (lo, n), centre and weight sum of output coordinate o
+template <int MODE>
+__device__ __forceinline__ void aa_window(int o, int n_in, float ratio, float sup, float inv, int& lo, int& n, float& center,
+                                          float& total) {
+  center = rs_rounded(ratio * ((float)o + 0.5f));
+  const int a = (int)((center - sup) + 0.5f), b = (int)((center + sup) + 0.5f);
+  lo = min(max(a, 0), n_in - 1);                  // finite sizes give 0 <= lo < hi <= n_in already; the clips are the guarantee
+  n = max(min(b, n_in), lo + 1) - lo;
+  total = 0.f;
+  for (int j = 0; j < n; ++j) total += aa_raw<MODE>(j, lo, center, inv);
+}
+
+struct aa_axes {                                  // the tile's windows, in LDS
+  int xlo[AA_TW], xn[AA_TW], ylo[AA_TH], yn[AA_TH];
+  float xc[AA_TW], xt[AA_TW], yc[AA_TH], yt[AA_TH];
+  int kmax[2];
+};
+
+// the chunk loop.  FIT: weights from the tables, taps from the staged chunk; else weights formed in place, taps from global memory
+template <int MODE, bool FIT>
+__device__ __forceinline__ void aa_chunks(const float* __restrict__ src, int w, const aa_axes& ax, float* win, float* mid,
+                                          const float* tabx, const float* taby, int KX, int KY, float invy, float invx,
+                                          int ncol, bool live, float (&acc)[4]) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int xlo = ax.xlo[0], fw = ax.xlo[AA_TW - 1] + ax.xn[AA_TW - 1] - xlo, fwp = fw | 1;     // odd pitch: rows spread over banks
+  const int ylo = ax.ylo[0], yhi = ax.ylo[AA_TH - 1] + ax.yn[AA_TH - 1];
+  const int cr_max = FIT ? min(AA_CR, AA_SRC / fwp) : AA_CR;
+  const int i = tid >> 4, c4 = 4 * (tid & 15);
+  const int mylo = ax.ylo[i], myhi = live ? mylo + ax.yn[i] : mylo;       // a thread past the image adds nothing
+  const float myc = ax.yc[i], myt = ax.yt[i];
+  for (int r0 = ylo; r0 < yhi; r0 += cr_max) {
+    const int cr = min(cr_max, yhi - r0);
+    if (FIT) {
+      for (int r = tid >> 6; r < cr; r += 4)
+        for (int q = lane; q < fw; q += 64) win[r * fwp + q] = src[(size_t)(r0 + r) * w + xlo + q];
+    }
+    __syncthreads();                              // the chunk is staged, and the previous chunk's mid has been read
+    // horizontal pass: a thread takes one tile column inside the image (mid beyond them is never used) and the four chunk rows
+    // g, g + ng, g + 2 ng, g + 3 ng, so a weight is read (or formed) once for four taps; g runs fastest, so a wave reads
+    // consecutive rows of a few columns, which the odd pitch spreads over the banks
+    const int ng = (cr + 3) >> 2;
+    for (int idx = tid; idx < ng * ncol; idx += 256) {
+      const int c = idx / ng, g = idx - c * ng;
+      const int lo = ax.xlo[c], n = ax.xn[c];
+      const float* row[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int r = g + k * ng < cr ? g + k * ng : g;        // a row past the chunk repeats row g and is not stored
+        row[k] = FIT ? win + r * fwp + (lo - xlo) : src + (size_t)(r0 + r) * w + lo;
+      }
+      const float* wt = tabx + c * KX;
+      const float ctr = ax.xc[c], tot = ax.xt[c];
+      float t[4];
+      const float w0 = FIT ? wt[0] : aa_norm(aa_raw<MODE>(0, lo, ctr, invx), tot);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) t[k] = w0 * row[k][0];
+      for (int q = 1; q < n; ++q) {
+        const float wq = FIT ? wt[q] : aa_norm(aa_raw<MODE>(q, lo, ctr, invx), tot);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) t[k] = fmaf(wq, row[k][q], t[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (g + k * ng < cr) mid[(g + k * ng) * AA_MP + c] = t[k];
+    }
+    __syncthreads();
+    const int ka = max(r0, mylo), kb = min(r0 + cr, myhi);
+    for (int r = ka; r < kb; ++r) {
+      const float wy = FIT ? taby[i * KY + (r - mylo)] : aa_norm(aa_raw<MODE>(r - mylo, mylo, myc, invy), myt);
+      const float4 m = *reinterpret_cast<const float4*>(mid + (r - r0) * AA_MP + c4);
+      const float mv[4] = {m.x, m.y, m.z, m.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] = r == mylo ? wy * mv[j] : fmaf(wy, mv[j], acc[j]);
+    }
+  }
+}
+
+template <int MODE, bool MOMENTS>
+__global__ __launch_bounds__(256) void resample_aa_kernel(const float* __restrict__ x, const int* __restrict__ chan_idx,
+                                                          int in_ctotal, const float* __restrict__ scale,
+                                                          const float* __restrict__ shift, float* __restrict__ out,
+                                                          const float* __restrict__ target, int Ht, int Wt,
+                                                          const float* __restrict__ lat_w, const float* __restrict__ clim,
+                                                          double* __restrict__ sums, int C, int h, int w, int H, int W, int ntx,
+                                                          float ry, float rx, float supy, float supx, float invy, float invx) {
+  __shared__ float win[AA_SRC];
+  __shared__ __attribute__((aligned(16))) float mid[AA_CR * AA_MP];
+  __shared__ float tabx[AA_WX], taby[AA_WY];
+  __shared__ aa_axes ax;
+  const int tid = threadIdx.x;
+  const int bc = blockIdx.y, b = bc / C, c = bc - b * C;
+  const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
+  const int y0 = ty * AA_TH, x0 = tx * AA_TW;
+  const int ci = chan_idx ? chan_idx[c] : c;
+  const float* src = x + ((size_t)b * in_ctotal + ci) * h * w;
+  if (tid < 2) ax.kmax[tid] = 0;
+  __syncthreads();
+  // a column or row past the image takes the last one's window: in range, never stored or summed
+  if (tid < AA_TW) {
+    aa_window<MODE>(min(x0 + tid, W - 1), w, rx, supx, invx, ax.xlo[tid], ax.xn[tid], ax.xc[tid], ax.xt[tid]);
+    atomicMax(&ax.kmax[0], ax.xn[tid]);
+  } else if (tid < AA_TW + AA_TH) {
+    const int i = tid - AA_TW;
+    aa_window<MODE>(min(y0 + i, H - 1), h, ry, supy, invy, ax.ylo[i], ax.yn[i], ax.yc[i], ax.yt[i]);
+    atomicMax(&ax.kmax[1], ax.yn[i]);
+  }
+  __syncthreads();
+  const int KX = ax.kmax[0], KY = ax.kmax[1];
+  const int fwp = (ax.xlo[AA_TW - 1] + ax.xn[AA_TW - 1] - ax.xlo[0]) | 1;
+  const bool fit = (int64_t)KX * AA_TW <= AA_WX && (int64_t)KY * AA_TH <= AA_WY && fwp <= AA_SRC;     // the same in every thread
+  const int y = y0 + (tid >> 4), xl = x0 + 4 * (tid & 15);
+  const int ncol = min(AA_TW, W - x0);
+  const bool live = y < H && xl < W;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  if (fit) {
+    if (tid < AA_TW) {
+      for (int j = 0; j < ax.xn[tid]; ++j)
+        tabx[tid * KX + j] = aa_norm(aa_raw<MODE>(j, ax.xlo[tid], ax.xc[tid], invx), ax.xt[tid]);
+    } else if (tid < AA_TW + AA_TH) {
+      const int i = tid - AA_TW;
+      for (int j = 0; j < ax.yn[i]; ++j) taby[i * KY + j] = aa_norm(aa_raw<MODE>(j, ax.ylo[i], ax.yc[i], invy), ax.yt[i]);
+    }
+    // its first barrier publishes the tables
+    aa_chunks<MODE, true>(src, w, ax, win, mid, tabx, taby, KX, KY, invy, invx, ncol, live, acc);
+  } else {
+    aa_chunks<MODE, false>(src, w, ax, win, mid, tabx, taby, KX, KY, invy, invx, ncol, live, acc);
+  }
+
+  float s[RS_NM];
+#pragma unroll
+  for (int k = 0; k < RS_NM; ++k) s[k] = 0.f;
+  if (live) {
+    if (scale) {
+      const float sc = scale[c], sh = shift[c];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] = fmaf(sc, acc[j], sh);
+    }
+    const bool full = xl + 3 < W;
+    if (!MOMENTS) {
+      float* o = out + ((size_t)bc * H + y) * W + xl;
+      // one float4 where the thread's four columns exist and sit on a 16-byte boundary, as in the plain kernel
+      if (full && ((uintptr_t)o & 15) == 0) {
+        *reinterpret_cast<float4*>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (xl + j < W) o[j] = acc[j];
+      }
+    } else {
+      const float* t = target + ((size_t)bc * Ht + y) * Wt + xl;
+      const float* cl = clim ? clim + ((size_t)c * H + y) * W + xl : nullptr;
+      float tv[4], cv[4] = {0.f, 0.f, 0.f, 0.f};
+      if (full && ((uintptr_t)t & 15) == 0) {
+        const float4 q = *reinterpret_cast<const float4*>(t);
+        tv[0] = q.x, tv[1] = q.y, tv[2] = q.z, tv[3] = q.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tv[j] = xl + j < W ? t[j] : 0.f;
+      }
+      if (cl) {
+        if (full && ((uintptr_t)cl & 15) == 0) {
+          const float4 q = *reinterpret_cast<const float4*>(cl);
+          cv[0] = q.x, cv[1] = q.y, cv[2] = q.z, cv[3] = q.w;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) cv[j] = xl + j < W ? cl[j] : 0.f;
+        }
+      }
+      const float lw = lat_w ? lat_w[y] : 1.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (xl + j < W) o2_moments_add(s, acc[j] - cv[j], tv[j] - cv[j], lw);
+    }
+  }
+  if (MOMENTS) o2_block_sums_add(s, sums + (size_t)bc * RS_NM);
+}
+
 // ceil(tile * in / out) + 4: no window of a tile at this ratio is larger (a bicubic footprint is the span of the floors + 4)
 inline int64_t rs_footprint(int tile, int n_in, int n_out) { return ((int64_t)tile * n_in + n_out - 1) / n_out + 4; }
 
@@ -215,17 +433,35 @@ int rs_launch(const float* x, const int* chan_idx, int in_ctotal, const float* s
               const float* target, int Ht, int Wt, const float* lat_w, const float* clim, double* sums, int B, int C, int h,
               int w, int H, int W, int mode, hipStream_t s) {
   if (!x || (MOMENTS ? (!sums || !target) : !out) || (scale == nullptr) != (shift == nullptr)) return O2_ERR_ARG;
-  if (B <= 0 || C <= 0 || in_ctotal <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || mode < 0 || mode > 2) return O2_ERR_ARG;
+  if (B <= 0 || C <= 0 || in_ctotal <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return O2_ERR_ARG;
+  // 0, 1, 2 plain; bilinear and bicubic also with ORBIT2_ANTIALIAS (5, 6); nearest has no antialiased form
+  const bool aa = mode == (1 | ORBIT2_ANTIALIAS) || mode == (2 | ORBIT2_ANTIALIAS);
+  if (!aa && (mode < 0 || mode > 2)) return O2_ERR_ARG;
   if (!chan_idx && C != in_ctotal) return O2_ERR_ARG;
   if (MOMENTS && (Ht < H || Wt < W)) return O2_ERR_ARG;
   if ((int64_t)B * C > 65535) return O2_ERR_ARG;
-  const int ntx = (W + RS_TW - 1) / RS_TW, nty = (H + RS_TH - 1) / RS_TH;
+  const int ntx = (W + (aa ? AA_TW : RS_TW) - 1) / (aa ? AA_TW : RS_TW), nty = (H + (aa ? AA_TH : RS_TH) - 1) / (aa ? AA_TH : RS_TH);
   if ((int64_t)ntx * nty > INT32_MAX) return O2_ERR_ARG;
   if (MOMENTS && hipMemsetAsync(sums, 0, sizeof(double) * (size_t)B * C * RS_NM, s) != hipSuccess) return O2_ERR_LAUNCH;
   const int stage = rs_footprint(RS_TH, h, H) * rs_footprint(RS_TW, w, W) <= RS_LDS;
   const dim3 grid(ntx * nty, B * C);
   // the two ratios of the contract, one correctly rounded fp32 division each: formed here once, not by every thread
   const float ry = (float)h / (float)H, rx = (float)w / (float)W;
+  if (aa) {
+    // support and inverse scale of the contract, one fp32 operation each: a window spans interp / 2 source pixels per unit of
+    // max(ratio, 1) to either side of its centre
+    const float half = mode == (1 | ORBIT2_ANTIALIAS) ? 1.f : 2.f;
+    const float supy = ry >= 1.f ? half * ry : half, supx = rx >= 1.f ? half * rx : half;
+    const float invy = ry >= 1.f ? 1.f / ry : 1.f, invx = rx >= 1.f ? 1.f / rx : 1.f;
+#define RS_AA_GO(M)                                                                                                            \
+  hipLaunchKernelGGL((resample_aa_kernel<M, MOMENTS>), grid, dim3(256), 0, s, x, chan_idx, in_ctotal, scale, shift, out, target, \
+                     Ht, Wt, lat_w, clim, sums, C, h, w, H, W, ntx, ry, rx, supy, supx, invy, invx)
+    if (mode == (1 | ORBIT2_ANTIALIAS)) RS_AA_GO(1);
+    else RS_AA_GO(2);
+#undef RS_AA_GO
+    O2_CHECK_LAUNCH();
+    return O2_OK;
+  }
 #define RS_GO(M)                                                                                                             \
   hipLaunchKernelGGL((resample_kernel<M, MOMENTS>), grid, dim3(256), 0, s, x, chan_idx, in_ctotal, scale, shift, out, target, \
                      Ht, Wt, lat_w, clim, sums, C, h, w, H, W, ntx, stage, ry, rx)

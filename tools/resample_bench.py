@@ -16,8 +16,17 @@ moments legs, per mode:
   aten+     `F.interpolate`, then `_hip.eval_moments`;
   moments   `_hip.eval_moments` alone on a resident field (what reading two fields costs).
 GB/s is each leg's time over the bytes it MUST move: the three source channels read plus the field written (ours, aten), plus
-the target read (fused), plus the field written, read back and the target read (two-step, aten+).  A tool beside bench.py, not
-part of it."""
+the target read (fused), plus the field written, read back and the target read (two-step, aten+).
+
+    python tools/resample_bench.py --antialias [--md profiles/resample_aa.md] [--rounds 5]
+
+measures the antialiased modes instead (the coarsening of a consistency score): x [16, 3, 512, 1024] -> [16, 3, 128, 256] (4x)
+and -> [16, 3, 64, 128] (8x), bilinear and bicubic, the same alternation and events.  Legs per size and mode: ours
+(`_hip.resample(..., antialias=True)` into a resident output), aten (`F.interpolate(..., antialias=True)`), fused
+(`_hip.resample_moments(..., antialias=True)`), two-step (ours, then `_hip.eval_moments`); and once, copy-src: `copy_` of the
+source field (the source bytes read and written once: no resampling kernel reads them faster).  GB/s counts the source read plus
+the field written (plus the target for fused, plus the field's second trip for two-step).  A tool beside bench.py, not part of
+it."""
 import argparse
 import json
 import os
@@ -93,13 +102,92 @@ def run(xshape, size, rounds, reps=20):
     return res
 
 
+AA_X, AA_SIZES, AA_MODES = (16, 3, 512, 1024), ((128, 256), (64, 128)), ("bilinear", "bicubic")
+
+
+def run_antialias(rounds, reps=20):
+    import torch
+    import torch.nn.functional as F
+    from climate_learn import _hip
+    g = torch.Generator(device="cuda").manual_seed(0)
+    x = torch.randn(AA_X, device="cuda", generator=g)
+    other = torch.empty_like(x)
+    B, C, h, w = AA_X
+    src = x.numel() * 4
+    legs, keep = {"copy-src": (lambda: other.copy_(x), 2 * src)}, []
+    for H, W in AA_SIZES:
+        out = torch.empty(B, C, H, W, device="cuda")
+        target = torch.randn(B, C, H, W, device="cuda", generator=g)
+        lat_w = torch.rand(H, device="cuda", generator=g) + 0.5
+        keep.append((out, target, lat_w))
+        field, tag = out.numel() * 4, "%dx%d" % (H, W)
+        for m in AA_MODES:
+            k = dict(size=(H, W), m=m, out=out, target=target, lat_w=lat_w)
+            legs["ours %s %s" % (m, tag)] = (lambda k=k: _hip.resample(x, k["size"], k["m"], out=k["out"], antialias=True), src + field)
+            legs["aten %s %s" % (m, tag)] = (lambda k=k: F.interpolate(x, k["size"], mode=k["m"], align_corners=False,
+                                                                     antialias=True), src + field)
+            legs["fused %s %s" % (m, tag)] = (lambda k=k: _hip.resample_moments(x, k["size"], k["m"], k["target"], lat_w=k["lat_w"],
+                                                                            antialias=True), src + field)
+            legs["two-step %s %s" % (m, tag)] = (lambda k=k: _hip.eval_moments(
+                _hip.resample(x, k["size"], k["m"], out=k["out"], antialias=True), k["target"], k["lat_w"]), src + 3 * field)
+    for fn, _ in legs.values():                          # warm-up: code objects, the allocator's blocks
+        for _ in range(3):
+            fn()
+    ms = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, (fn, _) in legs.items():
+            ms[k].append(_ev(fn, reps))
+    res = {"x": list(AA_X), "sizes": [list(v) for v in AA_SIZES], "rounds": rounds, "reps": reps, "legs": {}, "agreement": {}}
+    for k, (_, nbytes) in legs.items():
+        mean = sum(ms[k]) / rounds
+        res["legs"][k] = {"ms": round(mean, 4), "min": round(min(ms[k]), 4), "max": round(max(ms[k]), 4),
+                          "spread": round((max(ms[k]) - min(ms[k])) / mean, 4), "GBps": round(nbytes / (1e6 * mean), 1)}
+    for (H, W), (out, target, lat_w) in zip(AA_SIZES, keep):
+        for m in AA_MODES:
+            a = _hip.resample(x, (H, W), m, antialias=True)
+            b = F.interpolate(x, (H, W), mode=m, align_corners=False, antialias=True)
+            s1 = _hip.resample_moments(x, (H, W), m, target, lat_w=lat_w, antialias=True)
+            s2 = _hip.eval_moments(a, target, lat_w)
+            res["agreement"]["%s %dx%d" % (m, H, W)] = {
+                "max_abs_vs_aten": float((a - b).abs().max()),
+                "sums_rel_vs_two_step": float(((s1 - s2).abs() / s2.abs().clamp_min(1e-30))[..., 5].max())}
+    return res
+
+
+def write_antialias_md(r, path):
+    L = r["legs"]
+    with open(path, "w") as f:
+        f.write("# Antialiased resampling: the antialiased kernel against ATen and a copy of the source (tools/resample_bench.py "
+                "--antialias)\n\n")
+        f.write("One MI355X, one process, all legs alternating, %d rounds of %d calls after a warm-up, HIP events; x [%s] fp32 -> "
+                "%s.\nGB/s counts the bytes a leg must move (the tool's docstring); the spread is (max - min) / mean over the "
+                "rounds.\n\n" % (r["rounds"], r["reps"], ", ".join(map(str, r["x"])),
+                                 " and ".join("[%d, %d, %d, %d]" % (r["x"][0], r["x"][1], H, W) for H, W in r["sizes"])))
+        f.write("| leg | ms per call (min .. max, spread) | GB/s of the bytes it must move |\n|---|---|---|\n")
+        for k, v in L.items():
+            f.write("| %s | %.4f (%.4f .. %.4f, %.1f %%) | %.1f |\n" % (k, v["ms"], v["min"], v["max"], 100 * v["spread"], v["GBps"]))
+        f.write("\n| mode and size | ours / aten | ours / copy-src | fused / two-step | max abs ours - aten | sum 5 fused vs two-step, "
+                "rel |\n|---|---|---|---|---|---|\n")
+        for k, ag in r["agreement"].items():
+            f.write("| %s | %.3f | %.3f | %.3f | %.3g | %.3g |\n"
+                    % (k, L["ours " + k]["ms"] / L["aten " + k]["ms"], L["ours " + k]["ms"] / L["copy-src"]["ms"],
+                       L["fused " + k]["ms"] / L["two-step " + k]["ms"], ag["max_abs_vs_aten"], ag["sums_rel_vs_two_step"]))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--antialias", action="store_true")
     ap.add_argument("--md")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--x", default="16,23,128,256")
     ap.add_argument("--size", default="512,1024")
     a = ap.parse_args()
+    if a.antialias:
+        r = run_antialias(a.rounds)
+        print(json.dumps(r), flush=True)
+        if a.md:
+            write_antialias_md(r, a.md)
+        return
     r = run(tuple(int(v) for v in a.x.split(",")), tuple(int(v) for v in a.size.split(",")), a.rounds)
     print(json.dumps(r), flush=True)
     if a.md:
