@@ -1,16 +1,22 @@
-// Interpolation baselines: F.interpolate(size=(H, W), mode=nearest | bilinear | bicubic, align_corners=False, no antialiasing)
-// of gathered channels of an fp32 [B, in_ctotal, h, w] field, with an optional per-channel affine, either stored
-// (orbit2_resample_fwd) or scored against a target without ever being stored (orbit2_resample_moments: the twelve sums of
-// orbit2_eval_moments).  include/orbit2_hip.h: orbit2_resample_*; models/hub/interpolation.py; DESIGN 4.10c.
-// The antialiased forms of bilinear and bicubic (mode | ORBIT2_ANTIALIAS) have a kernel of their own further down; what follows
-// here is the plain modes'.
+// Interpolation baselines: F.interpolate(size=(H, W), mode=nearest | bilinear | bicubic, align_corners=False) of gathered channels
+// of an fp32 [B, in_ctotal, h, w] field, with an optional per-channel affine, either stored (orbit2_resample_fwd) or scored
+// against a target without ever being stored (orbit2_resample_moments: the twelve sums of orbit2_eval_moments).
+// include/orbit2_hip.h: orbit2_resample_*; models/hub/interpolation.py; DESIGN 4.10c.
+// Two kernels: the plain modes' (no antialiasing) and, further down, the antialiased forms of bilinear and bicubic
+// (mode | ORBIT2_ANTIALIAS).  They differ in how a pixel is formed and in their tiles.  What they share is stated once:
+//   RsArgs     the operands of a call, one struct by value; what only one kernel needs stays an argument of that kernel
+//   rs_frame   a workgroup's place in the call: its (b, c) image, tile origin, gathered source plane, the channel's affine pair
+//   rs_load4   four consecutive floats of a row: one float4 where all four exist and sit on a 16-byte boundary
+//   rs_emit    the epilogue of a thread's FOUR CONSECUTIVE output columns of one row: the affine, then the store, or the target
+//              and climatology quads and the twelve moments, columns ascending
+//   rs_launch  the argument checks, tile sizes, grid and mode dispatch of both entries
 //
-// A workgroup owns one RS_TH x RS_TW tile of one (b, c) output image.  A lane owns FOUR CONSECUTIVE output columns, so a wave
-// covers the tile's 256 columns and stores (or reads the target as) one float4 per lane and row; wave v takes rows v, v + 4, ...
-// of the tile.  The column taps (source indices and weights of the lane's four columns) are computed once and stay in registers
-// for all rows; the row taps are computed once per row from a wave-uniform row number.  The source pixels under the tile are
-// staged in LDS once when the call's full-tile footprint fits ORBIT2_RESAMPLE_LDS_FLOATS (every upsampling ratio and the
-// identity), else the taps are read straight from global memory (a downsampling footprint can be arbitrarily large).
+// The plain kernel: a workgroup owns one RS_TH x RS_TW tile of one (b, c) output image.  A lane owns four consecutive output
+// columns, so a wave covers the tile's 256 columns and stores (or reads the target as) one float4 per lane and row; wave v takes
+// rows v, v + 4, ... of the tile.  The column taps (source indices and weights of the lane's four columns) are computed once and
+// stay in registers for all rows; the row taps are computed once per row from a wave-uniform row number.  The source pixels under
+// the tile are staged in LDS once when the call's full-tile footprint fits ORBIT2_RESAMPLE_LDS_FLOATS (every upsampling ratio and
+// the identity), else the taps are read straight from global memory (a downsampling footprint can be arbitrarily large).
 //
 // COORDINATES ARE PART OF THE CONTRACT: fp32, every product and difference rounded on its own (rs_rounded in rs_taps:
 // hipcc contracts a * b - c into one fma otherwise, which moves a coordinate that sits on an integer to the other side of it).
@@ -30,6 +36,77 @@ constexpr int RS_TH = ORBIT2_RESAMPLE_TILE_H, RS_TW = ORBIT2_RESAMPLE_TILE_W, RS
 constexpr int RS_NM = O2_NMOMENTS;
 static_assert(RS_TW == 256 && RS_TH % 4 == 0, "a wave's 64 lanes x 4 columns span the tile, four waves share its rows");
 
+// ---- what the two kernels share -----------------------------------------------------------------------------------------------
+// The operands of a call, as the two entries take them: out for orbit2_resample_fwd; target [B, C, Ht, Wt], lat_w, clim and sums
+// for orbit2_resample_moments.  ntx (tiles across), ry and rx (the contract's ratios) are filled in by rs_launch.  The members
+// carry no __restrict__; the source plane reaches the pixel loops through a __restrict__ parameter (rs_rows, aa_chunks).
+struct RsArgs {
+  const float* x; const int* chan_idx; const float* scale; const float* shift;
+  float* out; const float* target; const float* lat_w; const float* clim; double* sums;
+  int in_ctotal, Ht, Wt, C, h, w, H, W, ntx;
+  float ry, rx;
+};
+
+struct rs_frame {
+  int bc, c, y0, x0;                              // the image (b * C + c), its channel, the tile's first row and column
+  const float* src;                               // the gathered source plane
+  bool affine;
+  float sc, sh;
+};
+template <int TH, int TW>
+__device__ __forceinline__ rs_frame rs_frame_of(const RsArgs& p) {
+  rs_frame f;
+  f.bc = blockIdx.y;
+  const int b = f.bc / p.C, ty = blockIdx.x / p.ntx, tx = blockIdx.x - ty * p.ntx;
+  f.c = f.bc - b * p.C;
+  f.y0 = ty * TH, f.x0 = tx * TW;
+  const int ci = p.chan_idx ? p.chan_idx[f.c] : f.c;
+  f.src = p.x + ((size_t)b * p.in_ctotal + ci) * p.h * p.w;
+  f.affine = p.scale != nullptr;
+  f.sc = f.affine ? p.scale[f.c] : 1.f, f.sh = f.affine ? p.shift[f.c] : 0.f;
+  return f;
+}
+
+// v = q[0 .. 3], q at column xl of a row of W: a column past the image reads 0 (an odd W misaligns every second row)
+__device__ __forceinline__ void rs_load4(const float* __restrict__ q, int xl, int W, float (&v)[4]) {
+  if (xl + 3 < W && ((uintptr_t)q & 15) == 0) {
+    const float4 t = *reinterpret_cast<const float4*>(q);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = xl + j < W ? q[j] : 0.f;
+  }
+}
+
+// columns xl .. xl + 3 of output row y (y < H, xl < W) of the frame's image
+template <bool MOMENTS>
+__device__ __forceinline__ void rs_emit(const RsArgs& p, const rs_frame& f, int y, int xl, float (&v)[4], float (&s)[RS_NM]) {
+  if (f.affine) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = fmaf(f.sc, v[j], f.sh);
+  }
+  if (!MOMENTS) {
+    float* o = p.out + ((size_t)f.bc * p.H + y) * p.W + xl;
+    // one float4 where the four columns exist and sit on a 16-byte boundary, as rs_load4 reads one
+    if (xl + 3 < p.W && ((uintptr_t)o & 15) == 0) {
+      *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (xl + j < p.W) o[j] = v[j];
+    }
+  } else {
+    float tv[4], cv[4] = {0.f, 0.f, 0.f, 0.f};
+    rs_load4(p.target + ((size_t)f.bc * p.Ht + y) * p.Wt + xl, xl, p.W, tv);
+    if (p.clim) rs_load4(p.clim + ((size_t)f.c * p.H + y) * p.W + xl, xl, p.W, cv);
+    const float lw = p.lat_w ? p.lat_w[y] : 1.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (xl + j < p.W) o2_moments_add(s, v[j] - cv[j], tv[j] - cv[j], lw);
+  }
+}
+
+// ---- the plain modes ----------------------------------------------------------------------------------------------------------
 template <int MODE> struct rs_ntaps { static constexpr int value = MODE == 0 ? 1 : (MODE == 1 ? 2 : 4); };
 
 __device__ __forceinline__ int rs_clamp(int i, int n) { return i < 0 ? 0 : (i > n - 1 ? n - 1 : i); }
@@ -76,29 +153,27 @@ __device__ __forceinline__ void rs_taps(int o, int n_in, float ratio, int* idx, 
 
 // The tile's rows.  SRC is the image in global memory (pitch w, offsets 0) or the staged window in LDS (pitch ww, offsets ylo, xlo).
 template <int MODE, bool MOMENTS, bool STAGED>
-__device__ __forceinline__ void rs_rows(const float* __restrict__ src, int pitch, int yoff, int xoff, int h, int w, int H,
-                                        int W, float ry, float rx, int y0, int x0, bool affine, float sc, float sh,
-                                        float* __restrict__ orow0, const float* __restrict__ trow0, int Wt,
-                                        const float* __restrict__ lat_w, const float* __restrict__ crow0, float (&s)[RS_NM]) {
+__device__ __forceinline__ void rs_rows(const float* __restrict__ src, int pitch, int yoff, int xoff, const RsArgs& p,
+                                        const rs_frame& f, float (&s)[RS_NM]) {
   constexpr int NT = rs_ntaps<MODE>::value;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int xl = x0 + 4 * lane;                    // the lane's first output column
+  const int xl = f.x0 + 4 * lane;                  // the lane's first output column
   int cx[4][NT];
   float wx[4][NT];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     // a column past the image takes the last column's taps: in range, never stored or summed
-    rs_taps<MODE>(xl + j < W ? xl + j : W - 1, w, rx, cx[j], wx[j]);
+    rs_taps<MODE>(xl + j < p.W ? xl + j : p.W - 1, p.w, p.rx, cx[j], wx[j]);
 #pragma unroll
     for (int k = 0; k < NT; ++k) cx[j][k] -= xoff;
   }
   for (int r = wave; r < RS_TH; r += 4) {
-    const int y = y0 + r;
-    if (y >= H) break;
+    const int y = f.y0 + r;
+    if (y >= p.H) break;
     int cy[NT];
     float wy[NT];
-    rs_taps<MODE>(y, h, ry, cy, wy);
+    rs_taps<MODE>(y, p.h, p.ry, cy, wy);
     float v[4];
 #pragma unroll
     for (int k = 0; k < NT; ++k) {
@@ -117,70 +192,15 @@ __device__ __forceinline__ void rs_rows(const float* __restrict__ src, int pitch
         else v[j] = k == 0 ? wy[0] * t : fmaf(wy[k], t, v[j]);
       }
     }
-    if (affine) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = fmaf(sc, v[j], sh);
-    }
-    if (!MOMENTS) {
-      float* o = orow0 + (size_t)y * W + xl;
-      // one float4 where the lane's four columns exist and sit on a 16-byte boundary (an odd W misaligns every second row)
-      if (xl + 3 < W && ((uintptr_t)o & 15) == 0) {
-        *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (xl + j < W) o[j] = v[j];
-      }
-    } else {
-      const float* t = trow0 + (size_t)y * Wt + xl;
-      const float* c = crow0 ? crow0 + (size_t)y * W + xl : nullptr;
-      float tv[4], cv[4] = {0.f, 0.f, 0.f, 0.f};
-      const bool full = xl + 3 < W;
-      if (full && ((uintptr_t)t & 15) == 0) {
-        const float4 q = *reinterpret_cast<const float4*>(t);
-        tv[0] = q.x, tv[1] = q.y, tv[2] = q.z, tv[3] = q.w;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tv[j] = xl + j < W ? t[j] : 0.f;
-      }
-      if (c) {
-        if (full && ((uintptr_t)c & 15) == 0) {
-          const float4 q = *reinterpret_cast<const float4*>(c);
-          cv[0] = q.x, cv[1] = q.y, cv[2] = q.z, cv[3] = q.w;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) cv[j] = xl + j < W ? c[j] : 0.f;
-        }
-      }
-      const float lw = lat_w ? lat_w[y] : 1.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (xl + j < W) o2_moments_add(s, v[j] - cv[j], tv[j] - cv[j], lw);
-      }
-    }
+    rs_emit<MOMENTS>(p, f, y, xl, v, s);
   }
 }
 
 template <int MODE, bool MOMENTS>
-__global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__ x, const int* __restrict__ chan_idx,
-                                                       int in_ctotal, const float* __restrict__ scale,
-                                                       const float* __restrict__ shift, float* __restrict__ out,
-                                                       const float* __restrict__ target, int Ht, int Wt,
-                                                       const float* __restrict__ lat_w, const float* __restrict__ clim,
-                                                       double* __restrict__ sums, int C, int h, int w, int H, int W, int ntx,
-                                                       int stage, float ry, float rx) {
+__global__ __launch_bounds__(256) void resample_kernel(const RsArgs p, int stage) {
   constexpr int NT = rs_ntaps<MODE>::value;
   __shared__ float win[RS_LDS];
-  const int bc = blockIdx.y, b = bc / C, c = bc - b * C;
-  const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
-  const int y0 = ty * RS_TH, x0 = tx * RS_TW;
-  const int ci = chan_idx ? chan_idx[c] : c;
-  const float* src = x + ((size_t)b * in_ctotal + ci) * h * w;
-  const bool affine = scale != nullptr;
-  const float sc = affine ? scale[c] : 1.f, sh = affine ? shift[c] : 0.f;
-  float* orow0 = MOMENTS ? nullptr : out + (size_t)bc * H * W;
-  const float* trow0 = MOMENTS ? target + (size_t)bc * Ht * Wt : nullptr;
-  const float* crow0 = MOMENTS && clim ? clim + (size_t)c * H * W : nullptr;
+  const rs_frame f = rs_frame_of<RS_TH, RS_TW>(p);
   float s[RS_NM];
 #pragma unroll
   for (int k = 0; k < RS_NM; ++k) s[k] = 0.f;
@@ -189,31 +209,30 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
   // the last tap of its last ones bound every tap in between
   int lo[NT], hi[NT];
   float wgt[NT];
-  rs_taps<MODE>(y0, h, ry, lo, wgt);
-  rs_taps<MODE>(min(y0 + RS_TH, H) - 1, h, ry, hi, wgt);
+  rs_taps<MODE>(f.y0, p.h, p.ry, lo, wgt);
+  rs_taps<MODE>(min(f.y0 + RS_TH, p.H) - 1, p.h, p.ry, hi, wgt);
   const int ylo = lo[0], wh = hi[NT - 1] - ylo + 1;
-  rs_taps<MODE>(x0, w, rx, lo, wgt);
-  rs_taps<MODE>(min(x0 + RS_TW, W) - 1, w, rx, hi, wgt);
+  rs_taps<MODE>(f.x0, p.w, p.rx, lo, wgt);
+  rs_taps<MODE>(min(f.x0 + RS_TW, p.W) - 1, p.w, p.rx, hi, wgt);
   const int xlo = lo[0], ww = hi[NT - 1] - xlo + 1;
   // `stage` is the host's rule (the full-tile footprint of this ratio fits); the window itself is checked all the same
   if (stage && wh > 0 && ww > 0 && (int64_t)wh * ww <= RS_LDS) {
     // a wave per window row, lanes along it: coalesced, and no division by the window's width
     for (int r = threadIdx.x >> 6; r < wh; r += 4)
-      for (int q = threadIdx.x & 63; q < ww; q += 64) win[r * ww + q] = src[(size_t)(ylo + r) * w + xlo + q];
+      for (int q = threadIdx.x & 63; q < ww; q += 64) win[r * ww + q] = f.src[(size_t)(ylo + r) * p.w + xlo + q];
     __syncthreads();
-    rs_rows<MODE, MOMENTS, true>(win, ww, ylo, xlo, h, w, H, W, ry, rx, y0, x0, affine, sc, sh, orow0, trow0, Wt, lat_w, crow0,
-                                 s);
+    rs_rows<MODE, MOMENTS, true>(win, ww, ylo, xlo, p, f, s);
   } else {
-    rs_rows<MODE, MOMENTS, false>(src, w, 0, 0, h, w, H, W, ry, rx, y0, x0, affine, sc, sh, orow0, trow0, Wt, lat_w, crow0, s);
+    rs_rows<MODE, MOMENTS, false>(f.src, p.w, 0, 0, p, f, s);
   }
-  if (MOMENTS) o2_block_sums_add(s, sums + (size_t)bc * RS_NM);
+  if (MOMENTS) o2_block_sums_add(s, p.sums + (size_t)f.bc * RS_NM);
 }
 
 // ---- antialiased bilinear / bicubic (mode | ORBIT2_ANTIALIAS): F.interpolate(..., antialias=True) -----------------------------
 // An output coordinate o reads a WINDOW of the source axis whose length grows with the downsampling ratio (include/orbit2_hip.h
-// states the rule): lo .. lo + n - 1, clipped to the grid, with weights f(.) / sum f(.).  The pixel is separable, horizontal
-// pass first.  A workgroup owns an AA_TH x AA_TW output tile of one (b, c) image; thread t owns row t / 16 and the four
-// consecutive columns 4 (t % 16) .. + 3 of it (one float4 store or target read, as in the plain kernel).
+// states the rule): lo .. lo + n - 1, clipped to the grid, with weights f(.) / sum f(.) (aa_weight).  The pixel is separable,
+// horizontal pass first.  A workgroup owns an AA_TH x AA_TW output tile of one (b, c) image; thread t owns row t / 16 and the four
+// consecutive columns 4 (t % 16) .. + 3 of it, which it hands to rs_emit once.
 //   1. threads 0 .. AA_TW - 1 form the window and the weight sum of one tile column each, the next AA_TH threads those of a
 //      tile row; when the tile's longest windows fit (AA_TW KX <= AA_WX, AA_TH KY <= AA_WY, KX / KY the longest window of a
 //      column / row) the normalised weights go into LDS tables of pitch KX / KY, once per workgroup.
@@ -241,12 +260,16 @@ __device__ __forceinline__ float aa_filter(float x) {
   return 0.f;
 }
 
-// the weight of tap j of a window that starts at lo, before (raw) and after normalisation by the window's sum
+// the weight of tap j of a window that starts at lo, before (aa_raw) and after (aa_weight) normalisation by the window's sum
 template <int MODE>
 __device__ __forceinline__ float aa_raw(int j, int lo, float center, float inv) {
   return aa_filter<MODE>(rs_rounded((((float)(j + lo) - center) + 0.5f) * inv));
 }
-__device__ __forceinline__ float aa_norm(float raw, float total) { return total != 0.f ? raw / total : raw; }
+template <int MODE>
+__device__ __forceinline__ float aa_weight(int j, int lo, float center, float inv, float total) {
+  const float raw = aa_raw<MODE>(j, lo, center, inv);
+  return total != 0.f ? raw / total : raw;
+}
 
 // window (lo, n), centre and weight sum of output coordinate o
 template <int MODE>
@@ -301,11 +324,11 @@ __device__ __forceinline__ void aa_chunks(const float* __restrict__ src, int w, 
       const float* wt = tabx + c * KX;
       const float ctr = ax.xc[c], tot = ax.xt[c];
       float t[4];
-      const float w0 = FIT ? wt[0] : aa_norm(aa_raw<MODE>(0, lo, ctr, invx), tot);
+      const float w0 = FIT ? wt[0] : aa_weight<MODE>(0, lo, ctr, invx, tot);
 #pragma unroll
       for (int k = 0; k < 4; ++k) t[k] = w0 * row[k][0];
       for (int q = 1; q < n; ++q) {
-        const float wq = FIT ? wt[q] : aa_norm(aa_raw<MODE>(q, lo, ctr, invx), tot);
+        const float wq = FIT ? wt[q] : aa_weight<MODE>(q, lo, ctr, invx, tot);
 #pragma unroll
         for (int k = 0; k < 4; ++k) t[k] = fmaf(wq, row[k][q], t[k]);
       }
@@ -316,7 +339,7 @@ __device__ __forceinline__ void aa_chunks(const float* __restrict__ src, int w, 
     __syncthreads();
     const int ka = max(r0, mylo), kb = min(r0 + cr, myhi);
     for (int r = ka; r < kb; ++r) {
-      const float wy = FIT ? taby[i * KY + (r - mylo)] : aa_norm(aa_raw<MODE>(r - mylo, mylo, myc, invy), myt);
+      const float wy = FIT ? taby[i * KY + (r - mylo)] : aa_weight<MODE>(r - mylo, mylo, myc, invy, myt);
       const float4 m = *reinterpret_cast<const float4*>(mid + (r - r0) * AA_MP + c4);
       const float mv[4] = {m.x, m.y, m.z, m.w};
 #pragma unroll
@@ -326,149 +349,88 @@ __device__ __forceinline__ void aa_chunks(const float* __restrict__ src, int w, 
 }
 
 template <int MODE, bool MOMENTS>
-__global__ __launch_bounds__(256) void resample_aa_kernel(const float* __restrict__ x, const int* __restrict__ chan_idx,
-                                                          int in_ctotal, const float* __restrict__ scale,
-                                                          const float* __restrict__ shift, float* __restrict__ out,
-                                                          const float* __restrict__ target, int Ht, int Wt,
-                                                          const float* __restrict__ lat_w, const float* __restrict__ clim,
-                                                          double* __restrict__ sums, int C, int h, int w, int H, int W, int ntx,
-                                                          float ry, float rx, float supy, float supx, float invy, float invx) {
+__global__ __launch_bounds__(256) void resample_aa_kernel(const RsArgs p, float supy, float supx, float invy, float invx) {
   __shared__ float win[AA_SRC];
   __shared__ __attribute__((aligned(16))) float mid[AA_CR * AA_MP];
   __shared__ float tabx[AA_WX], taby[AA_WY];
   __shared__ aa_axes ax;
   const int tid = threadIdx.x;
-  const int bc = blockIdx.y, b = bc / C, c = bc - b * C;
-  const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
-  const int y0 = ty * AA_TH, x0 = tx * AA_TW;
-  const int ci = chan_idx ? chan_idx[c] : c;
-  const float* src = x + ((size_t)b * in_ctotal + ci) * h * w;
+  const rs_frame f = rs_frame_of<AA_TH, AA_TW>(p);
   if (tid < 2) ax.kmax[tid] = 0;
   __syncthreads();
   // a column or row past the image takes the last one's window: in range, never stored or summed
   if (tid < AA_TW) {
-    aa_window<MODE>(min(x0 + tid, W - 1), w, rx, supx, invx, ax.xlo[tid], ax.xn[tid], ax.xc[tid], ax.xt[tid]);
+    aa_window<MODE>(min(f.x0 + tid, p.W - 1), p.w, p.rx, supx, invx, ax.xlo[tid], ax.xn[tid], ax.xc[tid], ax.xt[tid]);
     atomicMax(&ax.kmax[0], ax.xn[tid]);
   } else if (tid < AA_TW + AA_TH) {
     const int i = tid - AA_TW;
-    aa_window<MODE>(min(y0 + i, H - 1), h, ry, supy, invy, ax.ylo[i], ax.yn[i], ax.yc[i], ax.yt[i]);
+    aa_window<MODE>(min(f.y0 + i, p.H - 1), p.h, p.ry, supy, invy, ax.ylo[i], ax.yn[i], ax.yc[i], ax.yt[i]);
     atomicMax(&ax.kmax[1], ax.yn[i]);
   }
   __syncthreads();
   const int KX = ax.kmax[0], KY = ax.kmax[1];
   const int fwp = (ax.xlo[AA_TW - 1] + ax.xn[AA_TW - 1] - ax.xlo[0]) | 1;
   const bool fit = (int64_t)KX * AA_TW <= AA_WX && (int64_t)KY * AA_TH <= AA_WY && fwp <= AA_SRC;     // the same in every thread
-  const int y = y0 + (tid >> 4), xl = x0 + 4 * (tid & 15);
-  const int ncol = min(AA_TW, W - x0);
-  const bool live = y < H && xl < W;
+  const int y = f.y0 + (tid >> 4), xl = f.x0 + 4 * (tid & 15);
+  const int ncol = min(AA_TW, p.W - f.x0);
+  const bool live = y < p.H && xl < p.W;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   if (fit) {
     if (tid < AA_TW) {
-      for (int j = 0; j < ax.xn[tid]; ++j)
-        tabx[tid * KX + j] = aa_norm(aa_raw<MODE>(j, ax.xlo[tid], ax.xc[tid], invx), ax.xt[tid]);
+      for (int j = 0; j < ax.xn[tid]; ++j) tabx[tid * KX + j] = aa_weight<MODE>(j, ax.xlo[tid], ax.xc[tid], invx, ax.xt[tid]);
     } else if (tid < AA_TW + AA_TH) {
       const int i = tid - AA_TW;
-      for (int j = 0; j < ax.yn[i]; ++j) taby[i * KY + j] = aa_norm(aa_raw<MODE>(j, ax.ylo[i], ax.yc[i], invy), ax.yt[i]);
+      for (int j = 0; j < ax.yn[i]; ++j) taby[i * KY + j] = aa_weight<MODE>(j, ax.ylo[i], ax.yc[i], invy, ax.yt[i]);
     }
     // its first barrier publishes the tables
-    aa_chunks<MODE, true>(src, w, ax, win, mid, tabx, taby, KX, KY, invy, invx, ncol, live, acc);
+    aa_chunks<MODE, true>(f.src, p.w, ax, win, mid, tabx, taby, KX, KY, invy, invx, ncol, live, acc);
   } else {
-    aa_chunks<MODE, false>(src, w, ax, win, mid, tabx, taby, KX, KY, invy, invx, ncol, live, acc);
+    aa_chunks<MODE, false>(f.src, p.w, ax, win, mid, tabx, taby, KX, KY, invy, invx, ncol, live, acc);
   }
 
   float s[RS_NM];
 #pragma unroll
   for (int k = 0; k < RS_NM; ++k) s[k] = 0.f;
-  if (live) {
-    if (scale) {
-      const float sc = scale[c], sh = shift[c];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = fmaf(sc, acc[j], sh);
-    }
-    const bool full = xl + 3 < W;
-    if (!MOMENTS) {
-      float* o = out + ((size_t)bc * H + y) * W + xl;
-      // one float4 where the thread's four columns exist and sit on a 16-byte boundary, as in the plain kernel
-      if (full && ((uintptr_t)o & 15) == 0) {
-        *reinterpret_cast<float4*>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (xl + j < W) o[j] = acc[j];
-      }
-    } else {
-      const float* t = target + ((size_t)bc * Ht + y) * Wt + xl;
-      const float* cl = clim ? clim + ((size_t)c * H + y) * W + xl : nullptr;
-      float tv[4], cv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (full && ((uintptr_t)t & 15) == 0) {
-        const float4 q = *reinterpret_cast<const float4*>(t);
-        tv[0] = q.x, tv[1] = q.y, tv[2] = q.z, tv[3] = q.w;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tv[j] = xl + j < W ? t[j] : 0.f;
-      }
-      if (cl) {
-        if (full && ((uintptr_t)cl & 15) == 0) {
-          const float4 q = *reinterpret_cast<const float4*>(cl);
-          cv[0] = q.x, cv[1] = q.y, cv[2] = q.z, cv[3] = q.w;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) cv[j] = xl + j < W ? cl[j] : 0.f;
-        }
-      }
-      const float lw = lat_w ? lat_w[y] : 1.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (xl + j < W) o2_moments_add(s, acc[j] - cv[j], tv[j] - cv[j], lw);
-    }
-  }
-  if (MOMENTS) o2_block_sums_add(s, sums + (size_t)bc * RS_NM);
+  if (live) rs_emit<MOMENTS>(p, f, y, xl, acc, s);
+  if (MOMENTS) o2_block_sums_add(s, p.sums + (size_t)f.bc * RS_NM);
 }
 
+// ---- the launch of both entries -------------------------------------------------------------------------------------------------
 // ceil(tile * in / out) + 4: no window of a tile at this ratio is larger (a bicubic footprint is the span of the floors + 4)
 inline int64_t rs_footprint(int tile, int n_in, int n_out) { return ((int64_t)tile * n_in + n_out - 1) / n_out + 4; }
 
 template <bool MOMENTS>
-int rs_launch(const float* x, const int* chan_idx, int in_ctotal, const float* scale, const float* shift, float* out,
-              const float* target, int Ht, int Wt, const float* lat_w, const float* clim, double* sums, int B, int C, int h,
-              int w, int H, int W, int mode, hipStream_t s) {
-  if (!x || (MOMENTS ? (!sums || !target) : !out) || (scale == nullptr) != (shift == nullptr)) return O2_ERR_ARG;
-  if (B <= 0 || C <= 0 || in_ctotal <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return O2_ERR_ARG;
+int rs_launch(RsArgs p, int B, int mode, hipStream_t s) {
+  if (!p.x || (MOMENTS ? (!p.sums || !p.target) : !p.out) || (p.scale == nullptr) != (p.shift == nullptr)) return O2_ERR_ARG;
+  if (B <= 0 || p.C <= 0 || p.in_ctotal <= 0 || p.h <= 0 || p.w <= 0 || p.H <= 0 || p.W <= 0) return O2_ERR_ARG;
   // 0, 1, 2 plain; bilinear and bicubic also with ORBIT2_ANTIALIAS (5, 6); nearest has no antialiased form
   const bool aa = mode == (1 | ORBIT2_ANTIALIAS) || mode == (2 | ORBIT2_ANTIALIAS);
   if (!aa && (mode < 0 || mode > 2)) return O2_ERR_ARG;
-  if (!chan_idx && C != in_ctotal) return O2_ERR_ARG;
-  if (MOMENTS && (Ht < H || Wt < W)) return O2_ERR_ARG;
-  if ((int64_t)B * C > 65535) return O2_ERR_ARG;
-  const int ntx = (W + (aa ? AA_TW : RS_TW) - 1) / (aa ? AA_TW : RS_TW), nty = (H + (aa ? AA_TH : RS_TH) - 1) / (aa ? AA_TH : RS_TH);
-  if ((int64_t)ntx * nty > INT32_MAX) return O2_ERR_ARG;
-  if (MOMENTS && hipMemsetAsync(sums, 0, sizeof(double) * (size_t)B * C * RS_NM, s) != hipSuccess) return O2_ERR_LAUNCH;
-  const int stage = rs_footprint(RS_TH, h, H) * rs_footprint(RS_TW, w, W) <= RS_LDS;
-  const dim3 grid(ntx * nty, B * C);
+  if (!p.chan_idx && p.C != p.in_ctotal) return O2_ERR_ARG;
+  if (MOMENTS && (p.Ht < p.H || p.Wt < p.W)) return O2_ERR_ARG;
+  if ((int64_t)B * p.C > 65535) return O2_ERR_ARG;
+  const int th = aa ? AA_TH : RS_TH, tw = aa ? AA_TW : RS_TW;
+  p.ntx = (p.W + tw - 1) / tw;
+  const int nty = (p.H + th - 1) / th;
+  if ((int64_t)p.ntx * nty > INT32_MAX) return O2_ERR_ARG;
+  if (MOMENTS && hipMemsetAsync(p.sums, 0, sizeof(double) * (size_t)B * p.C * RS_NM, s) != hipSuccess) return O2_ERR_LAUNCH;
+  const int stage = rs_footprint(RS_TH, p.h, p.H) * rs_footprint(RS_TW, p.w, p.W) <= RS_LDS;
+  const dim3 grid(p.ntx * nty, B * p.C);
   // the two ratios of the contract, one correctly rounded fp32 division each: formed here once, not by every thread
-  const float ry = (float)h / (float)H, rx = (float)w / (float)W;
-  if (aa) {
-    // support and inverse scale of the contract, one fp32 operation each: a window spans interp / 2 source pixels per unit of
-    // max(ratio, 1) to either side of its centre
-    const float half = mode == (1 | ORBIT2_ANTIALIAS) ? 1.f : 2.f;
-    const float supy = ry >= 1.f ? half * ry : half, supx = rx >= 1.f ? half * rx : half;
-    const float invy = ry >= 1.f ? 1.f / ry : 1.f, invx = rx >= 1.f ? 1.f / rx : 1.f;
-#define RS_AA_GO(M)                                                                                                            \
-  hipLaunchKernelGGL((resample_aa_kernel<M, MOMENTS>), grid, dim3(256), 0, s, x, chan_idx, in_ctotal, scale, shift, out, target, \
-                     Ht, Wt, lat_w, clim, sums, C, h, w, H, W, ntx, ry, rx, supy, supx, invy, invx)
-    if (mode == (1 | ORBIT2_ANTIALIAS)) RS_AA_GO(1);
-    else RS_AA_GO(2);
-#undef RS_AA_GO
-    O2_CHECK_LAUNCH();
-    return O2_OK;
+  const float ry = p.ry = (float)p.h / (float)p.H, rx = p.rx = (float)p.w / (float)p.W;
+  // support and inverse scale of the antialiased contract, one fp32 operation each: a window spans interp / 2 source pixels per
+  // unit of max(ratio, 1) to either side of its centre
+  const float half = mode == (1 | ORBIT2_ANTIALIAS) ? 1.f : 2.f;
+  const float supy = ry >= 1.f ? half * ry : half, supx = rx >= 1.f ? half * rx : half;
+  const float invy = ry >= 1.f ? 1.f / ry : 1.f, invx = rx >= 1.f ? 1.f / rx : 1.f;
+  switch (mode) {
+    case 0: hipLaunchKernelGGL((resample_kernel<0, MOMENTS>), grid, dim3(256), 0, s, p, stage); break;
+    case 1: hipLaunchKernelGGL((resample_kernel<1, MOMENTS>), grid, dim3(256), 0, s, p, stage); break;
+    case 2: hipLaunchKernelGGL((resample_kernel<2, MOMENTS>), grid, dim3(256), 0, s, p, stage); break;
+    case 1 | ORBIT2_ANTIALIAS:
+      hipLaunchKernelGGL((resample_aa_kernel<1, MOMENTS>), grid, dim3(256), 0, s, p, supy, supx, invy, invx); break;
+    default: hipLaunchKernelGGL((resample_aa_kernel<2, MOMENTS>), grid, dim3(256), 0, s, p, supy, supx, invy, invx); break;
   }
-#define RS_GO(M)                                                                                                             \
-  hipLaunchKernelGGL((resample_kernel<M, MOMENTS>), grid, dim3(256), 0, s, x, chan_idx, in_ctotal, scale, shift, out, target, \
-                     Ht, Wt, lat_w, clim, sums, C, h, w, H, W, ntx, stage, ry, rx)
-  if (mode == 0) RS_GO(0);
-  else if (mode == 1) RS_GO(1);
-  else RS_GO(2);
-#undef RS_GO
   O2_CHECK_LAUNCH();
   return O2_OK;
 }
@@ -476,14 +438,14 @@ int rs_launch(const float* x, const int* chan_idx, int in_ctotal, const float* s
 
 extern "C" int orbit2_resample_fwd(const float* x, const int* chan_idx, int in_ctotal, const float* scale, const float* shift,
                                    float* out, int B, int C, int h, int w, int H, int W, int mode, void* stream) {
-  return rs_launch<false>(x, chan_idx, in_ctotal, scale, shift, out, nullptr, 0, 0, nullptr, nullptr, nullptr, B, C, h, w, H, W,
-                          mode, (hipStream_t)stream);
+  const RsArgs p{x, chan_idx, scale, shift, out, nullptr, nullptr, nullptr, nullptr, in_ctotal, 0, 0, C, h, w, H, W};
+  return rs_launch<false>(p, B, mode, (hipStream_t)stream);
 }
 
 extern "C" int orbit2_resample_moments(const float* x, const int* chan_idx, int in_ctotal, const float* scale,
                                        const float* shift, const float* target, int Ht, int Wt, const float* lat_w,
                                        const float* clim, double* out, int B, int C, int h, int w, int H, int W, int mode,
                                        void* stream) {
-  return rs_launch<true>(x, chan_idx, in_ctotal, scale, shift, nullptr, target, Ht, Wt, lat_w, clim, out, B, C, h, w, H, W, mode,
-                         (hipStream_t)stream);
+  const RsArgs p{x, chan_idx, scale, shift, nullptr, target, lat_w, clim, out, in_ctotal, Ht, Wt, C, h, w, H, W};
+  return rs_launch<true>(p, B, mode, (hipStream_t)stream);
 }

@@ -25,89 +25,29 @@ import torch
 import yaml
 
 from tests import resample_aa_ref as A
+from tests import resample_gpu_body as B
 from tests import resample_ref as R
 from tests._child import free_port
 from tests.conftest import ROOT
 
 pytestmark = pytest.mark.gpu
-CASE_IDS = ["%dx%d-%dx%d" % (hw + HW) for hw, HW in A.GPU_CASES]
-GUARD = 64
-
-
-def _affine(on):
-    return (A.GPU_SCALE, A.GPU_SHIFT) if on else (None, None)
-
-
-def _dev(v):
-    return None if v is None else torch.as_tensor(np.asarray(v, np.float32)).cuda()
-
-
-def _run_into_guards(x, HW, mode, scale, shift, lead):
-    """_hip.resample(antialias=True) into the middle of a NaN-filled buffer; checks that nothing else was written"""
-    from climate_learn import _hip
-    n = x.shape[0] * len(A.GPU_CHANNELS) * HW[0] * HW[1]
-    buf = torch.full((lead + n + GUARD,), float("nan"), dtype=torch.float32, device="cuda")
-    out = buf[lead:lead + n].view(x.shape[0], len(A.GPU_CHANNELS), *HW)
-    got = _hip.resample(x, HW, mode, channels=A.GPU_CHANNELS, scale=_dev(scale), shift=_dev(shift), out=out, antialias=True)
-    assert got.data_ptr() == out.data_ptr()
-    torch.cuda.synchronize()
-    host = buf.cpu().numpy()
-    assert np.isnan(host[:lead]).all() and np.isnan(host[lead + n:]).all(), "wrote outside the output"
-    field = host[lead:lead + n].reshape(out.shape)
-    assert not np.isnan(field).any(), "left pixels unwritten"
-    return field
+CASE_IDS = B.case_ids(A.GPU_CASES)
 
 
 @pytest.mark.parametrize("hw,HW", A.GPU_CASES, ids=CASE_IDS)
 def test_resample_aa_fwd(hw, HW):
-    for off in A.OFFSETS:
-        xh = A.gpu_input(hw, off)
-        x = torch.from_numpy(xh).cuda()
-        xmax = float(np.abs(xh[:, list(A.GPU_CHANNELS)]).max())
-        for mode in A.MODES:
-            for aff in (False, True):
-                scale, shift = _affine(aff)
-                rep = A.replica_aa(xh, HW, mode, A.GPU_CHANNELS, scale, shift)
-                for lead in (GUARD, GUARD - 3):              # the output on a 16-byte boundary, and off it
-                    got = _run_into_guards(x, HW, mode, scale, shift, lead)
-                    err = np.abs(got.astype(np.float64) - rep)
-                    tol = 0.0 if hw == HW else A.field_tol(mode, hw, HW) * xmax
-                    if aff:
-                        bound = np.abs(np.asarray(scale))[None, :, None, None] * tol + 2.0 ** -23 * np.abs(rep)
-                    else:
-                        bound = np.full_like(rep, tol)
-                    print("%s %s offset %d affine %d lead %d: worst %.4g = %.3g ulp(max|x|), bound %.4g"
-                          % (R.case_key(hw, HW), mode, off, aff, lead, err.max(), err.max() / xmax / R.ULP, bound.max()))
-                    assert (err <= bound).all()
-                    if hw == HW and not aff:
-                        assert np.array_equal(got, xh[:, list(A.GPU_CHANNELS)]), "the identity is not exact"
+    def identity_bits(got, xh, mode, off):
+        if hw == HW:
+            assert np.array_equal(got, xh[:, list(A.GPU_CHANNELS)]), "the identity is not exact"
+
+    B.check_fwd(hw, HW, lambda off: A.gpu_input(hw, off), A.replica_aa,
+                lambda mode: 0.0 if hw == HW else A.field_tol(mode, hw, HW), A.MODES, True, identity_bits)
 
 
 @pytest.mark.parametrize("hw,HW", A.GPU_CASES, ids=CASE_IDS)
 def test_resample_aa_moments(hw, HW):
-    from climate_learn import _hip
-    for off in A.OFFSETS:
-        xh = A.gpu_input(hw, off)
-        th, lat, clim = R.gpu_target(HW, off)                 # a target larger than the field, NaN outside the crop
-        x, t = torch.from_numpy(xh).cuda(), torch.from_numpy(th).cuda()
-        for mode in A.MODES:
-            rtol = A.MOMENTS_RTOL[(int(off), A.tile_fits(mode, hw, HW))]
-            for aff in ((False, True) if off == 0 else (False,)):
-                scale, shift = _affine(aff)
-                sc, sh = _dev(scale), _dev(shift)
-                rep = A.replica_aa(xh, HW, mode, A.GPU_CHANNELS, scale, shift)
-                field = _hip.resample(x, HW, mode, channels=A.GPU_CHANNELS, scale=sc, shift=sh, antialias=True)
-                for lw in (None, lat):
-                    for cl in (None, clim):
-                        got = _hip.resample_moments(x, HW, mode, t, channels=A.GPU_CHANNELS, scale=sc, shift=sh, lat_w=_dev(lw),
-                                                    clim=_dev(cl), antialias=True).cpu().numpy()
-                        two = _hip.eval_moments(field, t, _dev(lw), _dev(cl)).cpu().numpy()
-                        want, mag = R.moments64(rep, th, lw, cl)
-                        assert got.shape == want.shape == (2, 3, 12) and np.isfinite(got).all()
-                        e1, e2 = float((np.abs(got - want) / mag).max()), float((np.abs(got - two) / mag).max())
-                        print("%s %s offset %d affine %d lat %d clim %d: against float64 %.3g, against the two-step path %.3g "
-                              "(bound %.3g)" % (R.case_key(hw, HW), mode, off, aff, lw is not None, cl is not None, e1, e2, rtol))
-                        assert e1 <= rtol and e2 <= rtol
+    B.check_moments(hw, HW, lambda off: A.gpu_input(hw, off), A.replica_aa,
+                    lambda mode, off: A.MOMENTS_RTOL[(int(off), A.tile_fits(mode, hw, HW))], A.MODES, True)
 
 
 def test_plain_modes_are_untouched_and_nearest_is_refused():

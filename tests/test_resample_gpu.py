@@ -18,12 +18,12 @@ import numpy as np
 import pytest
 import torch
 
+from tests import resample_gpu_body as B
 from tests import resample_ref as R
 from tests.conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
-CASE_IDS = ["%dx%d-%dx%d" % (hw + HW) for hw, HW in R.GPU_CASES]
-GUARD = 64
+CASE_IDS = B.case_ids(R.GPU_CASES)
 
 
 @pytest.fixture(scope="module")
@@ -31,26 +31,8 @@ def golden():
     return dict(np.load(os.path.join(GOLDEN, "resample.npz")))
 
 
-def _affine(on):
-    return (R.GPU_SCALE, R.GPU_SHIFT) if on else (None, None)
-
-
-def _run_into_guards(x, HW, mode, scale, shift, lead):
-    """_hip.resample into the middle of a NaN-filled buffer; returns the field and checks that nothing else was written"""
-    from climate_learn import _hip
-    n = x.shape[0] * len(R.GPU_CHANNELS) * HW[0] * HW[1]
-    buf = torch.full((lead + n + GUARD,), float("nan"), dtype=torch.float32, device="cuda")
-    out = buf[lead:lead + n].view(x.shape[0], len(R.GPU_CHANNELS), *HW)
-    sc = None if scale is None else torch.tensor(scale, device="cuda")
-    sh = None if shift is None else torch.tensor(shift, device="cuda")
-    got = _hip.resample(x, HW, mode, channels=R.GPU_CHANNELS, scale=sc, shift=sh, out=out)
-    assert got.data_ptr() == out.data_ptr()
-    torch.cuda.synchronize()
-    host = buf.cpu().numpy()
-    assert np.isnan(host[:lead]).all() and np.isnan(host[lead + n:]).all(), "wrote outside the output"
-    field = host[lead:lead + n].reshape(out.shape)
-    assert not np.isnan(field).any(), "left pixels unwritten"
-    return field
+def _exact(mode, hw, HW):
+    return mode == "nearest" or hw == HW
 
 
 @pytest.mark.parametrize("hw,HW", R.GPU_CASES, ids=CASE_IDS)
@@ -59,67 +41,20 @@ def test_resample_fwd(golden, hw, HW):
     assert _hip.resample_staged(*hw, *HW) == (hw != (9, 13)), "9x13 -> 4x5 is the case that must read from global memory"
     if hw == (9, 130):
         assert -(-HW[0] // _hip.RESAMPLE_TILE[0]) >= 3 and -(-HW[1] // _hip.RESAMPLE_TILE[1]) >= 3
-    worst = dict.fromkeys(R.MODES, 0.0)
-    for off in R.OFFSETS:
-        xh = R.gpu_input(hw, HW, off, golden)
-        x = torch.from_numpy(xh).cuda()
-        xmax = float(np.abs(xh[:, list(R.GPU_CHANNELS)]).max())
-        for mode in R.MODES:
-            for aff in (False, True):
-                scale, shift = _affine(aff)
-                rep = R.replica(xh, HW, mode, R.GPU_CHANNELS, scale, shift)
-                for lead in (GUARD, GUARD - 3):              # the output on a 16-byte boundary, and off it
-                    got = _run_into_guards(x, HW, mode, scale, shift, lead)
-                    err = np.abs(got.astype(np.float64) - rep)
-                    exact = mode == "nearest" or hw == HW
-                    tol = 0.0 if exact else R.FIELD_TOL[mode] * xmax
-                    if aff:
-                        bound = np.abs(np.asarray(scale))[None, :, None, None] * tol + 2.0 ** -23 * np.abs(rep)
-                    else:
-                        bound = np.full_like(rep, tol)
-                        worst[mode] = max(worst[mode], float(err.max()) / xmax)
-                    print("%s %s offset %d affine %d lead %d: worst %.4g = %.3g ulp(max|x|), bound %.4g"
-                          % (R.case_key(hw, HW), mode, off, aff, lead, err.max(), err.max() / xmax / R.ULP, bound.max()))
-                    assert (err <= bound).all()
-                    key = R.case_key(hw, HW, mode, off)
-                    if mode == "nearest" and not aff and key in golden:
-                        assert np.array_equal(got, golden[key]), "nearest differs from the reference's bits"
-                    if exact and not aff:
-                        assert np.array_equal(got.astype(np.float64), rep)
-    print("worst |kernel - replica| / max|x| in ulp:", {m: round(v / R.ULP, 3) for m, v in worst.items()})
+
+    def golden_bits(got, xh, mode, off):
+        key = R.case_key(hw, HW, mode, off)
+        if mode == "nearest" and key in golden:
+            assert np.array_equal(got, golden[key]), "nearest differs from the reference's bits"
+
+    B.check_fwd(hw, HW, lambda off: R.gpu_input(hw, HW, off, golden), R.replica,
+                lambda mode: 0.0 if _exact(mode, hw, HW) else R.FIELD_TOL[mode], R.MODES, False, golden_bits)
 
 
 @pytest.mark.parametrize("hw,HW", R.GPU_CASES, ids=CASE_IDS)
 def test_resample_moments(golden, hw, HW):
-    from climate_learn import _hip
-    worst = 0.0
-    for off in R.OFFSETS:
-        xh = R.gpu_input(hw, HW, off, golden)
-        th, lat, clim = R.gpu_target(HW, off)
-        x, t = torch.from_numpy(xh).cuda(), torch.from_numpy(th).cuda()
-        for mode in R.MODES:
-            for aff in ((False, True) if off == 0 else (False,)):
-                scale, shift = _affine(aff)
-                sc = None if scale is None else torch.tensor(scale, device="cuda")
-                sh = None if shift is None else torch.tensor(shift, device="cuda")
-                rep = R.replica(xh, HW, mode, R.GPU_CHANNELS, scale, shift)
-                field = _hip.resample(x, HW, mode, channels=R.GPU_CHANNELS, scale=sc, shift=sh)
-                for lw in (None, lat):
-                    for cl in (None, clim):
-                        lwd = None if lw is None else torch.from_numpy(lw).cuda()
-                        cld = None if cl is None else torch.from_numpy(cl).cuda()
-                        got = _hip.resample_moments(x, HW, mode, t, channels=R.GPU_CHANNELS, scale=sc, shift=sh, lat_w=lwd,
-                                                    clim=cld).cpu().numpy()
-                        two = _hip.eval_moments(field, t, lwd, cld).cpu().numpy()
-                        want, mag = R.moments64(rep, th, lw, cl)
-                        assert got.shape == want.shape == (2, 3, 12) and np.isfinite(got).all()
-                        e1, e2 = float((np.abs(got - want) / mag).max()), float((np.abs(got - two) / mag).max())
-                        worst = max(worst, e1 / R.MOMENTS_RTOL[int(off)])
-                        print("%s %s offset %d affine %d lat %d clim %d: against float64 %.3g, against the two-step path %.3g "
-                              "(bound %.3g)" % (R.case_key(hw, HW), mode, off, aff, lw is not None, cl is not None, e1, e2,
-                                                R.MOMENTS_RTOL[int(off)]))
-                        assert e1 <= R.MOMENTS_RTOL[int(off)] and e2 <= R.MOMENTS_RTOL[int(off)]
-    print("worst error of the twelve sums as a fraction of its bound: %.3g" % worst)
+    B.check_moments(hw, HW, lambda off: R.gpu_input(hw, HW, off, golden), R.replica,
+                    lambda mode, off: R.MOMENTS_RTOL[int(off)], R.MODES, False)
 
 
 def test_resample_binding_refusals():

@@ -50,6 +50,30 @@ def _ev(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def measure(legs, rounds, reps):
+    """legs: name -> (call, bytes it must move).  A warm-up of every leg, then all legs alternating `rounds` times; per leg the
+    mean, min, max, spread and GB/s of its ms per call"""
+    for fn, _ in legs.values():                          # warm-up: code objects, the allocator's blocks
+        for _ in range(3):
+            fn()
+    ms = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, (fn, _) in legs.items():
+            ms[k].append(_ev(fn, reps))
+    res = {}
+    for k, (_, nbytes) in legs.items():
+        mean = sum(ms[k]) / rounds
+        res[k] = {"ms": round(mean, 4), "min": round(min(ms[k]), 4), "max": round(max(ms[k]), 4),
+                  "spread": round((max(ms[k]) - min(ms[k])) / mean, 4), "GBps": round(nbytes / (1e6 * mean), 1)}
+    return res
+
+
+def agreement(ours, aten, fused, two_step):
+    """agreement of the two routes to the sums and of ours with ATen, at one shape"""
+    return {"max_abs_vs_aten": float((ours - aten).abs().max()),
+            "sums_rel_vs_two_step": float(((fused - two_step).abs() / two_step.abs().clamp_min(1e-30))[..., 5].max())}
+
+
 def run(xshape, size, rounds, reps=20):
     import torch
     import torch.nn.functional as F
@@ -78,27 +102,13 @@ def run(xshape, size, rounds, reps=20):
         legs["aten+ " + m] = (lambda m=m: _hip.eval_moments(F.interpolate(x[:, idx], size, mode=m), target, lat_w),
                               src + 3 * field)
     legs["moments"] = (lambda: _hip.eval_moments(other, target, lat_w), 2 * field)
-    for fn, _ in legs.values():                          # warm-up: code objects, the allocator's blocks
-        for _ in range(3):
-            fn()
-    ms = {k: [] for k in legs}
-    for _ in range(rounds):
-        for k, (fn, _) in legs.items():
-            ms[k].append(_ev(fn, reps))
-    res = {"x": list(xshape), "size": list(size), "rounds": rounds, "reps": reps, "legs": {}}
-    for k, (_, nbytes) in legs.items():
-        mean = sum(ms[k]) / rounds
-        res["legs"][k] = {"ms": round(mean, 4), "min": round(min(ms[k]), 4), "max": round(max(ms[k]), 4),
-                          "spread": round((max(ms[k]) - min(ms[k])) / mean, 4), "GBps": round(nbytes / (1e6 * mean), 1)}
-    # agreement of the two routes to the sums and of ours with ATen, at this shape
-    res["agreement"] = {}
+    res = {"x": list(xshape), "size": list(size), "rounds": rounds, "reps": reps, "legs": measure(legs, rounds, reps),
+           "agreement": {}}
     for m in MODES:
         a = _hip.resample(x, size, m, CHANNELS)
-        b = F.interpolate(x[:, idx], size, mode=m)
-        s1 = _hip.resample_moments(x, size, m, target, CHANNELS, lat_w=lat_w)
-        s2 = _hip.eval_moments(a, target, lat_w)
-        res["agreement"][m] = {"max_abs_vs_aten": float((a - b).abs().max()),
-                               "sums_rel_vs_two_step": float(((s1 - s2).abs() / s2.abs().clamp_min(1e-30))[..., 5].max())}
+        res["agreement"][m] = agreement(a, F.interpolate(x[:, idx], size, mode=m),
+                                        _hip.resample_moments(x, size, m, target, CHANNELS, lat_w=lat_w),
+                                        _hip.eval_moments(a, target, lat_w))
     return res
 
 
@@ -130,48 +140,42 @@ def run_antialias(rounds, reps=20):
                                                                             antialias=True), src + field)
             legs["two-step %s %s" % (m, tag)] = (lambda k=k: _hip.eval_moments(
                 _hip.resample(x, k["size"], k["m"], out=k["out"], antialias=True), k["target"], k["lat_w"]), src + 3 * field)
-    for fn, _ in legs.values():                          # warm-up: code objects, the allocator's blocks
-        for _ in range(3):
-            fn()
-    ms = {k: [] for k in legs}
-    for _ in range(rounds):
-        for k, (fn, _) in legs.items():
-            ms[k].append(_ev(fn, reps))
-    res = {"x": list(AA_X), "sizes": [list(v) for v in AA_SIZES], "rounds": rounds, "reps": reps, "legs": {}, "agreement": {}}
-    for k, (_, nbytes) in legs.items():
-        mean = sum(ms[k]) / rounds
-        res["legs"][k] = {"ms": round(mean, 4), "min": round(min(ms[k]), 4), "max": round(max(ms[k]), 4),
-                          "spread": round((max(ms[k]) - min(ms[k])) / mean, 4), "GBps": round(nbytes / (1e6 * mean), 1)}
+    res = {"x": list(AA_X), "sizes": [list(v) for v in AA_SIZES], "rounds": rounds, "reps": reps,
+           "legs": measure(legs, rounds, reps), "agreement": {}}
     for (H, W), (out, target, lat_w) in zip(AA_SIZES, keep):
         for m in AA_MODES:
             a = _hip.resample(x, (H, W), m, antialias=True)
-            b = F.interpolate(x, (H, W), mode=m, align_corners=False, antialias=True)
-            s1 = _hip.resample_moments(x, (H, W), m, target, lat_w=lat_w, antialias=True)
-            s2 = _hip.eval_moments(a, target, lat_w)
-            res["agreement"]["%s %dx%d" % (m, H, W)] = {
-                "max_abs_vs_aten": float((a - b).abs().max()),
-                "sums_rel_vs_two_step": float(((s1 - s2).abs() / s2.abs().clamp_min(1e-30))[..., 5].max())}
+            res["agreement"]["%s %dx%d" % (m, H, W)] = agreement(
+                a, F.interpolate(x, (H, W), mode=m, align_corners=False, antialias=True),
+                _hip.resample_moments(x, (H, W), m, target, lat_w=lat_w, antialias=True), _hip.eval_moments(a, target, lat_w))
     return res
 
 
-def write_antialias_md(r, path):
+# what the two tables differ in: the title, the name of the first column of the second table and its ratios (numerator leg,
+# denominator leg; a name that ends in a blank is completed by the row's key)
+PLAIN_MD = ("Interpolation baselines: the resample kernels against ATen and plain streams (tools/resample_bench.py)", "mode",
+            (("ours ", "aten "), ("ours ", "fill"), ("fused ", "two-step "), ("fused ", "aten+ ")))
+AA_MD = ("Antialiased resampling: the antialiased kernel against ATen and a copy of the source (tools/resample_bench.py "
+         "--antialias)", "mode and size", (("ours ", "aten "), ("ours ", "copy-src"), ("fused ", "two-step ")))
+
+
+def write_md(r, path, shapes, title, first, ratios):
+    """shapes: the run's `x [...] fp32 -> ...` sentence"""
     L = r["legs"]
+    leg = lambda name, k: L[name + k if name.endswith(" ") else name]["ms"]
     with open(path, "w") as f:
-        f.write("# Antialiased resampling: the antialiased kernel against ATen and a copy of the source (tools/resample_bench.py "
-                "--antialias)\n\n")
-        f.write("One MI355X, one process, all legs alternating, %d rounds of %d calls after a warm-up, HIP events; x [%s] fp32 -> "
-                "%s.\nGB/s counts the bytes a leg must move (the tool's docstring); the spread is (max - min) / mean over the "
-                "rounds.\n\n" % (r["rounds"], r["reps"], ", ".join(map(str, r["x"])),
-                                 " and ".join("[%d, %d, %d, %d]" % (r["x"][0], r["x"][1], H, W) for H, W in r["sizes"])))
+        f.write("# %s\n\n" % title)
+        f.write("One MI355X, one process, all legs alternating, %d rounds of %d calls after a warm-up, HIP events; %s\nGB/s counts "
+                "the bytes a leg must move (the tool's docstring); the spread is (max - min) / mean over the rounds.\n\n"
+                % (r["rounds"], r["reps"], shapes))
         f.write("| leg | ms per call (min .. max, spread) | GB/s of the bytes it must move |\n|---|---|---|\n")
         for k, v in L.items():
             f.write("| %s | %.4f (%.4f .. %.4f, %.1f %%) | %.1f |\n" % (k, v["ms"], v["min"], v["max"], 100 * v["spread"], v["GBps"]))
-        f.write("\n| mode and size | ours / aten | ours / copy-src | fused / two-step | max abs ours - aten | sum 5 fused vs two-step, "
-                "rel |\n|---|---|---|---|---|---|\n")
+        cols = [first] + ["%s/ %s" % (n, d.strip()) for n, d in ratios] + ["max abs ours - aten", "sum 5 fused vs two-step, rel"]
+        f.write("\n| %s |\n%s|\n" % (" | ".join(cols), "|---" * len(cols)))
         for k, ag in r["agreement"].items():
-            f.write("| %s | %.3f | %.3f | %.3f | %.3g | %.3g |\n"
-                    % (k, L["ours " + k]["ms"] / L["aten " + k]["ms"], L["ours " + k]["ms"] / L["copy-src"]["ms"],
-                       L["fused " + k]["ms"] / L["two-step " + k]["ms"], ag["max_abs_vs_aten"], ag["sums_rel_vs_two_step"]))
+            f.write("| %s | %s | %.3g | %.3g |\n" % (k, " | ".join("%.3f" % (leg(n, k) / leg(d, k)) for n, d in ratios),
+                                                    ag["max_abs_vs_aten"], ag["sums_rel_vs_two_step"]))
 
 
 def main():
@@ -184,32 +188,15 @@ def main():
     a = ap.parse_args()
     if a.antialias:
         r = run_antialias(a.rounds)
-        print(json.dumps(r), flush=True)
-        if a.md:
-            write_antialias_md(r, a.md)
-        return
-    r = run(tuple(int(v) for v in a.x.split(",")), tuple(int(v) for v in a.size.split(",")), a.rounds)
+        shapes = "x [%s] fp32 -> %s." % (", ".join(map(str, r["x"])),
+                                         " and ".join("[%d, %d, %d, %d]" % (r["x"][0], r["x"][1], H, W) for H, W in r["sizes"]))
+    else:
+        r = run(tuple(int(v) for v in a.x.split(",")), tuple(int(v) for v in a.size.split(",")), a.rounds)
+        shapes = "x [%s] fp32 -> [%d, 3, %s], channels %s picked by name." % (", ".join(map(str, r["x"])), r["x"][0],
+                                                                             ", ".join(map(str, r["size"])), list(CHANNELS))
     print(json.dumps(r), flush=True)
     if a.md:
-        L = r["legs"]
-        with open(a.md, "w") as f:
-            f.write("# Interpolation baselines: the resample kernels against ATen and plain streams (tools/resample_bench.py)\n\n")
-            f.write("One MI355X, one process, all legs alternating, %d rounds of %d calls after a warm-up, HIP events; x [%s] fp32 -> "
-                    "[%d, 3, %s], channels %s picked by name.\nGB/s counts the bytes a leg must move (the tool's docstring); the "
-                    "spread is (max - min) / mean over the rounds.\n\n"
-                    % (r["rounds"], r["reps"], ", ".join(map(str, r["x"])), r["x"][0], ", ".join(map(str, r["size"])),
-                       list(CHANNELS)))
-            f.write("| leg | ms per call (min .. max, spread) | GB/s of the bytes it must move |\n|---|---|---|\n")
-            for k, v in L.items():
-                f.write("| %s | %.4f (%.4f .. %.4f, %.1f %%) | %.1f |\n" % (k, v["ms"], v["min"], v["max"], 100 * v["spread"], v["GBps"]))
-            f.write("\n| mode | ours / aten | ours / fill | fused / two-step | fused / aten+ | max abs ours - aten | sum 5 fused vs two-step, rel |\n"
-                    "|---|---|---|---|---|---|---|\n")
-            for m in MODES:
-                ag = r["agreement"][m]
-                f.write("| %s | %.3f | %.3f | %.3f | %.3f | %.3g | %.3g |\n"
-                        % (m, L["ours " + m]["ms"] / L["aten " + m]["ms"], L["ours " + m]["ms"] / L["fill"]["ms"],
-                           L["fused " + m]["ms"] / L["two-step " + m]["ms"], L["fused " + m]["ms"] / L["aten+ " + m]["ms"],
-                           ag["max_abs_vs_aten"], ag["sums_rel_vs_two_step"]))
+        write_md(r, a.md, shapes, *(AA_MD if a.antialias else PLAIN_MD))
 
 
 if __name__ == "__main__":
