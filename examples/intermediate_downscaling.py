@@ -118,6 +118,13 @@ def main():
     data_type, train_loss_str = tr.get("data_type", "bfloat16"), tr["train_loss"]
     if data_type not in ("bfloat16", "float32"):
         raise RuntimeError("Data type not supported")
+    # `trainer.consistency: {weight: ..., mode: ...}` tunes the consistency term of mse_consistency / bayesian_tv_consistency
+    cons = tr.get("consistency") or {}
+    if cons and not getattr(cl.metrics.METRICS_REGISTRY.get(train_loss_str), "takes_source", False):
+        raise ValueError("trainer.consistency goes with a consistency loss (mse_consistency, bayesian_tv_consistency), "
+                         "not with train_loss %r" % (train_loss_str,))
+    if cons.get("mode", "bilinear") not in ("bilinear", "bicubic"):
+        raise ValueError("trainer.consistency.mode is bilinear or bicubic, got %r" % (cons["mode"],))
     tiling = conf.get("tiling", {}) or {}
     div, overlap = (tiling.get("div", 1), tiling.get("overlap", 0)) if tiling.get("do_tiling", False) else (1, 0)
     fsdp_size, ddp_size = par.get("fsdp", 1), par.get("simple_ddp", 1)
@@ -154,6 +161,8 @@ def main():
                                   "drop_rate": mc["drop_rate"], "tensor_par_size": tp, "tensor_par_group": tp_group,
                                   "FusedAttn_option": FusedAttn.CK if data_type == "bfloat16" else FusedAttn.DEFAULT})
             model, train_loss = out[0], out[1]
+            if cons:
+                train_loss.weight, train_loss.mode = float(cons.get("weight", 1.0)), cons.get("mode", "bilinear")
             val_losses, val_transforms = out[2], out[5]
             ck = None
             suffix = "_rank_" + str(tp_rank) if tp > 1 else ""      # per tensor-parallel rank files (reference :52,:72)

@@ -34,7 +34,8 @@ extern "C" {
  * orbit2_gaussian_scores).  Added during version 8, changing nothing that exists: orbit2_ensemble_scores; the folded patch-embed
  * entries that carry the patch size (orbit2_varagg_fwd_p, orbit2_varagg_fwd_f32_p, orbit2_varagg_bwd_p and its two queries);
  * orbit2_ssim; orbit2_resample_fwd and orbit2_resample_moments; the mode values 5 and 6 of those two (bilinear and bicubic with
- * ORBIT2_ANTIALIAS), which earlier builds of version 8 refuse with O2_ERR_ARG. */
+ * ORBIT2_ANTIALIAS), which earlier builds of version 8 refuse with O2_ERR_ARG; the mode values 21 and 22 of orbit2_resample_fwd
+ * (those two with ORBIT2_TRANSPOSE: the adjoint of the coarsening), which earlier builds of version 8 refuse as well. */
 int orbit2_abi_version(void);
 
 /* ---- bf16 MFMA GEMM with fused epilogue ------------------------------------------------
@@ -517,8 +518,32 @@ int orbit2_ssim(const float* pred, const float* target, int Ht, int Wt, const fl
  * about 11, bilinear beyond 23, a long axis reduced to a few pixels) it forms the weights where it uses them and reads the taps
  * from global memory, in chunks of CHUNK_ROWS rows.  The choice is per workgroup; the operations and their order are the same,
  * so are the bits.  LDS use does not depend on the sizes.  Per-lane fp32 partial sums of the moments cover 4 pixels here.
- * No window index depends on a value: non-finite inputs give unspecified values, never a fault. */
+ * No window index depends on a value: non-finite inputs give unspecified values, never a fault.
+ *
+ * THE ADJOINT OF THE ANTIALIASED MODES: orbit2_resample_fwd with mode = base | ORBIT2_ANTIALIAS | ORBIT2_TRANSPOSE,
+ * base 1 (21) or 2 (22), applies the transpose of the antialiased resample that takes an (H, W) grid to an (h, w) grid.  The
+ * operands keep their places: x is the gradient g on the COARSE grid, fp32 [B][C][h][w]; out is the gradient d on the FINE
+ * grid, fp32 [B][C][H][W].  With (lo_o, n_o, Wy[o][j]) the window rule above for the forward call that resamples H -> h rows
+ * (in = H, out = h) and (lo_p, n_p, Wx[p][q]) the same for W -> w columns,
+ *   d[Y][X] = sum over o with lo_o <= Y < lo_o + n_o, sum over p with lo_p <= X < lo_p + n_p, of
+ *             Wy[o][Y - lo_o] * Wx[p][X - lo_p] * g[o][p]
+ * and the weights are that forward call's fp32 weights bit for bit, so <A p, g> = <p, A^T g> holds to summation error only.
+ * ORDER: t[o][X] is the sum over the windows p that hold X, p ascending: the first is a product, every later one a fused
+ * multiply-add, and t is ROUNDED TO fp32; d[Y][X] is the sum over the windows o that hold Y, o ascending, of Wy * t[o][X] in the
+ * same way.  Every element of out is written, and the result is the same bits from call to call (no atomics).  The identity
+ * (h == H, w == W) returns g exactly for finite g that holds no negative zero.
+ * Only coarsening is built: at every ratio >= 1 a fine coordinate lies in at least 1 and at most 3 (bilinear) or 5 (bicubic)
+ * windows, and lo and lo + n do not decrease with o, so the footprint of a fine pixel is fixed.  A workgroup owns an
+ * ORBIT2_AT_TILE_H x ORBIT2_AT_TILE_W tile of the fine grid and keeps at most ORBIT2_AT_COVER windows per fine coordinate.
+ * Refused with O2_ERR_ARG before any launch: h > H or w > W; chan_idx != NULL or C != in_ctotal; scale or shift non-NULL;
+ * ORBIT2_TRANSPOSE with any base other than 5 or 6 (16, 17, 18, 20, 23, ...), and in orbit2_resample_moments always; a pair of
+ * sizes whose windows decrease or cover a fine coordinate more than ORBIT2_AT_COVER times; and everything the plain call
+ * refuses (null pointers, non-positive sizes, B * C > 65535). */
 #define ORBIT2_ANTIALIAS 4
+#define ORBIT2_TRANSPOSE 16
+#define ORBIT2_AT_TILE_H 32
+#define ORBIT2_AT_TILE_W 64
+#define ORBIT2_AT_COVER 5
 #define ORBIT2_AA_TILE_H 16
 #define ORBIT2_AA_TILE_W 64
 #define ORBIT2_AA_CHUNK_ROWS 32

@@ -1150,6 +1150,8 @@ RESAMPLE_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}
 RESAMPLE_TILE = (32, 256)       # (ORBIT2_RESAMPLE_TILE_H, ORBIT2_RESAMPLE_TILE_W): output pixels per workgroup
 RESAMPLE_LDS_FLOATS = 10240     # ORBIT2_RESAMPLE_LDS_FLOATS: the staged source window of a tile
 ANTIALIAS = 4                   # ORBIT2_ANTIALIAS: or-ed into the mode code of bilinear and bicubic
+TRANSPOSE = 16                  # ORBIT2_TRANSPOSE: or-ed into 5 and 6 of orbit2_resample_fwd, the adjoint of the coarsening
+RESAMPLE_ADJOINT_TILE = (32, 64)        # (ORBIT2_AT_TILE_H, ORBIT2_AT_TILE_W): fine pixels per workgroup of the adjoint
 
 
 _RESAMPLE_IDX = {}              # (channels, device) -> the validated device int32 copy
@@ -1233,6 +1235,32 @@ def resample_moments(x, size, mode, target, channels=None, scale=None, shift=Non
     out = torch.empty(B, Cc, 12, dtype=torch.float64, device=x.device)
     _call("orbit2_resample_moments", x, idx, Cin, scale, shift, target, target.shape[2], target.shape[3], lat_w, clim, out,
           B, Cc, h, w, H, W, m)
+    return out
+
+
+def resample_adjoint(g, size, mode="bilinear"):
+    """fp32 [B,C,H,W]: the adjoint of resample(., (h, w), mode, antialias=True) on a field of `size` = (H, W), applied to the
+    gradient g [B,C,h,w] of the coarsened field (include/orbit2_hip.h: orbit2_resample_fwd with ORBIT2_TRANSPOSE, mode codes 21
+    and 22).  Coarsening only: H >= h and W >= w.  The weights are the forward kernel's bit for bit."""
+    if not torch.is_tensor(g) or g.dim() != 4:
+        raise HipBackendError("resample_adjoint takes an [B,C,h,w] gradient")
+    if mode not in ("bilinear", "bicubic"):
+        raise HipBackendError("resample_adjoint: mode is bilinear or bicubic (the antialiased modes), got %r" % (mode,))
+    try:
+        H, W = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise HipBackendError("resample_adjoint: size is (H, W), got %r" % (size,)) from None
+    B, C, h, w = g.shape
+    if min(B, C, h, w) < 1:
+        raise HipBackendError("resample_adjoint: every size must be positive (g %s)" % (tuple(g.shape),))
+    if H < h or W < w:
+        raise HipBackendError("resample_adjoint: only the adjoint of a coarsening is built: size %s is smaller than g's %s"
+                              % ((H, W), (h, w)))
+    _dev(g, F32, "g")
+    if B * C > 65535:
+        raise HipBackendError("resample_adjoint: B * C = %d images, at most 65535 are served in one call" % (B * C))
+    out = torch.empty(B, C, H, W, dtype=F32, device=g.device)
+    _call("orbit2_resample_fwd", g, None, C, None, None, out, B, C, h, w, H, W, RESAMPLE_MODES[mode] | ANTIALIAS | TRANSPOSE)
     return out
 
 

@@ -1009,3 +1009,19 @@ class MaskedLossFn(torch.autograd.Function):
         dp = _hip.masked_loss_bwd(pred, target, lat_w if lat_w.numel() else None, chan_w if chan_w.numel() else None, gs, cnt,
                                   ctx.kind, mask if mask.numel() else None, ctx.mask_strides)
         return dp, None, None, None, None, None, None, None, None
+
+
+class CoarsenFn(torch.autograd.Function):
+    """antialiased coarsening of a prediction with a backward: forward _hip.resample(pred, size, mode, antialias=True), backward
+    its adjoint kernel (_hip.resample_adjoint) with the forward's fp32 weights bit for bit.  The one differentiable
+    use of the resample kernels (metrics.functional.consistency_mse): _hip.resample and models.hub.Interpolation stay without a
+    backward.  Nothing here reads the device or copies to it, so forward + backward can be captured in a hipGraph."""
+
+    @staticmethod
+    def forward(ctx, pred, size, mode):
+        ctx.fine, ctx.mode = tuple(pred.shape[-2:]), mode
+        return _hip.resample(_f32(pred).detach(), size, mode, antialias=True)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return _hip.resample_adjoint(_f32(grad), ctx.fine, ctx.mode), None, None

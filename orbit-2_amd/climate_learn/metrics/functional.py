@@ -56,6 +56,78 @@ def image_gradient(pred, target, var_names: Optional[List[str]] = None, var_weig
     return _fused(pred, target, var_names, var_weights, True, None, 2)
 
 
+# ---- consistency with the input: the prediction, coarsened WITH antialiasing, against the field the model was
+# given.  The training form of utils.visualize.consistency_scores: the coarsening has a backward (_ops.CoarsenFn, the adjoint
+# kernel of the antialiased resample), the score is the fused mse. ----------------------------------------------------------------
+_CONSISTENCY_IDX = {}               # (channels, device) -> the device int64 index of index_select
+
+
+def _consistency_given(source, channels, rescale, device):
+    """source[:, channels] * scale + shift, fp32 on `device`; the index and the affine pair are cached device tensors, so a step
+    copies nothing from the host (a captured hipGraph forbids it)"""
+    given = source.detach()
+    if given.device != device:
+        given = given.to(device)
+    given = given.float()
+    if channels is not None:
+        chans = tuple(int(c) for c in channels)
+        bad = [c for c in chans if not 0 <= c < source.shape[1]]
+        if bad or not chans:
+            raise ValueError("consistency_mse: channels %s outside 0..%d" % (list(chans), source.shape[1] - 1))
+        key = (chans, str(device))
+        idx = _CONSISTENCY_IDX.get(key)
+        if idx is None:
+            idx = _CONSISTENCY_IDX[key] = torch.tensor(chans, dtype=torch.int64, device=device)
+        given = given.index_select(1, idx)
+    if rescale is not None and rescale[0] is not None:
+        scale, shift = rescale
+        if not torch.is_tensor(scale):
+            key = (tuple(float(v) for v in scale), tuple(float(v) for v in shift), str(device))
+            pair = _CW_CACHE.get(key)
+            if pair is None:
+                pair = _CW_CACHE[key] = (torch.tensor(key[0], dtype=torch.float32, device=device).view(1, -1, 1, 1),
+                                         torch.tensor(key[1], dtype=torch.float32, device=device).view(1, -1, 1, 1))
+            scale, shift = pair
+        else:
+            scale, shift = scale.reshape(1, -1, 1, 1), shift.reshape(1, -1, 1, 1)
+        if scale.shape[1] != given.shape[1] or shift.shape[1] != given.shape[1]:
+            raise ValueError("consistency_mse: rescale needs one (scale, shift) per channel (%d), got %d and %d"
+                             % (given.shape[1], scale.shape[1], shift.shape[1]))
+        given = given * scale + shift
+    return given.contiguous()
+
+
+def consistency_mse(pred, source, var_names: Optional[List[str]] = None, var_weights: Optional[Dict[str, float]] = None,
+                    aggregate_only: bool = False, lat_weights=None, mode: str = "bilinear", channels=None, rescale=None):
+    """mse(coarsen(pred), given), [C + 1] as mse returns it, differentiable in pred.  pred [B,C,H,W]; source [B,V,h,w] the
+    (normalised) input of the model.  With s = H // h the prediction is coarsened to (H // s, W // s) in `mode` (bilinear or
+    bicubic) with antialiasing, and scored against given = source[:, channels] * scale + shift (`rescale` = (scale, shift) per
+    channel moves the inputs' normalisation to the outputs', utils.loaders._interpolation_rescale), read through its top-left
+    crop where the prediction covers less: the arithmetic of utils.visualize.consistency_scores.  `lat_weights` are those of
+    the LOW-resolution rows.  The gradient reaches pred through the adjoint kernel of the antialiased resample."""
+    from ..models.hub.interpolation import Resampled
+    if isinstance(pred, Resampled):
+        raise TypeError("consistency_mse: a Resampled prediction (an interpolation baseline) has no backward -- score it with "
+                        "utils.visualize.consistency_scores")
+    if isinstance(pred, torch.distributions.Normal):
+        pred = pred.loc
+    if pred.dim() != 4 or source.dim() != 4 or source.shape[0] != pred.shape[0]:
+        raise ValueError("consistency_mse takes a prediction [B,C,H,W] and a source [B,V,h,w], got %s and %s"
+                         % (tuple(pred.shape), tuple(source.shape)))
+    H, W = pred.shape[-2:]
+    s = H // source.shape[2]
+    if s < 1 or H // s > source.shape[2] or W // s > source.shape[3]:
+        raise ValueError("consistency_mse: a prediction of %s does not coarsen onto a source of %s"
+                         % (tuple(pred.shape), tuple(source.shape)))
+    given = _consistency_given(source, channels, rescale, pred.device)
+    if given.shape[1] != pred.shape[1]:
+        raise ValueError("consistency_mse: %d source channels for %d predicted ones -- name them with `channels`"
+                         % (given.shape[1], pred.shape[1]))
+    coarse = _ops.CoarsenFn.apply(pred, (H // s, W // s), mode)
+    out = _ops.LossFn.apply(coarse, given, _lat(lat_weights, coarse), _chan_weights(coarse, var_names, var_weights), 0)
+    return out[-1] if aggregate_only else out
+
+
 # ---- missing data: losses and metrics over the VALID pixels only (csrc/masked.hip, DESIGN 4.10d) ------------------------------
 # valid = the target is finite there, and the mask (if one is given) is non-zero.  The reference has no such loss
 # (examples/era5_daymet_downscaling.py names `masked_mse` but its metrics package has none) and a `mask` argument on rmse /

@@ -45,6 +45,56 @@ class Bayesian_TV(Metric):
         return bayesian_tv(pred, target, var_names, var_weights, self.aggregate_only)
 
 
+class _WithConsistency:
+    """base loss + weight x functional.consistency_mse(pred, source): the prediction, coarsened with antialiasing, is held to the
+    field the model was given.  Per channel and in aggregate, as the base loss returns them.
+    set_source(x, in_variables) hands over a step's input (trainer.training_step does, for a loss with `takes_source`);
+    set_rescale(scale, shift) the affine that moves the inputs' normalisation to the outputs', once (utils.loaders).  A constant
+    output variable (CONSTANTS) has weight 0 in the term: clip_replace_constant overwrites it with the truth.  Every output
+    variable must be among the inputs."""
+
+    takes_source = True
+    graph_capturable = True       # no host read and no host-to-device copy per step: the index and weights are cached device tensors
+    weight = 1.0
+    mode = "bilinear"
+    _source = _in_variables = _rescale = None
+    _base = None                  # the functional of the base loss
+
+    def set_source(self, x, in_variables):
+        self._source, self._in_variables = x, list(in_variables)
+        return self
+
+    def set_rescale(self, scale, shift):
+        self._rescale = None if scale is None else (tuple(float(v) for v in scale), tuple(float(v) for v in shift))
+        return self
+
+    def __call__(self, pred, target, var_names: Optional[List[str]] = None,
+                 var_weights: Optional[Dict[str, float]] = None):
+        from ..data.processing.era5_constants import CONSTANTS
+        if self._source is None:
+            raise RuntimeError("%s: set_source(x, in_variables) must be called with the step's input before the loss"
+                               % getattr(self, "name", type(self).__name__))
+        names = list(var_names) if var_names is not None else list(self.metainfo.out_vars)
+        if any(v not in self._in_variables for v in names):
+            raise RuntimeError("consistency_scores requires the output variables to be among the input variables.")
+        base = type(self)._base(pred, target, var_names, var_weights, False)
+        weights = {v: (0.0 if v in CONSTANTS else float((var_weights or {}).get(v, 1.0))) for v in names}
+        term = _F.consistency_mse(pred, self._source, names, weights, False, None, self.mode,
+                                  [self._in_variables.index(v) for v in names], self._rescale)
+        out = base + self.weight * term
+        return out[-1] if self.aggregate_only else out
+
+
+@register("mse_consistency")
+class MSEConsistency(_WithConsistency, Metric):
+    _base = staticmethod(mse)
+
+
+@register("bayesian_tv_consistency")
+class BayesianTVConsistency(_WithConsistency, Metric):
+    _base = staticmethod(bayesian_tv)
+
+
 @register("imagegradient")
 class IMAGEGRADIENT(Metric):
     def __call__(self, pred, target, var_names: Optional[List[str]] = None,

@@ -28,6 +28,8 @@ def training_step(batch, batch_idx, net, device, var_weights: Optional[Dict[str,
     y = y.to(device, non_blocking=True)
     yhat = net.forward(x, in_variables, out_variables)
     yhat = clip_replace_constant(y, yhat, out_variables)
+    if getattr(train_loss_metric, "takes_source", False):       # a consistency loss reads the prediction against its input
+        train_loss_metric.set_source(x, in_variables)
     losses = train_loss_metric(yhat, y, var_names=out_variables, var_weights=var_weights)
     return losses if losses.dim() == 0 else losses[-1]
 

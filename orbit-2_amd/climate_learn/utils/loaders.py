@@ -151,6 +151,10 @@ def load_model_module(device, data_module, task: str, architecture: Optional[str
         train_loss = load_loss(device, model, train_loss, True, metainfo("train"))
     elif not isinstance(train_loss, Callable):
         raise TypeError("'train_loss' must be str or Callable")
+    if getattr(train_loss, "takes_source", False):      # a consistency loss compares with the input in the outputs' normalisation
+        if not set(out_vars) <= set(in_vars):
+            raise RuntimeError("consistency_scores requires the output variables to be among the input variables.")
+        train_loss.set_rescale(*_interpolation_rescale(data_module, out_vars))
 
     def load_many(names, split):
         out = []

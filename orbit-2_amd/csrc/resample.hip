@@ -1,15 +1,17 @@
 // Interpolation baselines: F.interpolate(size=(H, W), mode=nearest | bilinear | bicubic, align_corners=False) of gathered channels
 // of an fp32 [B, in_ctotal, h, w] field, with an optional per-channel affine, either stored (orbit2_resample_fwd) or scored
 // against a target without ever being stored (orbit2_resample_moments: the twelve sums of orbit2_eval_moments).
-// include/orbit2_hip.h: orbit2_resample_*; models/hub/interpolation.py; DESIGN 4.10c.
-// Two kernels: the plain modes' (no antialiasing) and, further down, the antialiased forms of bilinear and bicubic
-// (mode | ORBIT2_ANTIALIAS).  They differ in how a pixel is formed and in their tiles.  What they share is stated once:
+// include/orbit2_hip.h: orbit2_resample_*; models/hub/interpolation.py; DESIGN 4.10c, 4.10g.
+// Three kernels: the plain modes' (no antialiasing); further down, the antialiased forms of bilinear and bicubic
+// (mode | ORBIT2_ANTIALIAS); and the adjoint of those when they coarsen (mode | ORBIT2_ANTIALIAS | ORBIT2_TRANSPOSE: the backward
+// of the consistency training loss).  They differ in how a pixel is formed and in their tiles.  What they share is stated once:
 //   RsArgs     the operands of a call, one struct by value; what only one kernel needs stays an argument of that kernel
 //   rs_frame   a workgroup's place in the call: its (b, c) image, tile origin, gathered source plane, the channel's affine pair
 //   rs_load4   four consecutive floats of a row: one float4 where all four exist and sit on a 16-byte boundary
 //   rs_emit    the epilogue of a thread's FOUR CONSECUTIVE output columns of one row: the affine, then the store, or the target
 //              and climatology quads and the twelve moments, columns ascending
 //   rs_launch  the argument checks, tile sizes, grid and mode dispatch of both entries
+// and the adjoint forms its windows and weights with the antialiased kernel's aa_window / aa_weight: the same bits.
 //
 // The plain kernel: a workgroup owns one RS_TH x RS_TW tile of one (b, c) output image.  A lane owns four consecutive output
 // columns, so a wave covers the tile's 256 columns and stores (or reads the target as) one float4 per lane and row; wave v takes
@@ -28,6 +30,7 @@
 // Summation order: a row interpolant is its taps left to right (first product, then fmaf), a pixel its row interpolants top to
 // bottom in the same way, then fmaf(scale[c], r, shift[c]).  Every source index is clamped into the grid and no address depends
 // on a data value: non-finite inputs give unspecified values, never a fault.
+#include <algorithm>
 #include "score_sums.h"
 #include "../../include/orbit2_hip.h"
 
@@ -395,21 +398,177 @@ __global__ __launch_bounds__(256) void resample_aa_kernel(const RsArgs p, float 
   if (MOMENTS) o2_block_sums_add(s, p.sums + (size_t)f.bc * RS_NM);
 }
 
+// ---- the adjoint of the antialiased modes (mode | ORBIT2_ANTIALIAS | ORBIT2_TRANSPOSE), coarsening only ------------------------
+// x is the gradient g on the coarse (h, w) grid, out the gradient d on the fine (H, W) grid of the forward call that resamples
+// (H, W) -> (h, w):  d[Y][X] = sum_o sum_p Wy[o][Y - lo_o] Wx[p][X - lo_p] g[o][p]  over the windows that hold Y and X, the
+// windows and weights being aa_window / aa_weight of that forward call (n_in = H or W, n_out = h or w), bit for bit.
+// A fine pixel lies in at most 3 (bilinear) or 5 (bicubic) windows per axis at every ratio >= 1, and in at least one; lo and
+// lo + n do not decrease with o.  So the adjoint is a gather with a fixed footprint: no atomics, one path, LDS use that does not
+// depend on the sizes.  A workgroup owns an AT_TH x AT_TW tile of the FINE grid of one (b, c) image:
+//   1. one thread per candidate forms the window of coarse column at_base + i (i < AT_NX) or coarse row (i < AT_NY): at_base is
+//      at least one below the first window that can reach the tile, and tile / ratio + 2 (interp / 2) + 3 candidates reach past
+//      the last one.  The candidates that meet the tile are one range per axis (first .. last, by atomicMin / atomicMax in LDS).
+//   2. one thread per fine column and row of the tile scans that range for the first window that holds it, counts the windows
+//      that follow and hold it too (at most AT_COVER), and forms their weights: the tables first / cnt / wgt.
+//   3. the coarse patch of g under those ranges is staged in LDS, a wave per row.
+//   4. horizontal pass: mid[o][X] = sum over the windows p of X, ascending, of wgt * g[o][p] (a product, then fused
+//      multiply-adds), rounded to fp32; a thread keeps its column's table in registers and takes every fourth coarse row.
+//   5. vertical pass: thread t owns the four columns 4 (t % 16) .. + 3 of tile rows t / 16 and t / 16 + 16; a pixel is the sum
+//      over the windows o of Y, ascending, of wgt * mid[o][X] in the same way, handed to rs_emit (one 16-byte store).
+// Every index is formed from the sizes alone and every range is clipped to its table: no address depends on a data value.
+constexpr int AT_TH = ORBIT2_AT_TILE_H, AT_TW = ORBIT2_AT_TILE_W, AT_COVER = ORBIT2_AT_COVER;
+constexpr int AT_NY = AT_TH + 10, AT_NX = AT_TW + 10;        // candidate windows per axis: tile / ratio + 2 * 2 + 3 at ratio 1, and slack
+constexpr int AT_PP = AT_NX | 1;                             // pitch of the staged patch: odd, its rows spread over the banks
+constexpr int AT_MP = AT_TW + 4;                             // pitch of mid: float4 reads stay aligned, rows shift by one 16-byte slot
+static_assert(AT_TW == 64 && AT_TH == 32, "256 threads: sixteen float4 columns, two rows each of sixteen");
+static_assert(AT_NX <= 128 && AT_NY <= 128 && AT_COVER == 5, "threads 0 .. 127 serve the columns, 128 .. 255 the rows");
+
+template <int NC, int NT>
+struct at_axis {                                  // one axis of a tile, in LDS
+  int lo[NC], n[NC];                              // the candidates' windows
+  float ctr[NC], tot[NC];
+  int range[2];                                   // first and last candidate that meets the tile
+  int first[NT], cnt[NT];                         // per fine coordinate: its first window (counted from range[0]) and how many
+  float wgt[AT_COVER][NT];
+};
+
+// the first candidate: (c0 + 0.5) / ratio - 0.5 - interp / 2 bounds the first window that reaches fine coordinate c0 from below
+template <int MODE>
+__device__ __forceinline__ int at_base(int c0, float ratio) {
+  return max((int)floorf((float)c0 / ratio - 0.5f - (MODE == 1 ? 1.f : 2.f)) - 1, 0);
+}
+
+// step 1, thread i of an axis: the tile holds the fine coordinates c0 .. c1 - 1
+template <int MODE, int NC, int NT>
+__device__ __forceinline__ void at_candidate(at_axis<NC, NT>& ax, int i, int base, int c0, int c1, int n_fine, int n_coarse,
+                                             float ratio, float sup, float inv) {
+  if (i >= NC || base + i >= n_coarse) return;
+  aa_window<MODE>(base + i, n_fine, ratio, sup, inv, ax.lo[i], ax.n[i], ax.ctr[i], ax.tot[i]);
+  if (ax.lo[i] < c1 && ax.lo[i] + ax.n[i] > c0) {
+    atomicMin(&ax.range[0], i);
+    atomicMax(&ax.range[1], i);
+  }
+}
+
+// step 2, thread j of an axis: fine coordinate c0 + j
+template <int MODE, int NC, int NT>
+__device__ __forceinline__ void at_table(at_axis<NC, NT>& ax, int j, int c0, int c1, float inv) {
+  if (j >= NT) return;
+  const int c = c0 + j, r0 = ax.range[0], r1 = ax.range[1];
+  int i = r0, cnt = 0;
+  if (c < c1) {
+    while (i <= r1 && !(ax.lo[i] <= c && c < ax.lo[i] + ax.n[i])) ++i;
+    while (cnt < AT_COVER && i + cnt <= r1 && ax.lo[i + cnt] <= c && c < ax.lo[i + cnt] + ax.n[i + cnt]) {
+      const int k = i + cnt;
+      ax.wgt[cnt][j] = aa_weight<MODE>(c - ax.lo[k], ax.lo[k], ax.ctr[k], inv, ax.tot[k]);
+      ++cnt;
+    }
+  }
+  ax.first[j] = cnt ? i - r0 : 0;
+  ax.cnt[j] = cnt;
+  for (int k = cnt; k < AT_COVER; ++k) ax.wgt[k][j] = 0.f;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void resample_aa_adjoint_kernel(const RsArgs p, float supy, float supx, float invy, float invx) {
+  __shared__ at_axis<AT_NX, AT_TW> axx;
+  __shared__ at_axis<AT_NY, AT_TH> axy;
+  __shared__ float patch[AT_NY * AT_PP];
+  __shared__ __attribute__((aligned(16))) float mid[AT_NY * AT_MP];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const rs_frame f = rs_frame_of<AT_TH, AT_TW>(p);            // f.src: the (b, c) plane of g, h x w
+  const int y1 = min(f.y0 + AT_TH, p.H), x1 = min(f.x0 + AT_TW, p.W);
+  const int basey = at_base<MODE>(f.y0, p.ry), basex = at_base<MODE>(f.x0, p.rx);
+  if (tid == 0) axx.range[0] = AT_NX, axx.range[1] = -1, axy.range[0] = AT_NY, axy.range[1] = -1;
+  __syncthreads();
+  if (tid < 128) at_candidate<MODE>(axx, tid, basex, f.x0, x1, p.W, p.w, p.rx, supx, invx);
+  else at_candidate<MODE>(axy, tid - 128, basey, f.y0, y1, p.H, p.h, p.ry, supy, invy);
+  __syncthreads();
+  if (tid < 128) at_table<MODE>(axx, tid, f.x0, x1, invx);
+  else at_table<MODE>(axy, tid - 128, f.y0, y1, invy);
+  // the coarse patch: rows oy0 .. oy0 + ny - 1, columns ox0 .. ox0 + nx - 1 of g (both ranges hold at least one window)
+  const int ny = axy.range[1] - axy.range[0] + 1, nx = axx.range[1] - axx.range[0] + 1;
+  const int oy0 = basey + axy.range[0], ox0 = basex + axx.range[0];
+  for (int r = tid >> 6; r < ny; r += 4)
+    for (int q = lane; q < nx; q += 64) patch[r * AT_PP + q] = f.src[(size_t)(oy0 + r) * p.w + ox0 + q];
+  __syncthreads();                                // the tables and the patch
+
+  {                                               // horizontal pass: this thread's fine column, every fourth coarse row
+    const int fx = axx.first[lane], cx = axx.cnt[lane];
+    float wx[AT_COVER];
+#pragma unroll
+    for (int k = 0; k < AT_COVER; ++k) wx[k] = axx.wgt[k][lane];
+    for (int o = tid >> 6; o < ny; o += 4) {
+      const float* row = patch + o * AT_PP + fx;
+      float t = 0.f;
+      if (cx > 0) {
+        t = wx[0] * row[0];
+#pragma unroll
+        for (int k = 1; k < AT_COVER; ++k)
+          if (k < cx) t = fmaf(wx[k], row[k], t);
+      }
+      mid[o * AT_MP + lane] = t;
+    }
+  }
+  __syncthreads();
+
+  const int xl = f.x0 + 4 * (tid & 15);
+  float none[RS_NM];                              // rs_emit's sums: not touched when it stores
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int i = (tid >> 4) + 16 * half, y = f.y0 + i;
+    if (y >= p.H || xl >= p.W) continue;
+    const int fy = axy.first[i], cy = axy.cnt[i];
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < AT_COVER; ++k) {
+      if (k < cy) {
+        const float wy = axy.wgt[k][i];
+        const float4 m = *reinterpret_cast<const float4*>(mid + (fy + k) * AT_MP + 4 * (tid & 15));
+        const float mv[4] = {m.x, m.y, m.z, m.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = k == 0 ? wy * mv[j] : fmaf(wy, mv[j], acc[j]);
+      }
+    }
+    rs_emit<false>(p, f, y, xl, acc, none);
+  }
+}
+
 // ---- the launch of both entries -------------------------------------------------------------------------------------------------
 // ceil(tile * in / out) + 4: no window of a tile at this ratio is larger (a bicubic footprint is the span of the floors + 4)
 inline int64_t rs_footprint(int tile, int n_in, int n_out) { return ((int64_t)tile * n_in + n_out - 1) / n_out + 4; }
+
+// The adjoint kernel's tables hold AT_COVER windows per fine coordinate.  The windows of one axis, lo and hi by aa_window's
+// arithmetic: true when lo and hi do not decrease with o and no fine coordinate lies in more than AT_COVER of them (window
+// o - AT_COVER ends at or before window o begins).  O(n_out) on the host, per call.
+inline bool at_windows_fit(int n_in, int n_out, float ratio, float sup) {
+  int his[AT_COVER], plo = 0, phi = 0;
+  for (int o = 0; o < n_out; ++o) {
+    const float center = ratio * ((float)o + 0.5f);
+    const int a = (int)((center - sup) + 0.5f), b = (int)((center + sup) + 0.5f);
+    const int lo = std::min(std::max(a, 0), n_in - 1), hi = std::max(std::min(b, n_in), lo + 1);
+    if (lo < plo || hi < phi) return false;
+    if (o >= AT_COVER && his[o % AT_COVER] > lo) return false;
+    his[o % AT_COVER] = hi, plo = lo, phi = hi;
+  }
+  return true;
+}
 
 template <bool MOMENTS>
 int rs_launch(RsArgs p, int B, int mode, hipStream_t s) {
   if (!p.x || (MOMENTS ? (!p.sums || !p.target) : !p.out) || (p.scale == nullptr) != (p.shift == nullptr)) return O2_ERR_ARG;
   if (B <= 0 || p.C <= 0 || p.in_ctotal <= 0 || p.h <= 0 || p.w <= 0 || p.H <= 0 || p.W <= 0) return O2_ERR_ARG;
-  // 0, 1, 2 plain; bilinear and bicubic also with ORBIT2_ANTIALIAS (5, 6); nearest has no antialiased form
-  const bool aa = mode == (1 | ORBIT2_ANTIALIAS) || mode == (2 | ORBIT2_ANTIALIAS);
+  // 0, 1, 2 plain; bilinear and bicubic also with ORBIT2_ANTIALIAS (5, 6); nearest has no antialiased form.  ORBIT2_TRANSPOSE
+  // goes with 5 and 6 of orbit2_resample_fwd alone (21, 22): the adjoint of the coarsening (H, W) -> (h, w), no gather, no affine
+  const bool tr = !MOMENTS && (mode == (1 | ORBIT2_ANTIALIAS | ORBIT2_TRANSPOSE) || mode == (2 | ORBIT2_ANTIALIAS | ORBIT2_TRANSPOSE));
+  const int base = tr ? mode ^ ORBIT2_TRANSPOSE : mode;
+  const bool aa = base == (1 | ORBIT2_ANTIALIAS) || base == (2 | ORBIT2_ANTIALIAS);
   if (!aa && (mode < 0 || mode > 2)) return O2_ERR_ARG;
   if (!p.chan_idx && p.C != p.in_ctotal) return O2_ERR_ARG;
+  if (tr && (p.chan_idx || p.C != p.in_ctotal || p.scale || p.shift || p.h > p.H || p.w > p.W)) return O2_ERR_ARG;
   if (MOMENTS && (p.Ht < p.H || p.Wt < p.W)) return O2_ERR_ARG;
   if ((int64_t)B * p.C > 65535) return O2_ERR_ARG;
-  const int th = aa ? AA_TH : RS_TH, tw = aa ? AA_TW : RS_TW;
+  const int th = tr ? AT_TH : (aa ? AA_TH : RS_TH), tw = tr ? AT_TW : (aa ? AA_TW : RS_TW);
   p.ntx = (p.W + tw - 1) / tw;
   const int nty = (p.H + th - 1) / th;
   if ((int64_t)p.ntx * nty > INT32_MAX) return O2_ERR_ARG;
@@ -417,19 +576,27 @@ int rs_launch(RsArgs p, int B, int mode, hipStream_t s) {
   const int stage = rs_footprint(RS_TH, p.h, p.H) * rs_footprint(RS_TW, p.w, p.W) <= RS_LDS;
   const dim3 grid(p.ntx * nty, B * p.C);
   // the two ratios of the contract, one correctly rounded fp32 division each: formed here once, not by every thread
-  const float ry = p.ry = (float)p.h / (float)p.H, rx = p.rx = (float)p.w / (float)p.W;
+  // (the adjoint's windows are those of the forward call that coarsens out's grid to x's: its ratios are that call's)
+  const float ry = p.ry = tr ? (float)p.H / (float)p.h : (float)p.h / (float)p.H;
+  const float rx = p.rx = tr ? (float)p.W / (float)p.w : (float)p.w / (float)p.W;
   // support and inverse scale of the antialiased contract, one fp32 operation each: a window spans interp / 2 source pixels per
   // unit of max(ratio, 1) to either side of its centre
-  const float half = mode == (1 | ORBIT2_ANTIALIAS) ? 1.f : 2.f;
+  const float half = base == (1 | ORBIT2_ANTIALIAS) ? 1.f : 2.f;
   const float supy = ry >= 1.f ? half * ry : half, supx = rx >= 1.f ? half * rx : half;
   const float invy = ry >= 1.f ? 1.f / ry : 1.f, invx = rx >= 1.f ? 1.f / rx : 1.f;
+  // more windows on a fine pixel than the adjoint's tables hold: refused, never clipped in silence
+  if (tr && !(at_windows_fit(p.H, p.h, ry, supy) && at_windows_fit(p.W, p.w, rx, supx))) return O2_ERR_ARG;
   switch (mode) {
     case 0: hipLaunchKernelGGL((resample_kernel<0, MOMENTS>), grid, dim3(256), 0, s, p, stage); break;
     case 1: hipLaunchKernelGGL((resample_kernel<1, MOMENTS>), grid, dim3(256), 0, s, p, stage); break;
     case 2: hipLaunchKernelGGL((resample_kernel<2, MOMENTS>), grid, dim3(256), 0, s, p, stage); break;
     case 1 | ORBIT2_ANTIALIAS:
       hipLaunchKernelGGL((resample_aa_kernel<1, MOMENTS>), grid, dim3(256), 0, s, p, supy, supx, invy, invx); break;
-    default: hipLaunchKernelGGL((resample_aa_kernel<2, MOMENTS>), grid, dim3(256), 0, s, p, supy, supx, invy, invx); break;
+    case 2 | ORBIT2_ANTIALIAS:
+      hipLaunchKernelGGL((resample_aa_kernel<2, MOMENTS>), grid, dim3(256), 0, s, p, supy, supx, invy, invx); break;
+    case 1 | ORBIT2_ANTIALIAS | ORBIT2_TRANSPOSE:
+      hipLaunchKernelGGL((resample_aa_adjoint_kernel<1>), grid, dim3(256), 0, s, p, supy, supx, invy, invx); break;
+    default: hipLaunchKernelGGL((resample_aa_adjoint_kernel<2>), grid, dim3(256), 0, s, p, supy, supx, invy, invx); break;
   }
   O2_CHECK_LAUNCH();
   return O2_OK;
