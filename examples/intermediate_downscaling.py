@@ -94,6 +94,20 @@ def load_checkpoint(model, path, rank):
     return cl.utils.load_checkpoint(model, path)
 
 
+SSIM_LOSSES = ("ssim_loss", "mse_ssim", "bayesian_tv_ssim")
+
+
+def ssim_settings(tr):
+    """`trainer.ssim: {weight: ..., data_range: ...}` tunes the SSIM term of ssim_loss / mse_ssim / bayesian_tv_ssim: the block
+    ({} if absent), refused by name with any other train_loss"""
+    conf = tr.get("ssim") or {}
+    if conf and tr["train_loss"] not in SSIM_LOSSES:
+        raise ValueError("trainer.ssim goes with an SSIM loss (%s), not with train_loss %r" % (", ".join(SSIM_LOSSES), tr["train_loss"]))
+    if isinstance(conf.get("data_range"), str) and conf["data_range"] != "target":
+        raise ValueError("trainer.ssim.data_range is a number, a dict per variable or 'target', got %r" % (conf["data_range"],))
+    return conf
+
+
 def main():
     cfg_path = sys.argv[1]
     conf = yaml.load(open(cfg_path), Loader=yaml.FullLoader)
@@ -125,6 +139,7 @@ def main():
                          "not with train_loss %r" % (train_loss_str,))
     if cons.get("mode", "bilinear") not in ("bilinear", "bicubic"):
         raise ValueError("trainer.consistency.mode is bilinear or bicubic, got %r" % (cons["mode"],))
+    ssim_conf = ssim_settings(tr)
     tiling = conf.get("tiling", {}) or {}
     div, overlap = (tiling.get("div", 1), tiling.get("overlap", 0)) if tiling.get("do_tiling", False) else (1, 0)
     fsdp_size, ddp_size = par.get("fsdp", 1), par.get("simple_ddp", 1)
@@ -163,6 +178,9 @@ def main():
             model, train_loss = out[0], out[1]
             if cons:
                 train_loss.weight, train_loss.mode = float(cons.get("weight", 1.0)), cons.get("mode", "bilinear")
+            if ssim_conf:
+                train_loss.weight = float(ssim_conf.get("weight", 1.0))
+                train_loss.data_range = ssim_conf.get("data_range", "target")
             val_losses, val_transforms = out[2], out[5]
             ck = None
             suffix = "_rank_" + str(tp_rank) if tp > 1 else ""      # per tensor-parallel rank files (reference :52,:72)

@@ -35,7 +35,8 @@ extern "C" {
  * entries that carry the patch size (orbit2_varagg_fwd_p, orbit2_varagg_fwd_f32_p, orbit2_varagg_bwd_p and its two queries);
  * orbit2_ssim; orbit2_resample_fwd and orbit2_resample_moments; the mode values 5 and 6 of those two (bilinear and bicubic with
  * ORBIT2_ANTIALIAS), which earlier builds of version 8 refuse with O2_ERR_ARG; the mode values 21 and 22 of orbit2_resample_fwd
- * (those two with ORBIT2_TRANSPOSE: the adjoint of the coarsening), which earlier builds of version 8 refuse as well. */
+ * (those two with ORBIT2_TRANSPOSE: the adjoint of the coarsening), which earlier builds of version 8 refuse as well; the kind
+ * value 3 of orbit2_loss_bwd (ORBIT2_LOSS_SSIM_VJP: the backward of orbit2_ssim's sums), which earlier builds refuse too. */
 int orbit2_abi_version(void);
 
 /* ---- bf16 MFMA GEMM with fused epilogue ------------------------------------------------
@@ -342,7 +343,36 @@ int orbit2_clamp_channel_bwd(const float* img_clamped, float* dimg, int B, int C
 #define ORBIT2_LOSS_BLOCKS 64
 int orbit2_loss_fwd(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* chan_w,
                     float* out, float* ws, int B, int C, int H, int W, int kind, void* stream);
-/* dpred = gscale[0] * d(aggregate)/dpred */
+/* kinds 0..2: dpred = gscale[0] * d(aggregate)/dpred.
+ *
+ * kind ORBIT2_LOSS_SSIM_VJP (3): the vector-Jacobian product of orbit2_ssim's sums with respect to pred (csrc/ssim.hip; DESIGN
+ * 4.10h; metrics.functional.ssim_loss).  It has no forward here: orbit2_loss_fwd refuses kind 3, the value is orbit2_ssim's.
+ *   pred fp32 [B,C,H,W]; target fp32 [B,C,Ht,Wt] (top-left crop); lat_w fp32 [H] or NULL (w = 1); chan_w must be NULL.
+ *   gscale fp32 [2][B*C]: gscale[bc] the coefficient g of image bc, gscale[B*C + bc] its data range R.
+ *   dpred fp32 [B,C,H,W]: every element written exactly once, no atomics: two calls give the same bits.
+ * With S_k the SSIM at valid centre k exactly as orbit2_ssim defines it (7 x 7 uniform window, K1 = 0.01, K2 = 0.03, sample
+ * covariance, C1 = (K1 R)^2, C2 = (K2 R)^2) and w_k = lat_w[row of k] or 1,
+ *   dpred[bc][p] = g_bc * sum over the valid centres k whose window holds p of w_k * dS_k / dpred[p],
+ * the gradient of sum_bc g_bc sums[bc][1] of orbit2_ssim (of sums[bc][0] with lat_w NULL); the target and R are constants.
+ * Closed form, with N = 49, A1 = 2 ux uy + C1, A2 = 2 vxy + C2, B1 = ux^2 + uy^2 + C1, B2 = vx + vy + C2 per centre:
+ *   alpha = 2 A2 / (B1 B2) (uy - ux A1 / B1),   beta = -S / B2,   gamma = 2 A1 / (B1 B2)
+ *   d[p] = g { box(w alpha) / 49 + [2 ((x_p - v) box(w beta) - box(w beta (ux - v)))
+ *                                   + (y_p - v) box(w gamma) - box(w gamma (uy - v))] / 48 }
+ * for any pivot v, box(E)[p] the sum of E over the valid centres within 3 rows and 3 columns of p.  The kernel folds the three
+ * box sums that no pixel value multiplies into one (box is linear), so it takes three.
+ * CENTRING IS PART OF THE CONTRACT, as in orbit2_ssim: v is a target value inside the workgroup's tile
+ * (ORBIT2_SSIM_VJP_TILE_H x ORBIT2_SSIM_VJP_TILE_W pixels of dpred); x_p - v, ux - v, the variances and the covariance come
+ * from centred values, never from raw ones, and uy - ux in alpha is the difference of the centred means: a field at 280 K with
+ * a range of 5 meets the tolerance of one at offset 0.
+ * An image with g_bc == 0.0f is zero-filled and none of its values enter any arithmetic (a constant target with R = 0, or NaN
+ * in that image, does not leak).  No address depends on a value.
+ * At kind 3, chan_w != NULL, H < 7 or W < 7, or B * C > 65535 return O2_ERR_ARG before any launch, with nothing written, as
+ * does everything kinds 0..2 refuse (NULL pred, target, gscale or dpred, a non-positive size, a target smaller than pred). */
+#define ORBIT2_LOSS_SSIM_VJP 3
+#ifndef ORBIT2_SSIM_VJP_TILE_H
+#define ORBIT2_SSIM_VJP_TILE_H 16       /* 16 or 32: chosen by measurement, profiles/ssim_loss.md */
+#endif
+#define ORBIT2_SSIM_VJP_TILE_W 64
 int orbit2_loss_bwd(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* chan_w,
                     const float* gscale, float* dpred, int B, int C, int H, int W, int kind, void* stream);
 

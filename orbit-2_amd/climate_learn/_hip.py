@@ -1146,6 +1146,29 @@ def ssim_sums(pred, target, lat_w=None, data_range=None, ssim_map=False):
     return (sums, smap) if ssim_map else sums
 
 
+LOSS_SSIM_VJP = 3               # ORBIT2_LOSS_SSIM_VJP: the kind of orbit2_loss_bwd that is the backward of orbit2_ssim's sums
+SSIM_VJP_TILE = (16, 64)        # (ORBIT2_SSIM_VJP_TILE_H, ORBIT2_SSIM_VJP_TILE_W): pixels of dpred per workgroup
+
+
+def ssim_vjp(pred, target, lat_w, coef, data_range):
+    """dpred fp32 [B,C,H,W] = the gradient with respect to pred of sum_bc coef[bc] * ssim_sums(...)[bc][1] (of [bc][0] with lat_w
+    None), every image at its data range data_range[bc]: orbit2_loss_bwd at kind 3 (include/orbit2_hip.h).  coef and data_range
+    are fp32 [B,C] device tensors; they are packed into the entry's gscale [2][B*C] on the device.  An image whose coef is 0.0 is
+    zero-filled without being read."""
+    if torch.is_tensor(pred) and pred.dim() == 4 and min(pred.shape[2:]) < SSIM_WIN:
+        raise HipBackendError("ssim_vjp: the prediction is %d x %d, the window needs at least %d x %d"
+                              % (pred.shape[2], pred.shape[3], SSIM_WIN, SSIM_WIN))
+    B, Cc, H, W = _scored_pair("ssim_vjp", pred, target, lat_w)
+    for name, t in (("coef", coef), ("data_range", data_range)):
+        if not torch.is_tensor(t) or tuple(_dev(t, F32, name).shape) != (B, Cc):
+            raise HipBackendError("ssim_vjp: %s must be an fp32 [B,C] = [%d,%d] device tensor" % (name, B, Cc))
+    gscale = torch.stack((coef.detach(), data_range.detach())).contiguous()
+    dpred = torch.empty_like(pred)
+    _call("orbit2_loss_bwd", pred, target, target.shape[2], target.shape[3], lat_w, None, gscale, dpred, B, Cc, H, W,
+          LOSS_SSIM_VJP)
+    return dpred
+
+
 RESAMPLE_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}
 RESAMPLE_TILE = (32, 256)       # (ORBIT2_RESAMPLE_TILE_H, ORBIT2_RESAMPLE_TILE_W): output pixels per workgroup
 RESAMPLE_LDS_FLOATS = 10240     # ORBIT2_RESAMPLE_LDS_FLOATS: the staged source window of a tile

@@ -1025,3 +1025,31 @@ class CoarsenFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad):
         return _hip.resample_adjoint(_f32(grad), ctx.fine, ctx.mode), None, None
+
+
+class SSIMFn(torch.autograd.Function):
+    """s [B,C]: the 7 x 7 structural similarity of every (b, c) image, differentiable in pred.  Forward
+    _hip.ssim_sums at the given `data_range` (fp32 [B,C] device tensor, or None: every image's own target range, read from the
+    forward's sums[..., 5] on the device and held constant), divided by (H-6)(W-6), or by (W-6) sum lat_w[3..H-4] with latitude
+    weights; backward _hip.ssim_vjp with coef = grad_s / that divisor.  Nothing here reads the device or copies to it."""
+
+    @staticmethod
+    def forward(ctx, pred, target, lat_w, data_range):
+        pred = _f32(pred).detach()
+        target = target.detach().contiguous()
+        sums = _hip.ssim_sums(pred, target, lat_w, data_range)
+        hv, wv = pred.shape[2] - _hip.SSIM_WIN + 1, pred.shape[3] - _hip.SSIM_WIN + 1
+        if lat_w is None:
+            div = torch.full((), float(hv * wv), dtype=torch.float64, device=pred.device)
+            s = sums[..., 0] / div
+        else:
+            div = wv * lat_w[_hip.SSIM_WIN // 2:_hip.SSIM_WIN // 2 + hv].double().sum()
+            s = sums[..., 1] / div
+        ctx.save_for_backward(pred, target, lat_w if lat_w is not None else pred.new_empty(0), sums[..., 5].float(), div)
+        return s.float()
+
+    @staticmethod
+    def backward(ctx, grad_s):
+        pred, target, lat_w, rng, div = ctx.saved_tensors
+        coef = (grad_s.double() / div).float().contiguous()
+        return _hip.ssim_vjp(pred, target, lat_w if lat_w.numel() else None, coef, rng.contiguous()), None, None, None

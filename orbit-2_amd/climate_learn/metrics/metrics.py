@@ -95,6 +95,42 @@ class BayesianTVConsistency(_WithConsistency, Metric):
     _base = staticmethod(bayesian_tv)
 
 
+class _WithSSIM:
+    """base loss + weight x functional.ssim_loss(pred, target): the usual `mse + lambda (1 - SSIM)` objective of super-resolution
+    (DESIGN 4.10h).  Per channel and in aggregate, as the base loss returns them.  `data_range`: a number, a dict per variable,
+    or "target" (every image's own target range).  A constant output variable (CONSTANTS) or one of weight 0 has coefficient 0 in
+    the term.  weight 0 is the base loss alone: the term is not computed."""
+
+    graph_capturable = True       # no host read and no host-to-device copy per step: weights and ranges are cached device tensors
+    weight = 1.0
+    data_range = _F.SSIM_LOSS_TARGET_RANGE
+    _base = None                  # the functional of the base loss; None: the term alone
+
+    def __call__(self, pred, target, var_names: Optional[List[str]] = None,
+                 var_weights: Optional[Dict[str, float]] = None):
+        base = type(self)._base
+        out = None if base is None else base(pred, target, var_names, var_weights, False)
+        if out is None or self.weight != 0:
+            term = self.weight * _F.ssim_loss(pred, target, var_names, var_weights, False, None, self.data_range)
+            out = term if out is None else out + term
+        return out[-1] if self.aggregate_only else out
+
+
+@register("ssim_loss")
+class SSIMLoss(_WithSSIM, Metric):
+    """weight x (1 - SSIM), per variable and in aggregate"""
+
+
+@register("mse_ssim")
+class MSESSIM(_WithSSIM, Metric):
+    _base = staticmethod(mse)
+
+
+@register("bayesian_tv_ssim")
+class BayesianTVSSIM(_WithSSIM, Metric):
+    _base = staticmethod(bayesian_tv)
+
+
 @register("imagegradient")
 class IMAGEGRADIENT(Metric):
     def __call__(self, pred, target, var_names: Optional[List[str]] = None,

@@ -441,8 +441,10 @@ extern "C" int orbit2_loss_bwd(const float* pred, const float* target, int Ht, i
                                const float* chan_w, const float* gscale, float* dpred, int B, int C, int H, int W,
                                int kind, void* stream) {
   if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !gscale || !dpred) return O2_ERR_ARG;
+  if (kind == ORBIT2_LOSS_SSIM_VJP)
+    return chan_w ? O2_ERR_ARG : o2_ssim_vjp(pred, target, Ht, Wt, lat_w, gscale, dpred, B, C, H, W, (hipStream_t)stream);
   if (kind < 0 || kind > 2) return O2_ERR_ARG;
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3(img_grid((int64_t)B * C * H * W)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(loss_bwd_kernel,dim3(img_grid((int64_t)B * C * H * W)), dim3(256), 0, (hipStream_t)stream,
                      pred, target, Ht, Wt, lat_w, chan_w, gscale, dpred, B, C, H, W, kind);
   O2_CHECK_LAUNCH();
   return O2_OK;

@@ -55,3 +55,9 @@ inline int o2_image_block_cap(int BC) { return BC >= 16 ? 64 : 1024 / BC; }
 inline bool o2_pair_ok(const void* pred, const void* target, int B, int C, int H, int W, int Ht, int Wt) {
   return pred && target && B > 0 && C > 0 && H > 0 && W > 0 && Ht >= H && Wt >= W;
 }
+
+// ---- the SSIM vector-Jacobian product (ssim.hip), reached through orbit2_loss_bwd (image.hip) at kind ORBIT2_LOSS_SSIM_VJP: not
+// an export, so the library's dynamic symbols stay those of the header
+__attribute__((visibility("hidden"))) int o2_ssim_vjp(const float* pred, const float* target, int Ht, int Wt, const float* lat_w,
+                                                      const float* gscale, float* dpred, int B, int C, int H, int W,
+                                                      hipStream_t s);

@@ -159,7 +159,199 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ pre
   const float s[3] = {s0, s1, se};
   o2_block_sums_add(s, S);
 }
+// ---- the vector-Jacobian product of the sums: orbit2_loss_bwd(kind = ORBIT2_LOSS_SSIM_VJP) -----------------------
+// dpred[p] = g sum over the valid centres k whose window holds p of w_k dS_k / dpred[p].  A workgroup owns SV_TH x SV_TW OUTPUT
+// pixels of one image.  It stages the pixels under them plus a halo of 6, of both fields, minus the tile's pivot (the target at
+// the tile's first pixel); forms, at the centres under the tile plus a halo of 3, three maps -- with the forward's window sums,
+// its register ring and its second, per-thread pivot, so S is the forward's S --; box-sums the maps 7 x 7, rows then columns,
+// through LDS (the row sums take the place of the staged pixels, whose tile part every thread has read into registers); and
+// writes every pixel of its tile once: no atomics, the same bits on every call.  With alpha, beta, gamma of the header and the
+// means mx = ux - v, my = uy - v relative to the tile's pivot v, the header's five box sums fold by linearity into three:
+//   E0 = w (alpha / 49 - (2 beta mx + gamma my) / 48),  E1 = 2 w beta / 48,  E2 = w gamma / 48
+//   d[p] = g (box(E0) + (x_p - v) box(E1) + (y_p - v) box(E2)).
+// alpha's factor uy - ux A1 / B1 is formed as (uy - ux) (uy (ux + uy) + C1) / B1 with uy - ux from the centred means: at 280 K
+// the literal form cancels seven digits away.  An invalid centre's maps are 0 by selection, never by a product.
+constexpr int SV_TH = ORBIT2_SSIM_VJP_TILE_H, SV_TW = ORBIT2_SSIM_VJP_TILE_W;
+constexpr int SV_PH = SV_TH + 2 * SS_HALO, SV_PW = SV_TW + 2 * SS_HALO;     // the staged pixels of a tile: 28 x 76
+constexpr int SV_MH = SV_TH + SS_HALO, SV_MW = SV_TW + SS_HALO;             // the centres whose windows touch the tile: 22 x 70
+constexpr int SV_NMAP = 3;
+constexpr int SV_STRIPS = 3, SV_RS = (SV_MH + SV_STRIPS - 1) / SV_STRIPS;   // a thread owns one column of SV_RS centre rows
+constexpr int SV_HB = SV_NMAP * SV_MH * SV_TW;                              // the row-summed maps
+constexpr int SV_PIX = 2 * SV_PH * SV_PW > SV_HB ? 2 * SV_PH * SV_PW : SV_HB;
+static_assert(SV_TW == 64 && SV_TH % 16 == 0 && SV_STRIPS * SV_MW <= 256, "16 x 16 threads of four pixels; a thread per column");
+static_assert((SV_PIX + SV_NMAP * SV_MH * SV_MW) * 4 <= 64 * 1024, "static LDS");
+
+__device__ __forceinline__ void sv_store4(float* __restrict__ d, int y, int x, int H, int W, bool vec, float4 v) {
+  if (y >= H || x >= W) return;
+  float* o = d + (size_t)y * W + x;
+  if (vec) {                                            // W % 4 == 0 and x % 4 == 0: the four pixels are inside, 16-byte aligned
+    *reinterpret_cast<float4*>(o) = v;
+    return;
+  }
+  o[0] = v.x;
+  if (x + 1 < W) o[1] = v.y;
+  if (x + 2 < W) o[2] = v.z;
+  if (x + 3 < W) o[3] = v.w;
+}
+
+__global__ __launch_bounds__(256) void ssim_vjp_kernel(const float* __restrict__ pred, const float* __restrict__ target, int Ht,
+                                                       int Wt, const float* __restrict__ lat_w,
+                                                       const float* __restrict__ gscale, float* __restrict__ dpred, int BC,
+                                                       int H, int W, int ntx) {
+  __shared__ __attribute__((aligned(16))) float pix[SV_PIX];
+  __shared__ float maps[SV_NMAP * SV_MH * SV_MW];
+  const int bc = blockIdx.y;
+  const int ty = blockIdx.x / ntx, tx = blockIdx.x - ty * ntx;
+  const int py0 = ty * SV_TH, px0 = tx * SV_TW;         // the tile's first pixel
+  float* d = dpred + (size_t)bc * H * W;
+  const bool vec = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(dpred) & 15) == 0;
+  const int orow = threadIdx.x >> 4, oc = (threadIdx.x & 15) * 4;   // output: rows orow + 16 k, four pixels from column oc
+  const float g = gscale[bc];
+  if (g == 0.f) {                                       // nothing of this image is read: its values may be anything
+    for (int r = orow; r < SV_TH; r += 16) sv_store4(d, py0 + r, px0 + oc, H, W, vec, make_float4(0.f, 0.f, 0.f, 0.f));
+    return;
+  }
+  const float* p = pred + (size_t)bc * H * W;
+  const float* t = target + (size_t)bc * Ht * Wt;
+  const float R = gscale[BC + bc];
+  const float c1 = (0.01f * R) * (0.01f * R), c2 = (0.03f * R) * (0.03f * R);
+  const float pivot = t[(size_t)py0 * Wt + px0];
+  float* sa = pix;
+  float* sb = pix + SV_PH * SV_PW;
+  for (int i = threadIdx.x; i < SV_PH * SV_PW; i += 256) {
+    const int r = i / SV_PW, c = i - r * SV_PW;
+    const int y = py0 - SS_HALO + r, x = px0 - SS_HALO + c;
+    float a = 0.f, b = 0.f;
+    if (y >= 0 && y < H && x >= 0 && x < W) {
+      a = p[(size_t)y * W + x] - pivot;
+      b = t[(size_t)y * Wt + x] - pivot;
+    }
+    sa[i] = a;
+    sb[i] = b;
+  }
+  __syncthreads();
+
+  float xa[SV_TH / 16][4], ya[SV_TH / 16][4];           // the thread's own pixels, centred on the tile's pivot
+#pragma unroll
+  for (int k = 0; k < SV_TH / 16; ++k)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = (orow + 16 * k + SS_HALO) * SV_PW + oc + q + SS_HALO;
+      xa[k][q] = sa[i];
+      ya[k][q] = sb[i];
+    }
+
+  if (threadIdx.x < SV_STRIPS * SV_MW) {
+    const int strip = threadIdx.x / SV_MW, c = threadIdx.x - strip * SV_MW, mr0 = strip * SV_RS;
+    // the second pivot, as in the forward: the stored target under the middle of the pixels this thread's windows cover,
+    // moved inside the image
+    const int prow = max(min(min(mr0 + SS_WIN / 2 + SV_RS / 2, SV_PH - 1), H - 1 - py0 + SS_HALO), SS_HALO - py0);
+    const int pcol = max(min(c + SS_WIN / 2, W - 1 - px0 + SS_HALO), SS_HALO - px0);
+    const float local = sb[prow * SV_PW + pcol];
+    const float shift = local + pivot;
+    const int cx = px0 - SS_WIN / 2 + c;                // the centre's pixel column
+    float ring[SS_WIN][5];
+#pragma unroll
+    for (int j = 0; j < SV_RS + SS_HALO; ++j) {
+      const int pr = min(mr0 + j, SV_PH - 1);
+      const float* ra = sa + pr * SV_PW + c;
+      const float* rb = sb + pr * SV_PW + c;
+      float ua = 0.f, ub = 0.f, uaa = 0.f, ubb = 0.f, uab = 0.f;
+#pragma unroll
+      for (int k = 0; k < SS_WIN; ++k) {
+        const float a = ra[k] - local, b = rb[k] - local;
+        ua += a;
+        ub += b;
+        uaa = fmaf(a, a, uaa);
+        ubb = fmaf(b, b, ubb);
+        uab = fmaf(a, b, uab);
+      }
+      ring[j % SS_WIN][0] = ua, ring[j % SS_WIN][1] = ub, ring[j % SS_WIN][2] = uaa, ring[j % SS_WIN][3] = ubb,
+      ring[j % SS_WIN][4] = uab;
+      if (j < SS_HALO) continue;
+      float w[5];
+#pragma unroll
+      for (int q = 0; q < 5; ++q) {
+        float v = ring[(j + 1) % SS_WIN][q];            // oldest first
+#pragma unroll
+        for (int k = 2; k <= SS_WIN; ++k) v += ring[(j + k) % SS_WIN][q];
+        w[q] = v;
+      }
+      const int mr = mr0 + j - SS_HALO;                 // the centre's map row; its pixel row is cy
+      const int cy = py0 - SS_WIN / 2 + mr;
+      if (mr >= SV_MH) continue;
+      const bool valid = cy >= SS_WIN / 2 && cy < H - SS_WIN / 2 && cx >= SS_WIN / 2 && cx < W - SS_WIN / 2;
+      const float inv_n = 1.f / (SS_WIN * SS_WIN), inv_n1 = 1.f / (SS_WIN * SS_WIN - 1);
+      const float ma = w[0] * inv_n, mb = w[1] * inv_n;                     // centred means
+      const float va = (w[2] - w[0] * ma) * inv_n1, vb = (w[3] - w[1] * mb) * inv_n1, vab = (w[4] - w[0] * mb) * inv_n1;
+      const float ux = ma + shift, uy = mb + shift;
+      const float A1 = 2.f * ux * uy + c1, A2 = 2.f * vab + c2;
+      const float B1 = ux * ux + uy * uy + c1, B2 = va + vb + c2;
+      const float rB = 1.f / (B1 * B2);
+      const float S = A1 * A2 * rB;
+      const float alpha = 2.f * A2 * rB * ((mb - ma) * (uy * (ux + uy) + c1)) / B1;
+      const float beta = -S / B2;
+      const float gamma = 2.f * A1 * rB;
+      const float mx = ma + local, my = mb + local;     // the means relative to the tile's pivot
+      const float wk = (valid && lat_w) ? lat_w[cy] : 1.f;
+      const float e0 = wk * (alpha * inv_n - (2.f * beta * mx + gamma * my) * inv_n1);
+      const float e1 = wk * (2.f * beta * inv_n1);
+      const float e2 = wk * (gamma * inv_n1);
+      float* m = maps + mr * SV_MW + c;
+      m[0] = valid ? e0 : 0.f;
+      m[SV_MH * SV_MW] = valid ? e1 : 0.f;
+      m[2 * SV_MH * SV_MW] = valid ? e2 : 0.f;
+    }
+  }
+  __syncthreads();
+
+  float* hb = pix;                                      // [map][centre row][tile column]: the seven centres across a pixel
+  for (int i = threadIdx.x; i < SV_HB; i += 256) {
+    const int qr = i / SV_TW, c = i - qr * SV_TW;
+    const float* m = maps + qr * SV_MW + c;
+    float v = m[0];
+#pragma unroll
+    for (int k = 1; k < SS_WIN; ++k) v += m[k];
+    hb[i] = v;
+  }
+  __syncthreads();
+
+#pragma unroll
+  for (int k = 0; k < SV_TH / 16; ++k) {
+    const int r = orow + 16 * k;
+    float4 bx[SV_NMAP];
+#pragma unroll
+    for (int q = 0; q < SV_NMAP; ++q) {
+      const float4* col = reinterpret_cast<const float4*>(hb + (q * SV_MH + r) * SV_TW + oc);
+      float4 v = col[0];
+#pragma unroll
+      for (int dy = 1; dy < SS_WIN; ++dy) {
+        const float4 u = col[dy * (SV_TW / 4)];
+        v.x += u.x, v.y += u.y, v.z += u.z, v.w += u.w;
+      }
+      bx[q] = v;
+    }
+    float4 o;
+    o.x = g * fmaf(ya[k][0], bx[2].x, fmaf(xa[k][0], bx[1].x, bx[0].x));
+    o.y = g * fmaf(ya[k][1], bx[2].y, fmaf(xa[k][1], bx[1].y, bx[0].y));
+    o.z = g * fmaf(ya[k][2], bx[2].z, fmaf(xa[k][2], bx[1].z, bx[0].z));
+    o.w = g * fmaf(ya[k][3], bx[2].w, fmaf(xa[k][3], bx[1].w, bx[0].w));
+    sv_store4(d, py0 + r, px0 + oc, H, W, vec, o);
+  }
+}
 }  // namespace
+
+// the kind ORBIT2_LOSS_SSIM_VJP of orbit2_loss_bwd (image.hip), which has checked the pair, gscale and dpred
+int o2_ssim_vjp(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* gscale, float* dpred,
+                int B, int C, int H, int W, hipStream_t s) {
+  if (H < SS_WIN || W < SS_WIN || (int64_t)B * C > 65535) return O2_ERR_ARG;
+  const int ntx = (W + SV_TW - 1) / SV_TW, nty = (H + SV_TH - 1) / SV_TH;
+  if ((int64_t)ntx * nty > INT32_MAX) return O2_ERR_ARG;
+  hipLaunchKernelGGL(ssim_vjp_kernel, dim3(ntx * nty, B * C), dim3(256), 0, s, pred, target, Ht, Wt, lat_w, gscale, dpred, B * C,
+                     H, W, ntx);
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
 
 extern "C" int orbit2_ssim(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* data_range,
                            double* sums, float* ssim_map, int B, int C, int H, int W, void* stream) {
