@@ -901,8 +901,37 @@ def transpose_bf16(src, dst):
 
 
 # ---- perceptual loss building blocks (csrc/lpips.hip) ----------------------------------------------------------
+# The entries take N, H, W, C from the caller and index with them: every wrapper compares them with the tensors it hands over
+# first, so a wrong argument is refused here instead of reading or writing past a buffer.
+def _holds(t, n, name, at_least=False):
+    """a tensor of exactly (at_least: no fewer than) n elements; None (an optional operand) passes"""
+    if t is not None and (t.numel() < n if at_least else t.numel() != n):
+        raise HipBackendError("%s holds %d elements, the sizes given need %s%d" % (name, t.numel(), "at least " if at_least else "", n))
+
+
+def _nhwc_dims(name, N, H, W, Cc, pool=False):
+    if min(N, H, W, Cc) <= 0 or Cc % 8:
+        raise HipBackendError("%s needs positive N, H, W and a positive multiple of 8 for C, got %r" % (name, (N, H, W, Cc)))
+    if pool and (H % 2 or W % 2):
+        raise HipBackendError("%s needs even H and W, got %d x %d" % (name, H, W))
+
+
+def _image_dims(name, img):
+    """N, H, W of an [N,3,H,W] image"""
+    if img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0:
+        raise HipBackendError("%s takes a non-empty [N,3,H,W] image, got %s" % (name, tuple(img.shape)))
+    return img.shape[0], img.shape[2], img.shape[3]
+
+
+def _tap_dims(name, feats, lin, B, HW, Cc):
+    if B <= 0 or HW <= 0 or Cc not in (64, 128, 256, 512):
+        raise HipBackendError("%s needs positive B and HW and C in {64, 128, 256, 512}, got %r" % (name, (B, HW, Cc)))
+    _holds(feats, 2 * B * HW * Cc, "feats"); _holds(lin, Cc, "lin")
+
+
 def im2col3x3(x, N, H, W, Cc):
     _dev(x, BF, "x")
+    _nhwc_dims("im2col3x3", N, H, W, Cc); _holds(x, N * H * W * Cc, "x")
     col = torch.empty(N * H * W, 9 * Cc, dtype=BF, device=x.device)
     _call("orbit2_im2col3x3", x, col, N, H, W, Cc)
     return col
@@ -910,6 +939,10 @@ def im2col3x3(x, N, H, W, Cc):
 
 def col2im3x3(dcol, N, H, W, Cc, act=None, tapg=None):
     _dev(dcol, BF, "dcol"); _dev_opt(act, BF, "act"); _dev_opt(tapg, BF, "tapg")
+    _nhwc_dims("col2im3x3", N, H, W, Cc)
+    if tapg is not None and act is None:
+        raise HipBackendError("col2im3x3 adds tapg only under the ReLU mask: tapg needs act")
+    _holds(dcol, N * H * W * 9 * Cc, "dcol"); _holds(act, N * H * W * Cc, "act"); _holds(tapg, N * H * W * Cc, "tapg")
     out = torch.empty(N * H * W, Cc, dtype=BF, device=dcol.device)
     _call("orbit2_col2im3x3", dcol, act, tapg, out, N, H, W, Cc)
     return out
@@ -917,6 +950,7 @@ def col2im3x3(dcol, N, H, W, Cc, act=None, tapg=None):
 
 def maxpool2_fwd(x, N, H, W, Cc):
     _dev(x, BF, "x")
+    _nhwc_dims("maxpool2_fwd", N, H, W, Cc, pool=True); _holds(x, N * H * W * Cc, "x")
     y = torch.empty(N * (H // 2) * (W // 2), Cc, dtype=BF, device=x.device)
     _call("orbit2_maxpool2_fwd", x, y, N, H, W, Cc)
     return y
@@ -924,6 +958,8 @@ def maxpool2_fwd(x, N, H, W, Cc):
 
 def maxpool2_bwd(g, x, N, H, W, Cc, tapg=None):
     _dev(g, BF, "g"); _dev(x, BF, "x"); _dev_opt(tapg, BF, "tapg")
+    _nhwc_dims("maxpool2_bwd", N, H, W, Cc, pool=True)
+    _holds(g, N * (H // 2) * (W // 2) * Cc, "g"); _holds(x, N * H * W * Cc, "x"); _holds(tapg, N * H * W * Cc, "tapg")
     dz = torch.empty(N * H * W, Cc, dtype=BF, device=g.device)
     _call("orbit2_maxpool2_bwd", g, x, tapg, dz, N, H, W, Cc)
     return dz
@@ -931,7 +967,8 @@ def maxpool2_bwd(g, x, N, H, W, Cc, tapg=None):
 
 def lpips_conv1_fwd(img, w1, b1):
     _dev(img, F32, "img"); _dev(w1, F32, "w1"); _dev(b1, F32, "b1")
-    N, _, H, W = img.shape
+    N, H, W = _image_dims("lpips_conv1_fwd", img)
+    _holds(w1, 27 * 64, "w1"); _holds(b1, 64, "b1")
     out = torch.empty(N * H * W, 64, dtype=BF, device=img.device)
     _call("orbit2_lpips_conv1_fwd", img, w1, b1, out, N, H, W)
     return out
@@ -939,7 +976,10 @@ def lpips_conv1_fwd(img, w1, b1):
 
 def lpips_conv1_bwd(dz, w1, pred, target, l1_coef, gscale=None):
     _dev(dz, BF, "dz"); _dev(w1, F32, "w1"); _dev(pred, F32, "pred"); _dev(target, F32, "target"); _dev_opt(gscale, F32, "gscale")
-    N, _, H, W = pred.shape
+    N, H, W = _image_dims("lpips_conv1_bwd", pred)
+    if target.shape != pred.shape:
+        raise HipBackendError("lpips_conv1_bwd: pred %s and target %s differ in shape" % (tuple(pred.shape), tuple(target.shape)))
+    _holds(dz, N * H * W * 64, "dz"); _holds(w1, 27 * 64, "w1"); _holds(gscale, 1, "gscale", at_least=True)
     dimg = torch.empty_like(pred)
     _call("orbit2_lpips_conv1_bwd", dz, w1, pred, target, l1_coef, gscale, dimg, N, H, W)
     return dimg
@@ -947,12 +987,14 @@ def lpips_conv1_bwd(dz, w1, pred, target, l1_coef, gscale=None):
 
 def lpips_tap_fwd(feats, lin, val, B, HW, Cc):
     _dev(feats, BF, "feats"); _dev(lin, F32, "lin"); _dev(val, F32, "val")
+    _tap_dims("lpips_tap_fwd", feats, lin, B, HW, Cc); _holds(val, B, "val", at_least=True)
     ws = _ws(lib().orbit2_lpips_tap_ws_floats, (B, HW, Cc), feats.device)
     _call("orbit2_lpips_tap_fwd", feats, lin, val, B, HW, Cc, ws)
 
 
 def lpips_tap_bwd(feats, lin, coef, B, HW, Cc, gscale=None):
     _dev(feats, BF, "feats"); _dev(lin, F32, "lin"); _dev_opt(gscale, F32, "gscale")
+    _tap_dims("lpips_tap_bwd", feats, lin, B, HW, Cc); _holds(gscale, 1, "gscale", at_least=True)
     g = torch.empty(B * HW, Cc, dtype=BF, device=feats.device)
     _call("orbit2_lpips_tap_bwd", feats, lin, g, coef, gscale, B, HW, Cc)
     return g
@@ -960,6 +1002,9 @@ def lpips_tap_bwd(feats, lin, coef, B, HW, Cc, gscale=None):
 
 def l1_mean(a, b, out):
     _dev(a, F32, "a"); _dev(b, F32, "b"); _dev(out, F32, "out")
+    if a.numel() == 0:
+        raise HipBackendError("l1_mean of no elements")
+    _holds(b, a.numel(), "b"); _holds(out, 1, "out", at_least=True)
     ws = _ws(lib().orbit2_l1_mean_ws_floats, (a.numel(),), a.device)
     _call("orbit2_l1_mean", a, b, out, a.numel(), ws)
 

@@ -126,6 +126,61 @@ def _tap_positions(acts):
     return pos
 
 
+def _input_gradient(net, acts, taps, dims, p32, t32, go, record=None):
+    """the backward stage loop: d(go * perceptual)/d pred from the activations of `_features`.  `record(kind, j, out, **operands)`,
+    if given, sees every kernel's output together with the operands it was computed from (the stage-by-stage tests)."""
+    B, H, W = dims
+
+    def tap(j):
+        """gradient of 0.5*mean_b(val) w.r.t. the pre-ReLU output of stage j (prediction half), or None"""
+        if j not in taps:
+            return None
+        _, f, h, w, c = acts[j]
+        g = _hip.lpips_tap_bwd(f, net.lins[taps[j]], 0.5 / (B * h * w), B, h * w, c, gscale=go)
+        if record:
+            record("tap", j, g, feats=f, lin=net.lins[taps[j]], coef=0.5 / (B * h * w))
+        return g
+
+    def pred_half(j):
+        _, f, h, w, c = acts[j]
+        return f[: B * h * w]
+
+    # gz = gradient w.r.t. the pre-ReLU output of conv stage j (prediction images only); start at relu5_3
+    j = len(acts) - 1
+    gz = tap(j)
+    conv_id = 12
+    while j > 0:
+        L = net.layers[conv_id - 1]
+        conv_id -= 1
+        _, _, h, w, _ = acts[j]
+        M = B * h * w
+        dcol = torch.empty(M, 9 * L["ci"], dtype=BF, device=gz.device)
+        _hip.gemm(gz, L["wt"], dcol, M, 9 * L["ci"], L["co"], L["co"], L["co"], 9 * L["ci"])
+        if record:
+            record("gemm", j, dcol, gz=gz, wt=L["wt"])
+        if acts[j - 1][0] == "conv":
+            tg = tap(j - 1)
+            gz = _hip.col2im3x3(dcol, B, h, w, L["ci"], act=pred_half(j - 1), tapg=tg)
+            if record:
+                record("col2im", j - 1, gz, dcol=dcol, act=pred_half(j - 1), tapg=tg, dims=(B, h, w, L["ci"]))
+            j -= 1
+        else:                                          # pool below: its input is the conv stage j-2
+            gp = _hip.col2im3x3(dcol, B, h, w, L["ci"])
+            if record:
+                record("col2im", j - 1, gp, dcol=dcol, act=None, tapg=None, dims=(B, h, w, L["ci"]))
+            _, _, sh, sw, sc = acts[j - 2]
+            tg = tap(j - 2)
+            gz = _hip.maxpool2_bwd(gp, pred_half(j - 2), B, sh, sw, sc, tapg=tg)
+            if record:
+                record("pool", j - 2, gz, g=gp, x=pred_half(j - 2), tapg=tg, dims=(B, sh, sw, sc))
+            j -= 2
+        del dcol
+    dimg = _hip.lpips_conv1_bwd(gz, net.w1, p32, t32, 1.0 / p32.numel(), gscale=go)
+    if record:
+        record("conv1", 0, dimg, dz=gz)
+    return dimg
+
+
 class _PerceptualFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target, net):
@@ -146,43 +201,8 @@ class _PerceptualFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        net, acts, taps = ctx.net, ctx.acts, ctx.taps
-        B, H, W = ctx.dims
         p32, t32 = ctx.saved_tensors
         # the scalar upstream gradient (loss scale included) stays ON THE DEVICE: the tap / first-conv kernels read it through
         # a pointer, so the backward has no host read (no pipeline stall, capturable in a hipGraph)
         go = gout.detach().reshape(1).to(F32).contiguous()
-
-        def tap(j):
-            """gradient of 0.5*mean_b(val) w.r.t. the pre-ReLU output of stage j (prediction half), or None"""
-            if j not in taps:
-                return None
-            _, f, h, w, c = acts[j]
-            return _hip.lpips_tap_bwd(f, net.lins[taps[j]], 0.5 / (B * h * w), B, h * w, c, gscale=go)
-
-        def pred_half(j):
-            _, f, h, w, c = acts[j]
-            return f[: B * h * w]
-
-        # gz = gradient w.r.t. the pre-ReLU output of conv stage j (prediction images only); start at relu5_3
-        j = len(acts) - 1
-        gz = tap(j)
-        conv_id = 12
-        while j > 0:
-            L = net.layers[conv_id - 1]
-            conv_id -= 1
-            _, _, h, w, _ = acts[j]
-            M = B * h * w
-            dcol = torch.empty(M, 9 * L["ci"], dtype=BF, device=gz.device)
-            _hip.gemm(gz, L["wt"], dcol, M, 9 * L["ci"], L["co"], L["co"], L["co"], 9 * L["ci"])
-            if acts[j - 1][0] == "conv":
-                gz = _hip.col2im3x3(dcol, B, h, w, L["ci"], act=pred_half(j - 1), tapg=tap(j - 1))
-                j -= 1
-            else:                                          # pool below: its input is the conv stage j-2
-                gp = _hip.col2im3x3(dcol, B, h, w, L["ci"])
-                _, _, sh, sw, sc = acts[j - 2]
-                gz = _hip.maxpool2_bwd(gp, pred_half(j - 2), B, sh, sw, sc, tapg=tap(j - 2))
-                j -= 2
-            del dcol
-        dimg = _hip.lpips_conv1_bwd(gz, net.w1, p32, t32, 1.0 / p32.numel(), gscale=go)
-        return dimg, None, None
+        return _input_gradient(ctx.net, ctx.acts, ctx.taps, ctx.dims, p32, t32, go), None, None
