@@ -12,15 +12,36 @@
 
 namespace {
 
-__device__ __forceinline__ void unpack8f(const u32x4& r, float* f) {
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { f[2 * k] = bf2f((bf16_t)(r[k] & 0xffff)); f[2 * k + 1] = bf2f((bf16_t)(r[k] >> 16)); }
+// ---- the steps the kernels share.  Every kernel but the tap head is one grid-stride loop of lp_grid(work) blocks of 256 over
+// flat indices of NHWC pixels (or of their 8-channel chunks) -------------------------------------------------------------------
+inline int lp_grid(int64_t work) { return grid_for(work, 256, 8192); }   // tests/lpips_ref.TRIP is this cap times 256
+
+// pixel p of an [N][H][W] grid
+struct LpPixel { int64_t n; int yy, xx; };
+__device__ __forceinline__ LpPixel lp_pixel(int64_t p, int H, int W) {
+  return {p / ((int64_t)W * H), (int)((p / W) % H), (int)(p % W)};
 }
-__device__ __forceinline__ u32x4 pack8f(const float* v) {
-  u32x4 o;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) o[k] = pack_bf2(v[2 * k], v[2 * k + 1]);
-  return o;
+// tap t = ky*3+kx of a 3x3 window around pixel p = (yy, xx), off_t = (ky-1, kx-1).  DIR = +1: the neighbour p + off_t a
+// convolution gathers from (im2col, conv1 fwd); DIR = -1: p - off_t, the pixel whose tap t reaches p, the adjoint's direction
+// (col2im, conv1 bwd).  in: that neighbour (sy, sx), pixel index q, lies inside the image
+struct LpTap { bool in; int sy, sx; int64_t q; };
+template <int DIR>
+__device__ __forceinline__ LpTap lp_tap(int t, int64_t p, const LpPixel px, int H, int W) {
+  const int dy = DIR * (t / 3 - 1), dx = DIR * (t % 3 - 1);
+  const int sy = px.yy + dy, sx = px.xx + dx;
+  return {sy >= 0 && sy < H && sx >= 0 && sx < W, sy, sx, p + (int64_t)dy * W + dx};
+}
+// element offset of position j (row-major) of a 2x2 pooling window from its first position
+__device__ __forceinline__ int64_t lp_win2(int j, int W, int C) { return (int64_t)(j >> 1) * W * C + (j & 1) * C; }
+// the block-partial tail: *dst = the workgroup's sum of v, fp32, stored by thread 0 -- dst is the block's own slab of a workspace
+// that o2_sum_parts adds in a fixed order (score_sums.h's o2_block_sums_add adds doubles with atomics: not this).  Every thread
+// of the workgroup calls it (it holds a barrier)
+__device__ __forceinline__ void lp_block_partial(float v, float* dst) {
+  __shared__ float red[256 / 64];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) *dst = red[0] + red[1] + red[2] + red[3];
 }
 
 // ---- im2col: col[p][t][c] = x[p + off_t][c] (zero outside the image), t = ky*3+kx, off = (ky-1, kx-1) ----------------
@@ -31,13 +52,10 @@ __global__ __launch_bounds__(256) void im2col3x3_kernel(const bf16_t* __restrict
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int c8 = (int)(e % c8n);
     const int64_t r = e / c8n;
-    const int t = (int)(r % 9);
     const int64_t p = r / 9;
-    const int xx = (int)(p % W), yy = (int)((p / W) % H);
-    const int sy = yy + t / 3 - 1, sx = xx + t % 3 - 1;
+    const LpTap tap = lp_tap<1>((int)(r % 9), p, lp_pixel(p, H, W), H, W);
     u32x4 v = {0u, 0u, 0u, 0u};
-    if (sy >= 0 && sy < H && sx >= 0 && sx < W)
-      v = *reinterpret_cast<const u32x4*>(x + ((p + (int64_t)(t / 3 - 1) * W + (t % 3 - 1)) * C + c8 * 8));
+    if (tap.in) v = *reinterpret_cast<const u32x4*>(x + (tap.q * C + c8 * 8));
     *reinterpret_cast<u32x4*>(col + e * 8) = v;
   }
 }
@@ -51,34 +69,33 @@ __global__ __launch_bounds__(256) void col2im3x3_kernel(const bf16_t* __restrict
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int c8 = (int)(e % c8n);
     const int64_t p = e / c8n;
-    const int xx = (int)(p % W), yy = (int)((p / W) % H);
+    const LpPixel px = lp_pixel(p, H, W);
     float acc[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc[k] = 0.f;
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-      const int qy = yy - (t / 3 - 1), qx = xx - (t % 3 - 1);
-      if (qy >= 0 && qy < H && qx >= 0 && qx < W) {
-        const int64_t q = p - (int64_t)(t / 3 - 1) * W - (t % 3 - 1);
+      const LpTap tap = lp_tap<-1>(t, p, px, H, W);
+      if (tap.in) {
         float f[8];
-        unpack8f(*reinterpret_cast<const u32x4*>(dcol + (q * 9 + t) * C + c8 * 8), f);
+        unpack8(*reinterpret_cast<const u32x4*>(dcol + (tap.q * 9 + t) * C + c8 * 8), f);
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] += f[k];
       }
     }
     if (act) {
       float a[8];
-      unpack8f(*reinterpret_cast<const u32x4*>(act + e * 8), a);
+      unpack8(*reinterpret_cast<const u32x4*>(act + e * 8), a);
       if (tapg) {
         float g[8];
-        unpack8f(*reinterpret_cast<const u32x4*>(tapg + e * 8), g);
+        unpack8(*reinterpret_cast<const u32x4*>(tapg + e * 8), g);
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] += g[k];
       }
 #pragma unroll
       for (int k = 0; k < 8; ++k) acc[k] = a[k] > 0.f ? acc[k] : 0.f;
     }
-    *reinterpret_cast<u32x4*>(out + e * 8) = pack8f(acc);
+    *reinterpret_cast<u32x4*>(out + e * 8) = pack8(acc);
   }
 }
 
@@ -89,20 +106,17 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_kernel(const bf16_t* __restr
   const int64_t total = (int64_t)N * Ho * Wo * c8n;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int c8 = (int)(e % c8n);
-    const int64_t po = e / c8n;
-    const int xo = (int)(po % Wo), yo = (int)((po / Wo) % Ho);
-    const int64_t n = po / ((int64_t)Wo * Ho);
-    const bf16_t* src = x + (((n * H + 2 * yo) * W + 2 * xo) * C + c8 * 8);
+    const LpPixel po = lp_pixel(e / c8n, Ho, Wo);
+    const bf16_t* src = x + (((po.n * H + 2 * po.yy) * W + 2 * po.xx) * C + c8 * 8);
     float m[8], f[8];
-    unpack8f(*reinterpret_cast<const u32x4*>(src), m);
-    const int64_t offs[3] = {(int64_t)C, (int64_t)W * C, (int64_t)W * C + C};
+    unpack8(*reinterpret_cast<const u32x4*>(src), m);
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      unpack8f(*reinterpret_cast<const u32x4*>(src + offs[j]), f);
+    for (int j = 1; j < 4; ++j) {
+      unpack8(*reinterpret_cast<const u32x4*>(src + lp_win2(j, W, C)), f);
 #pragma unroll
       for (int k = 0; k < 8; ++k) m[k] = fmaxf(m[k], f[k]);
     }
-    *reinterpret_cast<u32x4*>(y + e * 8) = pack8f(m);
+    *reinterpret_cast<u32x4*>(y + e * 8) = pack8(m);
   }
 }
 
@@ -114,15 +128,12 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const bf16_t* __restr
   const int64_t total = (int64_t)N * Ho * Wo * c8n;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int c8 = (int)(e % c8n);
-    const int64_t po = e / c8n;
-    const int xo = (int)(po % Wo), yo = (int)((po / Wo) % Ho);
-    const int64_t n = po / ((int64_t)Wo * Ho);
-    const int64_t base = ((n * H + 2 * yo) * W + 2 * xo) * C + c8 * 8;
-    const int64_t offs[4] = {0, (int64_t)C, (int64_t)W * C, (int64_t)W * C + C};
+    const LpPixel po = lp_pixel(e / c8n, Ho, Wo);
+    const int64_t base = ((po.n * H + 2 * po.yy) * W + 2 * po.xx) * C + c8 * 8;
     float xv[4][8], gv[8];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) unpack8f(*reinterpret_cast<const u32x4*>(x + base + offs[j]), xv[j]);
-    unpack8f(*reinterpret_cast<const u32x4*>(g + e * 8), gv);
+    for (int j = 0; j < 4; ++j) unpack8(*reinterpret_cast<const u32x4*>(x + base + lp_win2(j, W, C)), xv[j]);
+    unpack8(*reinterpret_cast<const u32x4*>(g + e * 8), gv);
     int am[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -135,14 +146,14 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const bf16_t* __restr
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float o[8], tg[8];
-      if (tapg) unpack8f(*reinterpret_cast<const u32x4*>(tapg + base + offs[j]), tg);
+      if (tapg) unpack8(*reinterpret_cast<const u32x4*>(tapg + base + lp_win2(j, W, C)), tg);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         float v = (am[k] == j) ? gv[k] : 0.f;
         if (tapg) v += tg[k];
         o[k] = xv[j][k] > 0.f ? v : 0.f;
       }
-      *reinterpret_cast<u32x4*>(dz + base + offs[j]) = pack8f(o);
+      *reinterpret_cast<u32x4*>(dz + base + lp_win2(j, W, C)) = pack8(o);
     }
   }
 }
@@ -162,18 +173,17 @@ __global__ __launch_bounds__(256) void lpips_conv1_fwd_kernel(const float* __res
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int c8 = (int)(e & 7);
     const int64_t p = e >> 3;
-    const int xx = (int)(p % W), yy = (int)((p / W) % H);
-    const int64_t n = p / ((int64_t)W * H);
+    const LpPixel px = lp_pixel(p, H, W);
     float acc[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc[k] = sw[27 * 64 + c8 * 8 + k];
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-      const int sy = yy + t / 3 - 1, sx = xx + t % 3 - 1;
-      if (sy < 0 || sy >= H || sx < 0 || sx >= W) continue;
+      const LpTap tap = lp_tap<1>(t, p, px, H, W);
+      if (!tap.in) continue;
 #pragma unroll
       for (int ci = 0; ci < 3; ++ci) {
-        const float v = (img[((n * 3 + ci) * H + sy) * W + sx] - kShift[ci]) / kScale[ci];
+        const float v = (img[((px.n * 3 + ci) * H + tap.sy) * W + tap.sx] - kShift[ci]) / kScale[ci];
         const float* wr = sw + (t * 3 + ci) * 64 + c8 * 8;
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] = fmaf(v, wr[k], acc[k]);
@@ -181,7 +191,7 @@ __global__ __launch_bounds__(256) void lpips_conv1_fwd_kernel(const float* __res
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc[k] = fmaxf(acc[k], 0.f);
-    *reinterpret_cast<u32x4*>(out + e * 8) = pack8f(acc);
+    *reinterpret_cast<u32x4*>(out + e * 8) = pack8(acc);
   }
 }
 
@@ -197,17 +207,16 @@ __global__ __launch_bounds__(256) void lpips_conv1_bwd_kernel(const bf16_t* __re
   __syncthreads();
   const int64_t total = (int64_t)N * H * W;
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < total; p += (int64_t)gridDim.x * 256) {
-    const int xx = (int)(p % W), yy = (int)((p / W) % H);
-    const int64_t n = p / ((int64_t)W * H);
+    const LpPixel px = lp_pixel(p, H, W);
     float acc[3] = {0.f, 0.f, 0.f};
     for (int t = 0; t < 9; ++t) {
-      const int qy = yy - (t / 3 - 1), qx = xx - (t % 3 - 1);
-      if (qy < 0 || qy >= H || qx < 0 || qx >= W) continue;
-      const bf16_t* src = dz + (p - (int64_t)(t / 3 - 1) * W - (t % 3 - 1)) * 64;
+      const LpTap tap = lp_tap<-1>(t, p, px, H, W);
+      if (!tap.in) continue;
+      const bf16_t* src = dz + tap.q * 64;
 #pragma unroll
       for (int c8 = 0; c8 < 8; ++c8) {
         float f[8];
-        unpack8f(*reinterpret_cast<const u32x4*>(src + c8 * 8), f);
+        unpack8(*reinterpret_cast<const u32x4*>(src + c8 * 8), f);
 #pragma unroll
         for (int ci = 0; ci < 3; ++ci) {
           const float* wr = sw + (t * 3 + ci) * 64 + c8 * 8;
@@ -218,7 +227,7 @@ __global__ __launch_bounds__(256) void lpips_conv1_bwd_kernel(const bf16_t* __re
     }
 #pragma unroll
     for (int ci = 0; ci < 3; ++ci) {
-      const int64_t o = ((n * 3 + ci) * H + yy) * W + xx;
+      const int64_t o = ((px.n * 3 + ci) * H + px.yy) * W + px.xx;
       const float d = pred[o] - target[o];
       dimg[o] = acc[ci] / kScale[ci] + l1_coef * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
     }
@@ -233,7 +242,6 @@ __global__ __launch_bounds__(256) void lpips_tap_kernel(const bf16_t* __restrict
                                                         const float* __restrict__ gscale, int B, int HW) {
   const float coef = (BWD && gscale) ? coef_arg * gscale[0] : coef_arg;       // upstream scalar gradient stays on the device
   constexpr int C = G * 8;
-  __shared__ float red[256 / 64];
   const int b = blockIdx.y;
   const int li = threadIdx.x % G, grp = threadIdx.x / G;
   constexpr int GPB = 256 / G;
@@ -243,8 +251,8 @@ __global__ __launch_bounds__(256) void lpips_tap_kernel(const bf16_t* __restrict
   float part = 0.f;
   for (int px = blockIdx.x * GPB + grp; px < HW; px += gridDim.x * GPB) {
     float a[8], t[8];
-    unpack8f(*reinterpret_cast<const u32x4*>(f + ((size_t)b * HW + px) * C + li * 8), a);
-    unpack8f(*reinterpret_cast<const u32x4*>(f + ((size_t)(B + b) * HW + px) * C + li * 8), t);
+    unpack8(*reinterpret_cast<const u32x4*>(f + ((size_t)b * HW + px) * C + li * 8), a);
+    unpack8(*reinterpret_cast<const u32x4*>(f + ((size_t)(B + b) * HW + px) * C + li * 8), t);
     float s0 = 0.f, s1 = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) { s0 = fmaf(a[k], a[k], s0); s1 = fmaf(t[k], t[k], s1); }
@@ -269,90 +277,65 @@ __global__ __launch_bounds__(256) void lpips_tap_kernel(const bf16_t* __restrict
       float g8[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) g8[k] = a[k] > 0.f ? coef * (2.f * w8[k] * e8[k] * i0 - a[k] * k2) : 0.f;   // ReLU mask of the tap
-      *reinterpret_cast<u32x4*>(gout + ((size_t)b * HW + px) * C + li * 8) = pack8f(g8);
+      *reinterpret_cast<u32x4*>(gout + ((size_t)b * HW + px) * C + li * 8) = pack8(g8);
     }
   }
-  if (!BWD) {
-    // every lane holds the contribution of its 8 channels over its group's pixels; reduce over the block
-    float v = part;
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) val[(size_t)blockIdx.x * B + b] = red[0] + red[1] + red[2] + red[3];     // the block's slab (forward: val = workspace)
-  }
+  // every lane holds the contribution of its 8 channels over its group's pixels; the block's slab (forward: val = workspace)
+  if (!BWD) lp_block_partial(part, val + (size_t)blockIdx.x * B + b);
 }
 
 __global__ __launch_bounds__(256) void l1_sum_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                     float* __restrict__ out, int64_t n, float inv_n) {
-  __shared__ float red[4];
+                                                     float* __restrict__ out, int64_t n) {
   float s = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s += fabsf(a[i] - b[i]);
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[blockIdx.x] = red[0] + red[1] + red[2] + red[3];      // out = workspace: one partial per block
+  lp_block_partial(s, out + blockIdx.x);                // out = workspace: one partial per block
 }
 
-unsigned grid_for(int64_t work) {
-  int64_t g = (work + 255) / 256;
-  if (g > 256 * 32) g = 256 * 32;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
 bool dims_ok(int N, int H, int W, int C) { return N > 0 && H > 0 && W > 0 && C > 0 && (C % 8) == 0; }
+
+// the one launch path of the grid-stride kernels: `work` items on lp_grid(work) blocks; every argument is converted to the
+// kernel's own parameter type (the entries hand bf16 buffers over as void*)
+template <class... P, class... A>
+int lp_launch(void (*kernel)(P...), int64_t work, void* stream, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(lp_grid(work)), dim3(256), 0, (hipStream_t)stream, static_cast<P>(args)...);
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
 
 }  // namespace
 
 extern "C" int orbit2_im2col3x3(const void* x, void* col, int N, int H, int W, int C, void* stream) {
   if (!x || !col || !dims_ok(N, H, W, C)) return O2_ERR_ARG;
-  hipLaunchKernelGGL(im2col3x3_kernel, dim3(grid_for((int64_t)N * H * W * 9 * (C / 8))), dim3(256), 0,
-                     (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)col, N, H, W, C);
-  O2_CHECK_LAUNCH();
-  return O2_OK;
+  return lp_launch(im2col3x3_kernel, (int64_t)N * H * W * 9 * (C / 8), stream, x, col, N, H, W, C);
 }
 
 extern "C" int orbit2_col2im3x3(const void* dcol, const void* act, const void* tapg, void* out, int N, int H, int W,
                                 int C, void* stream) {
   if (!dcol || !out || !dims_ok(N, H, W, C) || (tapg && !act)) return O2_ERR_ARG;
-  hipLaunchKernelGGL(col2im3x3_kernel, dim3(grid_for((int64_t)N * H * W * (C / 8))), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)dcol, (const bf16_t*)act, (const bf16_t*)tapg, (bf16_t*)out, N, H, W, C);
-  O2_CHECK_LAUNCH();
-  return O2_OK;
+  return lp_launch(col2im3x3_kernel, (int64_t)N * H * W * (C / 8), stream, dcol, act, tapg, out, N, H, W, C);
 }
 
 extern "C" int orbit2_maxpool2_fwd(const void* x, void* y, int N, int H, int W, int C, void* stream) {
   if (!x || !y || !dims_ok(N, H, W, C) || (H & 1) || (W & 1)) return O2_ERR_ARG;
-  hipLaunchKernelGGL(maxpool2_fwd_kernel, dim3(grid_for((int64_t)N * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0,
-                     (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y, N, H, W, C);
-  O2_CHECK_LAUNCH();
-  return O2_OK;
+  return lp_launch(maxpool2_fwd_kernel, (int64_t)N * (H / 2) * (W / 2) * (C / 8), stream, x, y, N, H, W, C);
 }
 
 extern "C" int orbit2_maxpool2_bwd(const void* g, const void* x, const void* tapg, void* dz, int N, int H, int W, int C,
                                    void* stream) {
   if (!g || !x || !dz || !dims_ok(N, H, W, C) || (H & 1) || (W & 1)) return O2_ERR_ARG;
-  hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(grid_for((int64_t)N * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0,
-                     (hipStream_t)stream, (const bf16_t*)g, (const bf16_t*)x, (const bf16_t*)tapg, (bf16_t*)dz, N, H, W, C);
-  O2_CHECK_LAUNCH();
-  return O2_OK;
+  return lp_launch(maxpool2_bwd_kernel, (int64_t)N * (H / 2) * (W / 2) * (C / 8), stream, g, x, tapg, dz, N, H, W, C);
 }
 
 extern "C" int orbit2_lpips_conv1_fwd(const float* img, const float* w1, const float* b1, void* out, int N, int H, int W,
                                       void* stream) {
   if (!img || !w1 || !b1 || !out || N <= 0 || H <= 0 || W <= 0) return O2_ERR_ARG;
-  hipLaunchKernelGGL(lpips_conv1_fwd_kernel, dim3(grid_for((int64_t)N * H * W * 8)), dim3(256), 0, (hipStream_t)stream,
-                     img, w1, b1, (bf16_t*)out, N, H, W);
-  O2_CHECK_LAUNCH();
-  return O2_OK;
+  return lp_launch(lpips_conv1_fwd_kernel, (int64_t)N * H * W * 8, stream, img, w1, b1, out, N, H, W);
 }
 
 extern "C" int orbit2_lpips_conv1_bwd(const void* dz, const float* w1, const float* pred, const float* target,
                                       float l1_coef, const float* gscale, float* dimg, int N, int H, int W, void* stream) {
   if (!dz || !w1 || !pred || !target || !dimg || N <= 0 || H <= 0 || W <= 0) return O2_ERR_ARG;
-  hipLaunchKernelGGL(lpips_conv1_bwd_kernel, dim3(grid_for((int64_t)N * H * W)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)dz, w1, pred, target, l1_coef, gscale, dimg, N, H, W);
-  O2_CHECK_LAUNCH();
-  return O2_OK;
+  return lp_launch(lpips_conv1_bwd_kernel, (int64_t)N * H * W, stream, dz, w1, pred, target, l1_coef, gscale, dimg, N, H, W);
 }
 
 static int lpips_tap_blocks(int HW, int C) {
@@ -362,19 +345,18 @@ static int lpips_tap_blocks(int HW, int C) {
 template <bool BWD>
 static int lpips_tap_launch(const void* f, const float* lin, float* val, void* gout, float coef, const float* gscale, int B,
                             int HW, int C, hipStream_t s) {
-  const int blocks = lpips_tap_blocks(HW, C);
-  dim3 grid((unsigned)blocks, (unsigned)B), block(256);
-#define O2_TAP(G)                                                                                               \
-  hipLaunchKernelGGL((lpips_tap_kernel<G, BWD>), grid, block, 0, s, (const bf16_t*)f, lin, val, (bf16_t*)gout, \
-                     coef, gscale, B, HW)
+  const dim3 grid((unsigned)lpips_tap_blocks(HW, C), (unsigned)B), block(256);
+  auto tap = [&](auto G) {                              // G = C / 8 lanes per pixel
+    hipLaunchKernelGGL((lpips_tap_kernel<G, BWD>), grid, block, 0, s, (const bf16_t*)f, lin, val, (bf16_t*)gout, coef, gscale,
+                       B, HW);
+  };
   switch (C) {
-    case 64: O2_TAP(8); break;
-    case 128: O2_TAP(16); break;
-    case 256: O2_TAP(32); break;
-    case 512: O2_TAP(64); break;
+    case 64: tap(o2_int<8>{}); break;
+    case 128: tap(o2_int<16>{}); break;
+    case 256: tap(o2_int<32>{}); break;
+    case 512: tap(o2_int<64>{}); break;
     default: return O2_ERR_UNSUPPORTED;
   }
-#undef O2_TAP
   O2_CHECK_LAUNCH();
   return O2_OK;
 }
@@ -401,12 +383,12 @@ extern "C" int orbit2_lpips_tap_bwd(const void* feats, const float* lin, void* g
   return lpips_tap_launch<true>(feats, lin, nullptr, gout, coef, gscale, B, HW, C, (hipStream_t)stream);
 }
 
-extern "C" int64_t orbit2_l1_mean_ws_floats(int64_t n) { return n > 0 ? (int64_t)grid_for(n) : 0; }
+extern "C" int64_t orbit2_l1_mean_ws_floats(int64_t n) { return n > 0 ? (int64_t)lp_grid(n) : 0; }
 extern "C" int orbit2_l1_mean(const float* a, const float* b, float* out, int64_t n, float* ws, void* stream) {
   if (!a || !b || !out || !ws || n <= 0) return O2_ERR_ARG;
-  const unsigned nb = grid_for(n);
-  hipLaunchKernelGGL(l1_sum_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, a, b, ws, n, 1.0f / (float)n);
-  o2_sum_parts(ws, (int)nb, 1, out, 1, 1.0f / (float)n, 1, (hipStream_t)stream);                        // out += mean |a - b|
+  const int nb = lp_grid(n);
+  hipLaunchKernelGGL(l1_sum_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, a, b, ws, n);
+  o2_sum_parts(ws, nb, 1, out, 1, 1.0f / (float)n, 1, (hipStream_t)stream);                             // out += mean |a - b|
   O2_CHECK_LAUNCH();
   return O2_OK;
 }

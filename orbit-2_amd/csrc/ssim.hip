@@ -31,6 +31,48 @@ constexpr int SS_STRIP = SS_TH / 4;                                  // centre r
 constexpr int SS_NS = 6;
 static_assert(SS_WIN == 7 && SS_TW == 64 && SS_TH % 4 == 0, "one column per lane, four waves, a 7-deep register ring");
 
+// ---- the window arithmetic, stated once: ssim_kernel and ssim_vjp_kernel both go through these four steps, so the S a training
+// loss differentiates is the metric's S (tests/ssim_loss_ref.emulate restates the order in numpy).  PITCH: the kernel's LDS pitch
+constexpr float SS_INV_N = 1.f / (SS_WIN * SS_WIN), SS_INV_N1 = 1.f / (SS_WIN * SS_WIN - 1);
+struct SsConsts { float c1, c2; };
+__device__ __forceinline__ SsConsts ss_consts(float R) { return {(0.01f * R) * (0.01f * R), (0.03f * R) * (0.03f * R)}; }
+// the row step: the five 7-tap sums (a, b, a^2, b^2, a b) of one staged row minus the thread's second pivot, into a ring slot
+template <int PITCH>
+__device__ __forceinline__ void ss_row_sums(const float* sa, const float* sb, int row, int col, float local, float (&slot)[5]) {
+  const float* ra = sa + row * PITCH + col;
+  const float* rb = sb + row * PITCH + col;
+  float ua = 0.f, ub = 0.f, uaa = 0.f, ubb = 0.f, uab = 0.f;
+#pragma unroll
+  for (int k = 0; k < SS_WIN; ++k) {
+    const float a = ra[k] - local, b = rb[k] - local;
+    ua += a;
+    ub += b;
+    uaa = fmaf(a, a, uaa);
+    ubb = fmaf(b, b, ubb);
+    uab = fmaf(a, b, uab);
+  }
+  slot[0] = ua, slot[1] = ub, slot[2] = uaa, slot[3] = ubb, slot[4] = uab;
+}
+// the window step: the sums of the window whose last row went into slot j % 7 (j a constant of an unrolled loop: every index is
+// a compile-time constant), the seven row sums added oldest first
+__device__ __forceinline__ void ss_window_sums(const float (&ring)[SS_WIN][5], int j, float (&w)[5]) {
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    float v = ring[(j + 1) % SS_WIN][q];                // oldest first
+#pragma unroll
+    for (int k = 2; k <= SS_WIN; ++k) v += ring[(j + k) % SS_WIN][q];
+    w[q] = v;
+  }
+}
+// the moments step: centred means, the variances and the covariance from the centred sums, and the means with both pivots
+// (shift = local + the tile's pivot) added back for the luminance term
+struct SsMoments { float ma, mb, va, vb, vab, ux, uy; };
+__device__ __forceinline__ SsMoments ss_moments(const float (&w)[5], float shift) {
+  const float ma = w[0] * SS_INV_N, mb = w[1] * SS_INV_N;                   // centred means
+  const float va = (w[2] - w[0] * ma) * SS_INV_N1, vb = (w[3] - w[1] * mb) * SS_INV_N1, vab = (w[4] - w[0] * mb) * SS_INV_N1;
+  return {ma, mb, va, vb, vab, ma + shift, mb + shift};
+}
+
 // sums[bc] = {0, 0, 0, +inf, -inf, 0}: the zeroing of the entry, with the neutral elements of min and max
 __global__ void ssim_init_kernel(double* __restrict__ sums, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -104,8 +146,7 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ pre
   }
   const double range = data_range ? (double)data_range[bc] : S[4] - S[3];
   if (blockIdx.x == 0 && threadIdx.x == 0) S[5] = range;
-  const float R = (float)range;
-  const float c1 = (0.01f * R) * (0.01f * R), c2 = (0.03f * R) * (0.03f * R);
+  const auto [c1, c2] = ss_consts((float)range);
   __syncthreads();
 
   const int lx = threadIdx.x & 63, ry0 = (threadIdx.x >> 6) * SS_STRIP;
@@ -119,33 +160,11 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ pre
   float s0 = 0.f, s1 = 0.f;
 #pragma unroll
   for (int j = 0; j < SS_STRIP + SS_HALO; ++j) {
-    const float* ra = sa + (ry0 + j) * SS_IW + lx;
-    const float* rb = sb + (ry0 + j) * SS_IW + lx;
-    float ua = 0.f, ub = 0.f, uaa = 0.f, ubb = 0.f, uab = 0.f;
-#pragma unroll
-    for (int k = 0; k < SS_WIN; ++k) {
-      const float a = ra[k] - local, b = rb[k] - local;
-      ua += a;
-      ub += b;
-      uaa = fmaf(a, a, uaa);
-      ubb = fmaf(b, b, ubb);
-      uab = fmaf(a, b, uab);
-    }
-    ring[j % SS_WIN][0] = ua, ring[j % SS_WIN][1] = ub, ring[j % SS_WIN][2] = uaa, ring[j % SS_WIN][3] = ubb,
-    ring[j % SS_WIN][4] = uab;
+    ss_row_sums<SS_IW>(sa, sb, ry0 + j, lx, local, ring[j % SS_WIN]);
     if (j < SS_HALO) continue;
     float w[5];
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-      float v = ring[(j + 1) % SS_WIN][q];              // oldest first
-#pragma unroll
-      for (int k = 2; k <= SS_WIN; ++k) v += ring[(j + k) % SS_WIN][q];
-      w[q] = v;
-    }
-    const float inv_n = 1.f / (SS_WIN * SS_WIN), inv_n1 = 1.f / (SS_WIN * SS_WIN - 1);
-    const float ma = w[0] * inv_n, mb = w[1] * inv_n;                       // centred means
-    const float va = (w[2] - w[0] * ma) * inv_n1, vb = (w[3] - w[1] * mb) * inv_n1, vab = (w[4] - w[0] * mb) * inv_n1;
-    const float ux = ma + shift, uy = mb + shift;
+    ss_window_sums(ring, j, w);
+    const auto [ma, mb, va, vb, vab, ux, uy] = ss_moments(w, shift);
     const float num = (2.f * ux * uy + c1) * (2.f * vab + c2);
     const float den = (ux * ux + uy * uy + c1) * (va + vb + c2);
     const float ssim = num / den;
@@ -162,8 +181,8 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float* __restrict__ pre
 // ---- the vector-Jacobian product of the sums: orbit2_loss_bwd(kind = ORBIT2_LOSS_SSIM_VJP) -----------------------
 // dpred[p] = g sum over the valid centres k whose window holds p of w_k dS_k / dpred[p].  A workgroup owns SV_TH x SV_TW OUTPUT
 // pixels of one image.  It stages the pixels under them plus a halo of 6, of both fields, minus the tile's pivot (the target at
-// the tile's first pixel); forms, at the centres under the tile plus a halo of 3, three maps -- with the forward's window sums,
-// its register ring and its second, per-thread pivot, so S is the forward's S --; box-sums the maps 7 x 7, rows then columns,
+// the tile's first pixel); forms, at the centres under the tile plus a halo of 3, three maps -- by the forward's own steps (the
+// ss_ functions above) and its second, per-thread pivot, so S is the forward's S --; box-sums the maps 7 x 7, rows then columns,
 // through LDS (the row sums take the place of the staged pixels, whose tile part every thread has read into registers); and
 // writes every pixel of its tile once: no atomics, the same bits on every call.  With alpha, beta, gamma of the header and the
 // means mx = ux - v, my = uy - v relative to the tile's pivot v, the header's five box sums fold by linearity into three:
@@ -213,8 +232,7 @@ __global__ __launch_bounds__(256) void ssim_vjp_kernel(const float* __restrict__
   }
   const float* p = pred + (size_t)bc * H * W;
   const float* t = target + (size_t)bc * Ht * Wt;
-  const float R = gscale[BC + bc];
-  const float c1 = (0.01f * R) * (0.01f * R), c2 = (0.03f * R) * (0.03f * R);
+  const auto [c1, c2] = ss_consts(gscale[BC + bc]);
   const float pivot = t[(size_t)py0 * Wt + px0];
   float* sa = pix;
   float* sb = pix + SV_PH * SV_PW;
@@ -253,38 +271,15 @@ __global__ __launch_bounds__(256) void ssim_vjp_kernel(const float* __restrict__
     float ring[SS_WIN][5];
 #pragma unroll
     for (int j = 0; j < SV_RS + SS_HALO; ++j) {
-      const int pr = min(mr0 + j, SV_PH - 1);
-      const float* ra = sa + pr * SV_PW + c;
-      const float* rb = sb + pr * SV_PW + c;
-      float ua = 0.f, ub = 0.f, uaa = 0.f, ubb = 0.f, uab = 0.f;
-#pragma unroll
-      for (int k = 0; k < SS_WIN; ++k) {
-        const float a = ra[k] - local, b = rb[k] - local;
-        ua += a;
-        ub += b;
-        uaa = fmaf(a, a, uaa);
-        ubb = fmaf(b, b, ubb);
-        uab = fmaf(a, b, uab);
-      }
-      ring[j % SS_WIN][0] = ua, ring[j % SS_WIN][1] = ub, ring[j % SS_WIN][2] = uaa, ring[j % SS_WIN][3] = ubb,
-      ring[j % SS_WIN][4] = uab;
+      ss_row_sums<SV_PW>(sa, sb, min(mr0 + j, SV_PH - 1), c, local, ring[j % SS_WIN]);
       if (j < SS_HALO) continue;
       float w[5];
-#pragma unroll
-      for (int q = 0; q < 5; ++q) {
-        float v = ring[(j + 1) % SS_WIN][q];            // oldest first
-#pragma unroll
-        for (int k = 2; k <= SS_WIN; ++k) v += ring[(j + k) % SS_WIN][q];
-        w[q] = v;
-      }
+      ss_window_sums(ring, j, w);
       const int mr = mr0 + j - SS_HALO;                 // the centre's map row; its pixel row is cy
       const int cy = py0 - SS_WIN / 2 + mr;
       if (mr >= SV_MH) continue;
       const bool valid = cy >= SS_WIN / 2 && cy < H - SS_WIN / 2 && cx >= SS_WIN / 2 && cx < W - SS_WIN / 2;
-      const float inv_n = 1.f / (SS_WIN * SS_WIN), inv_n1 = 1.f / (SS_WIN * SS_WIN - 1);
-      const float ma = w[0] * inv_n, mb = w[1] * inv_n;                     // centred means
-      const float va = (w[2] - w[0] * ma) * inv_n1, vb = (w[3] - w[1] * mb) * inv_n1, vab = (w[4] - w[0] * mb) * inv_n1;
-      const float ux = ma + shift, uy = mb + shift;
+      const auto [ma, mb, va, vb, vab, ux, uy] = ss_moments(w, shift);
       const float A1 = 2.f * ux * uy + c1, A2 = 2.f * vab + c2;
       const float B1 = ux * ux + uy * uy + c1, B2 = va + vb + c2;
       const float rB = 1.f / (B1 * B2);
@@ -294,9 +289,9 @@ __global__ __launch_bounds__(256) void ssim_vjp_kernel(const float* __restrict__
       const float gamma = 2.f * A1 * rB;
       const float mx = ma + local, my = mb + local;     // the means relative to the tile's pivot
       const float wk = (valid && lat_w) ? lat_w[cy] : 1.f;
-      const float e0 = wk * (alpha * inv_n - (2.f * beta * mx + gamma * my) * inv_n1);
-      const float e1 = wk * (2.f * beta * inv_n1);
-      const float e2 = wk * (gamma * inv_n1);
+      const float e0 = wk * (alpha * SS_INV_N - (2.f * beta * mx + gamma * my) * SS_INV_N1);
+      const float e1 = wk * (2.f * beta * SS_INV_N1);
+      const float e2 = wk * (gamma * SS_INV_N1);
       float* m = maps + mr * SV_MW + c;
       m[0] = valid ? e0 : 0.f;
       m[SV_MH * SV_MW] = valid ? e1 : 0.f;
@@ -339,14 +334,18 @@ __global__ __launch_bounds__(256) void ssim_vjp_kernel(const float* __restrict__
     sv_store4(d, py0 + r, px0 + oc, H, W, vec, o);
   }
 }
+// what both entries refuse: an image smaller than one window, more images than blockIdx.y holds, more tiles (ntx along W, nty
+// along H, of the entry's own tile) than the int that blockIdx.x is decoded in
+inline bool ss_grid_ok(int B, int C, int H, int W, int ntx, int nty) {
+  return H >= SS_WIN && W >= SS_WIN && (int64_t)B * C <= 65535 && (int64_t)ntx * nty <= INT32_MAX;
+}
 }  // namespace
 
 // the kind ORBIT2_LOSS_SSIM_VJP of orbit2_loss_bwd (image.hip), which has checked the pair, gscale and dpred
 int o2_ssim_vjp(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* gscale, float* dpred,
                 int B, int C, int H, int W, hipStream_t s) {
-  if (H < SS_WIN || W < SS_WIN || (int64_t)B * C > 65535) return O2_ERR_ARG;
   const int ntx = (W + SV_TW - 1) / SV_TW, nty = (H + SV_TH - 1) / SV_TH;
-  if ((int64_t)ntx * nty > INT32_MAX) return O2_ERR_ARG;
+  if (!ss_grid_ok(B, C, H, W, ntx, nty)) return O2_ERR_ARG;
   hipLaunchKernelGGL(ssim_vjp_kernel, dim3(ntx * nty, B * C), dim3(256), 0, s, pred, target, Ht, Wt, lat_w, gscale, dpred, B * C,
                      H, W, ntx);
   O2_CHECK_LAUNCH();
@@ -355,10 +354,8 @@ int o2_ssim_vjp(const float* pred, const float* target, int Ht, int Wt, const fl
 
 extern "C" int orbit2_ssim(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* data_range,
                            double* sums, float* ssim_map, int B, int C, int H, int W, void* stream) {
-  if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !sums || H < SS_WIN || W < SS_WIN) return O2_ERR_ARG;
-  if ((int64_t)B * C > 65535) return O2_ERR_ARG;
   const int ntx = (W - SS_HALO + SS_TW - 1) / SS_TW, nty = (H - SS_HALO + SS_TH - 1) / SS_TH;
-  if ((int64_t)ntx * nty > INT32_MAX) return O2_ERR_ARG;
+  if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !sums || !ss_grid_ok(B, C, H, W, ntx, nty)) return O2_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const int BC = B * C;
   hipLaunchKernelGGL(ssim_init_kernel, dim3((BC + 255) / 256), dim3(256), 0, s, sums, BC);
