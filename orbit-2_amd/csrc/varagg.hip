@@ -37,6 +37,46 @@ __device__ __forceinline__ float va_row(const f32x4* g, const float* p, int j) {
 
 constexpr int VA_LDS_LIMIT = 160 * 1024;   // LDS of a gfx950 CU: a launch that needs more is refused on the host
 
+// ---- the steps that the scalar kernel, the ds kernel and the table-gradient kernel share --------------------------------------
+// (the staging of aw / da, the score dot and the scalar softmax backward stay written out in their kernels: as helpers they give
+// the same instructions in another order in the P = 2 kernels, which are kept as they were: profiles/varagg_shared_parts_equivalence.txt)
+// one patch value of (token, variable): x[b][v][P*pr + c/P][P*pc + c%P], the token being (pr, pc) of sample b's [h/P][w/P] grid.
+// The caller has checked tok < the token count and c < P*P (stated to the compiler too: without it c / P and c % P are compiled
+// for a negative c).  TOK is the kernel's token type (int64_t, or int where the host guarantees the count fits).
+template <int P, class TOK>
+__device__ __forceinline__ float va_patch_value(const float* x, TOK tok, int v, int c, int V, int h, int w, int L, int Lw) {
+  __builtin_assume(c >= 0 && c < P * P);
+  const int b = (int)(tok / L), l = (int)(tok - (TOK)b * L);
+  const int pr = l / Lw, pc = l - pr * Lw;
+  return x[(((size_t)b * V + v) * h + (P * pr + c / P)) * w + P * pc + c % P];
+}
+
+// the patch image of a workgroup's VA_T tokens: pt[t][v][c] = the patch value for c < P*P, 1 at c == P*P (the constant term of
+// the tables), 0 for a token past the last
+template <int P>
+__device__ __forceinline__ void va_stage_patches(const float* x, float* pt, int64_t tok0, int64_t ntok, int V, int h, int w,
+                                                 int L, int Lw) {
+  constexpr int PP = P * P, C = PP + 1;
+  const int tid = threadIdx.x;
+  for (int e = tid; e < VA_T * V * C; e += 256) {
+    const int c = e % C, v = (e / C) % V, t = e / (C * V);
+    const int64_t tok = tok0 + t;
+    float val = 0.f;
+    if (tok < ntok) {
+      if (c == PP) val = 1.f;
+      else val = va_patch_value<P>(x, tok, v, c, V, h, w, L, Lw);
+    }
+    pt[e] = val;
+  }
+}
+
+// four consecutive bf16 of dz (one 8-byte load; p is 8-byte aligned: D % 4 == 0) as four floats
+__device__ __forceinline__ void va_load_dz4(const bf16_t* p, float* o) {
+  const u32x2 r = *reinterpret_cast<const u32x2*>(p);
+  o[0] = bf2f((bf16_t)(r[0] & 0xffff)); o[1] = bf2f((bf16_t)(r[0] >> 16));
+  o[2] = bf2f((bf16_t)(r[1] & 0xffff)); o[3] = bf2f((bf16_t)(r[1] >> 16));
+}
+
 // LDS: pt[T][V][C], aw[T][H][V]  (+ da[T][H][V] in the backward)
 // ZF32 (forward only): z is written as fp32 and attw may be NULL (the fp32 forward path saves nothing for a backward)
 template <bool BWD, bool ZF32 = false, int P = 2>
@@ -57,20 +97,7 @@ __global__ __launch_bounds__(256) void varagg_kernel(const float* __restrict__ x
   const int dh = D / H;
 
   // ---- patches ---------------------------------------------------------------------------------
-  for (int e = tid; e < VA_T * V * C; e += 256) {
-    const int c = e % C, v = (e / C) % V, t = e / (C * V);
-    const int64_t tok = tok0 + t;
-    float val = 0.f;
-    if (tok < ntok) {
-      if (c == PP) val = 1.f;
-      else {
-        const int b = (int)(tok / L), l = (int)(tok - (int64_t)b * L);
-        const int pr = l / Lw, pc = l - pr * Lw;
-        val = x[(((size_t)b * V + v) * h + (P * pr + c / P)) * w + P * pc + c % P];
-      }
-    }
-    pt[e] = val;
-  }
+  va_stage_patches<P>(x, pt, tok0, ntok, V, h, w, L, Lw);
   __syncthreads();
   // ---- scores + softmax over variables (one thread per (token, head)) -----------------------------
   if (!BWD) {
@@ -150,11 +177,8 @@ __global__ __launch_bounds__(256) void varagg_kernel(const float* __restrict__ x
 #pragma unroll
       for (int t = 0; t < VA_T; ++t) {
         const int64_t tok = tok0 + t;
-        if (tok < ntok) {
-          const u32x2 r = *reinterpret_cast<const u32x2*>(dz + (size_t)tok * D + i0);
-          dzv[t][0] = bf2f((bf16_t)(r[0] & 0xffff)); dzv[t][1] = bf2f((bf16_t)(r[0] >> 16));
-          dzv[t][2] = bf2f((bf16_t)(r[1] & 0xffff)); dzv[t][3] = bf2f((bf16_t)(r[1] >> 16));
-        } else { dzv[t][0] = dzv[t][1] = dzv[t][2] = dzv[t][3] = 0.f; }
+        if (tok < ntok) va_load_dz4(dz + (size_t)tok * D + i0, dzv[t]);
+        else { dzv[t][0] = dzv[t][1] = dzv[t][2] = dzv[t][3] = 0.f; }
       }
       for (int v = 0; v < V; ++v) {
         f32x4 g[C];
@@ -443,29 +467,6 @@ static int varagg_bwd_splits(int ntok, int H, int* cpw_out) {
   return (nchunk + cpw - 1) / cpw;
 }
 
-template <int DH>
-static void varagg_bwd_mfma_launch(const float* x, const float* gtab, const float* attw, const void* dz, float* dstab,
-                                   float* dgtab, int B, int V, int h, int w, int H, int D, int ntok, float* ws, hipStream_t s) {
-  // every (head, token range) workgroup stores its partial tables in the range's slab of `ws`; the ranges are then added in
-  // a fixed order (round 4: instead of one fp32 atomic flush per workgroup -- bitwise reproducible)
-  int cpw;
-  const int splits = varagg_bwd_splits(ntok, H, &cpw);
-  float* ws_s = ws;
-  float* ws_g = ws + (size_t)splits * H * V * 5;
-  const size_t shm = (size_t)VM_T * DH * 2 + 2 * (size_t)VM_T * VM_NV * 2 +
-                     sizeof(float) * (size_t)(VM_T * VM_GS + VM_T * V * 4 + 2 * VM_T * V);
-  static bool attr_set = false;   // one flag per instantiation
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)varagg_bwd_mfma_kernel<DH>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(varagg_bwd_mfma_kernel<DH>, dim3((unsigned)H, (unsigned)splits), dim3(256), shm, s, x, gtab, attw,
-                     (const bf16_t*)dz, ws_s, ws_g, B, V, h, w, H, D, cpw);
-  o2_sum_parts(ws_s, splits, (int64_t)H * V * 5, dstab, (int64_t)H * V * 5, 1.0f, 1, s);     // += , as the atomics did
-  o2_sum_parts(ws_g, splits, (int64_t)V * 5 * D, dgtab, (int64_t)V * 5 * D, 1.0f, 1, s);
-}
-
 
 // ---------------------------------------------------------------------------------------------------------
 // Backward for P != 2 (C = 2 or 17): two stages, no float atomics anywhere, every sum in an order fixed by the shape.
@@ -499,20 +500,7 @@ __global__ __launch_bounds__(256) void varagg_ds_kernel(const float* __restrict_
   const int dh = D / H;
   const int gs = dh / 4;                // threads (4-channel chunks) per head
 
-  for (int e = tid; e < VA_T * V * C; e += 256) {
-    const int c = e % C, v = (e / C) % V, t = e / (C * V);
-    const int64_t tok = tok0 + t;
-    float val = 0.f;
-    if (tok < ntok) {
-      if (c == PP) val = 1.f;
-      else {
-        const int b = (int)(tok / L), l = (int)(tok - (int64_t)b * L);
-        const int pr = l / Lw, pc = l - pr * Lw;
-        val = x[(((size_t)b * V + v) * h + (P * pr + c / P)) * w + P * pc + c % P];
-      }
-    }
-    pt[e] = val;
-  }
+  va_stage_patches<P>(x, pt, tok0, ntok, V, h, w, L, Lw);
   for (int e = tid; e < VA_T * H * V; e += 256) {
     const int64_t tok = tok0 + e / (H * V);
     aw[e] = tok < ntok ? attw[(size_t)tok0 * H * V + e] : 0.f;
@@ -528,11 +516,8 @@ __global__ __launch_bounds__(256) void varagg_ds_kernel(const float* __restrict_
 #pragma unroll
     for (int t = 0; t < VA_T; ++t) {
       const int64_t tok = tok0 + t;
-      if (on && tok < ntok) {
-        const u32x2 r = *reinterpret_cast<const u32x2*>(dz + (size_t)tok * D + i0);
-        dzv[t][0] = bf2f((bf16_t)(r[0] & 0xffff)); dzv[t][1] = bf2f((bf16_t)(r[0] >> 16));
-        dzv[t][2] = bf2f((bf16_t)(r[1] & 0xffff)); dzv[t][3] = bf2f((bf16_t)(r[1] >> 16));
-      } else { dzv[t][0] = dzv[t][1] = dzv[t][2] = dzv[t][3] = 0.f; }
+      if (on && tok < ntok) va_load_dz4(dz + (size_t)tok * D + i0, dzv[t]);
+      else { dzv[t][0] = dzv[t][1] = dzv[t][2] = dzv[t][3] = 0.f; }
     }
     // the heads whose chunks lie in [cb, cb + 256): head hh owns chunks [hh * gs, (hh + 1) * gs)
     const int h_lo = cb / gs, h_hi = min(H, (min(nchunk, cb + 256) + gs - 1) / gs);
@@ -618,12 +603,7 @@ __global__ __launch_bounds__(256) void varagg_tabgrad_kernel(const float* __rest
         float val = 0.f;
         if (t < nt) {
           if (c == PP) val = 1.f;
-          else {
-            const int tok = tok0 + t;
-            const int b = tok / L, l = tok - b * L;
-            const int pr = l / Lw, pc = l - pr * Lw;
-            val = x[(((size_t)b * V + v) * h + (P * pr + c / P)) * w + P * pc + c % P];
-          }
+          else val = va_patch_value<P>(x, tok0 + t, v, c, V, h, w, L, Lw);
         }
         pt[t][c] = val;
       }
@@ -637,10 +617,10 @@ __global__ __launch_bounds__(256) void varagg_tabgrad_kernel(const float* __rest
       if (on) {
 #pragma unroll 4
         for (int t = 0; t < nt; ++t) {
-          const u32x2 q = *reinterpret_cast<const u32x2*>(dz + (size_t)(tok0 + t) * D + i0);
+          float q[4];
+          va_load_dz4(dz + (size_t)(tok0 + t) * D + i0, q);
           const float a = aw[t][hh];
-          const float ad[4] = {a * bf2f((bf16_t)(q[0] & 0xffff)), a * bf2f((bf16_t)(q[0] >> 16)),
-                               a * bf2f((bf16_t)(q[1] & 0xffff)), a * bf2f((bf16_t)(q[1] >> 16))};
+          const float ad[4] = {a * q[0], a * q[1], a * q[2], a * q[3]};
 #pragma unroll
           for (int c = 0; c < C; ++c) {
             const float pc_ = pt[t][c];
@@ -691,50 +671,42 @@ static int varagg_tabgrad_splits(int ntok, int V, int* rpw_out) {
   return (nround + rpw - 1) / rpw;
 }
 
-// dynamic LDS of the kernels above, bytes
-static size_t va_fwd_lds(int P, int V, int H) {          // the forward of P != 2: pt + aw
-  return sizeof(float) * ((size_t)VA_T * V * (P * P + 1) + (size_t)VA_T * H * V);
-}
-static size_t va_ds_lds(int P, int V, int H) {           // varagg_ds_kernel: pt + aw + da + part
-  return sizeof(float) * ((size_t)VA_T * V * (P * P + 1) + 2 * (size_t)VA_T * H * V + 2 * (size_t)VA_T * 256);
+// dynamic LDS of each kernel form, bytes.  The scalar kernel lays out pt + aw + da; the forward at P = 2 asks for that too although
+// it never touches da, the second T*H*V half (the request it has always made: dropping it changes how many workgroups share a CU)
+enum va_form { VA_FWD, VA_BWD_SCALAR, VA_BWD_DS, VA_BWD_MFMA };
+static size_t va_lds(va_form form, int P, int V, int H, int DH = 0) {
+  const size_t pt = (size_t)VA_T * V * (P * P + 1), thv = (size_t)VA_T * H * V;
+  switch (form) {
+    case VA_FWD: return sizeof(float) * (pt + (P == 2 ? 2 : 1) * thv);               // pt + aw (+ the unused half at P = 2)
+    case VA_BWD_SCALAR: return sizeof(float) * (pt + 2 * thv);                        // pt + aw + da
+    case VA_BWD_DS: return sizeof(float) * (pt + 2 * thv + 2 * (size_t)VA_T * 256);   // pt + aw + da + part
+    default:                                                                          // zt + a2hi + a2lo + gimg + pt + aw + dsv
+      return (size_t)VM_T * DH * 2 + 2 * (size_t)VM_T * VM_NV * 2 + sizeof(float) * (size_t)(VM_T * VM_GS + VM_T * V * 4 + 2 * VM_T * V);
+  }
 }
 
-template <int P, bool ZF32>
-static int varagg_fwd_launch_p(const float* x, const float* stab, const float* gtab, void* z, float* attw, int B, int V, int h,
-                               int w, int H, int D, hipStream_t s) {
-  const int64_t ntok = (int64_t)B * (h / P) * (w / P);
-  const size_t shm = va_fwd_lds(P, V, H);
-  if (shm > (size_t)VA_LDS_LIMIT) return O2_ERR_UNSUPPORTED;
+// lets a kernel ask for up to a CU's whole LDS; one host call on the first launch of each instantiation
+template <auto KERNEL>
+static void va_allow_large_lds() {
   static bool attr_set = false;   // one flag per instantiation
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)varagg_kernel<false, ZF32, P>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              VA_LDS_LIMIT);
+    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, VA_LDS_LIMIT);
     attr_set = true;
   }
-  hipLaunchKernelGGL((varagg_kernel<false, ZF32, P>), dim3((unsigned)((ntok + VA_T - 1) / VA_T)), dim3(256), shm, s, x, stab,
-                     gtab, (bf16_t*)z, attw, (const bf16_t*)nullptr, (float*)nullptr, (float*)nullptr, B, V, h, w, H, D);
-  return O2_OK;
 }
 
-template <int P>
-static void varagg_bwd_launch_p(const float* x, const float* gtab, const float* attw, const void* dz, float* dstab,
-                                float* dgtab, int B, int V, int h, int w, int H, int D, int ntok, float* ws, hipStream_t s) {
-  constexpr int C = P * P + 1;
-  int rpw;
-  const int splits = varagg_tabgrad_splits(ntok, V, &rpw);
-  float* ws_ds = ws;                                           // [tokens][H][V]
-  float* ws_s = ws_ds + (size_t)ntok * H * V;                  // [range][H][V][C]
-  float* ws_g = ws_s + (size_t)splits * H * V * C;             // [range][V][C][D]
-  static bool attr_set = false;   // one flag per instantiation
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)varagg_ds_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, VA_LDS_LIMIT);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(varagg_ds_kernel<P>, dim3((unsigned)((ntok + VA_T - 1) / VA_T)), dim3(256), va_ds_lds(P, V, H), s, x, gtab,
-                     attw, (const bf16_t*)dz, ws_ds, B, V, h, w, H, D);
-  hipLaunchKernelGGL(varagg_tabgrad_kernel<P>, dim3((unsigned)V, (unsigned)splits), dim3(256), 0, s, x, attw, ws_ds,
-                     (const bf16_t*)dz, ws_s, ws_g, B, V, h, w, H, D, rpw);
-  o2_sum_parts(ws_s, splits, (int64_t)H * V * C, dstab, (int64_t)H * V * C, 1.0f, 1, s);     // += into the caller's tables
+// f(o2_int<P>) for the patch size the host has checked (va_check: 1, 2 or 4)
+template <class F>
+static void va_with_patch(int P, F&& f) {
+  if (P == 1) f(o2_int<1>{});
+  else if (P == 2) f(o2_int<2>{});
+  else f(o2_int<4>{});
+}
+
+// the token ranges' slabs of a two-stage backward, added in order: += into the caller's tables, as the atomics did
+static void va_sum_ranges(const float* ws_s, const float* ws_g, int splits, int V, int H, int D, int C, float* dstab,
+                          float* dgtab, hipStream_t s) {
+  o2_sum_parts(ws_s, splits, (int64_t)H * V * C, dstab, (int64_t)H * V * C, 1.0f, 1, s);
   o2_sum_parts(ws_g, splits, (int64_t)V * C * D, dgtab, (int64_t)V * C * D, 1.0f, 1, s);
 }
 
@@ -747,135 +719,159 @@ static int va_check(int B, int V, int h, int w, int H, int D, int P = 2) {
   return O2_OK;
 }
 
-extern "C" int orbit2_varagg_fwd(const float* x, const float* stab, const float* gtab, void* z, float* attw, int B,
-                                 int V, int h, int w, int H, int D, void* stream) {
-  if (!x || !stab || !gtab || !z || !attw) return O2_ERR_ARG;
-  int rc = va_check(B, V, h, w, H, D);
+// ---- the forward of every patch size, z as bf16 or (zf32) as fp32 -----------------------------------------------------------------
+static int va_forward(int P, bool zf32, const float* x, const float* stab, const float* gtab, void* z, float* attw, int B, int V,
+                      int h, int w, int H, int D, void* stream) {
+  int rc = va_check(B, V, h, w, H, D, P);
   if (rc) return rc;
-  const int64_t ntok = (int64_t)B * (h / 2) * (w / 2);
-  const size_t shm = sizeof(float) * (size_t)(VA_T * V * 5 + 2 * VA_T * H * V);
-  hipLaunchKernelGGL(varagg_kernel<false>, dim3((unsigned)((ntok + VA_T - 1) / VA_T)), dim3(256), shm,
-                     (hipStream_t)stream, x, stab, gtab, (bf16_t*)z, attw, (const bf16_t*)nullptr, (float*)nullptr,
-                     (float*)nullptr, B, V, h, w, H, D);
+  const int64_t ntok = (int64_t)B * (h / P) * (w / P);
+  const size_t shm = va_lds(VA_FWD, P, V, H);
+  if (shm > (size_t)VA_LDS_LIMIT) return O2_ERR_UNSUPPORTED;          // (P = 4 only: at most 138 KiB at P = 2, V = H = 32)
+  va_with_patch(P, [&](auto PC) {
+    o2_with_flags([&](auto ZF32) {
+      va_allow_large_lds<varagg_kernel<false, ZF32, PC>>();
+      hipLaunchKernelGGL((varagg_kernel<false, ZF32, PC>), dim3((unsigned)((ntok + VA_T - 1) / VA_T)), dim3(256), shm,
+                         (hipStream_t)stream, x, stab, gtab, (bf16_t*)z, attw, (const bf16_t*)nullptr, (float*)nullptr,
+                         (float*)nullptr, B, V, h, w, H, D);
+    }, zf32);
+  });
   O2_CHECK_LAUNCH();
   return O2_OK;
 }
 
-extern "C" int orbit2_varagg_fwd_f32(const float* x, const float* stab, const float* gtab, float* z, float* attw, int B,
-                                     int V, int h, int w, int H, int D, void* stream) {
-  if (!x || !stab || !gtab || !z) return O2_ERR_ARG;              // attw may be NULL
-  int rc = va_check(B, V, h, w, H, D);
-  if (rc) return rc;
-  const int64_t ntok = (int64_t)B * (h / 2) * (w / 2);
-  const size_t shm = sizeof(float) * (size_t)(VA_T * V * 5 + 2 * VA_T * H * V);
-  hipLaunchKernelGGL((varagg_kernel<false, true>), dim3((unsigned)((ntok + VA_T - 1) / VA_T)), dim3(256), shm,
-                     (hipStream_t)stream, x, stab, gtab, (bf16_t*)z, attw, (const bf16_t*)nullptr, (float*)nullptr,
-                     (float*)nullptr, B, V, h, w, H, D);
-  O2_CHECK_LAUNCH();
-  return O2_OK;
-}
-
-extern "C" int64_t orbit2_varagg_bwd_ws_floats(int B, int V, int h, int w, int H, int D) {
-  if (va_check(B, V, h, w, H, D)) return 0;
-  const int64_t ntok = (int64_t)B * (h / 2) * (w / 2);
-  if (ntok >= (1ll << 31) - 64) return 0;
-  return (int64_t)varagg_bwd_splits((int)ntok, H, nullptr) * ((int64_t)H * V * 5 + (int64_t)V * 5 * D);
-}
-
-// 1 when orbit2_varagg_bwd takes the two-stage fixed-order path for this shape (bitwise reproducible gradients), 0 when it falls
-// back to the scalar kernel whose table gradients are accumulated with fp32 atomics
+// ---- the backward.  P = 2: the MFMA kernel where it serves the shape, the scalar kernel with its atomics otherwise.  P = 1, 4:
+// the two-stage kernels or a refusal.  Both fixed-order forms store per token range into `ws` and add the ranges in order -----------
 static bool varagg_bwd_fixed_order(int64_t ntok, int V, int H, int D) {
   static const bool force_scalar = getenv("ORBIT2_VARAGG_SCALAR") != nullptr;   // debugging aid: the fp32 VALU kernel
   const int dh = D / H;
   return !force_scalar && (dh == 64 || dh == 128 || dh == 256) && 5 * V <= VM_NV && ntok < (1ll << 31) - 64;
 }
-extern "C" int orbit2_varagg_bwd_is_fixed_order(int B, int V, int h, int w, int H, int D) {
+
+// whether the backward at patch != 2 serves the shape: valid arguments, token count in int range, LDS within a CU's
+static bool varagg_bwd_p_served(int B, int V, int h, int w, int patch, int H, int D) {
+  if (va_check(B, V, h, w, H, D, patch)) return false;
+  if ((int64_t)B * (h / patch) * (w / patch) >= (1ll << 31) - 64) return false;
+  return va_lds(VA_BWD_DS, patch, V, H) <= (size_t)VA_LDS_LIMIT;
+}
+
+static int va_backward(int P, const float* x, const float* gtab, const float* attw, const void* dz, float* dstab, float* dgtab,
+                       int B, int V, int h, int w, int H, int D, float* ws, void* stream) {
+  int rc = va_check(B, V, h, w, H, D, P);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t ntok = (int64_t)B * (h / P) * (w / P);
+  const dim3 tok_grid((unsigned)((ntok + VA_T - 1) / VA_T));
+  if (P != 2) {
+    if (!varagg_bwd_p_served(B, V, h, w, P, H, D)) return O2_ERR_UNSUPPORTED;
+    va_with_patch(P, [&](auto PC) {
+      if constexpr (PC != 2) {
+        constexpr int C = PC * PC + 1;
+        int rpw;
+        const int splits = varagg_tabgrad_splits((int)ntok, V, &rpw);
+        float* ws_ds = ws;                                           // [tokens][H][V]
+        float* ws_s = ws_ds + (size_t)ntok * H * V;                  // [range][H][V][C]
+        float* ws_g = ws_s + (size_t)splits * H * V * C;             // [range][V][C][D]
+        va_allow_large_lds<varagg_ds_kernel<PC>>();
+        hipLaunchKernelGGL(varagg_ds_kernel<PC>, tok_grid, dim3(256), va_lds(VA_BWD_DS, PC, V, H), s, x, gtab, attw,
+                           (const bf16_t*)dz, ws_ds, B, V, h, w, H, D);
+        hipLaunchKernelGGL(varagg_tabgrad_kernel<PC>, dim3((unsigned)V, (unsigned)splits), dim3(256), 0, s, x, attw, ws_ds,
+                           (const bf16_t*)dz, ws_s, ws_g, B, V, h, w, H, D, rpw);
+        va_sum_ranges(ws_s, ws_g, splits, V, H, D, C, dstab, dgtab, s);
+      }
+    });
+  } else if (varagg_bwd_fixed_order(ntok, V, H, D)) {
+    // every (head, token range) workgroup stores its partial tables in the range's slab of `ws`; the ranges are then added in
+    // a fixed order (round 4: instead of one fp32 atomic flush per workgroup -- bitwise reproducible)
+    int cpw;
+    const int splits = varagg_bwd_splits((int)ntok, H, &cpw);
+    float* ws_s = ws;
+    float* ws_g = ws + (size_t)splits * H * V * 5;
+    auto launch = [&](auto DH) {
+      va_allow_large_lds<varagg_bwd_mfma_kernel<DH>>();
+      hipLaunchKernelGGL(varagg_bwd_mfma_kernel<DH>, dim3((unsigned)H, (unsigned)splits), dim3(256),
+                         va_lds(VA_BWD_MFMA, 2, V, H, DH), s, x, gtab, attw, (const bf16_t*)dz, ws_s, ws_g, B, V, h, w, H, D, cpw);
+    };
+    if (D / H == 64) launch(o2_int<64>{});
+    else if (D / H == 128) launch(o2_int<128>{});
+    else launch(o2_int<256>{});
+    va_sum_ranges(ws_s, ws_g, splits, V, H, D, 5, dstab, dgtab, s);
+  } else {
+    va_allow_large_lds<varagg_kernel<true>>();
+    hipLaunchKernelGGL(varagg_kernel<true>, tok_grid, dim3(256), va_lds(VA_BWD_SCALAR, 2, V, H), s, x, (const float*)nullptr, gtab,
+                       (bf16_t*)nullptr, (float*)attw, (const bf16_t*)dz, dstab, dgtab, B, V, h, w, H, D);
+  }
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+// floats of `ws` that va_backward writes; 0 for what it refuses.  At P = 2 the MFMA form's, whichever kernel then runs
+static int64_t va_backward_ws_floats(int P, int B, int V, int h, int w, int H, int D) {
+  if (va_check(B, V, h, w, H, D, P)) return 0;
+  const int64_t ntok = (int64_t)B * (h / P) * (w / P);
+  if (ntok >= (1ll << 31) - 64) return 0;
+  if (P != 2 && va_lds(VA_BWD_DS, P, V, H) > (size_t)VA_LDS_LIMIT) return 0;
+  const int64_t C = P * P + 1;
+  if (P == 2) return (int64_t)varagg_bwd_splits((int)ntok, H, nullptr) * ((int64_t)H * V * C + (int64_t)V * C * D);
+  return ntok * H * V + (int64_t)varagg_tabgrad_splits((int)ntok, V, nullptr) * ((int64_t)H * V * C + (int64_t)V * C * D);
+}
+
+// 1 when va_backward takes a two-stage fixed-order path for this shape (bitwise reproducible gradients), 0 when it falls back to the
+// scalar kernel whose table gradients are accumulated with fp32 atomics, or refuses; the only path at patch 1 / 4 is fixed-order
+static int va_backward_is_fixed_order(int P, int B, int V, int h, int w, int H, int D) {
+  if (P != 2) return varagg_bwd_p_served(B, V, h, w, P, H, D) ? 1 : 0;
   if (va_check(B, V, h, w, H, D)) return 0;
   return varagg_bwd_fixed_order((int64_t)B * (h / 2) * (w / 2), V, H, D) ? 1 : 0;
 }
 
-extern "C" int orbit2_varagg_bwd(const float* x, const float* gtab, const float* attw, const void* dz, float* dstab,
-                                 float* dgtab, int B, int V, int h, int w, int H, int D, float* ws, void* stream) {
-  if (!x || !gtab || !attw || !dz || !dstab || !dgtab || !ws) return O2_ERR_ARG;
-  int rc = va_check(B, V, h, w, H, D);
-  if (rc) return rc;
-  const int64_t ntok = (int64_t)B * (h / 2) * (w / 2);
-  const int dh = D / H;
-  if (varagg_bwd_fixed_order(ntok, V, H, D)) {
-    hipStream_t s = (hipStream_t)stream;
-    if (dh == 64) varagg_bwd_mfma_launch<64>(x, gtab, attw, dz, dstab, dgtab, B, V, h, w, H, D, (int)ntok, ws, s);
-    else if (dh == 128) varagg_bwd_mfma_launch<128>(x, gtab, attw, dz, dstab, dgtab, B, V, h, w, H, D, (int)ntok, ws, s);
-    else varagg_bwd_mfma_launch<256>(x, gtab, attw, dz, dstab, dgtab, B, V, h, w, H, D, (int)ntok, ws, s);
-    O2_CHECK_LAUNCH();
-    return O2_OK;
-  }
-  const size_t shm = sizeof(float) * (size_t)(VA_T * V * 5 + 2 * VA_T * H * V);
-  hipLaunchKernelGGL(varagg_kernel<true>, dim3((unsigned)((ntok + VA_T - 1) / VA_T)), dim3(256), shm,
-                     (hipStream_t)stream, x, (const float*)nullptr, gtab, (bf16_t*)nullptr, (float*)attw,
-                     (const bf16_t*)dz, dstab, dgtab, B, V, h, w, H, D);
-  O2_CHECK_LAUNCH();
-  return O2_OK;
+// ---- the entries: NULL checks and a call.  The plain ones are patch 2; the `_p` ones carry the patch size (1, 2 or 4) and at 2 are
+// the plain call: same kernels, same launch ----------------------------------------------------------------------------------
+extern "C" int orbit2_varagg_fwd(const float* x, const float* stab, const float* gtab, void* z, float* attw, int B,
+                                 int V, int h, int w, int H, int D, void* stream) {
+  if (!x || !stab || !gtab || !z || !attw) return O2_ERR_ARG;
+  return va_forward(2, false, x, stab, gtab, z, attw, B, V, h, w, H, D, stream);
 }
 
-// ---- the entries that carry the patch size (1, 2 or 4).  patch = 2 is the call above: same kernels, same launch --------------
+extern "C" int orbit2_varagg_fwd_f32(const float* x, const float* stab, const float* gtab, float* z, float* attw, int B,
+                                     int V, int h, int w, int H, int D, void* stream) {
+  if (!x || !stab || !gtab || !z) return O2_ERR_ARG;              // attw may be NULL
+  return va_forward(2, true, x, stab, gtab, z, attw, B, V, h, w, H, D, stream);
+}
+
 extern "C" int orbit2_varagg_fwd_p(const float* x, const float* stab, const float* gtab, void* z, float* attw, int B, int V,
                                    int h, int w, int patch, int H, int D, void* stream) {
   if (!x || !stab || !gtab || !z || !attw) return O2_ERR_ARG;
-  int rc = va_check(B, V, h, w, H, D, patch);
-  if (rc) return rc;
-  if (patch == 2) return orbit2_varagg_fwd(x, stab, gtab, z, attw, B, V, h, w, H, D, stream);
-  rc = patch == 1 ? varagg_fwd_launch_p<1, false>(x, stab, gtab, z, attw, B, V, h, w, H, D, (hipStream_t)stream)
-                  : varagg_fwd_launch_p<4, false>(x, stab, gtab, z, attw, B, V, h, w, H, D, (hipStream_t)stream);
-  if (rc) return rc;
-  O2_CHECK_LAUNCH();
-  return O2_OK;
+  return va_forward(patch, false, x, stab, gtab, z, attw, B, V, h, w, H, D, stream);
 }
 
 extern "C" int orbit2_varagg_fwd_f32_p(const float* x, const float* stab, const float* gtab, float* z, float* attw, int B,
                                        int V, int h, int w, int patch, int H, int D, void* stream) {
   if (!x || !stab || !gtab || !z) return O2_ERR_ARG;              // attw may be NULL
-  int rc = va_check(B, V, h, w, H, D, patch);
-  if (rc) return rc;
-  if (patch == 2) return orbit2_varagg_fwd_f32(x, stab, gtab, z, attw, B, V, h, w, H, D, stream);
-  rc = patch == 1 ? varagg_fwd_launch_p<1, true>(x, stab, gtab, z, attw, B, V, h, w, H, D, (hipStream_t)stream)
-                  : varagg_fwd_launch_p<4, true>(x, stab, gtab, z, attw, B, V, h, w, H, D, (hipStream_t)stream);
-  if (rc) return rc;
-  O2_CHECK_LAUNCH();
-  return O2_OK;
+  return va_forward(patch, true, x, stab, gtab, z, attw, B, V, h, w, H, D, stream);
 }
 
-// whether orbit2_varagg_bwd_p serves the shape at patch != 2: valid arguments, token count in int range, LDS within a CU's
-static bool varagg_bwd_p_served(int B, int V, int h, int w, int patch, int H, int D) {
-  if (va_check(B, V, h, w, H, D, patch)) return false;
-  if ((int64_t)B * (h / patch) * (w / patch) >= (1ll << 31) - 64) return false;
-  return va_ds_lds(patch, V, H) <= (size_t)VA_LDS_LIMIT;
-}
-
-extern "C" int64_t orbit2_varagg_bwd_p_ws_floats(int B, int V, int h, int w, int patch, int H, int D) {
-  if (patch == 2) return orbit2_varagg_bwd_ws_floats(B, V, h, w, H, D);
-  if (!varagg_bwd_p_served(B, V, h, w, patch, H, D)) return 0;
-  const int64_t ntok = (int64_t)B * (h / patch) * (w / patch);
-  const int64_t C = patch * patch + 1;
-  return ntok * H * V + (int64_t)varagg_tabgrad_splits((int)ntok, V, nullptr) * ((int64_t)H * V * C + (int64_t)V * C * D);
-}
-
-extern "C" int orbit2_varagg_bwd_p_is_fixed_order(int B, int V, int h, int w, int patch, int H, int D) {
-  if (patch == 2) return orbit2_varagg_bwd_is_fixed_order(B, V, h, w, H, D);
-  return varagg_bwd_p_served(B, V, h, w, patch, H, D) ? 1 : 0;     // the only path at patch 1 / 4 is the fixed-order one
+extern "C" int orbit2_varagg_bwd(const float* x, const float* gtab, const float* attw, const void* dz, float* dstab,
+                                 float* dgtab, int B, int V, int h, int w, int H, int D, float* ws, void* stream) {
+  if (!x || !gtab || !attw || !dz || !dstab || !dgtab || !ws) return O2_ERR_ARG;
+  return va_backward(2, x, gtab, attw, dz, dstab, dgtab, B, V, h, w, H, D, ws, stream);
 }
 
 extern "C" int orbit2_varagg_bwd_p(const float* x, const float* gtab, const float* attw, const void* dz, float* dstab,
                                    float* dgtab, int B, int V, int h, int w, int patch, int H, int D, float* ws, void* stream) {
   if (!x || !gtab || !attw || !dz || !dstab || !dgtab || !ws) return O2_ERR_ARG;
-  int rc = va_check(B, V, h, w, H, D, patch);
-  if (rc) return rc;
-  if (patch == 2) return orbit2_varagg_bwd(x, gtab, attw, dz, dstab, dgtab, B, V, h, w, H, D, ws, stream);
-  if (!varagg_bwd_p_served(B, V, h, w, patch, H, D)) return O2_ERR_UNSUPPORTED;
-  const int ntok = B * (h / patch) * (w / patch);
-  if (patch == 1) varagg_bwd_launch_p<1>(x, gtab, attw, dz, dstab, dgtab, B, V, h, w, H, D, ntok, ws, (hipStream_t)stream);
-  else varagg_bwd_launch_p<4>(x, gtab, attw, dz, dstab, dgtab, B, V, h, w, H, D, ntok, ws, (hipStream_t)stream);
-  O2_CHECK_LAUNCH();
-  return O2_OK;
+  return va_backward(patch, x, gtab, attw, dz, dstab, dgtab, B, V, h, w, H, D, ws, stream);
+}
+
+extern "C" int64_t orbit2_varagg_bwd_ws_floats(int B, int V, int h, int w, int H, int D) {
+  return va_backward_ws_floats(2, B, V, h, w, H, D);
+}
+extern "C" int64_t orbit2_varagg_bwd_p_ws_floats(int B, int V, int h, int w, int patch, int H, int D) {
+  return va_backward_ws_floats(patch, B, V, h, w, H, D);
+}
+extern "C" int orbit2_varagg_bwd_is_fixed_order(int B, int V, int h, int w, int H, int D) {
+  return va_backward_is_fixed_order(2, B, V, h, w, H, D);
+}
+extern "C" int orbit2_varagg_bwd_p_is_fixed_order(int B, int V, int h, int w, int patch, int H, int D) {
+  return va_backward_is_fixed_order(patch, B, V, h, w, H, D);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -71,6 +71,8 @@ KCASES = {
     "p4_8tok_v30": (256, 2, 30, (8, 16), 1, 4),            # fewer tokens than one workgroup
     "p1_45tok_dh16": (64, 4, 5, (3, 5), 3, 1),             # token grid 3 x 5, 45 tokens
     "p1_64tok_dh64": (256, 4, 23, (4, 8), 2, 1),           # four full workgroups
+    "p2_45tok_dh64": (256, 4, 23, (6, 10), 3, 2),          # 45 tokens = 2 x 16 + 13 = 32 + 13: partial last workgroup and MFMA chunk
+    "p2_8tok_dh128": (384, 3, 7, (4, 8), 1, 2),            # fewer tokens than one workgroup and than one MFMA chunk
 }
 
 
@@ -193,7 +195,7 @@ def test_patch_two_through_the_new_entries_is_the_old_call(hip, D, heads, V, hw)
         assert torch.equal(a, b), name
 
 
-@pytest.mark.parametrize("name", ["p4_45tok_dh64", "p1_45tok_dh16"])
+@pytest.mark.parametrize("name", ["p4_45tok_dh64", "p1_45tok_dh16", "p2_45tok_dh64"])
 def test_outputs_accumulate_and_guard_rows_stay_untouched(hip, name):
     """dstab / dgtab are `+=` (buffers pre-filled with a constant come back as constant + gradient); z, the fp32 z and attw
     allocated with guard rows behind the last token keep them (45 tokens: the last workgroup is partial)"""

@@ -1,7 +1,7 @@
 """Same-box, same-process A/B of two builds of the loss kernels (csrc/ssim.hip, csrc/lpips.hip):
     tools/ab_build.sh <git-rev> <name>;   on the GPU box:  python tools/loss_lib_ab.py orbit-2_amd/lib/alt/<name>.so [other.so]
 loads the working-tree library (or other.so in its place: an A/A run of two builds of one revision) and the other build (of the
-same ABI version: _hip.load) side by side, calls every entry of the two files in both and prints one line per case, then a summary.
+same ABI version: _hip.load) side by side (tools/lib_ab.py: the loading, the guarded buffers, the timing and the summary), calls every entry of the two files in both and prints one line per case, then a summary.
 Cases, all taken from the test modules:
   orbit2_ssim (sums and map)   tests/test_ssim_gpu.py's 7 x 7, the two thin bands, 39 x 71 against a 41 x 72 target and the four seam
                                shapes, at offsets 0 and 280, lat_w off and on, the range found and given;
@@ -20,71 +20,15 @@ Then the kernels are timed one by one, both builds interleaved, the median of 5 
 gap of the medians: orbit2_ssim (sums; sums + map) and the VJP at tools/ssim_bench.py's [16, 3, 512, 1024]; every kernel of
 lpips.hip at the largest VGG stage it serves for sixteen [3, 128, 256] images (8 predictions + 8 targets).  The timed lines are compared by the same rules (at [16, 3, 512, 1024], where the float64 oracle
 would take minutes, the magnitudes come from the working-tree build's own sums and map).  Exit status 1 if a rule is broken."""
-import itertools, os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "orbit-2_amd")]
+import itertools
 import numpy as np
 import torch
-from climate_learn import _hip
+from lib_ab import GUARD, P, S, _hip, bitwise, count, guarded, libs, ok, summary, tally
 from tests import lpips_ref as L, ssim_loss_ref as V, test_ssim_gpu as TS
 
-libs = {"alt": _hip.load(os.path.abspath(sys.argv[1])),
-        "tree": _hip.load(os.path.abspath(sys.argv[2])) if len(sys.argv) > 2 else _hip.lib()}
-P = lambda t: None if t is None else t.data_ptr()
-S = lambda: torch.cuda.current_stream().cuda_stream
 dev = lambda v, dtype=np.float32: None if v is None else torch.as_tensor(np.asarray(v, dtype)).cuda()
 bf = lambda t: None if t is None else t.to(torch.bfloat16).cuda()
-ok = lambda rc: rc == 0 or sys.exit("rc = %d" % rc)
-GUARD = 64
-BITS = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float64: torch.int64}
-count = {}                                                                   # kind -> [lines, lines that pass]
 multi_equal = 0
-gaps = []
-
-
-def t(f, n=4):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n): f()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n
-med = lambda v: sorted(v)[len(v) // 2]
-
-
-def timed(run, outs):
-    ms = {k: [] for k in libs}
-    for _ in range(5):
-        for k, lib in libs.items(): ms[k].append(t(lambda: run(lib, outs[k])))
-    gap = med(ms["tree"]) / med(ms["alt"]) - 1
-    return gap, "   alt %8.4f ms | tree %8.4f ms (%+.1f %%)" % (med(ms["alt"]), med(ms["tree"]), 100 * gap)
-
-
-def tally(kind, line, passed, run=None, outs=None):
-    count.setdefault(kind, [0, 0])
-    count[kind][0] += 1; count[kind][1] += bool(passed)
-    if run is not None:
-        gap, text = timed(run, outs); gaps.append((gap, line.split(":")[0])); line += text
-    print(line, flush=True)
-
-
-def guarded(n, dtype, lead=GUARD, prefill=None):
-    """per build: a NaN-filled buffer of lead + n + GUARD elements (the n in the middle prefilled where the entry adds)"""
-    bufs = {k: torch.full((lead + n + GUARD,), float("nan"), dtype=dtype, device="cuda") for k in libs}
-    if prefill is not None:
-        for b in bufs.values(): b[lead:lead + n] = prefill
-    return bufs
-
-
-def bitwise(kind, tag, call, n, dtype, lead=GUARD, prefill=None, timing=False):
-    """call(lib, address of the destination) in both builds; the whole buffers bit for bit, and the destination was written"""
-    bufs = guarded(n, dtype, lead, prefill)
-    run = lambda lib, b: ok(call(lib, b.data_ptr() + lead * b.element_size()))
-    for k, lib in libs.items(): run(lib, bufs[k])
-    torch.cuda.synchronize()
-    eq = torch.equal(bufs["tree"].view(BITS[dtype]), bufs["alt"].view(BITS[dtype])) \
-        and not bool(torch.isnan(bufs["tree"][lead:lead + n]).any())
-    tally(kind, "%-9s %s: bitwise equal %s" % (kind, tag, eq), eq, run if timing else None, bufs)
-    return bufs["tree"][lead:lead + n]
 
 
 # ---- csrc/ssim.hip ---------------------------------------------------------------------------------------------------------------
@@ -273,11 +217,7 @@ def main():
     vjp_cases()
     lpips_cases()
     timed_cases()
-    worst = max(gaps, key=lambda v: abs(v[0]))
-    print("%d lines; %s; %d of the several-tile lines also bitwise equal; gaps of the medians in percent %s; largest %+.1f %% (%s)"
-          % (sum(v[0] for v in count.values()), "; ".join("%s: %d of %d" % (k, v[1], v[0]) for k, v in count.items()),
-             multi_equal, " ".join("%+.1f" % (100 * v[0]) for v in gaps), 100 * worst[0], worst[1]))
-    sys.exit(any(v[0] != v[1] for v in count.values()))
+    summary("%d of the several-tile lines also bitwise equal" % multi_equal)
 
 
 main()
