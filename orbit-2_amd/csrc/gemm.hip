@@ -22,10 +22,11 @@ constexpr int TILE_BYTES = 128 * 64 * 2;  // 16 KiB per operand per stage
 // 16 zero bytes every lane may fetch: the source of LDS-DMA pieces that lie past the end of the contraction (K tail)
 __device__ __attribute__((aligned(16))) const unsigned int o2_zero16[4] = {0u, 0u, 0u, 0u};
 
-template <bool KC, int NP = 4>   // NP pieces per wave: 4 = a 128-row tile; 2 = the 64-row tile of a K-contiguous operand
+template <bool KC, int NP = 4>   // NP pieces per wave: 4 = a 128-row tile of 4 waves; 2 = the 64-row tile of a K-contiguous operand
+                                 // (4 waves), or a whole unit of the 8-phase kernel (8 waves: stage_unit4)
 __device__ __forceinline__ void stage_tile(const bf16_t* __restrict__ G, int ld, int r0, int rmax, int k0, int kmax,
                                            char* tile, int wave, int lane) {
-  static_assert(NP == 4 || KC, "the 64-row tile exists for K-contiguous operands only");
+  static_assert(NP == 4 || NP == 2, "16 pieces of 1 KiB over 4 waves, or 8 pieces (64 rows) over 4 waves = 16 over 8 waves");
   const bool tail = k0 + BK > kmax;   // wave-uniform: only the last k-step of a ragged K pays the per-lane redirect
 #pragma unroll
   for (int t = 0; t < NP; ++t) {
@@ -328,8 +329,7 @@ __device__ __forceinline__ int xcd_tile_id() { return o2_xcd_range_id((int)block
 // Infinity Cache runs 13 % faster at the same MFMA-busy share).  Bijective for any grid size.
 // (both walks are o2_xcd_range_id / o2_xcd_round_id of tail_queue.h; nwg: the workgroups that walk statically -- the grid, or the
 // static part of a launch with a tail queue)
-__device__ __forceinline__ int xcd_round_tile_id(int b, int nwg) { return o2_xcd_round_id(b, nwg); }
-__device__ __forceinline__ int xcd_round_tile_id() { return xcd_round_tile_id((int)blockIdx.x, (int)gridDim.x); }
+__device__ __forceinline__ int w4_tile_id(int b, int nwg) { return o2_xcd_round_id(b, nwg); }
 // Start barrier of a round's XCD cohort (long contractions only: the weight-gradient launch, 2048 K-tiles per tile).  Within a
 // round the 32 workgroups of an XCD keep step by themselves -- same instruction stream, same clock -- and fetch every strip
 // K-tile ONCE beyond L2 (profiles/r06_l2_share_probe.txt: one round = 1.00-1.01 x the ideal bytes at any K).  What breaks the
@@ -377,11 +377,18 @@ __device__ __forceinline__ const unsigned int* w4_cohort_start(int& n_out, int n
   return nullptr;
 }
 
-#ifndef O2_W4_WALK
-#define O2_W4_WALK 1        // 1: round-major ids for the 4-wave kernels; 0: the contiguous-range-per-XCD ids of rounds 2-5 (A/B builds)
-#endif
-__device__ __forceinline__ int w4_tile_id() { return O2_W4_WALK ? xcd_round_tile_id() : xcd_tile_id(); }
-__device__ __forceinline__ int w4_tile_id(int b, int nwg) { return O2_W4_WALK ? xcd_round_tile_id(b, nwg) : o2_xcd_range_id(b, nwg); }
+// The tile walk of every family: ids walk groups of GROUP tile-rows (the major index), the major index fastest inside a group, so
+// neighbouring ids share panels; *a = the major tile index, *b = the minor one.  The 4-wave kernel walks wide problems with columns
+// as the major index (gemm256w_tile)
+template <int GROUP>
+__device__ __forceinline__ void tile_walk(int id, int t_major, int t_minor, int* a, int* b) {
+  const int per_group = GROUP * t_minor;
+  const int grp = id / per_group;
+  const int first = grp * GROUP;
+  const int gsz = (t_major - first) < GROUP ? (t_major - first) : GROUP;
+  *a = first + (id % per_group) % gsz;
+  *b = (id % per_group) / gsz;
+}
 
 // one 128x128 output tile (tile `id` of the problem; tiles are walked in groups of 8 tile-rows so neighbours
 // share panels)
@@ -398,13 +405,8 @@ __device__ __forceinline__ void gemm128_tile(const bf16_t* __restrict__ A, const
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  constexpr int GROUP = 8 * (128 / MT);
-  const int per_group = GROUP * tiles_n;
-  const int grp = id / per_group;
-  const int first_m = grp * GROUP;
-  const int gsz = (tiles_m - first_m) < GROUP ? (tiles_m - first_m) : GROUP;
-  const int tm = first_m + (id % per_group) % gsz;
-  const int tn = (id % per_group) / gsz;
+  int tm, tn;
+  tile_walk<8 * (128 / MT)>(id, tiles_m, tiles_n, &tm, &tn);
   const int m0 = tm * MT, n0 = tn * BN;
 
   f32x4 acc[FI][4];
@@ -497,10 +499,8 @@ template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(256, 2) void gemm128_grouped_kernel(GArgs g) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE_BYTES];
   const int id = xcd_tile_id();
-  int pi = 0;
-  while (pi + 1 < g.n && id >= g.p[pi].tile_end) ++pi;
-  const int first = pi ? g.p[pi - 1].tile_end : 0;
-  const GProb& P = g.p[pi];
+  int first;
+  const GProb& P = g.p[o2_group_problem(g, id, first)];
   const Epi epi = P.epi;
   gemm128_tile<A_KC, B_KC>(P.A, P.B, P.M, P.N, P.K, P.lda, P.ldb, P.tiles_m, P.tiles_n, epi, id - first, smem);
 }
@@ -613,40 +613,11 @@ constexpr int BM2 = 256, BN2 = 256;
 constexpr int BK3 = 64;
 constexpr int UNIT3 = 128 * 64 * 2;   // 16 KiB
 
-__device__ __forceinline__ bf16x8 read_frag3(const char* unit, int ubase, int kk, int lane) {
-  const int u = ubase + (lane & 15);
-  const int c = kk * 4 + (lane >> 4);
-  return *reinterpret_cast<const bf16x8*>(unit + u * 128 + ((c ^ (u & 7)) << 4));
-}
-
+// unit h of an operand whose tile starts at row / column r0: 8 waves x 2 pieces, stage_tile's addresses, whole K-tiles (no K tail)
 template <bool KC>
 __device__ __forceinline__ void stage_unit4(const bf16_t* __restrict__ G, int ld, int r0, int rmax, int k0, int h,
                                             char* unit, int wave, int lane) {
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int i = wave * 2 + t;               // 1-KiB piece 0..15 of the unit
-    if (KC) {
-      const int u = i * 8 + (lane >> 3);
-      const int chunk = (lane & 7) ^ (u & 7);
-      int gr = r0 + h * 128 + u;
-      gr = gr < rmax ? gr : rmax - 1;
-      glds16(G + (size_t)gr * ld + k0 + chunk * 8, unit + i * 1024);
-    } else {
-      const int krow = i * 4 + (lane >> 4);
-      const int cp = lane & 15;
-      const int sw = (krow & 3) | (((krow >> 3) & 1) << 2);
-      const int chunk = ((((cp >> 1) ^ sw)) << 1) | (cp & 1);
-      int col = r0 + h * 128 + chunk * 8;
-      col = col <= rmax - 8 ? col : rmax - 8;
-      glds16(G + (size_t)(k0 + krow) * ld + col, unit + i * 1024);
-    }
-  }
-}
-
-template <bool KC>
-__device__ __forceinline__ bf16x8 read_frag4(const char* unit, int ubase, int kk, int lane) {
-  if (KC) return read_frag3(unit, ubase, kk, lane);
-  return read_frag<false>(unit, ubase, kk, lane);
+  stage_tile<KC, 2>(G, ld, r0 + h * 128, rmax, k0, k0 + BK, unit, wave, lane);
 }
 
 template <bool A_KC, bool B_KC>
@@ -657,13 +628,8 @@ __device__ __forceinline__ void gemm256t_tile(const bf16_t* __restrict__ A, cons
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
-  constexpr int GROUP = 4;                       // an XCD's 32 concurrent tiles: 4 tile rows x 8 tile columns
-  const int per_group = GROUP * tiles_n;
-  const int grp = id / per_group;
-  const int first_m = grp * GROUP;
-  const int gsz = (tiles_m - first_m) < GROUP ? (tiles_m - first_m) : GROUP;
-  const int tm = first_m + (id % per_group) % gsz;
-  const int tn = (id % per_group) / gsz;
+  int tm, tn;
+  tile_walk<4>(id, tiles_m, tiles_n, &tm, &tn);  // an XCD's 32 concurrent tiles: 4 tile rows x 8 tile columns
   const int m0 = tm * BM2, n0 = tn * BN2;
 
   f32x4 acc[8][4];
@@ -703,12 +669,12 @@ __device__ __forceinline__ void gemm256t_tile(const bf16_t* __restrict__ A, cons
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) fb0[j][kk] = read_frag4<B_KC>(ub + 2 * UNIT3, wn * 32 + j * 16, kk, lane);
+      for (int kk = 0; kk < 2; ++kk) fb0[j][kk] = read_frag<B_KC>(ub + 2 * UNIT3, wn * 32 + j * 16, kk, lane);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) fa[i][kk] = read_frag4<A_KC>(ub, wm * 64 + i * 16, kk, lane);
+      for (int kk = 0; kk < 2; ++kk) fa[i][kk] = read_frag<A_KC>(ub, wm * 64 + i * 16, kk, lane);
     __builtin_amdgcn_sched_barrier(0);
     // LDS reads return in order: all but the A reads (8 ds_read_b128, or 16 transposing reads -- 15 is the counter's
     // largest encodable value) have landed = every B-nh0 read, the unit that p1 re-fills
@@ -726,7 +692,7 @@ __device__ __forceinline__ void gemm256t_tile(const bf16_t* __restrict__ A, cons
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) fb1[j][kk] = read_frag4<B_KC>(ub + 3 * UNIT3, wn * 32 + j * 16, kk, lane);
+      for (int kk = 0; kk < 2; ++kk) fb1[j][kk] = read_frag<B_KC>(ub + 3 * UNIT3, wn * 32 + j * 16, kk, lane);
     __builtin_amdgcn_sched_barrier(0);
     O2_SEG(tL)
     __builtin_amdgcn_s_barrier();
@@ -741,7 +707,7 @@ __device__ __forceinline__ void gemm256t_tile(const bf16_t* __restrict__ A, cons
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) fa[i][kk] = read_frag4<A_KC>(ub + UNIT3, wm * 64 + i * 16, kk, lane);
+      for (int kk = 0; kk < 2; ++kk) fa[i][kk] = read_frag<A_KC>(ub + UNIT3, wm * 64 + i * 16, kk, lane);
     __builtin_amdgcn_sched_barrier(0);
     O2_SEG(tL)
     __builtin_amdgcn_s_barrier();
@@ -789,10 +755,8 @@ template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(512, 2) void gemm256t_grouped_kernel(GArgs g) {
   __shared__ __attribute__((aligned(16))) char smem[8 * UNIT3];
   const int id = xcd_tile_id();
-  int pi = 0;
-  while (pi + 1 < g.n && id >= g.p[pi].tile_end) ++pi;
-  const int first = pi ? g.p[pi - 1].tile_end : 0;
-  const GProb& P = g.p[pi];
+  int first;
+  const GProb& P = g.p[o2_group_problem(g, id, first)];
   const Epi epi = P.epi;
   gemm256t_tile<A_KC, B_KC>(P.A, P.B, P.M, P.N, P.K, P.lda, P.ldb, P.tiles_m, P.tiles_n, epi, id - first, smem);
 }
@@ -834,6 +798,23 @@ extern "C" int orbit2_debug_read_w4_trace(unsigned long long* host_dst, int n) {
 // reads), and leave it row by row: a lane owns 8 consecutive n of a row, 32 lanes one 512-byte row segment, so every
 // epilogue load and store is a whole-line dwordx4 -- and the epilogue code (every runtime option of Epi) exists ONCE, in
 // a loop, instead of once per accumulator block (the unrolled per-block form of the 8-wave kernel is 100+ KB of code).
+// image row lr (0..127) of pass hh -> output row m; the two swizzled 16-byte reads of a lane's 8 values (columns 8 q .. 8 q + 7)
+// of an image row; one pass of the accumulators into the image
+__device__ __forceinline__ int w4_row_m(int m0, int hh, int lr) { return m0 + (lr >> 6) * 128 + hh * 64 + (lr & 63); }
+__device__ __forceinline__ void w4_image_row8(const char* smem, int lr, int q, float* v) {
+  const char* row = smem + lr * 1024;
+  const int sw = lr & 7;
+  const f32x4 lo = *reinterpret_cast<const f32x4*>(row + (((2 * q) ^ sw) << 4));
+  const f32x4 hi = *reinterpret_cast<const f32x4*>(row + (((2 * q + 1) ^ sw) << 4));
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { v[k] = lo[k]; v[4 + k] = hi[k]; }
+}
+__device__ __forceinline__ void w4_stage_image(int hh, uint32_t be, uint32_t bo) {
+  __syncthreads();                                // pass 0: every wave's last LDS-DMA pieces have landed, nobody reads the stages
+  if (hh == 0) asm volatile(O2_W4_CSTAGE0 : : [be] "v"(be), [bo] "v"(bo) : "memory");
+  else asm volatile(O2_W4_CSTAGE1 : : [be] "v"(be), [bo] "v"(bo) : "memory");
+  __syncthreads();
+}
 __device__ __forceinline__ void w4_epilogue_rows(const Epi& epi, const char* smem, int m0, int n0, int hh, int tid) {
   const int q = tid & 31;
   const int n = n0 + 8 * q;
@@ -846,21 +827,17 @@ __device__ __forceinline__ void w4_epilogue_rows(const Epi& epi, const char* sme
     unpack8(b, bias8);
   }
   // lean path (bias / column scale only; whole tiles by construction of this kernel): per 8 values two LDS reads, the adds
-  // and multiplies of epi8_finish in its order (bit-identical), four conversions and one 16-byte store
-  const bool lean = !epi.out_fp32 && !epi.save_pre && epi.act == 0 && !epi.residual && epi.thr == 0 && !epi.dgelu_pre &&
-                    !epi.rowscale && epi.beta == 0.f && !epi.mul;
-  if (lean) {
+  // and multiplies of epi8_finish in its order (bit-identical), four conversions and one 16-byte store.  gemm256w_tile decides
+  // `lean` and calls this function for its lean and its fp32 epilogues only: bf16 output here means lean
+  if (!epi.out_fp32) {
     const float mul = n < epi.colscale_n ? epi.colscale : 1.0f;
     const int r8 = tid >> 5;
     bf16_t* cp = reinterpret_cast<bf16_t*>(epi.C) + (size_t)(m0 + hh * 64 + r8) * epi.ldc + n;
     const size_t step8 = (size_t)8 * epi.ldc;
-    const char* lp = smem + r8 * 1024;
-    const uint32_t c0 = (uint32_t)(((2 * q) ^ r8) << 4), c1 = (uint32_t)(((2 * q + 1) ^ r8) << 4);   // (it*8 + r8) & 7 == r8
 #pragma unroll      // all 16 rows in flight: +0.6 % on the K = 3072 GEMMs over unroll 4 (profiles/r04_gemm_lean_unroll.txt), same bits
     for (int it = 0; it < 16; ++it) {
-      const f32x4 lo = *reinterpret_cast<const f32x4*>(lp + it * 8192 + c0);
-      const f32x4 hi = *reinterpret_cast<const f32x4*>(lp + it * 8192 + c1);
-      float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      float v[8];
+      w4_image_row8(smem, it * 8 + r8, q, v);
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = (v[k] + bias8[k]) * mul;
       *reinterpret_cast<u32x4*>(cp + (size_t)(it + (it >= 8 ? 8 : 0)) * step8) = pack8(v);
@@ -871,7 +848,7 @@ __device__ __forceinline__ void w4_epilogue_rows(const Epi& epi, const char* sme
 #pragma unroll 1
     for (int it = 0; it < 16; ++it) {
       const int lr = it * 8 + (tid >> 5);                            // image row 0..127
-      const int m = m0 + (lr >> 6) * 128 + hh * 64 + (lr & 63);
+      const int m = w4_row_m(m0, hh, lr);
       const char* row = smem + lr * 1024;
       const int sw = lr & 7;
       epilogue4(epi, m, n, *reinterpret_cast<const f32x4*>(row + (((2 * q) ^ sw) << 4)));
@@ -885,13 +862,9 @@ __device__ __forceinline__ void w4_epilogue_rows(const Epi& epi, const char* sme
 // loads (residual / pre-activation / old C) two steps ahead of their use -- the first two steps' loads are issued BEFORE the
 // accumulators are staged through LDS: with one wave per SIMD nobody else hides their latency (at one step ahead the
 // epilogue ran at the ~2 TB/s its 32 KB in flight per CU allow)
-__device__ __forceinline__ int w4_row_m(int m0, int hh, int tid, int it, int k) {
-  const int lr = (it * 2 + k) * 8 + (tid >> 5);
-  return m0 + (lr >> 6) * 128 + hh * 64 + (lr & 63);
-}
 __device__ __forceinline__ void w4_generic_load(const Epi& epi, int m0, int n, int hh, int tid, int it, Pre8 (&pq)[2]) {
 #pragma unroll
-  for (int k = 0; k < 2; ++k) epi8_load(epi, w4_row_m(m0, hh, tid, it, k), n, pq[k]);
+  for (int k = 0; k < 2; ++k) epi8_load(epi, w4_row_m(m0, hh, (it * 2 + k) * 8 + (tid >> 5)), n, pq[k]);
 }
 __device__ __forceinline__ void w4_generic_finish(const Epi& epi, const char* smem, int m0, int n, int hh, int tid, int it,
                                                   const float* bias8, const Pre8 (&pq)[2]) {
@@ -899,12 +872,9 @@ __device__ __forceinline__ void w4_generic_finish(const Epi& epi, const char* sm
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int lr = (it * 2 + k) * 8 + (tid >> 5);
-    const char* row = smem + lr * 1024;
-    const int sw = lr & 7;
-    const f32x4 lo = *reinterpret_cast<const f32x4*>(row + (((2 * q) ^ sw) << 4));
-    const f32x4 hi = *reinterpret_cast<const f32x4*>(row + (((2 * q + 1) ^ sw) << 4));
-    float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    epi8_finish(epi, w4_row_m(m0, hh, tid, it, k), n, v, bias8, pq[k]);
+    float v[8];
+    w4_image_row8(smem, lr, q, v);
+    epi8_finish(epi, w4_row_m(m0, hh, lr), n, v, bias8, pq[k]);
   }
 }
 
@@ -947,27 +917,16 @@ __device__ __forceinline__ void gemm256w_tile(const bf16_t* __restrict__ A, cons
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-#ifndef O2_W4_GROUP
-#define O2_W4_GROUP 4
-#endif
-  constexpr int GROUP = O2_W4_GROUP;
+  constexpr int GROUP = 4;
   // ids walk groups of GROUP tile-rows, m fastest: 32 consecutive ids = 4 x 8 tiles (12 panel strips per K-tile for 32 tiles).  A
   // problem that is wider than tall (tiles_n > tiles_m: the fc2 weight gradient, 12 x 48) is walked the other way round, groups of
-  // GROUP tile-columns with n fastest: the 256 consecutive ids of a round (xcd_round_tile_id) then cover ~21 x 12 tiles = 33 strips
+  // GROUP tile-columns with n fastest: the 256 consecutive ids of a round (w4_tile_id) then cover ~21 x 12 tiles = 33 strips
   // instead of 5 x 48 = 53
-#ifndef O2_W4_TWALK
-#define O2_W4_TWALK 1
-#endif
-  const bool tw = O2_W4_TWALK && tiles_n > tiles_m;
-  const int t_major = tw ? tiles_n : tiles_m, t_minor = tw ? tiles_m : tiles_n;
-  const int per_group = GROUP * t_minor;
-  const int grp = id / per_group;
-  const int first_g = grp * GROUP;
-  const int gsz = (t_major - first_g) < GROUP ? (t_major - first_g) : GROUP;
+  const bool tw = tiles_n > tiles_m;
   // (measured and not kept, round 6: the minor index fastest inside 8-wide chunks -- four workgroups dispatched together then hold
   // four different minor strips: the same time, 11 % more bytes fetched; profiles/r06_nfast_ab.txt, r06_w4_trace_nfast.txt)
-  const int t_a = first_g + (id % per_group) % gsz;
-  const int t_b = (id % per_group) / gsz;
+  int t_a, t_b;
+  tile_walk<GROUP>(id, tw ? tiles_n : tiles_m, tw ? tiles_m : tiles_n, &t_a, &t_b);
   const int tm = tw ? t_b : t_a, tn = tw ? t_a : t_b;
   const int m0 = tm * BM2, n0 = tn * BN2;
 
@@ -1123,24 +1082,19 @@ __device__ __forceinline__ void gemm256w_tile(const bf16_t* __restrict__ A, cons
       if (EK == 2 || EK == 3) {
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-          const int lr = g * 8 + r8;
-          const int m = m0 + (lr >> 6) * 128 + hh * 64 + (lr & 63);
+          const int m = w4_row_m(m0, hh, g * 8 + r8);
           ld[g] = EK == 2 ? *reinterpret_cast<const u32x4*>(epi.residual + (size_t)m * epi.ldr + ne)
                           : *reinterpret_cast<const u32x4*>(epi.mul + (size_t)m * epi.ldc + ne);
         }
       }
-      __syncthreads();
-      if (hh == 0) asm volatile(O2_W4_CSTAGE0 : : [be] "v"(be), [bo] "v"(bo) : "memory");
-      else asm volatile(O2_W4_CSTAGE1 : : [be] "v"(be), [bo] "v"(bo) : "memory");
-      __syncthreads();
+      w4_stage_image(hh, be, bo);
 #pragma unroll UNR
       for (int g = 0; g < 16; ++g) {
-        const int lr = g * 8 + r8;                       // (lr & 7) == r8
-        const int m = m0 + (lr >> 6) * 128 + hh * 64 + (lr & 63);
-        const char* row = smem + lr * 1024;
-        const f32x4 lo = *reinterpret_cast<const f32x4*>(row + (((2 * q) ^ r8) << 4));
-        const f32x4 hi = *reinterpret_cast<const f32x4*>(row + (((2 * q + 1) ^ r8) << 4));
-        float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        const int lr = g * 8 + r8;
+        const int m = m0 + (lr >> 6) * 128 + hh * 64 + (lr & 63);   // (w4_row_m written out: through the call the address
+                                                                    // arithmetic of kind 1 is scheduled otherwise)
+        float v[8];
+        w4_image_row8(smem, lr, q, v);
         Pre8 pq;
         if (EK == 2) pq.res = ld[g];
         if (EK == 3) pq.pre = ld[g];
@@ -1179,10 +1133,7 @@ __device__ __forceinline__ void gemm256w_tile(const bf16_t* __restrict__ A, cons
       w4_generic_load(epi, m0, ne, hh, tid, 0, qa);
       w4_generic_load(epi, m0, ne, hh, tid, 1, qb);
     }
-    __syncthreads();                                 // pass 0: every wave's last LDS-DMA pieces have landed, nobody reads the stages
-    if (hh == 0) asm volatile(O2_W4_CSTAGE0 : : [be] "v"(be), [bo] "v"(bo) : "memory");
-    else asm volatile(O2_W4_CSTAGE1 : : [be] "v"(be), [bo] "v"(bo) : "memory");
-    __syncthreads();
+    w4_stage_image(hh, be, bo);
     if (hh == 0) { O2_TS(2); } else { O2_TS(4); }
     if (generic) {
 #pragma unroll 1
@@ -1216,7 +1167,8 @@ __global__ __launch_bounds__(256, 1) void gemm256w_kernel(const bf16_t* __restri
                                                           int tiles_n, Epi epi) {
   __shared__ __attribute__((aligned(16))) char smem[8 * O2_W4_UNIT];
   O2_TQ_TRACE_BEGIN();
-  gemm256w_tile<FORM, STAMP, EK>(A, B, M, N, K, lda, ldb, tiles_m, tiles_n, epi, w4_tile_id(), smem);
+  gemm256w_tile<FORM, STAMP, EK>(A, B, M, N, K, lda, ldb, tiles_m, tiles_n, epi, w4_tile_id((int)blockIdx.x, (int)gridDim.x),
+                                 smem);
   O2_TQ_TRACE_END(o2_tq_trace_gemm, 0);
 }
 
@@ -1253,14 +1205,12 @@ template <int FORM>
 __global__ __launch_bounds__(256, 1) void gemm256w_grouped_kernel(GArgs g) {
   __shared__ __attribute__((aligned(16))) char smem[8 * O2_W4_UNIT];
   O2_TQ_TRACE_BEGIN();
-  const int id = w4_tile_id();
+  const int id = w4_tile_id((int)blockIdx.x, (int)gridDim.x);
   int pace_n = 0;
   const unsigned int* pace_ctr = g.pace ? w4_cohort_start(pace_n, (int)gridDim.x) : nullptr;
   if (g.pace < 2) pace_ctr = nullptr;                                   // pace 1: the start barrier only
-  int pi = 0;
-  while (pi + 1 < g.n && id >= g.p[pi].tile_end) ++pi;
-  const int first = pi ? g.p[pi - 1].tile_end : 0;
-  const GProb& P = g.p[pi];
+  int first;
+  const GProb& P = g.p[o2_group_problem(g, id, first)];
   const Epi epi = P.epi;
   gemm256w_tile<FORM, false>(P.A, P.B, P.M, P.N, P.K, P.lda, P.ldb, P.tiles_m, P.tiles_n, epi, id - first, smem, pace_ctr, pace_n,
                              P.kgate, P.k_per_gate);
@@ -1625,7 +1575,7 @@ static int gemm_group_plan(const orbit2_gemm_args* args, int n, const float* con
     // slowest group's rate, which is what a round takes anyway.  Kept selectable, not default.
     static const int pace_env = [] { const char* e = getenv("ORBIT2_W4_PACE"); return e ? atoi(e) : 1; }();
     // ("more than one round" is about the workgroups that walk statically: all of them, or the ones in front of the tail)
-    g.pace = (O2_W4_WALK && pace_env && kmin >= 512 * BK3 && p.tail.S > 256) ? pace_env : 0;
+    g.pace = (pace_env && kmin >= 512 * BK3 && p.tail.S > 256) ? pace_env : 0;
   }
   return O2_OK;
 }

@@ -217,11 +217,12 @@ def test_gemm_4wave_kernel_takes_whole_tiles_only(hip):
 
 def test_gemm_grouped_4wave_matches_single_launches(hip):
     """a grouped launch of whole-tile problems runs on the 4-wave kernel: equal, bit for bit, to the same problems launched
-    one by one on it (weight-gradient form with a beta-accumulating member, and the forward form)"""
+    one by one on it, in every operand form, with a beta-accumulating member.  (Every member has two K-tiles or more: with a
+    one-K-tile member the plan gives the whole group to the 128-tile kernel.)"""
     g = torch.Generator().manual_seed(78)
-    for a_kc, b_kc in ((False, False), (True, True)):
+    for a_kc, b_kc in ((False, False), (True, True), (True, False), (False, True)):
         probs, refs = [], []
-        for i, (M, N, K) in enumerate([(256, 512, 192), (768, 256, 128), (256, 256, 320), (512, 1024, 64)]):
+        for i, (M, N, K) in enumerate([(256, 512, 192), (768, 256, 128), (256, 256, 320), (512, 1024, 128)]):
             A = bf(torch.randn((M, K) if a_kc else (K, M), generator=g)).cuda()
             B = bf(torch.randn((N, K) if b_kc else (K, N), generator=g)).cuda()
             beta = 1.0 if i == 1 else 0.0
@@ -237,6 +238,34 @@ def test_gemm_grouped_4wave_matches_single_launches(hip):
         torch.cuda.synchronize()
         for pr, ref in zip(probs, refs):
             assert torch.equal(pr[2], ref)
+
+
+@pytest.mark.parametrize("form", ["tn", "nt", "nn", "tt"])
+def test_gemm_grouped_8phase_matches_single_launches(hip, form):
+    """hint 256 on the first problem gives the group to the 8-phase kernel: ragged M and N, two to five K-tiles, a
+    beta-accumulating member; equal, bit for bit, to the same problems launched one by one under hint 256, the single launches
+    within one bf16 rounding (plus that of the accumulated C) of the fp32 product, and the rows behind every output untouched"""
+    g = torch.Generator().manual_seed(79)
+    a_kc, b_kc = form[0] == "n", form[1] == "t"
+    probs, refs = [], []
+    for i, (M, N, K) in enumerate([(264, 520, 128), (256, 256, 192), (520, 264, 128), (256, 512, 64 * 5)]):
+        A = bf(torch.randn((M, K) if a_kc else (K, M), generator=g)).cuda()
+        B = bf(torch.randn((N, K) if b_kc else (K, N), generator=g)).cuda()
+        beta = 1.0 if i == 2 else 0.0
+        c0 = torch.full((M + 8, N), 7.0, dtype=torch.bfloat16, device="cuda")        # 8 guard rows
+        c0[:M] = bf(torch.randn(M, N, generator=g)).cuda()
+        single = c0.clone()
+        hip.gemm(A, B, single, M, N, K, A.shape[1], B.shape[1], N, a_kc=a_kc, b_kc=b_kc, beta=beta, tile=256)
+        out = c0.clone()
+        probs.append((A, B, out, M, N, K, A.shape[1], B.shape[1], N, dict(a_kc=a_kc, b_kc=b_kc, beta=beta, tile=256)))
+        refs.append(single)
+        ref32 = (A.float().cpu() if a_kc else A.float().cpu().t()) @ (B.float().cpu().t() if b_kc else B.float().cpu())
+        assert nerr(single[:M], ref32 + beta * c0[:M].float().cpu()) < 8e-3
+    hip.gemm_grouped(probs)
+    torch.cuda.synchronize()
+    for pr, ref in zip(probs, refs):
+        assert torch.equal(pr[2], ref)
+        assert torch.all(pr[2][pr[3]:] == 7.0) and torch.all(ref[pr[3]:] == 7.0)
 
 
 @pytest.mark.parametrize("tile", [128, 256])
@@ -313,7 +342,7 @@ def test_gemm_ragged_contraction_length(hip, form, K):
     assert nerr(out, A @ B.t()) < 2e-5
 
 
-@pytest.mark.parametrize("form", ["tn", "nt"])
+@pytest.mark.parametrize("form", ["tn", "nt", "nn", "tt"])
 def test_gemm_grouped_matches_single_launches(hip, form):
     """one grouped launch == the same problems launched one by one (same kernel, same tile walk: bit-identical),
     with ragged tile counts and a beta-accumulating member"""

@@ -212,7 +212,7 @@ def test_weight_gradient_group_units():
 
 
 def test_round_major_tile_ids_are_a_bijection():
-    """mirror of csrc/gemm.hip:xcd_round_tile_id (block b runs on XCD b & 7; the 256 blocks of a round take 256 consecutive ids,
+    """mirror of csrc/gemm.hip:w4_tile_id (csrc/tail_queue.h:o2_xcd_round_id; block b runs on XCD b & 7; the 256 blocks of a round take 256 consecutive ids,
     each XCD a consecutive run of them) and of gemm256w_tile's id -> (tm, tn) walk incl. the column-major form of wide problems:
     every tile exactly once for any grid size, a round's ids contiguous, an XCD's ids of a round contiguous"""
     def rid(b, nwg):
