@@ -382,7 +382,7 @@ int orbit2_loss_bwd(const float* pred, const float* target, int Ht, int Wt, cons
 int orbit2_eval_moments(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* clim,
                         double* out, int B, int C, int H, int W, void* stream);
 
-/* ---- missing-data masks (csrc/masked.hip; metrics/functional.py masked_mse / masked_bayesian_tv / rmse(mask=) ...) ------
+/* ---- missing-data masks (csrc/loss.hip; metrics/functional.py masked_mse / masked_bayesian_tv / rmse(mask=) ...) ------
  * A pixel is VALID where the target is finite and the mask (if any) is non-zero:
  *   v[b][c][i][j] = isfinite(target[b][c][i][j]) && (mask == NULL || mask[b * mask_sb + c * mask_sc + i * mask_pitch + j] != 0)
  * mask: bytes, read through its top-left H x W crop; mask_pitch >= W elements between rows; mask_sb / mask_sc the batch and

@@ -1041,7 +1041,7 @@ def eval_moments(pred, target, lat_w=None, clim=None):
     return out
 
 
-# ---- missing-data masks (csrc/masked.hip) --------------------------------------------------------------------------------------
+# ---- missing-data masks (csrc/loss.hip) ----------------------------------------------------------------------------------------
 def _mask_args(mask, strides, pred, target):
     """(mask, row pitch, batch stride, channel stride) of the mask operand: uint8 device bytes whose `strides` =
     (pitch, batch stride, channel stride) address an H x W crop of at least the prediction's size; (None, 0, 0, 0) without one"""

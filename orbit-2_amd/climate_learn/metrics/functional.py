@@ -185,7 +185,7 @@ def ssim_loss(pred, target, var_names: Optional[List[str]] = None, var_weights: 
     return out[-1] if aggregate_only else out
 
 
-# ---- missing data: losses and metrics over the VALID pixels only (csrc/masked.hip) ------------------------------
+# ---- missing data: losses and metrics over the VALID pixels only (csrc/loss.hip) ------------------------------
 # valid = the target is finite there, and the mask (if one is given) is non-zero.  The reference has no such loss
 # (examples/era5_daymet_downscaling.py names `masked_mse` but its metrics package has none) and a `mask` argument on rmse /
 # lat_rmse / acc only.

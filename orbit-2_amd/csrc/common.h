@@ -285,6 +285,9 @@ static inline int grid_for(int64_t work_items, int per_block, int max_blocks = 4
   return (int)g;
 }
 
+// the loop header of a grid-stride sweep by 256-thread workgroups over the n items of a whole tensor: e = this thread's items
+#define O2_GRID_STRIDE(e, n) for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < (n); e += (int64_t)gridDim.x * 256)
+
 #define O2_CHECK_LAUNCH()                                   \
   do {                                                      \
     hipError_t e__ = hipGetLastError();                     \

@@ -1,5 +1,6 @@
+// Ensembles: the all-member scores, then the streamed MC-dropout statistics and the scores of their Gaussian.
 // All-member (non-Gaussian) scores of an ensemble: CRPS, rank histogram, quantile fields (include/orbit2_hip.h:
-// orbit2_ensemble_scores; metrics/functional.py ensemble_*; DESIGN 4.10).
+// orbit2_ensemble_scores; metrics/functional.py ensemble_*).
 //
 // One pixel per lane, consecutive lanes on consecutive pixels: every member load is one coalesced wave access, the N values of
 // a pixel live in registers and are read exactly once.  blockIdx.y = the (b, c) image, grid-stride over its pixels.  The raw
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(256) void ensemble_scores_kernel(const float* __res
   const float fN = (float)N, inv_n = 1.f / fN;
   const float inv_pairs = fair ? 1.f / (fN * (fN - 1.f)) : 1.f / (fN * fN);
   float s[ES_NM] = {0.f, 0.f, 0.f, 0.f};
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < HW; i += gridDim.x * 256) {
+  O2_IMAGE_STRIDE(i, HW) {
     const int y = i / W, x = i - y * W;
     float v[P];
 #pragma unroll
@@ -144,12 +145,95 @@ __global__ __launch_bounds__(256) void ensemble_scores_kernel(const float* __res
   }
 }
 
-template <int P>
-void launch(dim3 grid, hipStream_t s, const float* members, int64_t member_stride, int N, const float* target, int Ht, int Wt,
-            const float* lat_w, double* sums, float* crps_field, int fair, int64_t* hist, uint64_t seed, float* quant,
-            const float* levels, int Q, int64_t field, int H, int W) {
-  hipLaunchKernelGGL(ensemble_scores_kernel<P>, grid, dim3(256), 0, s, members, member_stride, N, target, Ht, Wt, lat_w, sums,
-                     crps_field, fair, reinterpret_cast<unsigned long long*>(hist), seed, quant, levels, Q, field, H, W);
+// ---- MC-dropout ensembles (utils/mc_dropout.py; metrics/functional.py:340-386 gaussian_crps / _spread / _spread_skill_ratio) ----
+// The k-th (1-based) Welford step of the running per-element mean and sum of squared deviations, in place:
+//   d = x - mean;  mean += d / k;  m2 += d * (x - mean)          (k = 1: mean = x, m2 = 0 -- neither is read)
+// so N members of a [B, C, H, W] field leave mean and m2 = (N - 1) * unbiased variance without N fields being held.  A pure
+// stream (12 bytes read, 8 written per element): float4 per lane when the three bases are 16-byte aligned, grid-stride over at
+// most 2048 workgroups, the n % 4 tail (or everything, for unaligned bases) by scalar lanes.
+__device__ __forceinline__ void welford_step(float x, float& mean, float& m2, float kf) {
+  const float d = x - mean;
+  mean += d / kf;
+  m2 = fmaf(d, x - mean, m2);
+}
+
+__global__ __launch_bounds__(256) void ensemble_update_kernel(const float* __restrict__ member, float* __restrict__ mean,
+                                                              float* __restrict__ m2, int64_t n, int64_t n4, int k) {
+  const float kf = (float)k;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nthr = (int64_t)gridDim.x * 256;
+  const f32x4* x4 = reinterpret_cast<const f32x4*>(member);
+  f32x4* mean4 = reinterpret_cast<f32x4*>(mean);
+  f32x4* m24 = reinterpret_cast<f32x4*>(m2);
+  if (k == 1) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = tid; i < n4; i += nthr) {
+      mean4[i] = x4[i];
+      m24[i] = zero;
+    }
+    for (int64_t i = 4 * n4 + tid; i < n; i += nthr) {
+      mean[i] = member[i];
+      m2[i] = 0.f;
+    }
+    return;
+  }
+  for (int64_t i = tid; i < n4; i += nthr) {
+    const f32x4 x = x4[i];
+    f32x4 mu = mean4[i], s = m24[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float mj = mu[j], sj = s[j];
+      welford_step(x[j], mj, sj, kf);
+      mu[j] = mj;
+      s[j] = sj;
+    }
+    mean4[i] = mu;
+    m24[i] = s;
+  }
+  for (int64_t i = 4 * n4 + tid; i < n; i += nthr) {
+    float mu = mean[i], s = m2[i];
+    welford_step(member[i], mu, s, kf);
+    mean[i] = mu;
+    m2[i] = s;
+  }
+}
+
+// Scores of a Gaussian prediction N(mean, std^2) against a target, four sums per (b, c) image (target: top-left crop,
+// w = lat_w[y] or 1), added up by o2_block_sums_add as in orbit2_eval_moments:
+//   0 sum w crps, 1 sum w std^2, 2 sum w (mean - target)^2, 3 sum 1{|target - mean| <= std}
+// crps is the closed form of the Gaussian CRPS, std (z (2 Phi(z) - 1) + 2 phi(z) - 1 / sqrt(pi)) with z = (target - mean) / std
+// (functional.py:353 there has 1 / pi, and cannot be called: see metrics/functional.py:gaussian_crps here).  It is evaluated as
+//   |d| erf(|z| / sqrt 2) + std (2 phi(z) - 1 / sqrt(pi)),  d = target - mean,
+// the same expression with std z = d multiplied out: no product of a huge z with a tiny std, and at std == 0 (constant output
+// channels are copied from the target into every member) it IS the limit |d| -- no NaN, no Inf, and such a point counts as
+// covered only where target == mean.
+constexpr int GS_NM = 4;
+__global__ __launch_bounds__(256) void gaussian_scores_kernel(const float* __restrict__ mean, const float* __restrict__ std_,
+                                                              const float* __restrict__ target, int Ht, int Wt,
+                                                              const float* __restrict__ lat_w, double* __restrict__ out, int H,
+                                                              int W) {
+  const int bc = blockIdx.y;
+  const float* m = mean + (size_t)bc * H * W;
+  const float* sd = std_ + (size_t)bc * H * W;
+  const float* t = target + (size_t)bc * Ht * Wt;
+  float s[GS_NM] = {0.f, 0.f, 0.f, 0.f};
+  O2_IMAGE_STRIDE(i, H * W) {
+    const int y = i / W, x = i - y * W;
+    const float sg = sd[i];
+    const float d = t[(size_t)y * Wt + x] - m[i];
+    const float w = lat_w ? lat_w[y] : 1.f;
+    const float ad = fabsf(d);
+    float crps = ad;
+    if (sg > 0.f) {
+      const float z = ad / sg;                         // may be +inf (a denormal std): erf -> 1, phi -> 0, crps -> |d| - std / sqrt(pi)
+      const float phi = 0.3989422804014327f * expf(-0.5f * z * z);
+      crps = ad * erff(z * 0.70710678118654752f) + sg * (2.f * phi - 0.5641895835477563f);
+    }
+    s[0] += w * crps;
+    s[1] += w * sg * sg;
+    s[2] += w * d * d;
+    s[3] += ad <= sg ? 1.f : 0.f;
+  }
+  o2_block_sums_add(s, out + (size_t)bc * GS_NM);
 }
 }  // namespace
 
@@ -168,15 +252,41 @@ extern "C" int orbit2_ensemble_scores(const float* members, int64_t member_strid
   if (hist && hipMemsetAsync(hist, 0, sizeof(int64_t) * (size_t)B * C * (N + 1), s) != hipSuccess) return O2_ERR_LAUNCH;
   const int cap = o2_image_block_cap(B * C), nblk = (H * W + 255) / 256;       // one pixel per lane and trip
   const dim3 grid(nblk < cap ? nblk : cap, B * C);
-#define ES_LAUNCH(P) \
-  launch<P>(grid, s, members, member_stride, N, target, Ht, Wt, lat_w, sums, crps_field, fair, hist, seed, quant, levels, Q, field, H, W)
-  if (N <= 2) ES_LAUNCH(2);
-  else if (N <= 4) ES_LAUNCH(4);
-  else if (N <= 8) ES_LAUNCH(8);
-  else if (N <= 16) ES_LAUNCH(16);
-  else if (N <= 32) ES_LAUNCH(32);
-  else ES_LAUNCH(64);
-#undef ES_LAUNCH
+  auto launch = [&](auto p) {                                                  // p = the padded size
+    hipLaunchKernelGGL(ensemble_scores_kernel<decltype(p)::value>, grid, dim3(256), 0, s, members, member_stride, N, target, Ht, Wt,
+                       lat_w, sums, crps_field, fair, reinterpret_cast<unsigned long long*>(hist), seed, quant, levels, Q, field, H, W);
+  };
+  if (N <= 2) launch(o2_int<2>{});
+  else if (N <= 4) launch(o2_int<4>{});
+  else if (N <= 8) launch(o2_int<8>{});
+  else if (N <= 16) launch(o2_int<16>{});
+  else if (N <= 32) launch(o2_int<32>{});
+  else launch(o2_int<64>{});
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+extern "C" int orbit2_ensemble_update(const float* member, float* mean, float* m2, int64_t n, int k, void* stream) {
+  if (!member || !mean || !m2 || n <= 0 || k < 1 || member == mean || member == m2 || mean == m2) return O2_ERR_ARG;
+  const bool aligned = (((uintptr_t)member | (uintptr_t)mean | (uintptr_t)m2) & 15) == 0;
+  const int64_t n4 = aligned ? n / 4 : 0;
+  const int64_t lanes = n4 > 0 ? n4 : n;
+  int64_t nblk = (lanes + 255) / 256;
+  if (nblk > 2048) nblk = 2048;
+  hipLaunchKernelGGL(ensemble_update_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, member, mean, m2, n, n4,
+                     k);
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+extern "C" int orbit2_gaussian_scores(const float* mean, const float* std_, const float* target, int Ht, int Wt,
+                                      const float* lat_w, double* out, int B, int C, int H, int W, void* stream) {
+  if (!o2_pair_ok(mean, target, B, C, H, W, Ht, Wt) || !std_ || !out) return O2_ERR_ARG;
+  if ((int64_t)B * C > 65535 || (int64_t)H * W > (int64_t)INT32_MAX - 64 * 256) return O2_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(out, 0, sizeof(double) * (size_t)B * C * GS_NM, s) != hipSuccess) return O2_ERR_LAUNCH;
+  hipLaunchKernelGGL(gaussian_scores_kernel, dim3(o2_image_blocks((int64_t)H * W), B * C), dim3(256), 0, s, mean, std_, target, Ht,
+                     Wt, lat_w, out, H, W);
   O2_CHECK_LAUNCH();
   return O2_OK;
 }

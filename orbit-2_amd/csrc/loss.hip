@@ -1,5 +1,6 @@
-// Missing-data masks: the training losses (mse, bayesian_tv) and the evaluation sums over the VALID pixels only (gfx950).
-// include/orbit2_hip.h: orbit2_masked_*; metrics/functional.py: masked_mse / masked_bayesian_tv / rmse(mask=) ...; DESIGN 4.10d.
+// The fused training losses (mse / bayesian_tv / image gradient with latitude and variable weights) and the twelve evaluation
+// moments, each plain and over the VALID pixels only (gfx950).  include/orbit2_hip.h: orbit2_loss_*, orbit2_eval_moments,
+// orbit2_masked_*; metrics/functional.py; DESIGN 4.10d.  orbit2_loss_bwd hands kind ORBIT2_LOSS_SSIM_VJP on to ssim.hip.
 //
 //   valid(b,c,i,j) = isfinite(target[b,c,i,j]) and (mask == NULL or mask[b,c,i,j] != 0)
 //
@@ -14,6 +15,180 @@
 #include "../../include/orbit2_hip.h"
 
 namespace {
+// ---- shared by the plain and the masked kernels -------------------------------------------------------------------------------
+// flat index over [B][C][H][Wq] -> its four coordinates (Wq = W, or the four-pixel items of a row)
+__device__ __forceinline__ void plane_of(int64_t q, int C, int H, int Wq, int& b, int& c, int& i, int& j) {
+  j = (int)(q % Wq); q /= Wq;
+  i = (int)(q % H); q /= H;
+  c = (int)(q % C); b = (int)(q / C);
+}
+
+// the epilogue of a forward workgroup (256 threads, all of them call it): its sums of a and of b, one LDS word per wave and
+// value, the four waves added by thread 0 in the order w0 + w1 + w2 + w3, stored in the workgroup's slot of the plane's partials
+template <class T>
+__device__ __forceinline__ void block_part2(float a, T b, float* __restrict__ part_a, T* __restrict__ part_b, int plane) {
+  a = wave_sum(a);
+  if constexpr (std::is_same<T, int>::value) b = wave_sum_i(b); else b = wave_sum(b);
+  __shared__ float sw[4];
+  __shared__ T sb[4];
+  if ((threadIdx.x & 63) == 0) { sw[threadIdx.x >> 6] = a; sb[threadIdx.x >> 6] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part_a[(size_t)plane * gridDim.x + blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
+    part_b[(size_t)plane * gridDim.x + blockIdx.x] = sb[0] + sb[1] + sb[2] + sb[3];
+  }
+}
+
+// one wave: the sum of channel c's B * nblk partials (COUNT: and of their counts; a channel may hold more than 2^31 pixels)
+template <bool COUNT>
+__device__ __forceinline__ float channel_part_sum(const float* __restrict__ part, int nblk, int B, int C, int c,
+                                                  const int* __restrict__ partn = nullptr, int64_t* count = nullptr) {
+  float s = 0.f;
+  int64_t n = 0;
+  for (int e = threadIdx.x; e < B * nblk; e += 64) {
+    const int b = e / nblk, k = e - b * nblk;
+    s += part[(size_t)(b * C + c) * nblk + k];
+    if (COUNT) n += partn[(size_t)(b * C + c) * nblk + k];
+  }
+  s = wave_sum(s);
+  if (COUNT) *count = wave_sum_i64(n);
+  return s;
+}
+
+// ---- losses ---------------------------------------------------------------------------------------
+// err(b,c,i,j) = [(p-t)^2 + 0.02*(dv + dh + 0.7*d1 + 0.7*d2)] * latw[i] * chanw[c]     (kind 1; kind 0: no TV)
+//   dv = |p[i+1][j]-p[i][j]| (i<H-1)        dh = |p[i][j+1]-p[i][j]| (j<W-1)
+//   d1 = |p[i+1][j+1]-p[i][j]| (i<H-1,j<W-1)   d2 = |p[i+1][j-1]-p[i][j]| (i<H-1, j>=1)
+
+__global__ __launch_bounds__(256) void loss_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                       int Ht, int Wt, const float* __restrict__ latw,
+                                                       const float* __restrict__ chanw, float* __restrict__ part,
+                                                       float* __restrict__ part2, int C, int H, int W, int kind) {
+  const int plane = blockIdx.y;  // b*C + c
+  const int c = plane % C, b = plane / C;
+  const float* p = pred + (size_t)plane * H * W;
+  const float* t = tgt + ((size_t)b * C + c) * Ht * Wt;
+  const float cw = chanw ? chanw[c] : 1.f;
+  float s = 0.f, s2 = 0.f;
+  O2_IMAGE_STRIDE(e, H * W) {
+    const int i = e / W, j = e - i * W;
+    const float pv = p[e];
+    const float tv0 = t[(size_t)i * Wt + j];
+    const float d = pv - tv0;
+    float err = d * d;
+    if (kind == 2) {   // image-gradient term (metrics/functional.py:59-114): forward differences, last row/col zero
+      if (j < W - 1) s2 += fabsf((t[(size_t)i * Wt + j + 1] - tv0) - (p[e + 1] - pv));
+      if (i < H - 1) s2 += fabsf((t[(size_t)(i + 1) * Wt + j] - tv0) - (p[e + W] - pv));
+    }
+    if (kind == 1) {
+      float tv = 0.f;
+      if (i < H - 1) {
+        tv += fabsf(p[e + W] - pv);
+        if (j < W - 1) tv += 0.7f * fabsf(p[e + W + 1] - pv);
+        if (j >= 1) tv += 0.7f * fabsf(p[e + W - 1] - pv);
+      }
+      if (j < W - 1) tv += fabsf(p[e + 1] - pv);
+      err += 0.02f * tv;
+    }
+    s += err * (latw ? latw[i] : 1.f) * cw;
+  }
+  block_part2(s, s2, part, part2, plane);
+}
+
+__global__ void loss_final_kernel(const float* __restrict__ part, const float* __restrict__ part2, int nblk, int B,
+                                  int C, int HW, const float* __restrict__ chanw, int kind, float* __restrict__ out) {
+  // one wave; out[c] = mean over (b, pixels) of channel c; out[C] = mean over everything
+  float tot = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float s = channel_part_sum<false>(part, nblk, B, C, c);
+    if (threadIdx.x == 0) out[c] = s / ((float)B * (float)HW);
+    tot += s;
+  }
+  float agg = tot / ((float)B * (float)C * (float)HW);
+  if (kind == 2) {   // + 0.1 * mean(|grad diff|) * mean(channel weights)
+    float s2 = 0.f;
+    for (int e = threadIdx.x; e < B * C * nblk; e += 64) s2 += part2[e];
+    s2 = wave_sum(s2);
+    float cwm = 1.f;
+    if (chanw) { cwm = 0.f; for (int c = 0; c < C; ++c) cwm += chanw[c]; cwm /= (float)C; }
+    agg += 0.1f * (s2 / ((float)B * (float)C * (float)HW)) * cwm;
+  }
+  if (threadIdx.x == 0) out[C] = agg;
+}
+
+__global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                       int Ht, int Wt, const float* __restrict__ latw,
+                                                       const float* __restrict__ chanw,
+                                                       const float* __restrict__ gscale, float* __restrict__ dpred,
+                                                       int B, int C, int H, int W, int kind) {
+  const int64_t n = (int64_t)B * C * H * W;
+  const float g0 = gscale[0] / (float)n;
+  O2_GRID_STRIDE(e, n) {
+    int b, c, i, j;
+    plane_of(e, C, H, W, b, c, i, j);
+    const float* p = pred + ((size_t)b * C + c) * H * W;
+    const int o = i * W + j;
+    const float pv = p[o];
+    const float wi = latw ? latw[i] : 1.f;
+    const float wim = (latw && i > 0) ? latw[i - 1] : 1.f;
+    float g = 2.f * (pv - tgt[(((size_t)b * C + c) * Ht + i) * Wt + j]) * wi;
+    if (kind == 2) {
+      const float* t = tgt + ((size_t)b * C + c) * Ht * Wt;
+      const float tv0 = t[(size_t)i * Wt + j];
+      float gs = 0.f;
+      if (j < W - 1) gs += sgn((t[(size_t)i * Wt + j + 1] - tv0) - (p[o + 1] - pv));
+      if (j > 0) gs -= sgn((tv0 - t[(size_t)i * Wt + j - 1]) - (pv - p[o - 1]));
+      if (i < H - 1) gs += sgn((t[(size_t)(i + 1) * Wt + j] - tv0) - (p[o + W] - pv));
+      if (i > 0) gs -= sgn((tv0 - t[(size_t)(i - 1) * Wt + j]) - (pv - p[o - W]));
+      float cwm = 1.f;
+      if (chanw) { cwm = 0.f; for (int cc = 0; cc < C; ++cc) cwm += chanw[cc]; cwm /= (float)C; }
+      dpred[e] = (g * (chanw ? chanw[c] : 1.f) + 0.1f * cwm * gs) * g0;
+      continue;
+    }
+    if (kind == 1) {
+      float tv = 0.f;
+      // terms stored at row i (weight wi) in which p[i][j] is the subtrahend
+      if (i < H - 1) {
+        tv -= sgn(p[o + W] - pv) * wi;
+        if (j < W - 1) tv -= 0.7f * sgn(p[o + W + 1] - pv) * wi;
+        if (j >= 1) tv -= 0.7f * sgn(p[o + W - 1] - pv) * wi;
+      }
+      if (j < W - 1) tv -= sgn(p[o + 1] - pv) * wi;
+      // terms in which p[i][j] is the minuend
+      if (j > 0) tv += sgn(pv - p[o - 1]) * wi;                              // dh stored at (i, j-1)
+      if (i > 0) {
+        tv += sgn(pv - p[o - W]) * wim;                                      // dv stored at (i-1, j)
+        if (j > 0) tv += 0.7f * sgn(pv - p[o - W - 1]) * wim;                // d1 stored at (i-1, j-1)
+        if (j < W - 1) tv += 0.7f * sgn(pv - p[o - W + 1]) * wim;            // d2 stored at (i-1, j+1)
+      }
+      g += 0.02f * tv;
+    }
+    dpred[e] = g * (chanw ? chanw[c] : 1.f) * g0;
+  }
+}
+
+// ---- evaluation metrics (metrics/functional.py:219-324: mae, rmse, acc, pearson, mean_bias) ------------------------------
+// the twelve sums of score_sums.h (o2_moments_add) per (b, c) image, clim optional [C][H][W]; one pixel per lane and trip.
+// orbit2_masked_moments with no mask is NOT this kernel with a count: on rows that are not 16-byte aligned its four-pixel items
+// of guarded scalar loads take 1.36 x the time of this sweep (profiles/score_sums.md), so both stay.
+__global__ __launch_bounds__(256) void eval_moments_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                           int Ht, int Wt, const float* __restrict__ lat_w,
+                                                           const float* __restrict__ clim, double* __restrict__ out,
+                                                           int C, int H, int W) {
+  const int bc = blockIdx.y;
+  const float* p = pred + (size_t)bc * H * W;
+  const float* t = target + (size_t)bc * Ht * Wt;
+  const float* cl = clim ? clim + (size_t)(bc % C) * H * W : nullptr;
+  float s[O2_NMOMENTS];
+#pragma unroll
+  for (int k = 0; k < O2_NMOMENTS; ++k) s[k] = 0.f;
+  O2_IMAGE_STRIDE(i, H * W) {
+    const int y = i / W, x = i - y * W;
+    const float c0 = cl ? cl[i] : 0.f;
+    o2_moments_add(s, p[i] - c0, t[(size_t)y * Wt + x] - c0, lat_w ? lat_w[y] : 1.f);
+  }
+  o2_block_sums_add(s, out + (size_t)bc * O2_NMOMENTS);
+}
 
 constexpr int MM_NM = O2_NMOMENTS + 1;   // the twelve sums of orbit2_eval_moments + the valid count
 
@@ -92,7 +267,7 @@ __global__ __launch_bounds__(256) void masked_loss_fwd_kernel(const float* __res
   const int W4 = (W + 3) >> 2;
   float s = 0.f;
   int n = 0;
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < H * W4; e += gridDim.x * 256) {
+  O2_IMAGE_STRIDE(e, H * W4) {
     const int i = e / W4, j0 = (e - i * W4) << 2;
     float p0[6], p1[6], t0[4], t1[4];
     bool v0[6], v1[6];
@@ -115,16 +290,7 @@ __global__ __launch_bounds__(256) void masked_loss_fwd_kernel(const float* __res
     }
     s += acc * (latw ? latw[i] : 1.f);
   }
-  s = wave_sum(s * (chanw ? chanw[c] : 1.f));
-  n = wave_sum_i(n);
-  __shared__ float sw[4];
-  __shared__ int sn[4];
-  if ((threadIdx.x & 63) == 0) { sw[threadIdx.x >> 6] = s; sn[threadIdx.x >> 6] = n; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[(size_t)plane * gridDim.x + blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
-    partn[(size_t)plane * gridDim.x + blockIdx.x] = sn[0] + sn[1] + sn[2] + sn[3];
-  }
+  block_part2(s * (chanw ? chanw[c] : 1.f), n, part, partn, plane);
 }
 
 // one wave: out[c] = num_c / n_c (0 if n_c == 0), out[C] = sum num / sum n (0 if nothing is valid); cnt[c] = n_c, cnt[C] = sum n
@@ -133,15 +299,8 @@ __global__ void masked_loss_final_kernel(const float* __restrict__ part, const i
   float tot = 0.f;
   int64_t ntot = 0;
   for (int c = 0; c < C; ++c) {
-    float s = 0.f;
-    int64_t n = 0;
-    for (int e = threadIdx.x; e < B * nblk; e += 64) {
-      const int b = e / nblk, k = e - b * nblk;
-      s += part[(size_t)(b * C + c) * nblk + k];
-      n += partn[(size_t)(b * C + c) * nblk + k];
-    }
-    s = wave_sum(s);
-    n = wave_sum_i64(n);            // a plane holds fewer than 2^31 pixels, a channel may hold more
+    int64_t n;
+    const float s = channel_part_sum<true>(part, nblk, B, C, c, partn, &n);
     if (threadIdx.x == 0) { out[c] = n ? s / (float)n : 0.f; cnt[c] = n; }
     tot += s;
     ntot += n;
@@ -163,10 +322,9 @@ __global__ __launch_bounds__(256) void masked_loss_bwd_kernel(const float* __res
   const float g0 = ntot ? gscale[0] / (float)ntot : 0.f;
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;           // one item per thread: the grid covers them all
   if (e < items) {
-    int64_t q = e;
-    const int j0 = (int)(q % W4) << 2; q /= W4;
-    const int i = (int)(q % H); q /= H;
-    const int c = (int)(q % C), b = (int)(q / C);
+    int b, c, i, j0;
+    plane_of(e, C, H, W4, b, c, i, j0);
+    j0 <<= 2;
     const size_t plane = (size_t)b * C + c;
     const float* p = pred + plane * H * W;
     const float* t = tgt + plane * Ht * Wt;
@@ -229,7 +387,7 @@ __global__ __launch_bounds__(256) void masked_moments_kernel(const float* __rest
 #pragma unroll
   for (int k = 0; k < O2_NMOMENTS; ++k) s[k] = 0.f;
   int n = 0;
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < H * W4; e += gridDim.x * 256) {
+  O2_IMAGE_STRIDE(e, H * W4) {
     const int i = e / W4, j0 = (e - i * W4) << 2;
     float p0[6], t0[4], c0[4] = {0.f, 0.f, 0.f, 0.f};
     bool v0[6];
@@ -276,6 +434,45 @@ inline bool vec_ok(const float* pred, const float* target, const MaskArg& mk, in
 }
 
 }  // namespace
+
+extern "C" int orbit2_loss_fwd(const float* pred, const float* target, int Ht, int Wt, const float* lat_w,
+                               const float* chan_w, float* out, float* ws, int B, int C, int H, int W, int kind,
+                               void* stream) {
+  if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !out || !ws) return O2_ERR_ARG;
+  if (kind < 0 || kind > 2) return O2_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  float* ws2 = ws + (size_t)B * C * ORBIT2_LOSS_BLOCKS;
+  hipLaunchKernelGGL(loss_fwd_kernel, dim3(ORBIT2_LOSS_BLOCKS, B * C), dim3(256), 0, s, pred, target, Ht, Wt, lat_w, chan_w, ws,
+                     ws2, C, H, W, kind);
+  O2_CHECK_LAUNCH();
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(64), 0, s, ws, ws2, ORBIT2_LOSS_BLOCKS, B, C, H * W, chan_w, kind, out);
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+extern "C" int orbit2_loss_bwd(const float* pred, const float* target, int Ht, int Wt, const float* lat_w,
+                               const float* chan_w, const float* gscale, float* dpred, int B, int C, int H, int W,
+                               int kind, void* stream) {
+  if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !gscale || !dpred) return O2_ERR_ARG;
+  if (kind == ORBIT2_LOSS_SSIM_VJP)
+    return chan_w ? O2_ERR_ARG : o2_ssim_vjp(pred, target, Ht, Wt, lat_w, gscale, dpred, B, C, H, W, (hipStream_t)stream);
+  if (kind < 0 || kind > 2) return O2_ERR_ARG;
+  hipLaunchKernelGGL(loss_bwd_kernel, dim3(grid_for((int64_t)B * C * H * W, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
+                     pred, target, Ht, Wt, lat_w, chan_w, gscale, dpred, B, C, H, W, kind);
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
+
+extern "C" int orbit2_eval_moments(const float* pred, const float* target, int Ht, int Wt, const float* lat_w,
+                                   const float* clim, double* out, int B, int C, int H, int W, void* stream) {
+  if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !out) return O2_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(out, 0, sizeof(double) * (size_t)B * C * O2_NMOMENTS, s) != hipSuccess) return O2_ERR_LAUNCH;
+  hipLaunchKernelGGL(eval_moments_kernel, dim3(o2_image_blocks((int64_t)H * W), B * C), dim3(256), 0, s, pred, target, Ht, Wt,
+                     lat_w, clim, out, C, H, W);
+  O2_CHECK_LAUNCH();
+  return O2_OK;
+}
 
 extern "C" int orbit2_masked_loss_fwd(const float* pred, const float* target, int Ht, int Wt, const uint8_t* mask,
                                       int mask_pitch, int64_t mask_sb, int64_t mask_sc, const float* lat_w,

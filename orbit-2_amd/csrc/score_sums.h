@@ -1,4 +1,4 @@
-// What the evaluation kernels share (image.hip, masked.hip, ensemble.hip, ssim.hip, resample.hip): the twelve evaluation moments,
+// What the evaluation kernels share (loss.hip, ensemble.hip, ssim.hip, resample.hip): the twelve evaluation moments,
 // the per-image block-sum epilogue, the grid rules and the operand check of a scored pair.  common.h keeps what GEMM and attention
 // need as well.
 #pragma once
@@ -47,6 +47,8 @@ inline int o2_image_blocks(int64_t pixels) {
   const int64_t n = (pixels + 256 * 8 - 1) / (256 * 8);
   return n > 64 ? 64 : (int)n;
 }
+// the loop header of such a sweep inside one image (blockIdx.y): 32-bit, the entries keep pixels + gridDim.x * 256 below 2^31
+#define O2_IMAGE_STRIDE(i, n) for (int i = blockIdx.x * 256 + threadIdx.x; i < (n); i += gridDim.x * 256)
 // the cap where a thread takes one pixel (or row) per trip: at most 64 workgroups per image, more only where B * C images alone
 // would not fill the card
 inline int o2_image_block_cap(int BC) { return BC >= 16 ? 64 : 1024 / BC; }
@@ -56,7 +58,7 @@ inline bool o2_pair_ok(const void* pred, const void* target, int B, int C, int H
   return pred && target && B > 0 && C > 0 && H > 0 && W > 0 && Ht >= H && Wt >= W;
 }
 
-// ---- the SSIM vector-Jacobian product (ssim.hip), reached through orbit2_loss_bwd (image.hip) at kind ORBIT2_LOSS_SSIM_VJP: not
+// ---- the SSIM vector-Jacobian product (ssim.hip), reached through orbit2_loss_bwd (loss.hip) at kind ORBIT2_LOSS_SSIM_VJP: not
 // an export, so the library's dynamic symbols stay those of the header
 __attribute__((visibility("hidden"))) int o2_ssim_vjp(const float* pred, const float* target, int Ht, int Wt, const float* lat_w,
                                                       const float* gscale, float* dpred, int B, int C, int H, int W,

@@ -341,7 +341,7 @@ inline bool ss_grid_ok(int B, int C, int H, int W, int ntx, int nty) {
 }
 }  // namespace
 
-// the kind ORBIT2_LOSS_SSIM_VJP of orbit2_loss_bwd (image.hip), which has checked the pair, gscale and dpred
+// the kind ORBIT2_LOSS_SSIM_VJP of orbit2_loss_bwd (loss.hip), which has checked the pair, gscale and dpred
 int o2_ssim_vjp(const float* pred, const float* target, int Ht, int Wt, const float* lat_w, const float* gscale, float* dpred,
                 int B, int C, int H, int W, hipStream_t s) {
   const int ntx = (W + SV_TW - 1) / SV_TW, nty = (H + SV_TH - 1) / SV_TH;

@@ -1,4 +1,4 @@
-"""The image-tail kernels (csrc/image.hip) at their partition edges, against the float64 references of tests/rowimage_ref.py.
+"""The image-tail kernels (csrc/image.hip; the losses: csrc/loss.hip) at their partition edges, against the float64 references of tests/rowimage_ref.py.
 
 conv3x3, fp32 against float64 with derived bounds (A = the same sum over absolute values, u = 2^-24):
   mode-0 out, pre (both modes), mode-0 din: per element n u A, n = 9 Cin + 2 (forward), 9 Cout (din)

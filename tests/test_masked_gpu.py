@@ -1,4 +1,4 @@
-"""Missing-data masks on the device (csrc/masked.hip: orbit2_masked_loss_fwd / _bwd / _moments; metrics.functional.masked_mse,
+"""Missing-data masks on the device (csrc/loss.hip: orbit2_masked_loss_fwd / _bwd / _moments; metrics.functional.masked_mse,
 masked_bayesian_tv, rmse / mae / pearson / mean_bias with a mask; the masked_* registry names) against tests/masked_ref.py, the
 float64 restatement that tests/test_masked_cpu.py ties to the reference's own numbers.
 

@@ -14,7 +14,7 @@ from tests import resample_ref as R
 pytestmark = pytest.mark.gpu
 
 # The bound the project already applies to these twelve sums (fields at offset 0): 6.4e-7.  eval_moments of the commit before
-# csrc/score_sums.h existed (the epilogue and the moments typed out in csrc/image.hip) measured 6.35e-8 at worst over every case
+# csrc/score_sums.h existed (the epilogue and the moments typed out in csrc/image.hip, now csrc/loss.hip) measured 6.35e-8 at worst over every case
 # below, inside that bound, so this is the bound.
 BOUND = R.MOMENTS_RTOL[0]
 SCALAR = ((2, 3, 19, 37), (2, 3, 23, 41))

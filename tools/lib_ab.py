@@ -1,5 +1,5 @@
 """The part that the same-process A/B tools of two builds of the library share (tools/loss_lib_ab.py, tools/varagg_lib_ab.py,
-tools/gemm_lib_ab.py):
+tools/gemm_lib_ab.py, tools/image_lib_ab.py):
     tools/ab_build.sh <git-rev> <name>;   on the GPU box:  python tools/<kernels>_lib_ab.py orbit-2_amd/lib/alt/<name>.so [other.so]
 `libs` holds the working-tree library ("tree"; or other.so in its place: an A/A run of two builds of one revision) and the other
 build ("alt"; of the same ABI version: _hip.load) side by side.  A tool calls every entry of its files in both and prints one line

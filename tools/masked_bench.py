@@ -5,8 +5,8 @@
 
 A [16, 3, 512, 1024] prediction against a [16, 3, 721, 1440] target (read through its top-left crop), in one process on one card,
 every leg alternating `--rounds` times after a warm-up of each, HIP events around 200 calls (windows of 10 to 60 ms):
-  loss <kind>            `_hip.loss_fwd` + `_hip.loss_bwd` (orbit2_loss_fwd / _bwd, csrc/image.hip: the unmasked kernels)
-  masked <kind> <form>   `_hip.masked_loss_fwd` + `_hip.masked_loss_bwd` (csrc/masked.hip) with no mask, an [H,W] mask and a
+  loss <kind>            `_hip.loss_fwd` + `_hip.loss_bwd` (orbit2_loss_fwd / _bwd, csrc/loss.hip: the unmasked kernels)
+  masked <kind> <form>   `_hip.masked_loss_fwd` + `_hip.masked_loss_bwd` (the same file) with no mask, an [H,W] mask and a
                          [B,C,H,W] mask; the masks are smooth blobs (coastlines, not salt and pepper) with about 40 % invalid
   moments                `_hip.eval_moments`;  masked moments <form>: `_hip.masked_moments`
 for kind in mse, bayesian_tv.  GB/s is each leg's time over its ALGORITHMIC bytes: forward = prediction + target crop (+ mask)
@@ -118,7 +118,7 @@ def write_md(path, r):
         f.write("# Missing-data masks: the masked kernels against the unmasked ones (tools/masked_bench.py)\n\n")
         f.write("One MI355X, one process, all legs alternating, %d rounds of %d calls after a warm-up, HIP events; prediction [%s] "
                 "fp32 against a target [.., %s] read through its top-left crop, latitude and variable weights on.  `loss` / `moments` "
-                "are the unmasked kernels of the same library (csrc/image.hip); a `masked` loss leg is forward + backward.  The "
+                "are the unmasked kernels of the same library (csrc/loss.hip); a `masked` loss leg is forward + backward.  The "
                 "masks are smooth blobs, valid fraction %.2f ([H,W]) and %.2f ([B,C,H,W]).  GB/s counts a leg's algorithmic bytes "
                 "(fields and mask once; not the stencil's re-reads of neighbouring rows).  `x parent` is measured time over the "
                 "unmasked leg's, `bytes x` the ratio a purely memory-bound kernel would show.\n\n"
