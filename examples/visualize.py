@@ -23,7 +23,13 @@ input, and the mean-squared-error skill of the first against the second (climate
 
 An optional `consistency: {mode: bilinear}` block (configs/inference_consistency.yaml; bilinear or bicubic) prints, before any
 `baseline_scores` line, one `consistency_scores` line per output variable: the stitched field coarsened back to the input grid
-with antialiasing and read against the field the model was given (climate_learn.utils.visualize.consistency_scores)."""
+with antialiasing and read against the field the model was given (climate_learn.utils.visualize.consistency_scores).
+
+An optional `extreme_scores: true` or `extreme_scores: {levels: [...]}` entry (configs/inference_extremes.yaml; default levels
++1 / +2 / +3 sigma) prints one `extreme_scores` line per output variable: for the upper tail at every level and the lower tail at
+the mirrored one, the exact quantile of the target and of the stitched field, their difference, and the rmse, bias, critical
+success index and frequency bias over the pixels whose target lies in that tail, in physical units
+(climate_learn.utils.visualize.extreme_scores)."""
 import os
 import sys
 
@@ -35,8 +41,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "orbit-2_amd")]
 
 import climate_learn as cl                                                        # noqa: E402
 from climate_learn.utils.fused_attn import FusedAttn                              # noqa: E402
-from climate_learn.utils.visualize import (baseline_scores, consistency_scores, stitched_scores, tiled_predict,    # noqa: E402
-                                           visualize_at_index)
+from climate_learn.utils.visualize import (baseline_scores, consistency_scores, extreme_scores, stitched_scores,  # noqa: E402
+                                           tiled_predict, visualize_at_index)
 
 
 def main():
@@ -96,6 +102,14 @@ def main():
         # sample on the host); latitude weights as the lat_* metrics build them
         for var, sc in stitched_scores(pred, gt, ov, _lat_weights(dm_vis)).items():
             print("stitched_scores", var, {k: round(v, 6) for k, v in sc.items()}, flush=True)
+    extremes = conf.get("extreme_scores")
+    if extremes:
+        # the tails of the stitched field in physical units: exact quantiles and the scores beyond them, on the device
+        # (climate_learn.utils.visualize.extreme_scores); unweighted, so level 0 is the rmse line above
+        levels = extremes.get("levels") if isinstance(extremes, dict) else None
+        for var, sc in extreme_scores(pred, gt, ov, levels).items():
+            print("extreme_scores", var, {side: [{k: round(v, 6) for k, v in row.items()} for row in rows]
+                                          for side, rows in sc.items()}, flush=True)
     consistency = conf.get("consistency")
     if consistency:
         # the stitched field coarsened back to the input grid and read against the input, both normalised as the outputs are;

@@ -36,7 +36,9 @@ extern "C" {
  * orbit2_ssim; orbit2_resample_fwd and orbit2_resample_moments; the mode values 5 and 6 of those two (bilinear and bicubic with
  * ORBIT2_ANTIALIAS), which earlier builds of version 8 refuse with O2_ERR_ARG; the mode values 21 and 22 of orbit2_resample_fwd
  * (those two with ORBIT2_TRANSPOSE: the adjoint of the coarsening), which earlier builds of version 8 refuse as well; the kind
- * value 3 of orbit2_loss_bwd (ORBIT2_LOSS_SSIM_VJP: the backward of orbit2_ssim's sums), which earlier builds refuse too. */
+ * value 3 of orbit2_loss_bwd (ORBIT2_LOSS_SSIM_VJP: the backward of orbit2_ssim's sums), which earlier builds refuse too; the
+ * kinds 3 and 4 of orbit2_masked_loss_fwd with the flag and count bits of its kind word (ORBIT2_MASKED_QUANTILES,
+ * ORBIT2_MASKED_TAIL: exact field quantiles and tail sums), which earlier builds refuse with O2_ERR_ARG as well. */
 int orbit2_abi_version(void);
 
 /* ---- bf16 MFMA GEMM with fused epilogue ------------------------------------------------
@@ -392,7 +394,7 @@ int orbit2_eval_moments(const float* pred, const float* target, int Ht, int Wt, 
  * the kernels read float4 / dword groups; any other layout is read by scalar lanes (same results to rounding of the sums' order).
  *
  * orbit2_masked_loss_fwd: kind 0 = mse, 1 = bayesian_tv (a difference term of the prior counts only if both of its pixels are
- * valid); any other kind is O2_ERR_ARG.  With num_c = sum_{b,i,j} v w_i cw_c err and n_c = sum_{b,i,j} v:
+ * valid); kinds 3 / 4 are the extreme-value scores below; any other kind is O2_ERR_ARG.  With num_c = sum_{b,i,j} v w_i cw_c err and n_c = sum_{b,i,j} v:
  *   out[c] = num_c / n_c (0 if n_c == 0), out[C] = sum_c num_c / sum_c n_c (0 if nothing is valid); cnt[c] = n_c, cnt[C] = sum_c n_c.
  * out fp32 [C+1], cnt int64 [C+1] (counted as integers: exact), ws >= 2*B*C*ORBIT2_LOSS_BLOCKS four-byte words.
  * Fixed-order sums, no atomics: two calls give the same bits.
@@ -408,6 +410,51 @@ int orbit2_masked_loss_bwd(const float* pred, const float* target, int Ht, int W
 int orbit2_masked_moments(const float* pred, const float* target, int Ht, int Wt, const uint8_t* mask, int mask_pitch,
                           int64_t mask_sb, int64_t mask_sc, const float* lat_w, const float* clim, double* out, int B, int C,
                           int H, int W, void* stream);
+
+/* ---- extreme-value scores (csrc/extremes.hip, csrc/quantile_select.h; metrics/functional.py field_quantiles / tail_rmse /
+ * exceedance_scores): two further kinds of orbit2_masked_loss_fwd, additive within ABI 8 -------------------------
+ * The entry's `kind` is a bit field: bits 0-3 the kind proper, bit 4 ORBIT2_MASKED_PER_IMAGE, bit 5 ORBIT2_MASKED_LOWER, bits
+ * 8-15 a count n (ORBIT2_MASKED_KIND(kind, flags, n)).  Any other set bit, a kind proper other than 0, 1, 3, 4, any flag or
+ * count on kinds 0 / 1, and ORBIT2_MASKED_LOWER on kind 3 are O2_ERR_ARG.  Validity, pred / target / mask and the float4 / scalar
+ * path choice are those of kinds 0 / 1.  Pixels are grouped: G = C groups by default (a channel pooled over the batch and all
+ * pixels), G = B * C with ORBIT2_MASKED_PER_IMAGE; invalid pixels enter nothing; a group of 2^31 or more pixels is refused.
+ *
+ * kind ORBIT2_MASKED_QUANTILES (3), n = Q in 1..ORBIT2_MASKED_MAX_LEVELS: exact order statistics by a radix select.
+ *   chan_w is read as levels fp32 [Q], each in [0, 1] (a level outside, or NaN, is clamped into it); lat_w must be NULL.
+ *   For field f (0 = target, 1 = pred) and group g with m valid pixels of sorted values x_(0) <= ... <= x_(m-1):
+ *   pos = q (m - 1) in double, lo = floor(pos), hi = min(lo + 1, m - 1),
+ *     out[f][g][q][3] = { (float)((double)x_(lo) + (pos - lo) ((double)x_(hi) - (double)x_(lo))), x_(lo), x_(hi) }
+ *   out fp32 [2][G][Q][3]; the two brackets are data values bit for bit (-0.0 and +0.0 are ordered -0.0 < +0.0 and either may
+ *   stand for the other); q = 0 / 1 give the minimum / maximum; cnt int64 [G] = m; m = 0 gives NaN in all three slots.  Values
+ *   are ordered by their bit patterns (sign-magnitude to unsigned), so denormals order exactly and a NaN in a valid pred pixel
+ *   sorts beyond the infinities of its sign.  pred == target (one pointer) is allowed.
+ *   ws >= ORBIT2_QUANTILE_WS_WORDS(G, Q) four-byte words, zeroed by the entry on the stream.  Nothing synchronises with the
+ *   host: m, the ranks, the digit prefixes and the interpolation stay on the device.  Integer atomics only: two calls give the
+ *   same bits.
+ *
+ * kind ORBIT2_MASKED_TAIL (4), n = T in 1..ORBIT2_MASKED_MAX_LEVELS: sums and counts beyond thresholds, one pass for all T.
+ *   chan_w is read as thresholds fp32 [G][T] (typically column 1 or 2 of kind 3's target rows, still on the device); lat_w is
+ *   optional.  A value v is IN THE TAIL of threshold t when v >= t, with ORBIT2_MASKED_LOWER when v <= t.  Per image (b, c) and
+ *   threshold, with d = pred - target and w = lat_w[row] or 1, over the valid pixels whose TARGET is in the tail:
+ *     out fp32 [B][C][T][4]  = { sum w, sum w d^2, sum w |d|, sum d }
+ *     cnt int64 [B][C][T][4] = { tail pixels, of those: pred in the tail too (hits), valid pixels outside the tail whose pred is
+ *                                in it (false alarms), valid pixels }
+ *   ws >= ORBIT2_TAIL_WS_WORDS(B, C, T).  Per-workgroup fp32 partials, added in a fixed order in double; counts are integers; no
+ *   float atomics: two calls give the same bits.
+ *
+ * Refused before any launch with nothing written: NULL chan_w, n outside 1..8, lat_w at kind 3, a group of 2^31 pixels or more,
+ * and everything kinds 0 / 1 refuse. */
+#define ORBIT2_MASKED_QUANTILES 3
+#define ORBIT2_MASKED_TAIL 4
+#define ORBIT2_MASKED_PER_IMAGE 16
+#define ORBIT2_MASKED_LOWER 32
+#define ORBIT2_MASKED_MAX_LEVELS 8
+#define ORBIT2_MASKED_KIND(kind, flags, n) ((kind) | (flags) | ((n) << 8))
+/* per (field, group): 64 state words, the 256-bin histogram of the top digit, and for each of the three lower digits one
+ * 256-bin histogram per tracked prefix (at most 2 Q: the two brackets of every level) */
+#define ORBIT2_QUANTILE_WS_WORDS(G, Q) (2 * (long long)(G) * (64 + 256 + 3 * 2 * (Q) * 256))
+/* per image and workgroup: T x 4 fp32 sums, then T x 4 int32 counts */
+#define ORBIT2_TAIL_WS_WORDS(B, C, T) ((long long)(B) * (C) * ORBIT2_LOSS_BLOCKS * 8 * (T))
 
 /* ---- MC-dropout ensembles (utils/mc_dropout.py) and the Gaussian scores (metrics/functional.py:340-386) ------
  * orbit2_ensemble_update: the k-th (1-based) Welford step over n fp32 elements, in place:

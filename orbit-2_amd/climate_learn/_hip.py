@@ -1092,6 +1092,74 @@ def masked_moments(pred, target, lat_w=None, clim=None, mask=None, mask_strides=
     return out
 
 
+# ---- extreme-value scores (csrc/extremes.hip): two further kinds of orbit2_masked_loss_fwd ------------------------------------
+MASKED_QUANTILES, MASKED_TAIL = 3, 4            # ORBIT2_MASKED_QUANTILES, ORBIT2_MASKED_TAIL: the kind proper (bits 0-3)
+MASKED_PER_IMAGE, MASKED_LOWER = 16, 32         # ORBIT2_MASKED_PER_IMAGE, ORBIT2_MASKED_LOWER: flags or-ed into the kind
+MASKED_MAX_LEVELS = 8                           # ORBIT2_MASKED_MAX_LEVELS: levels / thresholds per call (bits 8-15 of the kind)
+
+
+def quantile_ws_words(G: int, Q: int) -> int:
+    """ORBIT2_QUANTILE_WS_WORDS(G, Q)"""
+    return 2 * G * (64 + 256 + 3 * 2 * Q * 256)
+
+
+def tail_ws_words(B: int, Cc: int, T: int) -> int:
+    """ORBIT2_TAIL_WS_WORDS(B, C, T)"""
+    return B * Cc * LOSS_BLOCKS * 8 * T
+
+
+def _levels(name, t, what, rows=None):
+    """the fp32 device vector (rows=None) or [rows, n] matrix a call of the extreme-value kinds reads as chan_w; returns n"""
+    _dev(t, F32, what)
+    n = t.shape[-1] if t.dim() else 0
+    if t.dim() != (1 if rows is None else 2) or not 1 <= n <= MASKED_MAX_LEVELS or (rows is not None and t.shape[0] != rows):
+        raise HipBackendError("%s: %s must be fp32 %s with 1..%d entries per row, got %s"
+                              % (name, what, "[n]" if rows is None else "[%d, n]" % rows, MASKED_MAX_LEVELS, tuple(t.shape)))
+    return n
+
+
+def _groups(name, B, Cc, H, W, per_image):
+    G, pixels = (B * Cc, H * W) if per_image else (Cc, B * H * W)
+    if pixels >= 1 << 31:
+        raise HipBackendError("%s: a group of %d pixels; the entry takes fewer than 2^31 per group" % (name, pixels))
+    return G
+
+
+def masked_quantiles(pred, target, levels, mask=None, mask_strides=(0, 0, 0), per_image=False):
+    """(out fp32 [2, G, Q, 3], cnt int64 [G]): for field 0 = target and 1 = pred and every group (G = C: a channel pooled over the
+    batch; per_image: G = B * C) the linear quantile at every level of `levels` (fp32 [Q], Q <= 8, on the device) over the valid
+    pixels, then its two bracketing order statistics, exact; cnt the valid pixels (include/orbit2_hip.h: ORBIT2_MASKED_QUANTILES).
+    pred may be target itself."""
+    B, Cc, H, W = _scored_pair("masked_quantiles", pred, target)
+    Q = _levels("masked_quantiles", levels, "levels")
+    mp = _mask_args(mask, mask_strides, pred, target)
+    G = _groups("masked_quantiles", B, Cc, H, W, per_image)
+    out = torch.empty(2, G, Q, 3, dtype=F32, device=pred.device)
+    cnt = torch.empty(G, dtype=torch.int64, device=pred.device)
+    ws = torch.empty(quantile_ws_words(G, Q), dtype=F32, device=pred.device)
+    kind = MASKED_QUANTILES | (MASKED_PER_IMAGE if per_image else 0) | (Q << 8)
+    _call("orbit2_masked_loss_fwd", pred, target, target.shape[2], target.shape[3], *mp, None, levels, out, cnt, ws, B, Cc, H, W,
+          kind)
+    return out, cnt
+
+
+def masked_tail(pred, target, thresholds, lat_w=None, mask=None, mask_strides=(0, 0, 0), lower=False, per_image=False):
+    """(sums fp32 [B, C, T, 4], cnt int64 [B, C, T, 4]) per image and threshold over the valid pixels whose target is at or beyond
+    the threshold (lower: at or below): {sum w, sum w d^2, sum w |d|, sum d} and {tail pixels, hits, false alarms, valid pixels}
+    (include/orbit2_hip.h: ORBIT2_MASKED_TAIL).  thresholds: fp32 [G, T] on the device, G = C or, per_image, B * C; T <= 8."""
+    B, Cc, H, W = _scored_pair("masked_tail", pred, target, lat_w)
+    G = _groups("masked_tail", B, Cc, H, W, per_image)
+    T = _levels("masked_tail", thresholds, "thresholds", G)
+    mp = _mask_args(mask, mask_strides, pred, target)
+    out = torch.empty(B, Cc, T, 4, dtype=F32, device=pred.device)
+    cnt = torch.empty(B, Cc, T, 4, dtype=torch.int64, device=pred.device)
+    ws = torch.empty(tail_ws_words(B, Cc, T), dtype=F32, device=pred.device)
+    kind = MASKED_TAIL | (MASKED_PER_IMAGE if per_image else 0) | (MASKED_LOWER if lower else 0) | (T << 8)
+    _call("orbit2_masked_loss_fwd", pred, target, target.shape[2], target.shape[3], *mp, lat_w, thresholds, out, cnt, ws, B, Cc,
+          H, W, kind)
+    return out, cnt
+
+
 def ensemble_update(member, mean, m2, k: int):
     """the k-th (1-based) Welford step of the running ensemble moments, in place on `mean` and `m2`
     (include/orbit2_hip.h:orbit2_ensemble_update); k = 1 initialises them, so they may be torch.empty"""

@@ -550,3 +550,109 @@ def psnr(pred, target, aggregate_only: bool = False, data_range=None):
     the kernel's sums; the mean over b, then over c."""
     s, pred = _ssim_sums(pred, target, None, data_range)
     return _with_aggregate(_psnr_per_image(s, pred).mean(0).float().to(pred.device), aggregate_only)
+
+
+# ---- extreme-value scores (DESIGN 4.10i): what a downscaled field does in its tails.  Exact quantiles of a field over its valid
+# pixels from a radix select (orbit2_masked_loss_fwd at ORBIT2_MASKED_QUANTILES: no sort, no host copy, no size limit below 2^31
+# pixels per group), and the error and the exceedance counts beyond a threshold from one pass for up to eight thresholds
+# (ORBIT2_MASKED_TAIL).  The levels of the reference's quantile loss (metrics/functional.py:45) at +1, +2, +3 sigma; its extreme
+# subsets are cut at the 5th / 95th percentile (data/processing/era5_extreme.py:84-88).  A pixel counts where the target is
+# finite and the `mask` (as rmse's, _mask_operand) is non-zero.  Nothing here copies to the host. --------------------------------
+SIGMA_LEVELS = (0.8413, 0.9772, 0.9987)
+
+
+def _level_tensor(q, device):
+    """levels as the fp32 device vector the kernels read; (vector, whether `q` was a single number)"""
+    if torch.is_tensor(q):
+        t = q.detach().to(device=device, dtype=torch.float32).reshape(-1)
+        return t.contiguous(), q.dim() == 0
+    single = not isinstance(q, (tuple, list))
+    return torch.tensor([float(q)] if single else [float(v) for v in q], dtype=torch.float32, device=device), single
+
+
+def _extreme_pair(pred, target):
+    if isinstance(pred, torch.distributions.Normal):
+        pred = pred.loc
+    return pred.detach().float().contiguous(), target.detach().float().contiguous()
+
+
+def _quantiles(pred, target, q, mask=None, per_image=False):
+    """(out [2,G,Q,3], cnt [G]) of _hip.masked_quantiles for levels given as numbers or a tensor"""
+    from .. import _hip
+    pred, target = _extreme_pair(pred, target)
+    m, pitch, sb, sc = _mask_operand(mask, pred, target)
+    return _hip.masked_quantiles(pred, target, _level_tensor(q, pred.device)[0], m, (pitch, sb, sc), per_image)
+
+
+def field_quantiles(x, q, mask=None, per_image=False):
+    """[G, Q]: the linear-interpolation quantiles (numpy's default) of x [B,C,H,W] at the levels q over its finite, unmasked
+    pixels; G = C groups, a channel pooled over the batch and all pixels, or per_image G = B * C.  Exact: the two order
+    statistics around every level are found by selection, the interpolation is done in double.  NaN for a group without data."""
+    return _quantiles(x, x, q, mask, per_image)[0][0, :, :, 0]
+
+
+def quantile_bias(pred, target, q, aggregate_only: bool = False, mask=None):
+    """[C+1, Q]: quantile of the prediction minus quantile of the target at every level of q (the Q-Q bias), per channel pooled
+    over the batch, both over the pixels where the target is valid; the last row is the mean over the channels"""
+    out = _quantiles(pred, target, q, mask)[0][..., 0]
+    per = out[1] - out[0]
+    agg = per.mean(0, keepdim=True)
+    return agg[0] if aggregate_only else torch.cat((per, agg))
+
+
+def _tail(pred, target, q, lower, lat_weights, mask, thresholds):
+    """(sums [C,T,4] float64, cnt [C,T,4] int64) over the batch: the tail of every channel beyond its own pooled target quantile
+    at the levels q (lower: the level 1 - q is NOT taken -- q is the level itself), or beyond explicit `thresholds` [C] / [C,T]"""
+    from .. import _hip
+    pred, target = _extreme_pair(pred, target)
+    m, pitch, sb, sc = _mask_operand(mask, pred, target)
+    if thresholds is None:
+        levels, _ = _level_tensor(q, pred.device)
+        out, _ = _hip.masked_quantiles(pred, target, levels, m, (pitch, sb, sc))      # field 0: the target through the pred's crop
+        thr = out[0, :, :, 0].contiguous()                       # the quantile itself, still on the device
+    else:
+        thr = torch.as_tensor(thresholds).detach().to(device=pred.device, dtype=torch.float32)
+        thr = thr.reshape(pred.shape[1], -1).contiguous()
+    s, n = _hip.masked_tail(pred, target, thr, _lat(lat_weights, pred), m, (pitch, sb, sc), lower)
+    return s.double().sum(0), n.sum(0)
+
+
+def _tail_score(per_channel, aggregate_only):
+    """[C] (one threshold per channel) -> [C+1] with the mean of the channels, or that mean alone"""
+    per_channel = per_channel[:, 0].float()
+    return _with_aggregate(per_channel, aggregate_only)
+
+
+def tail_rmse(pred, target, q=0.9772, lower: bool = False, aggregate_only: bool = False, lat_weights=None, mask=None,
+              thresholds=None):
+    """[C+1]: sqrt(sum_b sum w d^2 / sum_b sum w) per channel over the valid pixels whose TARGET is at or beyond the channel's own
+    pooled target quantile at level q (lower: at or below it), d = pred - target; the last entry is the mean of the channels.
+    `thresholds` [C] replaces the quantile (e.g. a climatological percentile).  An empty tail gives NaN."""
+    s, _ = _tail(pred, target, q, lower, lat_weights, mask, thresholds)
+    return _tail_score((s[..., 1] / s[..., 0]).sqrt(), aggregate_only)
+
+
+def tail_mae(pred, target, q=0.9772, lower: bool = False, aggregate_only: bool = False, lat_weights=None, mask=None,
+             thresholds=None):
+    """[C+1]: sum w |d| / sum w over the tail of tail_rmse"""
+    s, _ = _tail(pred, target, q, lower, lat_weights, mask, thresholds)
+    return _tail_score(s[..., 2] / s[..., 0], aggregate_only)
+
+
+def tail_bias(pred, target, q=0.9772, lower: bool = False, aggregate_only: bool = False, mask=None, thresholds=None):
+    """[C+1]: mean of pred - target over the pixels of the tail of tail_rmse (unweighted: sum d / their number)"""
+    s, n = _tail(pred, target, q, lower, None, mask, thresholds)
+    return _tail_score(s[..., 3] / n[..., 0].double(), aggregate_only)
+
+
+def exceedance_scores(pred, target, q=0.9772, lower: bool = False, mask=None, thresholds=None):
+    """{"csi", "pod", "far", "frequency_bias"}, each [C]: the contingency scores of the event "the value is at or beyond the
+    channel's pooled target quantile at level q" (or `thresholds` [C]) over the valid pixels and the batch.  With hits h, misses m
+    and false alarms f: csi = h / (h + m + f), pod = h / (h + m), far = f / (h + f), frequency_bias = (h + f) / (h + m).
+    0 / 0 is NaN."""
+    _, n = _tail(pred, target, q, lower, None, mask, thresholds)
+    n = n[:, 0].double()
+    h, f = n[:, 1], n[:, 2]
+    ms = n[:, 0] - h
+    return {"csi": (h / (h + ms + f)).float(), "pod": (h / (h + ms)).float(), "far": (f / (h + f)).float(),
+            "frequency_bias": ((h + f) / (h + ms)).float()}

@@ -259,6 +259,40 @@ class PSNR(Metric):
         return psnr(pred, target, self.aggregate_only)
 
 
+# ---- extreme values (functional.tail_rmse / quantile_bias): called as (pred, target) like ssim / psnr, so
+# evaluate_func runs them unchanged; the level is an attribute
+class _AtLevel:
+    """level: the quantile level of the score (default +2 sigma, functional.SIGMA_LEVELS[1]); set_level(q) changes it"""
+
+    level = 0.9772
+
+    def set_level(self, q):
+        self.level = float(q)
+        return self
+
+
+@register("tail_rmse")
+class TailRMSE(_AtLevel, Metric):
+    """rmse over the pixels whose target is at or beyond the channel's own target quantile at `level`"""
+    def __call__(self, pred, target):
+        return _F.tail_rmse(pred, target, self.level, False, self.aggregate_only)
+
+
+@register("lat_tail_rmse")
+class LatWeightedTailRMSE(_AtLevel, LatitudeWeightedMetric):
+    def __call__(self, pred, target):
+        self.cast_to_device(pred)
+        return _F.tail_rmse(pred, target, self.level, False, self.aggregate_only, self.lat_weights)
+
+
+@register("quantile_bias")
+class QuantileBias(_AtLevel, Metric):
+    """quantile of the prediction minus quantile of the target at `level`, per channel and their mean"""
+    def __call__(self, pred, target):
+        out = _F.quantile_bias(pred, target, self.level, self.aggregate_only)
+        return out[..., 0]
+
+
 # ---- missing data (functional.masked_*; DESIGN 4.10d): the same call signatures as their unmasked namesakes, so that
 # training_step and evaluate_func run unchanged on targets that are NaN where there is no data (land-only Daymet / PRISM).
 # A pixel counts where the target is finite AND the mask (if any) is non-zero; without any mask the finite test alone decides.

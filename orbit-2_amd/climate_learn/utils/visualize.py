@@ -235,6 +235,37 @@ def consistency_scores(x, pred, in_variables, out_variables, mode="bilinear", la
     return {v: {k: float(col[c]) for k, col in cols.items()} for c, v in enumerate(out_variables)}
 
 
+def extreme_scores(preds, y, out_variables, levels=None, lat_weights=None):
+    """What a stitched prediction does in its tails, per output variable: {variable: {"upper": [...], "lower": [...]}}, one entry
+    per level q of `levels` (default metrics.functional.SIGMA_LEVELS, at most 8) -- "upper" at q, "lower" at the mirrored 1 - q --
+    each {"level", "target_quantile", "pred_quantile", "quantile_bias", "tail_rmse", "tail_bias", "csi", "frequency_bias"}.
+    `preds` [B,C,yout,xout] from tiled_predict, `y` the target [B,C,>=yout,>=xout] (its top-left crop; NaN = no data).  The
+    quantiles are exact and pooled over the batch per variable (orbit2_masked_loss_fwd at ORBIT2_MASKED_QUANTILES); the tail is
+    the pixels whose TARGET is at or beyond its own quantile (upper: >=, lower: <=), scored in one pass for all levels
+    (ORBIT2_MASKED_TAIL): tail_rmse = sqrt(sum w d^2 / sum w) with w the latitude weight if given, tail_bias = mean(pred - target),
+    csi = hits / (hits + misses + false alarms), frequency_bias = (hits + false alarms) / (hits + misses).  Everything stays on the
+    device until the few numbers are read out."""
+    from .. import _hip
+    from ..metrics import functional as fn
+    levels = tuple(float(q) for q in (fn.SIGMA_LEVELS if levels is None else levels))
+    preds = preds.detach().float().contiguous()
+    y = y.detach().float().contiguous()
+    lat = fn._lat(lat_weights, preds)
+    res = {v: {} for v in out_variables}
+    for side, qs, lower in (("upper", levels, False), ("lower", tuple(1.0 - q for q in levels), True)):
+        quant, _ = _hip.masked_quantiles(preds, y, torch.tensor(qs, dtype=torch.float32, device=preds.device))
+        s, n = _hip.masked_tail(preds, y, quant[0, :, :, 0].contiguous(), lat, lower=lower)
+        s, n, quant = s.double().sum(0).cpu(), n.sum(0).double().cpu(), quant[..., 0].double().cpu()        # [C,L,4] x 2, [2,C,L]
+        hits, alarms = n[..., 1], n[..., 2]
+        misses = n[..., 0] - hits
+        cols = {"target_quantile": quant[0], "pred_quantile": quant[1], "quantile_bias": quant[1] - quant[0],
+                "tail_rmse": (s[..., 1] / s[..., 0]).sqrt(), "tail_bias": s[..., 3] / n[..., 0],
+                "csi": hits / (hits + misses + alarms), "frequency_bias": (hits + alarms) / (hits + misses)}
+        for c, v in enumerate(out_variables):
+            res[v][side] = [dict(level=q, **{k: float(col[c, j]) for k, col in cols.items()}) for j, q in enumerate(qs)]
+    return res
+
+
 def visualize_at_index(mm, dm, dm_vis, out_list, in_transform, out_transform, variable, src, device, div, overlap, index=0,
                        tensor_par_size=1, tensor_par_group=None, save_png: bool = True, prefix: str = ""):
     """Stitched input / prediction / ground truth of test sample `index` for `variable` (reference :38-490; the PNG

@@ -9,9 +9,11 @@
 //
 // One work item is 4 consecutive pixels of one row.  When every row of pred, target and mask starts on a 16-byte (mask:
 // 4-byte) boundary the item's centre is one float4 / one dword per operand (VEC); otherwise the same item is read by four
-// guarded scalar lanes.  The total-variation stencil needs the pixels left and right of the group and the rows above (backward)
-// and below: those edge pixels are scalar loads, and a pixel outside the plane is invalid.
-#include "score_sums.h"
+// guarded scalar lanes (masked_rows.h: load_row, vec_ok).  The total-variation stencil needs the pixels left and right of the
+// group and the rows above (backward) and below: those edge pixels are scalar loads, and a pixel outside the plane is invalid.
+//
+// orbit2_masked_loss_fwd hands the kinds ORBIT2_MASKED_QUANTILES and ORBIT2_MASKED_TAIL on to extremes.hip.
+#include "masked_rows.h"
 #include "../../include/orbit2_hip.h"
 
 namespace {
@@ -192,62 +194,6 @@ __global__ __launch_bounds__(256) void eval_moments_kernel(const float* __restri
 
 constexpr int MM_NM = O2_NMOMENTS + 1;   // the twelve sums of orbit2_eval_moments + the valid count
 
-struct MaskArg {
-  const uint8_t* m;                  // NULL: no mask
-  int pitch;                         // bytes (= elements) between two rows
-  int64_t sb, sc;                    // batch and channel strides; 0 = broadcast
-};
-
-// One row of one (b, c) plane around the item's columns j0 .. j0+3:
-//   pv[k], vv[k]  k = 0..5  <->  column j0 - 1 + k   (pv = 0 and vv = false outside the plane or where invalid is irrelevant:
-//                                                    pv is only ever used under vv)
-//   tc[k]         k = 0..3  <->  target at column j0 + k (only meaningful where vv[k + 1])
-// EDGES = false: columns j0-1 and j0+4 are not read (vv false).
-template <bool VEC, bool EDGES>
-__device__ __forceinline__ void load_row(const float* __restrict__ p, const float* __restrict__ t, const uint8_t* __restrict__ m,
-                                         int i, int j0, int H, int W, int Wt, int mp, float (&pv)[6], bool (&vv)[6],
-                                         float (&tc)[4]) {
-#pragma unroll
-  for (int k = 0; k < 6; ++k) { pv[k] = 0.f; vv[k] = false; }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) tc[k] = 0.f;
-  if (i < 0 || i >= H) return;
-  const float* pr = p + (size_t)i * W;
-  const float* tr = t + (size_t)i * Wt;
-  const uint8_t* mr = m ? m + (size_t)i * mp : nullptr;
-  if (VEC) {                                           // W % 4 == 0: the whole group is inside the row
-    const f32x4 p4 = *reinterpret_cast<const f32x4*>(pr + j0);
-    const f32x4 t4 = *reinterpret_cast<const f32x4*>(tr + j0);
-    const uint32_t m4 = mr ? *reinterpret_cast<const uint32_t*>(mr + j0) : 0x01010101u;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      pv[k + 1] = p4[k];
-      tc[k] = t4[k];
-      vv[k + 1] = finite_f(t4[k]) && ((m4 >> (8 * k)) & 0xffu) != 0;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int j = j0 + k;
-      if (j < W) {
-        pv[k + 1] = pr[j];
-        tc[k] = tr[j];
-        vv[k + 1] = finite_f(tc[k]) && (!mr || mr[j] != 0);
-      }
-    }
-  }
-  if (EDGES) {
-    if (j0 > 0) {
-      pv[0] = pr[j0 - 1];
-      vv[0] = finite_f(tr[j0 - 1]) && (!mr || mr[j0 - 1] != 0);
-    }
-    if (j0 + 4 < W) {
-      pv[5] = pr[j0 + 4];
-      vv[5] = finite_f(tr[j0 + 4]) && (!mr || mr[j0 + 4] != 0);
-    }
-  }
-}
-
 // |a - b| if both pixels are valid, else 0 (select: a and b may be NaN where invalid)
 __device__ __forceinline__ float absdiff_if(bool v, float a, float b) { return v ? fabsf(a - b) : 0.f; }
 __device__ __forceinline__ float sgndiff_if(bool v, float a, float b) { return v ? sgn(a - b) : 0.f; }
@@ -419,20 +365,6 @@ __global__ __launch_bounds__(256) void masked_moments_kernel(const float* __rest
     atomicAdd(out + (size_t)plane * MM_NM + MM_NM - 1, (double)(redn[0] + redn[1] + redn[2] + redn[3]));   // exact below 2^53
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-// the mask argument as given; false if it cannot be what it says
-inline bool mask_arg(MaskArg& mk, const uint8_t* mask, int pitch, int64_t sb, int64_t sc, int Ht, int Wt, int W) {
-  mk.m = mask; mk.pitch = pitch; mk.sb = sb; mk.sc = sc;
-  if ((int64_t)Ht * Wt > 0x7fffffff) return false;                   // a plane is indexed with 32 bits
-  return !mask || (pitch >= W && sb >= 0 && sc >= 0);
-}
-// float4 / dword centres: every row of every operand starts aligned (and W % 4 == 0: no partial group)
-inline bool vec_ok(const float* pred, const float* target, const MaskArg& mk, int W, int Wt) {
-  if (W % 4 || Wt % 4 || !aligned(pred, 16) || !aligned(target, 16)) return false;
-  return !mk.m || (aligned(mk.m, 4) && mk.pitch % 4 == 0 && mk.sb % 4 == 0 && mk.sc % 4 == 0);
-}
-
 }  // namespace
 
 extern "C" int orbit2_loss_fwd(const float* pred, const float* target, int Ht, int Wt, const float* lat_w,
@@ -479,10 +411,17 @@ extern "C" int orbit2_masked_loss_fwd(const float* pred, const float* target, in
                                       const float* chan_w, float* out, int64_t* cnt, float* ws, int B, int C, int H, int W,
                                       int kind, void* stream) {
   if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !out || !cnt || !ws) return O2_ERR_ARG;
-  if (kind != 0 && kind != 1) return O2_ERR_ARG;
+  // the kind word: bits 0-3 the kind proper, bits 4-5 the flags, bits 8-15 a count; kinds 0 / 1 take neither flag nor count
+  constexpr int FLAGS = ORBIT2_MASKED_PER_IMAGE | ORBIT2_MASKED_LOWER;
+  if (kind < 0 || (kind & ~(15 | FLAGS | 0xff00))) return O2_ERR_ARG;
+  const int base = kind & 15;
+  if (base != ORBIT2_MASKED_QUANTILES && base != ORBIT2_MASKED_TAIL && kind != 0 && kind != 1) return O2_ERR_ARG;
   MaskArg mk;
   if (!mask_arg(mk, mask, mask_pitch, mask_sb, mask_sc, Ht, Wt, W)) return O2_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
+  if (base >= ORBIT2_MASKED_QUANTILES)
+    return o2_masked_extremes(pred, target, Ht, Wt, mk, lat_w, chan_w, out, cnt, ws, B, C, H, W, base, kind & FLAGS,
+                              (kind >> 8) & 0xff, s);
   int* wsn = reinterpret_cast<int*>(ws + (size_t)B * C * ORBIT2_LOSS_BLOCKS);
   o2_with_flags(
       [&](auto vec, auto tv) {
