@@ -29,7 +29,13 @@ An optional `extreme_scores: true` or `extreme_scores: {levels: [...]}` entry (c
 +1 / +2 / +3 sigma) prints one `extreme_scores` line per output variable: for the upper tail at every level and the lower tail at
 the mirrored one, the exact quantile of the target and of the stitched field, their difference, and the rmse, bias, critical
 success index and frequency bias over the pixels whose target lies in that tail, in physical units
-(climate_learn.utils.visualize.extreme_scores)."""
+(climate_learn.utils.visualize.extreme_scores).
+
+An optional `neighbourhood_scores: true` or `neighbourhood_scores: {levels: [...], windows: [...]}` entry
+(configs/inference_fss.yaml; default levels +1 / +2 / +3 sigma, windows 1 .. 65) prints, after any `extreme_scores` line, one
+`neighbourhood_scores` line per output variable: at every level the target's quantile, the base rate of the event "at or beyond
+it", the fractions skill score of the stitched field at every window, the score 0.5 + base_rate / 2 that counts as skilful, and the
+smallest window that reaches it (climate_learn.utils.visualize.neighbourhood_scores)."""
 import os
 import sys
 
@@ -41,8 +47,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "orbit-2_amd")]
 
 import climate_learn as cl                                                        # noqa: E402
 from climate_learn.utils.fused_attn import FusedAttn                              # noqa: E402
-from climate_learn.utils.visualize import (baseline_scores, consistency_scores, extreme_scores, stitched_scores,  # noqa: E402
-                                           tiled_predict, visualize_at_index)
+from climate_learn.utils.visualize import (baseline_scores, consistency_scores, extreme_scores, neighbourhood_scores,  # noqa: E402
+                                           stitched_scores, tiled_predict, visualize_at_index)
 
 
 def main():
@@ -110,6 +116,14 @@ def main():
         for var, sc in extreme_scores(pred, gt, ov, levels).items():
             print("extreme_scores", var, {side: [{k: round(v, 6) for k, v in row.items()} for row in rows]
                                           for side, rows in sc.items()}, flush=True)
+    neighbourhood = conf.get("neighbourhood_scores")
+    if neighbourhood:
+        # at which scale the stitched field places its events rightly: the fractions skill score across windows, on the device
+        # (climate_learn.utils.visualize.neighbourhood_scores)
+        opts = {k: neighbourhood[k] for k in ("levels", "windows") if isinstance(neighbourhood, dict) and k in neighbourhood}
+        for var, rows in neighbourhood_scores(pred, gt, ov, **opts).items():
+            print("neighbourhood_scores", var, [{k: ({w: round(s, 6) for w, s in v.items()} if k == "fss" else round(v, 6))
+                                                 for k, v in row.items()} for row in rows], flush=True)
     consistency = conf.get("consistency")
     if consistency:
         # the stitched field coarsened back to the input grid and read against the input, both normalised as the outputs are;

@@ -38,7 +38,9 @@ extern "C" {
  * (those two with ORBIT2_TRANSPOSE: the adjoint of the coarsening), which earlier builds of version 8 refuse as well; the kind
  * value 3 of orbit2_loss_bwd (ORBIT2_LOSS_SSIM_VJP: the backward of orbit2_ssim's sums), which earlier builds refuse too; the
  * kinds 3 and 4 of orbit2_masked_loss_fwd with the flag and count bits of its kind word (ORBIT2_MASKED_QUANTILES,
- * ORBIT2_MASKED_TAIL: exact field quantiles and tail sums), which earlier builds refuse with O2_ERR_ARG as well. */
+ * ORBIT2_MASKED_TAIL: exact field quantiles and tail sums), which earlier builds refuse with O2_ERR_ARG as well; the kind 5 of
+ * that entry with the window bits 16-23 of its kind word (ORBIT2_FSS_KIND: the fractions skill score), refused by earlier builds
+ * in the same way. */
 int orbit2_abi_version(void);
 
 /* ---- bf16 MFMA GEMM with fused epilogue ------------------------------------------------
@@ -394,7 +396,7 @@ int orbit2_eval_moments(const float* pred, const float* target, int Ht, int Wt, 
  * the kernels read float4 / dword groups; any other layout is read by scalar lanes (same results to rounding of the sums' order).
  *
  * orbit2_masked_loss_fwd: kind 0 = mse, 1 = bayesian_tv (a difference term of the prior counts only if both of its pixels are
- * valid); kinds 3 / 4 are the extreme-value scores below; any other kind is O2_ERR_ARG.  With num_c = sum_{b,i,j} v w_i cw_c err and n_c = sum_{b,i,j} v:
+ * valid); kinds 3 / 4 are the extreme-value scores and kind 5 the fractions skill score below; any other kind is O2_ERR_ARG.  With num_c = sum_{b,i,j} v w_i cw_c err and n_c = sum_{b,i,j} v:
  *   out[c] = num_c / n_c (0 if n_c == 0), out[C] = sum_c num_c / sum_c n_c (0 if nothing is valid); cnt[c] = n_c, cnt[C] = sum_c n_c.
  * out fp32 [C+1], cnt int64 [C+1] (counted as integers: exact), ws >= 2*B*C*ORBIT2_LOSS_BLOCKS four-byte words.
  * Fixed-order sums, no atomics: two calls give the same bits.
@@ -414,7 +416,7 @@ int orbit2_masked_moments(const float* pred, const float* target, int Ht, int Wt
 /* ---- extreme-value scores (csrc/extremes.hip, csrc/quantile_select.h; metrics/functional.py field_quantiles / tail_rmse /
  * exceedance_scores): two further kinds of orbit2_masked_loss_fwd, additive within ABI 8 -------------------------
  * The entry's `kind` is a bit field: bits 0-3 the kind proper, bit 4 ORBIT2_MASKED_PER_IMAGE, bit 5 ORBIT2_MASKED_LOWER, bits
- * 8-15 a count n (ORBIT2_MASKED_KIND(kind, flags, n)).  Any other set bit, a kind proper other than 0, 1, 3, 4, any flag or
+ * 8-15 a count n (ORBIT2_MASKED_KIND(kind, flags, n)).  Any other set bit, a kind proper other than 0, 1, 3, 4 (and 5, further below), any flag or
  * count on kinds 0 / 1, and ORBIT2_MASKED_LOWER on kind 3 are O2_ERR_ARG.  Validity, pred / target / mask and the float4 / scalar
  * path choice are those of kinds 0 / 1.  Pixels are grouped: G = C groups by default (a channel pooled over the batch and all
  * pixels), G = B * C with ORBIT2_MASKED_PER_IMAGE; invalid pixels enter nothing; a group of 2^31 or more pixels is refused.
@@ -455,6 +457,38 @@ int orbit2_masked_moments(const float* pred, const float* target, int Ht, int Wt
 #define ORBIT2_QUANTILE_WS_WORDS(G, Q) (2 * (long long)(G) * (64 + 256 + 3 * 2 * (Q) * 256))
 /* per image and workgroup: T x 4 fp32 sums, then T x 4 int32 counts */
 #define ORBIT2_TAIL_WS_WORDS(B, C, T) ((long long)(B) * (C) * ORBIT2_LOSS_BLOCKS * 8 * (T))
+
+/* ---- the fractions skill score (csrc/fss.hip, csrc/fss_window.h; metrics/functional.py fss / fss_profile): one more
+ * kind of orbit2_masked_loss_fwd, additive within ABI 8 -----------------------------------------------------------------------
+ * Neighbourhood verification (Roberts & Lean 2008): the fraction of a window in which an event occurs, compared between target
+ * and prediction.  A pixel is VALID exactly as for the other kinds (target finite, mask NULL or non-zero); the target is read
+ * through the prediction's top-left crop.  For a threshold t the INDICATOR of a field value v at a pixel is valid && v >= t,
+ * with ORBIT2_MASKED_LOWER valid && v <= t; a NaN prediction at a valid pixel compares false; invalid pixels and pixels outside
+ * the plane hold 0 in both indicators (zero padding).  For the odd window n = 2 r + 1, cO(i, j) and cM(i, j) are the integer
+ * numbers of set target and prediction indicators in rows i - r .. i + r and columns j - r .. j + r.  Per image (b, c) and
+ * threshold, summed over the VALID centres only:
+ *   cnt int64 [B][C][T][4] = { valid centres, sum cO^2, sum cM^2, sum (cO - cM)^2 }
+ *   out fp32  [B][C][T]    = (float)(1.0 - (double)cnt[3] / ((double)cnt[1] + (double)cnt[2])), NaN when cnt[1] + cnt[2] == 0
+ * The factor n^4 of the fractions cancels, so the score is a ratio of exact integers; a score pooled over images is formed by
+ * the caller from the summed integers.  n = 1 is the grid-scale score; a window larger than the plane is clamped to it.
+ *
+ * The kind word, ORBIT2_FSS_WORD(flags, T, n): bits 0-3 = ORBIT2_FSS_KIND (5); bit 4 ORBIT2_MASKED_PER_IMAGE: the thresholds
+ * are [B*C][T] instead of [C][T], as at ORBIT2_MASKED_TAIL; bit 5 ORBIT2_MASKED_LOWER; bits 8-15 T in
+ * 1..ORBIT2_MASKED_MAX_LEVELS; bits 16-23 the window n, odd, 1..ORBIT2_FSS_MAX_WINDOW.  No other kind takes bits 16 and up.
+ * chan_w is read as thresholds fp32 [G][T] (G = C, or B * C with ORBIT2_MASKED_PER_IMAGE); lat_w must be NULL: the score is
+ * unweighted, integer sums are what make it exact.  ws holds ORBIT2_FSS_WS_WORDS(B, C, H, W, T) four-byte words and is 8-byte
+ * aligned: the valid plane and the 2 T indicator planes as bits, [B*C][2 T + 1][H][ceil(W / 64)] 64-bit words.  cnt is zeroed by
+ * the entry on the stream.  255^2 = 65025 and 65025^2 = 4 228 250 625 < 2^32, so a pixel's term fits an unsigned 32-bit word;
+ * (2^63 - 1) / 255^4 = 2 181 368 337 > 2^31, so an int64 sum over fewer than 2^31 pixels cannot overflow, per image or pooled.
+ * Integer atomics only: two calls give the same bits.  No address depends on a data value.
+ *
+ * Refused before any launch with nothing written: any other set bit, an even or zero window, T outside 1..8, NULL chan_w,
+ * non-NULL lat_w, a ws that is not 8-byte aligned, a group (a channel over the batch, or with ORBIT2_MASKED_PER_IMAGE an image)
+ * of 2^31 pixels or more, and everything kinds 0 / 1 refuse. */
+#define ORBIT2_FSS_KIND 5
+#define ORBIT2_FSS_MAX_WINDOW 255
+#define ORBIT2_FSS_WORD(flags, T, n) (ORBIT2_FSS_KIND | (flags) | ((T) << 8) | ((n) << 16))
+#define ORBIT2_FSS_WS_WORDS(B, C, H, W, T) (2 * (long long)(B) * (C) * (2 * (T) + 1) * (H) * (((W) + 63) / 64))
 
 /* ---- MC-dropout ensembles (utils/mc_dropout.py) and the Gaussian scores (metrics/functional.py:340-386) ------
  * orbit2_ensemble_update: the k-th (1-based) Welford step over n fp32 elements, in place:

@@ -1160,6 +1160,49 @@ def masked_tail(pred, target, thresholds, lat_w=None, mask=None, mask_strides=(0
     return out, cnt
 
 
+# ---- the fractions skill score (csrc/fss.hip): one more kind of orbit2_masked_loss_fwd, its window in bits 16-23 ----------------
+FSS_KIND = 5                    # ORBIT2_FSS_KIND
+FSS_MAX_WINDOW = 255            # ORBIT2_FSS_MAX_WINDOW: odd windows 1 .. 255
+FSS_STRIP = 256                 # csrc/fss_window.h FSS_STRIP: columns of a workgroup of the window pass
+FSS_BANDS = (128, 32, 1024)     # FSS_MAX_BAND, FSS_MIN_BAND, FSS_FILL: centre rows of a workgroup, halved while the launch is small
+
+
+def fss_ws_words(B: int, Cc: int, H: int, W: int, T: int) -> int:
+    """ORBIT2_FSS_WS_WORDS(B, C, H, W, T)"""
+    return 2 * B * Cc * (2 * T + 1) * H * ((W + 63) // 64)
+
+
+def fss_partition(B: int, Cc: int, H: int, W: int, T: int):
+    """(columns of a strip, centre rows of a band) of the window pass at these sizes (csrc/fss_window.h: fss_strips,
+    fss_band_rows)"""
+    band, low, fill = FSS_BANDS
+    groups = B * Cc * T * ((W + FSS_STRIP - 1) // FSS_STRIP)
+    while band > low and groups * ((H + band - 1) // band) < fill:
+        band >>= 1
+    return FSS_STRIP, band
+
+
+def masked_fss(pred, target, thresholds, window, mask=None, mask_strides=(0, 0, 0), lower=False, per_image=False):
+    """(fss fp32 [B, C, T], cnt int64 [B, C, T, 4]) per image and threshold: with cO / cM the numbers of target / prediction
+    pixels at or beyond the threshold (lower: at or below) in the `window` x `window` neighbourhood of a pixel, zero beyond the
+    plane and at invalid pixels, cnt = {valid centres, sum cO^2, sum cM^2, sum (cO - cM)^2} over the valid centres and
+    fss = 1 - cnt[3] / (cnt[1] + cnt[2]), NaN at 0 / 0 (include/orbit2_hip.h: ORBIT2_FSS_KIND).  thresholds: fp32 [G, T] on the
+    device, G = C or, per_image, B * C; T <= 8; window odd, 1 .. 255."""
+    B, Cc, H, W = _scored_pair("masked_fss", pred, target)
+    G = _groups("masked_fss", B, Cc, H, W, per_image)
+    T = _levels("masked_fss", thresholds, "thresholds", G)
+    if isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= FSS_MAX_WINDOW or window % 2 == 0:
+        raise HipBackendError("masked_fss: the window must be an odd int in 1..%d, got %r" % (FSS_MAX_WINDOW, window))
+    mp = _mask_args(mask, mask_strides, pred, target)
+    out = torch.empty(B, Cc, T, dtype=F32, device=pred.device)
+    cnt = torch.empty(B, Cc, T, 4, dtype=torch.int64, device=pred.device)
+    ws = torch.empty(fss_ws_words(B, Cc, H, W, T) // 2, dtype=torch.int64, device=pred.device)       # 8-byte aligned words
+    kind = FSS_KIND | (MASKED_PER_IMAGE if per_image else 0) | (MASKED_LOWER if lower else 0) | (T << 8) | (window << 16)
+    _call("orbit2_masked_loss_fwd", pred, target, target.shape[2], target.shape[3], *mp, None, thresholds, out, cnt, ws, B, Cc,
+          H, W, kind)
+    return out, cnt
+
+
 def ensemble_update(member, mean, m2, k: int):
     """the k-th (1-based) Welford step of the running ensemble moments, in place on `mean` and `m2`
     (include/orbit2_hip.h:orbit2_ensemble_update); k = 1 initialises them, so they may be torch.empty"""

@@ -656,3 +656,61 @@ def exceedance_scores(pred, target, q=0.9772, lower: bool = False, mask=None, th
     ms = n[:, 0] - h
     return {"csi": (h / (h + ms + f)).float(), "pod": (h / (h + ms)).float(), "far": (f / (h + f)).float(),
             "frequency_bias": ((h + f) / (h + ms)).float()}
+
+
+# ---- neighbourhood verification (DESIGN 4.10j): the fractions skill score of Roberts & Lean (2008).  An event placed a few pixels
+# aside is a miss and a false alarm to csi, and a field without the event is neither; the FSS compares the FRACTION of a window
+# in which the event occurs, so it answers at which scale a field places its events rightly.  The event is "at or beyond the
+# channel's pooled target quantile" (or explicit thresholds), the window counts come from orbit2_masked_loss_fwd at
+# ORBIT2_FSS_KIND as exact integers, at a cost that does not grow with the window.  Nothing here copies to the host. --------------
+def _fss_thresholds(pred, target, q, m, strides, thresholds):
+    """[C, T] fp32 on the device: the pooled target quantiles at the levels q, exactly as _tail obtains them, or `thresholds`"""
+    from .. import _hip
+    if thresholds is None:
+        out, _ = _hip.masked_quantiles(pred, target, _level_tensor(q, pred.device)[0], m, strides)
+        return out[0, :, :, 0].contiguous()
+    thr = torch.as_tensor(thresholds).detach().to(device=pred.device, dtype=torch.float32)
+    return thr.reshape(pred.shape[1], -1).contiguous()
+
+
+def _fss_ratio(n):
+    """[..., 4] integer sums -> 1 - sum (cO - cM)^2 / (sum cO^2 + sum cM^2) in double; 0 / 0 is NaN"""
+    n = n.double()
+    return 1.0 - n[..., 3] / (n[..., 1] + n[..., 2])
+
+
+def fss(pred, target, window: int = 9, q=0.9772, lower: bool = False, aggregate_only: bool = False, mask=None, thresholds=None):
+    """[C+1]: the fractions skill score of the event "at or beyond the channel's own pooled target quantile at level q" (lower:
+    at or below; `thresholds` [C] replaces the quantile) in windows of `window` x `window` pixels (odd, 1 .. 255; zero beyond
+    the field and at invalid pixels), per channel from the integer sums over the batch and the valid centres:
+    1 - sum (cO - cM)^2 / (sum cO^2 + sum cM^2); the last entry is the mean of the channels.  1 is a perfect placement at that
+    scale, 0 no overlap at all; no event in either field gives NaN."""
+    from .. import _hip
+    pred, target = _extreme_pair(pred, target)
+    m, pitch, sb, sc = _mask_operand(mask, pred, target)
+    thr = _fss_thresholds(pred, target, q, m, (pitch, sb, sc), thresholds)
+    _, n = _hip.masked_fss(pred, target, thr, int(window), m, (pitch, sb, sc), lower)
+    return _with_aggregate(_fss_ratio(n.sum(0))[:, 0].float(), aggregate_only)
+
+
+def fss_profile(pred, target, windows, q=SIGMA_LEVELS, lower: bool = False, mask=None, thresholds=None):
+    """The score across scales, one kernel call per window of `windows` (S of them, each odd in 1 .. 255) for all levels of q
+    (Q <= 8; or `thresholds` [C, Q]): {"fss": [C, Q, S]; "base_rate": [C, Q], f0 = the fraction of the valid pixels at which the
+    target has the event; "uniform": [C, Q] = 0.5 + f0 / 2, the score above which a field counts as skilful at a scale;
+    "skilful_window": [C, Q] int64, the smallest of `windows` with fss >= uniform, 0 if none}."""
+    from .. import _hip
+    pred, target = _extreme_pair(pred, target)
+    m, pitch, sb, sc = _mask_operand(mask, pred, target)
+    thr = _fss_thresholds(pred, target, q, m, (pitch, sb, sc), thresholds)
+    windows = [int(w) for w in windows]
+    # at window 1 cO is the indicator itself, so sum cO^2 counts the target's events
+    n1 = _hip.masked_fss(pred, target, thr, 1, m, (pitch, sb, sc), lower)[1].sum(0).double()
+    base = n1[..., 1] / n1[..., 0]
+    uniform = 0.5 + 0.5 * base
+    score = torch.stack([_fss_ratio(n1 if w == 1 else _hip.masked_fss(pred, target, thr, w, m, (pitch, sb, sc), lower)[1].sum(0))
+                         for w in windows], dim=-1)
+    sizes = torch.tensor(windows, dtype=torch.int64, device=score.device)
+    big = torch.iinfo(torch.int64).max
+    first = torch.where(score >= uniform.unsqueeze(-1), sizes, torch.full_like(sizes, big)).amin(-1)
+    return {"fss": score.float(), "base_rate": base.float(), "uniform": uniform.float(),
+            "skilful_window": torch.where(first == big, torch.zeros_like(first), first)}

@@ -293,6 +293,21 @@ class QuantileBias(_AtLevel, Metric):
         return out[..., 0]
 
 
+@register("fss")
+class FSS(_AtLevel, Metric):
+    """the fractions skill score of the event "at or beyond the channel's own target quantile at `level`" in windows of
+    `window` x `window` pixels (odd, 1 .. 255; default 9); set_window(n) changes it"""
+
+    window = 9
+
+    def set_window(self, n):
+        self.window = int(n)
+        return self
+
+    def __call__(self, pred, target):
+        return _F.fss(pred, target, self.window, self.level, False, self.aggregate_only)
+
+
 # ---- missing data (functional.masked_*; DESIGN 4.10d): the same call signatures as their unmasked namesakes, so that
 # training_step and evaluate_func run unchanged on targets that are NaN where there is no data (land-only Daymet / PRISM).
 # A pixel counts where the target is finite AND the mask (if any) is non-zero; without any mask the finite test alone decides.

@@ -266,6 +266,30 @@ def extreme_scores(preds, y, out_variables, levels=None, lat_weights=None):
     return res
 
 
+def neighbourhood_scores(preds, y, out_variables, levels=None, windows=(1, 3, 5, 9, 17, 33, 65)):
+    """At which scale a stitched prediction places its events rightly, per output variable: {variable: [row per level q of
+    `levels` (default metrics.functional.SIGMA_LEVELS, at most 8)]}, each row {"level", "threshold", "base_rate", "uniform",
+    "skilful_window", "fss": {window: value}}.  The event is "at or beyond the variable's exact pooled target quantile at q"
+    (`threshold`, orbit2_masked_loss_fwd at ORBIT2_MASKED_QUANTILES); "fss" is the fractions skill score in every window of
+    `windows` (odd, 1 .. 255 pixels; ORBIT2_FSS_KIND, one call per window), "base_rate" the fraction of the valid pixels at which
+    the target has the event, "uniform" = 0.5 + base_rate / 2 the score that counts as skilful, and "skilful_window" the smallest
+    window that reaches it (0: none does).  `preds`, `y` as extreme_scores.  Only these few numbers leave the device."""
+    from .. import _hip
+    from ..metrics import functional as fn
+    levels = tuple(float(q) for q in (fn.SIGMA_LEVELS if levels is None else levels))
+    windows = tuple(int(w) for w in windows)
+    preds = preds.detach().float().contiguous()
+    y = y.detach().float().contiguous()
+    quant, _ = _hip.masked_quantiles(preds, y, torch.tensor(levels, dtype=torch.float32, device=preds.device))
+    thr = quant[0, :, :, 0].contiguous()
+    prof = fn.fss_profile(preds, y, windows, thresholds=thr)
+    thr, prof = thr.double().cpu(), {k: v.double().cpu() for k, v in prof.items()}
+    return {v: [dict(level=q, threshold=float(thr[c, j]), base_rate=float(prof["base_rate"][c, j]),
+                     uniform=float(prof["uniform"][c, j]), skilful_window=int(prof["skilful_window"][c, j]),
+                     fss={w: float(prof["fss"][c, j, k]) for k, w in enumerate(windows)})
+                for j, q in enumerate(levels)] for c, v in enumerate(out_variables)}
+
+
 def visualize_at_index(mm, dm, dm_vis, out_list, in_transform, out_transform, variable, src, device, div, overlap, index=0,
                        tensor_par_size=1, tensor_par_group=None, save_png: bool = True, prefix: str = ""):
     """Stitched input / prediction / ground truth of test sample `index` for `variable` (reference :38-490; the PNG

@@ -411,14 +411,19 @@ extern "C" int orbit2_masked_loss_fwd(const float* pred, const float* target, in
                                       const float* chan_w, float* out, int64_t* cnt, float* ws, int B, int C, int H, int W,
                                       int kind, void* stream) {
   if (!o2_pair_ok(pred, target, B, C, H, W, Ht, Wt) || !out || !cnt || !ws) return O2_ERR_ARG;
-  // the kind word: bits 0-3 the kind proper, bits 4-5 the flags, bits 8-15 a count; kinds 0 / 1 take neither flag nor count
+  // the kind word: bits 0-3 the kind proper, bits 4-5 the flags, bits 8-15 a count; kinds 0 / 1 take neither flag nor count;
+  // ORBIT2_FSS_KIND alone takes bits 16-23, its window
   constexpr int FLAGS = ORBIT2_MASKED_PER_IMAGE | ORBIT2_MASKED_LOWER;
-  if (kind < 0 || (kind & ~(15 | FLAGS | 0xff00))) return O2_ERR_ARG;
   const int base = kind & 15;
-  if (base != ORBIT2_MASKED_QUANTILES && base != ORBIT2_MASKED_TAIL && kind != 0 && kind != 1) return O2_ERR_ARG;
+  if (kind < 0 || (kind & ~(15 | FLAGS | 0xff00 | (base == ORBIT2_FSS_KIND ? 0xff0000 : 0)))) return O2_ERR_ARG;
+  if (base != ORBIT2_MASKED_QUANTILES && base != ORBIT2_MASKED_TAIL && base != ORBIT2_FSS_KIND && kind != 0 && kind != 1)
+    return O2_ERR_ARG;
   MaskArg mk;
   if (!mask_arg(mk, mask, mask_pitch, mask_sb, mask_sc, Ht, Wt, W)) return O2_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
+  if (base == ORBIT2_FSS_KIND)
+    return o2_masked_fss(pred, target, Ht, Wt, mk, lat_w, chan_w, out, cnt, ws, B, C, H, W, kind & FLAGS, (kind >> 8) & 0xff,
+                         (kind >> 16) & 0xff, s);
   if (base >= ORBIT2_MASKED_QUANTILES)
     return o2_masked_extremes(pred, target, Ht, Wt, mk, lat_w, chan_w, out, cnt, ws, B, C, H, W, base, kind & FLAGS,
                               (kind >> 8) & 0xff, s);

@@ -83,3 +83,10 @@ __attribute__((visibility("hidden"))) int o2_masked_extremes(const float* pred, 
                                                              const MaskArg& mk, const float* lat_w, const float* chan_w,
                                                              float* out, int64_t* cnt, float* ws, int B, int C, int H, int W,
                                                              int base, int flags, int n, hipStream_t s);
+
+// ---- the fractions skill score (fss.hip), reached the same way at the kind ORBIT2_FSS_KIND; T and n are the threshold count and
+// the window of the kind word, flags its ORBIT2_MASKED_PER_IMAGE / ORBIT2_MASKED_LOWER bits
+__attribute__((visibility("hidden"))) int o2_masked_fss(const float* pred, const float* target, int Ht, int Wt, const MaskArg& mk,
+                                                        const float* lat_w, const float* chan_w, float* out, int64_t* cnt,
+                                                        float* ws, int B, int C, int H, int W, int flags, int T, int n,
+                                                        hipStream_t s);
